@@ -6,11 +6,16 @@ synthetic 100M x 128-d Gaussian-mixture base, 8192 coarse cells, nprobe w = 32, 
 sub-quantizers, k = 100.  One "step" = one pass of the hot path (coarse top-w -> residual LUTs ->
 list scan -> top-k merge) over one batch of queries already resident in HBM.
 
-  python bench.py --gpus 1 --steps K --warmup W            (defaults finish in a few minutes)
+  python bench.py --gpus 1 --steps K --warmup W            (the headline alone: index build, warm-up, K timed steps)
+  python bench.py --gpus 1 --steps K --warmup W --full     (every side measurement below as well: a few minutes)
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
-The JSON line carries, next to the headline (SURVEY 8d's generator: mixture noise 0.15, on which the exact coarse
+`--dump-outputs DIR` writes the answers of the last timed step (ids, distances, counts; float64) to DIR/<name>.npy: every input
+is generated from fixed seeds, so two builds run with the same arguments can be compared answer for answer.
+
+With --full the JSON line carries, next to the headline (SURVEY 8d's generator: mixture noise 0.15, on which the exact coarse
 bound removes 31 of the 32 probes):
+  `recall_at_1`   against exact fp64 brute force on --gt queries of the first batch;
   `roofline`      the dominant kernel of the headline step (pass A, k_scan_hist), HIP events on the launch stream;
   `hard`          the same engine on data that defeats the coarse bound (mixture noise --hard-sigma: clusters overlap,
                   every one of the 32 probes goes through the filtered scan k_scan_grp), with its own qps, roofline
@@ -369,6 +374,25 @@ def parity_of(res_iid, res_dist, rid, rd):
             "max_abs_ddist": float(np.max(np.abs(res_dist[:n][fin] - rd[fin]), initial=0.0))}
 
 
+DUMP_LIMIT = 64 << 20  # bytes of --dump-outputs in all
+
+
+def dump_outputs(out_dir, arrays, suffix="", limit=DUMP_LIMIT):
+    """--dump-outputs: every array (one row per query) as out_dir/<name><suffix>.npy in float64 (int32 ids and counts are exact in
+    it).  A batch larger than `limit` is cut to a fixed sample of rows (seed 0, ascending), whose indices go to rows<suffix>.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = len(next(iter(arrays.values())))
+    row_bytes = sum(8 * (a.size // max(1, n)) for a in arrays.values())
+    if n * row_bytes > limit:
+        keep = (limit - 4096) // (row_bytes + 8)  # (the row indices and the .npy headers inside the limit as well)
+        rows = np.sort(np.random.default_rng(0).choice(n, size=keep, replace=False))
+        arrays = dict({k_: a[rows] for k_, a in arrays.items()}, rows=rows)
+    elif os.path.exists(os.path.join(out_dir, f"rows{suffix}.npy")):  # (a sample list of an earlier run would describe these arrays)
+        os.remove(os.path.join(out_dir, f"rows{suffix}.npy"))
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def java_probe():
     """is there a JVM on this box?  If there is, and MMIDX_REFERENCE_CLASSPATH names the reference jar and its four
     dependencies (LingPipe / Trove / BDB-JE / EJML: not in the image), tools/java_crosscheck/run.sh drives the REAL classes with the
@@ -438,6 +462,12 @@ def main():
     ap.add_argument("--extra-out", default=os.path.join(ROOT, "bench_extra.json"),
                     help="file that receives every side measurement (hard / spread / other configs / cfg5 / yfcc / host path ...); the JSON line names it")
     ap.add_argument("--dump", default="", metavar="PREFIX", help="write batch 0's answers of every rank to PREFIX.rank<r>.npz")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the answers of the last timed step (ids, distances, counts) to DIR/<name>.npy as float64 (a fixed "
+                         "sample of rows, listed in rows.npy, when the whole batch would exceed 64 MB)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every side measurement: recall, rooflines, CPU baseline and parity gates, batch 131072, hard / spread, "
+                         "other configs, cfg5, yfcc, host path, snapshot, shard balance, the sharded dry run (off: the headline alone)")
     ap.add_argument("--sharded-self-test", action="store_true",
                     help="(internal) build a small index on the sharded handle over --gpus devices and on a plain handle, compare the answers, exit 0 / 1")
     ap.add_argument("--native-sharded", action="store_true",
@@ -600,7 +630,7 @@ def run(cx, args, json_out, native, ndev, dist, rank, world, local, fallback_rea
 
     # measured ceilings (a few tens of ms): what the LDS pipe delivers for pass A's gather pattern, the f64 matrix peak
     probes = None
-    if rank == 0 and args.extras:
+    if rank == 0 and args.full and args.extras:
         try:
             probes = importlib.import_module("bench_extras").probes(L, nat, local)
             log(f"probes: {probes}")
@@ -612,6 +642,7 @@ def run(cx, args, json_out, native, ndev, dist, rank, world, local, fallback_rea
     coarse_h, pq_h = same_codebooks(cx, coarse_h, pq_h)
     nq_total = B * args.nbatches
     big_B = args.big_batch if (world == 1 and not native and not args.force_sharded and args.big_batch > B) else 0
+    # (the queries are drawn for the big batch with or without --full: the headline's batches are the same in either run)
     nq_total = max(nq_total, big_B)
     rccl_ranks = None
     if native:
@@ -635,7 +666,7 @@ def run(cx, args, json_out, native, ndev, dist, rank, world, local, fallback_rea
     else:
         h, Q = build_index(cx, mu, args.sigma, coarse_h, pq_h, nq_total, sharded_build=not single)
     Qb = [Q[i * B:(i + 1) * B].contiguous() for i in range(args.nbatches)]
-    ngt = min(args.gt, B)
+    ngt = min(args.gt, B) if args.full else 0
     gt_arg = ground_truth(cx, mu, args.sigma, Qb[0][:ngt]) if rank == 0 and ngt > 0 else None
 
     iid_out = torch.empty(B, k, dtype=torch.int32, device=dev)
@@ -700,7 +731,8 @@ def run(cx, args, json_out, native, ndev, dist, rank, world, local, fallback_rea
         step(Qb[i % args.nbatches])
     barrier()
     # the timed region carries only the two HIP events around pass A of every step (the dominant kernel's launch time for
-    # the roofline object; resolved after the region): every event record is a ~5 us bubble in the stream
+    # the roofline object; resolved after the region): every event record is a ~5 us bubble in the stream.  A run without
+    # --full keeps them, so that its headline is measured exactly as the full run's
     chk(L.mmidx_set_profiling(h, 2))
     barrier()
     t0 = time.perf_counter()
@@ -710,20 +742,29 @@ def run(cx, args, json_out, native, ndev, dist, rank, world, local, fallback_rea
     elapsed = time.perf_counter() - t0
     st_light = nat.Stats()
     chk(L.mmidx_get_stats(h, C.byref(st_light)))
-    # stage times and code counters: the same batches once more with full profiling, outside the timed region
-    chk(L.mmidx_set_profiling(h, 1))
-    detail_steps = max(args.nbatches, min(args.steps, 8))
-    for i in range(detail_steps):
-        step(Qb[i % args.nbatches])
-    barrier()
-    st = nat.Stats()
-    chk(L.mmidx_get_stats(h, C.byref(st)))
     chk(L.mmidx_set_profiling(h, 0))
-    if st.passa_mfma_launches > 0:  # K3ma served pass A (batches of >= 8 queries per list): its stages, HIP events of the detail steps
-        nl = st.passa_mfma_launches
-        log(f"K3ma pass A per step: sweep 1 {st.passa_mfma_sweep1_ms / nl:.3f} ms, select {st.passa_mfma_select_ms / nl:.3f}, sweep 2 "
-            f"{st.passa_mfma_sweep2_ms / nl:.3f}, verify {st.passa_mfma_verify_ms / nl:.3f}; {st.verified_codes / max(1, detail_steps) / B:.1f} codes verified per query, "
-            f"{st.mfma_redo_queries / max(1, detail_steps):.1f} queries per step handed to the exact kernels")
+    if args.dump_outputs:  # what the last timed step handed back, before any other step overwrites it
+        gather_native()
+        n_own = B if sharded is None else per_rank
+        dump_outputs(args.dump_outputs, {"ids": iid_out[:n_own].cpu().numpy(), "distances": dist_out[:n_own].cpu().numpy(),
+                                         "counts": cnt_out[:n_own].cpu().numpy()},
+                     suffix="" if sharded is None else f"_rank{rank}", limit=DUMP_LIMIT if sharded is None else DUMP_LIMIT // world)
+    st, detail_steps = None, 0
+    if args.full:
+        # stage times and code counters: the same batches once more with full profiling, outside the timed region
+        chk(L.mmidx_set_profiling(h, 1))
+        detail_steps = max(args.nbatches, min(args.steps, 8))
+        for i in range(detail_steps):
+            step(Qb[i % args.nbatches])
+        barrier()
+        st = nat.Stats()
+        chk(L.mmidx_get_stats(h, C.byref(st)))
+        chk(L.mmidx_set_profiling(h, 0))
+        if st.passa_mfma_launches > 0:  # K3ma served pass A (batches of >= 8 queries per list): its stages, HIP events of the detail steps
+            nl = st.passa_mfma_launches
+            log(f"K3ma pass A per step: sweep 1 {st.passa_mfma_sweep1_ms / nl:.3f} ms, select {st.passa_mfma_select_ms / nl:.3f}, sweep 2 "
+                f"{st.passa_mfma_sweep2_ms / nl:.3f}, verify {st.passa_mfma_verify_ms / nl:.3f}; {st.verified_codes / max(1, detail_steps) / B:.1f} codes verified per query, "
+                f"{st.mfma_redo_queries / max(1, detail_steps):.1f} queries per step handed to the exact kernels")
     if dist is not None:
         tt = torch.tensor([elapsed], device=dev, dtype=f64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -741,7 +782,7 @@ def run(cx, args, json_out, native, ndev, dist, rank, world, local, fallback_rea
     # the same steps with every exact shortcut switched off (each probed code read and summed in fp64):
     # the configuration on which the exact scan kernel's HBM roofline fraction is a meaningful figure
     exhaustive = None
-    if single and args.exhaustive_steps > 0:
+    if args.full and single and args.exhaustive_steps > 0:
         chk(L.mmidx_set_option(h, b"exhaustive", 1))
         step(Qb[0])
         barrier()
@@ -762,97 +803,99 @@ def run(cx, args, json_out, native, ndev, dist, rank, world, local, fallback_rea
                       "unit": "GB/s", "frac": round(ex_ach / 8000.0, 4), "frac_of_measured_copy_ceiling": round(ex_ach / 6290.0, 4),
                       "bound": "lds (bank conflicts of the fp64 gather), see DESIGN.md 5.1"}
 
-    # recall@1 and results of batch 0 (for the parity gate)
-    step(Qb[0])
-    barrier()
-    gather_native()
-    res_iid = iid_out.cpu().numpy().copy()
-    res_dist = dist_out.cpu().numpy().copy()
-    recall1 = None
-    if rank == 0 and ngt > 0:
-        recall1 = float((iid_out[:ngt, 0].long() == gt_arg).double().mean().item())
+    res_iid = res_dist = recall1 = None
+    roofline = whole = None
+    if args.full:
+        # recall@1 and results of batch 0 (for the parity gate)
+        step(Qb[0])
+        barrier()
+        gather_native()
+        res_iid = iid_out.cpu().numpy().copy()
+        res_dist = dist_out.cpu().numpy().copy()
+        if rank == 0 and ngt > 0:
+            recall1 = float((iid_out[:ngt, 0].long() == gt_arg).double().mean().item())
 
-    launches = max(1, st.scan_launches)
-    scan_ms = st.scan_ms / launches
-    alg_bytes = float(m) * st.scan_codes / launches
-    achieved = alg_bytes / (scan_ms * 1e-3) / 1e9 if scan_ms > 0 else 0.0
-    # physical HBM bytes per launch: PMC FETCH_SIZE (x2 on gfx950) from the committed profile of this exact workload --
-    # PMC collection cannot run inside the timed region, so the figure is read from profiles/, not measured in this run
-    traffic = None
-    traffic_passa = None
-    traffic_source = None
-    # which kernel family served pass A of the timed steps (mmidx_get_dispatch; K3q since round 6 from 1.25 queries per non-empty list)
-    passa_kernel = "?"
-    try:
-        buf = C.create_string_buffer(512)
-        chk(L.mmidx_get_dispatch(h, buf, 512))
-        passa_kernel = dict(kv.split("=", 1) for kv in buf.value.decode().split(";")).get("pass_a", "?")
-    except Exception:  # noqa: BLE001
-        pass
-    try:
-        tj = json.load(open(os.path.join(ROOT, "profiles", "hbm_traffic.json")))
-        wl = tj["workload"]
-        if world == 1 and (wl["n"], wl["dim"], wl["cells"], wl["nprobe"], wl["m"], wl["k"]) == (N, D, Cc, w, m, k) and args.sigma == 0.15:
-            pa = tj.get("pass_a", {}).get(passa_kernel)  # {fetch_kib_per_step, write_kib_per_step, kernel, source}
-            if pa is not None:
-                traffic_passa = (pa["fetch_kib_per_step"] * 2.0 + pa.get("write_kib_per_step", 0.0)) * 1024.0 * B / wl["batch"]
-                traffic = traffic_passa
-                traffic_source = ("profiles/hbm_traffic.json: rocprofv3 --pmc FETCH_SIZE x 2 (gfx950 correction) + WRITE_SIZE of %s on this workload, "
-                                  "separate pass (%s) -- not measured in this run" % (pa.get("kernel", passa_kernel), pa.get("source", "profiles/")))
-    except Exception:
+        launches = max(1, st.scan_launches)
+        scan_ms = st.scan_ms / launches
+        alg_bytes = float(m) * st.scan_codes / launches
+        achieved = alg_bytes / (scan_ms * 1e-3) / 1e9 if scan_ms > 0 else 0.0
+        # physical HBM bytes per launch: PMC FETCH_SIZE (x2 on gfx950) from the committed profile of this exact workload --
+        # PMC collection cannot run inside the timed region, so the figure is read from profiles/, not measured in this run
         traffic = None
-    # The dominant kernel of the headline step is pass A (k_scan_hist: every query's nearest list, read and summed exactly:
-    # ~65 % of the step).  Its algorithmic bytes are m x the codes of those lists -- no pruning is involved, so this is a plain
-    # HBM roofline fraction: the kernel is bound by the LDS gather and the VALU work around it, not by HBM.
-    pa_ms = st_light.passa_ms / max(1, st_light.passa_launches)  # (timed region)
-    pa_bytes = float(m) * st.passa_codes / max(1, st.passa_launches)  # (per launch; the detail run covers the same batches)
-    if native:
-        pa_bytes /= ndev  # (stats of a sharded handle: times = the slowest shard, code counts = the sum over shards -> per device)
-    pa_ach = pa_bytes / (pa_ms * 1e-3) / 1e9 if pa_ms > 0 else 0.0
-    # the LDS roofline of the same kernel: its gather alone (mmidx_probe_lds_gather: m random ds_read_b64 per code over 2 KiB
-    # rows + the fp64 adds, three codes in flight per lane, four 256-thread blocks per CU as K3h runs) measured in this run
-    lds_roof = None
-    if isinstance(probes, dict) and f"lds_gather_m{m}_chains3" in probes:
-        pk = probes[f"lds_gather_m{m}_chains3"]["algorithmic_GBps"]
-        lds_roof = {"bound": "lds", "achieved": round(pa_ach, 1), "peak": pk, "unit": "GB/s of codes (m random 8-byte table reads per code)",
-                    "frac": round(pa_ach / pk, 4) if pk > 0 else None,
-                    "peak_source": "mmidx_probe_lds_gather(m, 3 chains): the scan loop with only the gather and the adds left, measured in this run",
-                    "wave_gathers_per_s_peak": probes[f"lds_gather_m{m}_chains3"]["wave_gathers_per_s"]}
-    if sharded is None and st.passa_launches > 0:
-        kdesc = {"K3q": "k_scan_q (K3q, pass A: every query's nearest list, four queries of a list per block -- packed u16 tables, integer "
-                        "top-6 per lane, exact fp64 sums for ~K1 + 10 candidates per query; the launch carries its pair sort and its empty hand-back launch)",
-                 "K3h": "k_scan_hist (K3h, pass A: the exact scan of every query's nearest list, a block per query; the launch also carries its empty "
-                        "hand-back launch)",
-                 "K3ma": "k_scan_mfma<.., 1/2> + k_a1_* (K3ma, pass A on the matrix cores)"}.get(passa_kernel, passa_kernel)
-        knote = {"K3q": "algorithmic bytes = m x the codes of EVERY query's nearest list (SURVEY 8d); K3q reads a list from HBM once per block of up to "
-                        "four queries, so the physical traffic (`traffic`) is below the algorithmic figure; the scan is bound by the LDS gather of the packed "
-                        "table (one random 8-byte read per code and sub-quantizer for four queries) and the VALU work of the sorted insertions, DESIGN.md 5.2",
-                 "K3h": "limited by the LDS gather (16 fp64 table entries per code, ~60 % of its LDS cycles are bank conflicts) and the VALU work around it "
-                        "(both pipes ~75 % busy, profiles/), not by HBM"}.get(passa_kernel, "")
-        roofline = {"bound": "hbm", "kernel": kdesc, "pass_a_kernel": passa_kernel,
-                    "achieved": round(pa_ach, 1), "peak": 8000.0, "unit": "GB/s", "frac": round(pa_ach / 8000.0, 4),
-                    "frac_of_measured_copy_ceiling": round(pa_ach / 6290.0, 4), "traffic": traffic_passa, "traffic_source": traffic_source,
-                    "algorithmic_bytes_per_launch": pa_bytes, "avg_launch_ms": round(pa_ms, 4), "launches": int(st_light.passa_launches),
-                    "lds": lds_roof if passa_kernel == "K3h" else None,
-                    "note": knote}
-    else:
-        roofline = None
-    # the whole search in algorithmic bytes (every probed list counted, although the coarse bound and the lower-bound filter
-    # keep almost all of them from being read): how far exact pruning takes the path beyond what HBM could stream
-    step_bytes = float(m) * st.scan_codes / max(1, detail_steps)  # (per step: every launch of a step)
-    whole = {"bound": "hbm", "kernel": "all scan launches of a step: k_scan_hist (pass A) + k_scan_grp / k_scan_filt (pass B)",
-             "achieved": round(achieved, 1), "peak": 8000.0, "unit": "GB/s", "frac": round(achieved / 8000.0, 4), "traffic": traffic,
-             "traffic_source": traffic_source,
-             "note": "achieved = algorithmic bytes (m x probed codes) / scan-kernel time; exact pruning (coarse bound, "
-                     "Smin >= T) and L2 reuse make it exceed the physical HBM rate: see traffic and DESIGN.md section 7",
-             "algorithmic_bytes_per_launch": alg_bytes, "avg_launch_ms": round(scan_ms, 4),
-             "algorithmic_bytes_per_step": step_bytes, "bytes_per_query": step_bytes / B, "scan_launches": int(st.scan_launches),
-             "coarse_ms_per_step": round(st.coarse_ms / max(1, detail_steps), 4),
-             "merge_ms_per_step": round(st.merge_ms / max(1, detail_steps), 4),
-             "passb_pairs_per_query": round(int(st.passb_items_last) / B, 3),
-             "measured": f"{detail_steps} steps with full profiling after the timed region"}
-    if roofline is None:
-        roofline = whole
+        traffic_passa = None
+        traffic_source = None
+        # which kernel family served pass A of the timed steps (mmidx_get_dispatch; K3q since round 6 from 1.25 queries per non-empty list)
+        passa_kernel = "?"
+        try:
+            buf = C.create_string_buffer(512)
+            chk(L.mmidx_get_dispatch(h, buf, 512))
+            passa_kernel = dict(kv.split("=", 1) for kv in buf.value.decode().split(";")).get("pass_a", "?")
+        except Exception:  # noqa: BLE001
+            pass
+        try:
+            tj = json.load(open(os.path.join(ROOT, "profiles", "hbm_traffic.json")))
+            wl = tj["workload"]
+            if world == 1 and (wl["n"], wl["dim"], wl["cells"], wl["nprobe"], wl["m"], wl["k"]) == (N, D, Cc, w, m, k) and args.sigma == 0.15:
+                pa = tj.get("pass_a", {}).get(passa_kernel)  # {fetch_kib_per_step, write_kib_per_step, kernel, source}
+                if pa is not None:
+                    traffic_passa = (pa["fetch_kib_per_step"] * 2.0 + pa.get("write_kib_per_step", 0.0)) * 1024.0 * B / wl["batch"]
+                    traffic = traffic_passa
+                    traffic_source = ("profiles/hbm_traffic.json: rocprofv3 --pmc FETCH_SIZE x 2 (gfx950 correction) + WRITE_SIZE of %s on this workload, "
+                                      "separate pass (%s) -- not measured in this run" % (pa.get("kernel", passa_kernel), pa.get("source", "profiles/")))
+        except Exception:
+            traffic = None
+        # The dominant kernel of the headline step is pass A (k_scan_hist: every query's nearest list, read and summed exactly:
+        # ~65 % of the step).  Its algorithmic bytes are m x the codes of those lists -- no pruning is involved, so this is a plain
+        # HBM roofline fraction: the kernel is bound by the LDS gather and the VALU work around it, not by HBM.
+        pa_ms = st_light.passa_ms / max(1, st_light.passa_launches)  # (timed region)
+        pa_bytes = float(m) * st.passa_codes / max(1, st.passa_launches)  # (per launch; the detail run covers the same batches)
+        if native:
+            pa_bytes /= ndev  # (stats of a sharded handle: times = the slowest shard, code counts = the sum over shards -> per device)
+        pa_ach = pa_bytes / (pa_ms * 1e-3) / 1e9 if pa_ms > 0 else 0.0
+        # the LDS roofline of the same kernel: its gather alone (mmidx_probe_lds_gather: m random ds_read_b64 per code over 2 KiB
+        # rows + the fp64 adds, three codes in flight per lane, four 256-thread blocks per CU as K3h runs) measured in this run
+        lds_roof = None
+        if isinstance(probes, dict) and f"lds_gather_m{m}_chains3" in probes:
+            pk = probes[f"lds_gather_m{m}_chains3"]["algorithmic_GBps"]
+            lds_roof = {"bound": "lds", "achieved": round(pa_ach, 1), "peak": pk, "unit": "GB/s of codes (m random 8-byte table reads per code)",
+                        "frac": round(pa_ach / pk, 4) if pk > 0 else None,
+                        "peak_source": "mmidx_probe_lds_gather(m, 3 chains): the scan loop with only the gather and the adds left, measured in this run",
+                        "wave_gathers_per_s_peak": probes[f"lds_gather_m{m}_chains3"]["wave_gathers_per_s"]}
+        if sharded is None and st.passa_launches > 0:
+            kdesc = {"K3q": "k_scan_q (K3q, pass A: every query's nearest list, four queries of a list per block -- packed u16 tables, integer "
+                            "top-6 per lane, exact fp64 sums for ~K1 + 10 candidates per query; the launch carries its pair sort and its empty hand-back launch)",
+                     "K3h": "k_scan_hist (K3h, pass A: the exact scan of every query's nearest list, a block per query; the launch also carries its empty "
+                            "hand-back launch)",
+                     "K3ma": "k_scan_mfma<.., 1/2> + k_a1_* (K3ma, pass A on the matrix cores)"}.get(passa_kernel, passa_kernel)
+            knote = {"K3q": "algorithmic bytes = m x the codes of EVERY query's nearest list (SURVEY 8d); K3q reads a list from HBM once per block of up to "
+                            "four queries, so the physical traffic (`traffic`) is below the algorithmic figure; the scan is bound by the LDS gather of the packed "
+                            "table (one random 8-byte read per code and sub-quantizer for four queries) and the VALU work of the sorted insertions, DESIGN.md 5.2",
+                     "K3h": "limited by the LDS gather (16 fp64 table entries per code, ~60 % of its LDS cycles are bank conflicts) and the VALU work around it "
+                            "(both pipes ~75 % busy, profiles/), not by HBM"}.get(passa_kernel, "")
+            roofline = {"bound": "hbm", "kernel": kdesc, "pass_a_kernel": passa_kernel,
+                        "achieved": round(pa_ach, 1), "peak": 8000.0, "unit": "GB/s", "frac": round(pa_ach / 8000.0, 4),
+                        "frac_of_measured_copy_ceiling": round(pa_ach / 6290.0, 4), "traffic": traffic_passa, "traffic_source": traffic_source,
+                        "algorithmic_bytes_per_launch": pa_bytes, "avg_launch_ms": round(pa_ms, 4), "launches": int(st_light.passa_launches),
+                        "lds": lds_roof if passa_kernel == "K3h" else None,
+                        "note": knote}
+        else:
+            roofline = None
+        # the whole search in algorithmic bytes (every probed list counted, although the coarse bound and the lower-bound filter
+        # keep almost all of them from being read): how far exact pruning takes the path beyond what HBM could stream
+        step_bytes = float(m) * st.scan_codes / max(1, detail_steps)  # (per step: every launch of a step)
+        whole = {"bound": "hbm", "kernel": "all scan launches of a step: k_scan_hist (pass A) + k_scan_grp / k_scan_filt (pass B)",
+                 "achieved": round(achieved, 1), "peak": 8000.0, "unit": "GB/s", "frac": round(achieved / 8000.0, 4), "traffic": traffic,
+                 "traffic_source": traffic_source,
+                 "note": "achieved = algorithmic bytes (m x probed codes) / scan-kernel time; exact pruning (coarse bound, "
+                         "Smin >= T) and L2 reuse make it exceed the physical HBM rate: see traffic and DESIGN.md section 7",
+                 "algorithmic_bytes_per_launch": alg_bytes, "avg_launch_ms": round(scan_ms, 4),
+                 "algorithmic_bytes_per_step": step_bytes, "bytes_per_query": step_bytes / B, "scan_launches": int(st.scan_launches),
+                 "coarse_ms_per_step": round(st.coarse_ms / max(1, detail_steps), 4),
+                 "merge_ms_per_step": round(st.merge_ms / max(1, detail_steps), 4),
+                 "passb_pairs_per_query": round(int(st.passb_items_last) / B, 3),
+                 "measured": f"{detail_steps} steps with full profiling after the timed region"}
+        if roofline is None:
+            roofline = whole
 
     # ---------------------------------------------------------------- the same index at a batch of 131072 (K3ma)
     def big_batch(ref):
@@ -957,7 +1000,7 @@ def run(cx, args, json_out, native, ndev, dist, rank, world, local, fallback_rea
     # ---------------------------------------------------------------- CPU baseline + parity gate (headline index)
     cpu_baseline, parity, ties = None, None, None
     cores, logical, quota, cpu_model = usable_cpus()
-    if rank == 0 and (world == 1 or native) and not args.no_cpu:
+    if args.full and rank == 0 and (world == 1 or native) and not args.no_cpu:
         t0 = time.time()
         ref = oracle_of_index(cx, h, coarse_h, pq_h)
         Qh = Qb[0].cpu().numpy()
@@ -1006,7 +1049,7 @@ def run(cx, args, json_out, native, ndev, dist, rank, world, local, fallback_rea
         del ref
         log(f"cpu baseline + parity in {time.time() - t0:.1f}s: {cpu_baseline['value']} q/s on {cores} cores; parity {parity}")
 
-    if big is None and big_B > 0 and rank == 0:
+    if args.full and big is None and big_B > 0 and rank == 0:
         try:
             big = big_batch(None)
         except Exception as e:  # noqa: BLE001
@@ -1015,7 +1058,7 @@ def run(cx, args, json_out, native, ndev, dist, rank, world, local, fallback_rea
     # whole inverted lists go to shard `cell mod n`: a round's work per shard = the (query, probed list) pairs whose list lives there.
     # Counted from this index's own coarse stage -- a measurement of the partition, not of a multi-GPU run.
     balance = None
-    if rank == 0 and single and h is not None:
+    if args.full and rank == 0 and single and h is not None:
         try:
             balance = {}
             for nqb in sorted({B, big_B} - {0}):
@@ -1037,7 +1080,7 @@ def run(cx, args, json_out, native, ndev, dist, rank, world, local, fallback_rea
             balance = {"error": repr(e)}
     # ---------------------------------------------------------------- restart through the native snapshot (ABI 8: mmidx_save / mmidx_load)
     snapshot = None
-    if rank == 0 and single and args.extras and h is not None:
+    if args.full and rank == 0 and single and args.extras and h is not None:
         import tempfile
 
         snap_path = os.path.join(tempfile.gettempdir(), f"mmidx_bench_{os.getpid()}.snap")
@@ -1079,7 +1122,7 @@ def run(cx, args, json_out, native, ndev, dist, rank, world, local, fallback_rea
             torch.cuda.empty_cache()
     # ---------------------------------------------------------------- the boundary's own path: host buffers, caller threads
     host = None
-    if rank == 0 and single and args.extras:
+    if args.full and rank == 0 and single and args.extras:
         try:
             t0 = time.time()
             host = importlib.import_module("bench_extras").host_path(L, nat, h, np.ascontiguousarray(Qb[0].cpu().numpy()), k)
@@ -1185,18 +1228,18 @@ def run(cx, args, json_out, native, ndev, dist, rank, world, local, fallback_rea
         return res
 
     hard, spread = None, None
-    if rank == 0 and single and (args.hard_steps > 0 or args.spread_steps > 0):
+    if args.full and rank == 0 and single and (args.hard_steps > 0 or args.spread_steps > 0):
         chk(L.mmidx_destroy(h))
         h = None
         del Q, Qb
         torch.cuda.empty_cache()
-    if rank == 0 and single and args.hard_steps > 0:
+    if args.full and rank == 0 and single and args.hard_steps > 0:
         hs = args.hard_sigma
         hard = side_workload(hs, False, args.hard_steps, args.hard_parity, "hard")
         hard["data"] = (f"same generator and means, mixture noise sigma = {hs} (headline: {args.sigma}): cluster radius "
                         f"{hs * D ** 0.5:.1f} against an inter-mean distance of {(2 * D) ** 0.5:.1f}; IVFPQ.java:414-447 scans all w probes, and here "
                         f"so does the engine")
-    if rank == 0 and single and args.spread_steps > 0:
+    if args.full and rank == 0 and single and args.spread_steps > 0:
         # no cluster structure at all and queries that are nobody's copy: the top-k of a query is spread over several of its
         # probed cells, far probes FEED the queue (IVFPQ.java:429-446 offers every probed code) and recall@1 is what 16-byte
         # codes give on such data -- reported, not required ("iid-Gaussian independent queries would not reach 0.9")
@@ -1206,7 +1249,7 @@ def run(cx, args, json_out, native, ndev, dist, rank, world, local, fallback_rea
 
     # ---------------------------------------------------------------- BASELINE configs 1-3 at their stated sizes
     other = None
-    if rank == 0 and single and args.other_configs and not args.no_cpu:
+    if args.full and rank == 0 and single and args.other_configs and not args.no_cpu:
         try:
             t0 = time.time()
             bc = importlib.import_module("bench_configs")
@@ -1217,7 +1260,7 @@ def run(cx, args, json_out, native, ndev, dist, rank, world, local, fallback_rea
 
     # ---------------------------------------------------------------- cfg5 front end, the reference's flagship shape
     cfg5, yfcc = None, None
-    if rank == 0 and single and args.extras:
+    if args.full and rank == 0 and single and args.extras:
         if h is not None:
             chk(L.mmidx_destroy(h))
             h = None
@@ -1241,7 +1284,7 @@ def run(cx, args, json_out, native, ndev, dist, rank, world, local, fallback_rea
 
     # ---------------------------------------------------------------- the 8-GPU configuration's code path on this one device
     dry = None
-    if rank == 0 and single and args.dry_run_shards > 1 and os.environ.get("MMIDX_BENCH_VIRTUAL_SHARDS") != "1":
+    if args.full and rank == 0 and single and args.dry_run_shards > 1 and os.environ.get("MMIDX_BENCH_VIRTUAL_SHARDS") != "1":
         # `bench.py --gpus 8` exactly as the driver runs it, but with eight IN-PROCESS shards on device 0 (no xGMI, no RCCL: in-process
         # collectives): what each rank of the 8-GPU run computes per round, and a parity-gated exercise of the sharded handle.  It is
         # NOT a scaling measurement -- nothing here has run on more than one physical GPU.
@@ -1256,7 +1299,7 @@ def run(cx, args, json_out, native, ndev, dist, rank, world, local, fallback_rea
             cmd = [sys.executable, os.path.abspath(__file__), "--gpus", str(ns), "--steps", "6", "--warmup", "2", "--settle", "3", "--hard-steps", "0",
                    "--spread-steps", "0", "--other-configs", "0", "--extras", "0", "--yfcc-n", "0", "--cfg5-images", "0", "--exhaustive-steps", "0",
                    "--cpu-seconds", "2", "--dry-run-shards", "0", "--big-batch", "0", "--vectors", str(N), "--batch", str(args.batch),
-                   "--extra-out", args.extra_out + ".dry_run"]
+                   "--extra-out", args.extra_out + ".dry_run", "--full"]
             pr = subprocess.run(cmd, env=dict(os.environ, MMIDX_BENCH_VIRTUAL_SHARDS="1"), capture_output=True, text=True, timeout=420)
             jl = [l for l in pr.stdout.splitlines() if l.startswith("{")]
             if pr.returncode == 0 and jl:

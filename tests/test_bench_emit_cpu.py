@@ -76,3 +76,30 @@ def test_bench_py_writes_nothing_after_the_emitter():
     tail = body[body.index('importlib.import_module("bench_emit").emit('):]
     assert "print(" not in tail and "log(" not in tail
     assert src.count("json.dumps(out)") == 0  # (the only writer of the line is the emitter)
+
+
+def test_dump_outputs_float64_and_capped(tmp_path):
+    """--dump-outputs: one float64 .npy per answer array, ids exact; above the cap a fixed (seeded) sample of rows, listed in rows.npy"""
+    import numpy as np
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    rng = np.random.default_rng(1)
+    n, k = 1000, 100
+    ids = rng.integers(-1, 100_000_000, size=(n, k)).astype(np.int32)
+    dist = rng.random((n, k))
+    cnt = np.full(n, k, np.int32)
+    small = tmp_path / "small"
+    bench.dump_outputs(str(small), {"ids": ids, "distances": dist, "counts": cnt})
+    assert sorted(os.listdir(small)) == ["counts.npy", "distances.npy", "ids.npy"]
+    got = np.load(small / "ids.npy")
+    assert got.dtype == np.float64 and np.array_equal(got.astype(np.int32), ids)
+    assert np.array_equal(np.load(small / "distances.npy"), dist)
+    limit = 400_000
+    for d in ("cap_a", "cap_b"):
+        bench.dump_outputs(str(tmp_path / d), {"ids": ids, "distances": dist, "counts": cnt}, limit=limit)
+        assert sum(os.path.getsize(tmp_path / d / f) for f in os.listdir(tmp_path / d)) <= limit
+    rows = np.load(tmp_path / "cap_a" / "rows.npy").astype(np.int64)
+    assert np.array_equal(rows, np.load(tmp_path / "cap_b" / "rows.npy")) and np.all(np.diff(rows) > 0)
+    assert np.array_equal(np.load(tmp_path / "cap_a" / "distances.npy"), dist[rows])

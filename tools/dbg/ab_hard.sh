@@ -5,7 +5,7 @@ out=gpurun_out/$1; shift
 mkdir -p $out
 for v in "$@"; do
   if [ "$v" = base ]; then unset MMIDX_LIB; else export MMIDX_LIB=$PWD/multimedia-indexing_amd/csrc/ab/libmmidx_$v.so; fi
-  timeout 400 python bench.py --steps 5 --warmup 2 --no-cpu --gt 0 --exhaustive-steps 0 --other-configs 0 --hard-steps 6 $ABARGS > $out/$v.json 2> $out/$v.log
+  timeout 400 python bench.py --full --steps 5 --warmup 2 --no-cpu --gt 0 --exhaustive-steps 0 --other-configs 0 --hard-steps 6 $ABARGS > $out/$v.json 2> $out/$v.log
   python - <<PY
 import json
 try:

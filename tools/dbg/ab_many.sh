@@ -1,6 +1,6 @@
 #!/bin/bash
 # same-box A/B of several builds on the headline: tools/dbg/ab_many.sh <lib|default> ... (each twice, interleaved)
-F="--extras 0 --other-configs 0 --exhaustive-steps 0 --steps 8 --spread-steps 0 --hard-steps 0 --no-cpu --gt 0"
+F="--full --extras 0 --other-configs 0 --exhaustive-steps 0 --steps 8 --spread-steps 0 --hard-steps 0 --no-cpu --gt 0"
 for rep in 1 2; do
 for L in "$@"; do
   if [ "$L" = default ]; then unset MMIDX_LIB; else export MMIDX_LIB=$PWD/multimedia-indexing_amd/csrc/ab/$L; fi

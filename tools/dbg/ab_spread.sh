@@ -4,7 +4,7 @@ out=gpurun_out/$1; shift
 mkdir -p $out
 for v in "$@"; do
   if [ "$v" = base ]; then unset MMIDX_LIB; else export MMIDX_LIB=$PWD/multimedia-indexing_amd/csrc/ab/libmmidx_$v.so; fi
-  timeout 600 python bench.py --steps 3 --warmup 1 --no-cpu --gt 0 --exhaustive-steps 0 --other-configs 1 --extras 0 --spread-steps 6 --hard-steps 0 > $out/$v.json 2> $out/$v.log
+  timeout 600 python bench.py --full --steps 3 --warmup 1 --no-cpu --gt 0 --exhaustive-steps 0 --other-configs 1 --extras 0 --spread-steps 6 --hard-steps 0 > $out/$v.json 2> $out/$v.log
   python - <<PY
 import json
 try:

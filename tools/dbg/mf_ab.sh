@@ -5,7 +5,7 @@ out=gpurun_out/$1; shift
 mkdir -p $out
 for v in "$@"; do
   if [ "$v" = base ]; then unset MMIDX_LIB; else export MMIDX_LIB=$PWD/tools/dbg/lib_$v.so; fi
-  timeout 400 python bench.py --sigma 1.0 --steps 8 --warmup 2 --no-cpu --gt 0 --exhaustive-steps 0 --other-configs 0 --extras 0 --hard-steps 0 --spread-steps ${SPREAD_STEPS:-0} $ABARGS > $out/$v.json 2> $out/$v.log
+  timeout 400 python bench.py --full --sigma 1.0 --steps 8 --warmup 2 --no-cpu --gt 0 --exhaustive-steps 0 --other-configs 0 --extras 0 --hard-steps 0 --spread-steps ${SPREAD_STEPS:-0} $ABARGS > $out/$v.json 2> $out/$v.log
   python - <<PY
 import json
 try:

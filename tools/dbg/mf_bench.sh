@@ -4,7 +4,7 @@ out=gpurun_out/$1; shift
 mkdir -p $out
 timeout 600 python -m pytest tests/test_gpu_parity.py -x -q -m gpu -k "mfma or union or smin or golden" 2>&1 | tail -5 > $out/tests.log
 tail -3 $out/tests.log
-timeout 900 python bench.py --no-cpu --gt 0 --exhaustive-steps 0 --other-configs 1 --extras 0 --spread-steps 6 --hard-steps 10 "$@" > $out/bench.json 2> $out/bench.err
+timeout 900 python bench.py --full --no-cpu --gt 0 --exhaustive-steps 0 --other-configs 1 --extras 0 --spread-steps 6 --hard-steps 10 "$@" > $out/bench.json 2> $out/bench.err
 python - <<PY
 import json
 try:

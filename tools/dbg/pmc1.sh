@@ -8,7 +8,7 @@ PMCS=("SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_WAVES SQ_INSTS
 i=0; rm -rf /tmp/pmc1_${NAME}_*
 for P in "${PMCS[@]}"; do
   i=$((i+1)); d=/tmp/pmc1_${NAME}_$i; mkdir -p $d
-  timeout 600 rocprofv3 --pmc $P --kernel-include-regex "$KRE" --output-format csv -d $d -o pmc -- python bench.py "$@" > $d/run.log 2>&1
+  timeout 600 rocprofv3 --pmc $P --kernel-include-regex "$KRE" --output-format csv -d $d -o pmc -- python bench.py --full "$@" > $d/run.log 2>&1
 done
 mkdir -p gpurun_out/dbg
 python tools/pmc_summary.py "/tmp/pmc1_${NAME}_*" "$KRE" > gpurun_out/dbg/pmc_$NAME.txt 2>&1

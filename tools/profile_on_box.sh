@@ -8,7 +8,7 @@ KRE=${2:-k_scan|k_coarse|k_merge}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/$TAG
 mkdir -p "$OUT" /tmp/prof_$TAG
-timeout 900 rocprofv3 --kernel-trace --stats -d /tmp/prof_$TAG/kt -o kt -- python bench.py --steps 10 --warmup 2 > "$OUT/bench_kernel_trace.log" 2>&1
+timeout 900 rocprofv3 --kernel-trace --stats -d /tmp/prof_$TAG/kt -o kt -- python bench.py --full --steps 10 --warmup 2 > "$OUT/bench_kernel_trace.log" 2>&1
 python tools/rocprof_summary.py /tmp/prof_$TAG/kt/kt_results.db 40 > "$OUT/kernel_stats.txt" 2>&1
 grep '"metric"' "$OUT/bench_kernel_trace.log" > "$OUT/bench.json"
 i=0
@@ -18,7 +18,7 @@ for P in "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_
   i=$((i+1))
   d=/tmp/prof_$TAG/pmc_$i
   mkdir -p $d
-  timeout 700 rocprofv3 --pmc $P --kernel-include-regex "$KRE" --output-format csv -d $d -o pmc -- python bench.py --steps 3 --warmup 1 --no-cpu --gt 0 > $d/bench.log 2>&1
+  timeout 700 rocprofv3 --pmc $P --kernel-include-regex "$KRE" --output-format csv -d $d -o pmc -- python bench.py --full --steps 3 --warmup 1 --no-cpu --gt 0 > $d/bench.log 2>&1
 done
 python tools/pmc_summary.py "/tmp/prof_$TAG/pmc_*" "$KRE" > "$OUT/pmc_kernels.txt" 2>&1
 ls -la "$OUT"

@@ -9,7 +9,7 @@ OUT=gpurun_out/$TAG
 mkdir -p "$OUT" /tmp/prof_$TAG
 LIGHT="--extras 0 --spread-steps 0 --other-configs 0 --exhaustive-steps 0"
 # 1. kernel trace: headline + hard
-timeout 900 rocprofv3 --kernel-trace --stats -d /tmp/prof_$TAG/kt -o kt -- python bench.py --steps 10 --warmup 2 $LIGHT > "$OUT/bench_kernel_trace.log" 2>&1
+timeout 900 rocprofv3 --kernel-trace --stats -d /tmp/prof_$TAG/kt -o kt -- python bench.py --full --steps 10 --warmup 2 $LIGHT > "$OUT/bench_kernel_trace.log" 2>&1
 python tools/rocprof_summary.py /tmp/prof_$TAG/kt/kt_results.db 45 > "$OUT/kernel_stats.txt" 2>&1
 grep '"metric"' "$OUT/bench_kernel_trace.log" > "$OUT/bench.json"
 # 2. kernel trace: the reference's flagship shape
@@ -26,7 +26,7 @@ for W in headline hard; do
     i=$((i+1))
     d=/tmp/prof_$TAG/pmc_${W}_$i
     mkdir -p $d
-    timeout 700 rocprofv3 --pmc $P --kernel-include-regex "$KRE" --output-format csv -d $d -o pmc -- python bench.py --steps 3 --warmup 1 --no-cpu --gt 0 --hard-steps 0 --sigma $SIG $LIGHT > $d/bench.log 2>&1
+    timeout 700 rocprofv3 --pmc $P --kernel-include-regex "$KRE" --output-format csv -d $d -o pmc -- python bench.py --full --steps 3 --warmup 1 --no-cpu --gt 0 --hard-steps 0 --sigma $SIG $LIGHT > $d/bench.log 2>&1
   done
   python tools/pmc_summary.py "/tmp/prof_$TAG/pmc_${W}_*" "$KRE" > "$OUT/${W}_pmc_kernels.txt" 2>&1
 done

@@ -8,7 +8,7 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/$TAG
 mkdir -p "$OUT" /tmp/prof_$TAG
 LIGHT="--extras 0 --spread-steps 0 --other-configs 0 --exhaustive-steps 0"
-timeout 900 rocprofv3 --kernel-trace --stats -d /tmp/prof_$TAG/kt -o kt -- python bench.py --steps 10 --warmup 2 $LIGHT > "$OUT/bench_kernel_trace.log" 2>&1
+timeout 900 rocprofv3 --kernel-trace --stats -d /tmp/prof_$TAG/kt -o kt -- python bench.py --full --steps 10 --warmup 2 $LIGHT > "$OUT/bench_kernel_trace.log" 2>&1
 python tools/rocprof_summary.py /tmp/prof_$TAG/kt/kt_results.db 45 > "$OUT/kernel_stats.txt" 2>&1
 grep '"metric"' "$OUT/bench_kernel_trace.log" > "$OUT/bench.json"
 timeout 900 rocprofv3 --kernel-trace --stats -d /tmp/prof_$TAG/ky -o ky -- python tests/bench_yfcc.py --parity 0 > "$OUT/yfcc.json" 2> "$OUT/yfcc_trace.log"

@@ -7,7 +7,7 @@ TAG=${1:-r04}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/$TAG
 mkdir -p "$OUT" /tmp/prof_$TAG
-timeout 900 rocprofv3 --kernel-trace --stats -d /tmp/prof_$TAG/kt -o kt -- python bench.py --steps 10 --warmup 2 --extras 0 --exhaustive-steps 0 > "$OUT/bench_kernel_trace.log" 2>&1
+timeout 900 rocprofv3 --kernel-trace --stats -d /tmp/prof_$TAG/kt -o kt -- python bench.py --full --steps 10 --warmup 2 --extras 0 --exhaustive-steps 0 > "$OUT/bench_kernel_trace.log" 2>&1
 python tools/rocprof_summary.py /tmp/prof_$TAG/kt/kt_results.db 45 > "$OUT/kernel_stats.txt" 2>&1
 python tools/kernel_calls.py /tmp/prof_$TAG/kt/kt_results.db 'k_scan_mfma|k_mfma_verify|k_mfma_redo|k_scan_hist|k_group_build|k_scan_filt|k_merge|k_pair|k_coarse|k_split' > "$OUT/kernel_calls.txt" 2>&1
 python tools/timeline_steps.py /tmp/prof_$TAG/kt/kt_results.db k_scan_hist 12 3 > "$OUT/timeline.txt" 2>&1
@@ -22,7 +22,7 @@ for W in hard spread; do
     i=$((i+1))
     d=/tmp/prof_$TAG/pmc_${W}_$i
     mkdir -p $d
-    timeout 700 rocprofv3 --pmc $P --kernel-include-regex "$KRE" --output-format csv -d $d -o pmc -- python bench.py --steps 3 --warmup 1 --no-cpu --gt 0 --extras 0 --other-configs 0 --exhaustive-steps 0 $ARGS > $d/bench.log 2>&1
+    timeout 700 rocprofv3 --pmc $P --kernel-include-regex "$KRE" --output-format csv -d $d -o pmc -- python bench.py --full --steps 3 --warmup 1 --no-cpu --gt 0 --extras 0 --other-configs 0 --exhaustive-steps 0 $ARGS > $d/bench.log 2>&1
   done
   python tools/pmc_summary.py "/tmp/prof_$TAG/pmc_${W}_*" "$KRE" > "$OUT/${W}_pmc_kernels.txt" 2>&1
 done

@@ -23,9 +23,9 @@ pmc() {  # pmc <name> <kernel regex> <command...>
 }
 SIDE0="--hard-steps 0 --spread-steps 0 --other-configs 0 --extras 0 --yfcc-n 0 --cfg5-images 0 --exhaustive-steps 0 --dry-run-shards 0 --no-cpu --gt 0"
 if [ "$PART" = 1 ]; then
-  timeout 900 python bench.py > "$OUT/bench_untraced.json" 2> "$OUT/bench_untraced.log"
+  timeout 900 python bench.py --full > "$OUT/bench_untraced.json" 2> "$OUT/bench_untraced.log"
   grep "summary:" "$OUT/bench_untraced.log" > "$OUT/bench_summary.txt"
-  timeout 1200 rocprofv3 --kernel-trace --stats -d /tmp/prof_$TAG/kt -o kt -- python bench.py --steps 10 --warmup 2 --extras 0 --exhaustive-steps 0 --dry-run-shards 0 --yfcc-n 0 > "$OUT/bench_kernel_trace.log" 2>&1
+  timeout 1200 rocprofv3 --kernel-trace --stats -d /tmp/prof_$TAG/kt -o kt -- python bench.py --full --steps 10 --warmup 2 --extras 0 --exhaustive-steps 0 --dry-run-shards 0 --yfcc-n 0 > "$OUT/bench_kernel_trace.log" 2>&1
   python tools/rocprof_summary.py /tmp/prof_$TAG/kt/kt_results.db 50 > "$OUT/kernel_stats.txt" 2>&1
   python tools/kernel_calls.py /tmp/prof_$TAG/kt/kt_results.db 'k_scan_mfma|k_mfma_verify|k_mfma_redo|k_scan_hist|k_group_build|k_scan_filt|k_merge|k_pair|k_coarse|k_split|k_a1_' > "$OUT/kernel_calls.txt" 2>&1
   python tools/timeline_steps.py /tmp/prof_$TAG/kt/kt_results.db k_scan_hist 12 2 > "$OUT/timeline.txt" 2>&1

@@ -5,7 +5,7 @@ TAG=${1:-r01x}; shift
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/$TAG
 mkdir -p "$OUT" /tmp/prof_$TAG
-timeout 900 rocprofv3 --kernel-trace --stats -d /tmp/prof_$TAG/kt -o kt -- python bench.py --steps 10 --warmup 2 "$@" > "$OUT/bench_kernel_trace.log" 2>&1
+timeout 900 rocprofv3 --kernel-trace --stats -d /tmp/prof_$TAG/kt -o kt -- python bench.py --full --steps 10 --warmup 2 "$@" > "$OUT/bench_kernel_trace.log" 2>&1
 python tools/rocprof_summary.py /tmp/prof_$TAG/kt/kt_results.db 40 > "$OUT/kernel_stats.txt" 2>&1
 python - > "$OUT/timeline.txt" 2>&1 <<PY
 import sqlite3
