@@ -352,8 +352,9 @@ int mmidx_set_profiling(mmidx_index *h, int enabled);
  * ncclRecv), "tie_slots" (flagged queries per owner and replay round, 0 = no replay), "shard_max_round"; every other option goes
  * to every shard.  Round 5: "no_split_table" (1: an exact table of twice the LDS -- m = 128 byte codes -- stays in global scratch instead
  * of being taken in two sweeps with half of it in LDS, k_scan_split).  Round 4: "no_mfma" (1: pass B through K3g / K3f instead of the matrix-core bound K3m / K3mk), "mfma_sub" (codes per
- * work item of K3m / K3mk, 0 = sized from the call), "mfma_qcap" (survivor records per launch; a small value sends queries through the
- * redo path), "mfma_blocks", "mfma_kc_v1" (1: K3mk without LDS-DMA, k_scan_mfma_kc, also where k_scan_mfma_kc2 applies),
+ * work item of K3m / K3mk, 0 = sized from the call), "mfma_qcap" (survivor records per launch, K3ma's record list included; a small value sends queries through the
+ * redo path), "passa_mfma_icnt_sat" (test switch: the point where K3ma's per-item record prefix saturates, 0 = default 0xFFFFFFFF;
+ * every item that reaches it sends its queries through the redo path), "mfma_blocks", "mfma_kc_v1" (1: K3mk without LDS-DMA, k_scan_mfma_kc, also where k_scan_mfma_kc2 applies),
  * "mfma_kc_tpw" (8 / 16 code tiles per wave of k_scan_mfma_kc), "lut_pre" (pass A's tables built by their own kernel),
  * "coarse_wave_sel" (0: the coarse stage's exact selection always by a block per query instead of k_coarse_front_sel),
  * "passb_small" (0: pass B through K3m / K3g also when the call before kept at most 64 pairs; default 1: K3f's looping kernel alone,

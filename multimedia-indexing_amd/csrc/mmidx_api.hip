@@ -316,6 +316,7 @@ struct mmidx_index {
     int no_split_table = 0;            // option "no_split_table" = 1: a table of twice the LDS (m = 128) stays in global scratch (A/B switch)
     int mfma_sub = 0;                  // option "mfma_sub": codes per K3m item (0 = sized from the call)
     int mfma_qcap = 0;                 // option "mfma_qcap": survivor records per launch (0 = sized from the call; tests force the redo path)
+    int passa_mfma_icnt_sat = 0;       // option "passa_mfma_icnt_sat": where K3ma's record prefix saturates (0 = 0xFFFFFFFF; tests force the overflow path)
     int mfma_blocks = 0;               // option "mfma_blocks": persistent blocks (0 = occupancy x CUs)
     int lut_pre = -1;                  // option "lut_pre": pass A's tables built ahead of K3h by k_lut_pre: 1 always, 0 never, -1 = where it pays (m >= 32)
     DevBuf<double> ws_lutpre;
@@ -1380,6 +1381,7 @@ int launch_passa_mfma(mmidx_index *h, const ScanParams &P, const SearchPlan &pl,
     MP.a_icnt = h->ws_aicnt.p;
     MP.a_rec = h->ws_arec.p;
     MP.a_rec_cap = (u32)rec_cap;
+    MP.a_icnt_sat = h->passa_mfma_icnt_sat > 0 ? (u32)h->passa_mfma_icnt_sat : 0xFFFFFFFFu;
     MP.a_rows = h->transform == MMIDX_TR_ROTATION ? h->ws_R.p : h->ws_arows.p;
     MP.a_meta = h->ws_ameta.p;
     MP.a_metaT = h->ws_ametaT.p;
@@ -3924,6 +3926,8 @@ int mmidx_set_option(mmidx_index *h, const char *name, int value) {
         h->mfma_sub = value > 0 ? value : 0;
     } else if (n == "mfma_qcap") {
         h->mfma_qcap = value > 0 ? value : 0;
+    } else if (n == "passa_mfma_icnt_sat") {  // K3ma's record prefix saturates here (0: at 0xFFFFFFFF); a small value sends its items to the redo
+        h->passa_mfma_icnt_sat = value > 0 ? value : 0;
     } else if (n == "coarse_wave_sel") {
         h->coarse_wave_sel = value != 0;
     } else if (n == "passb_small") {

@@ -76,6 +76,7 @@ struct MfmaParams {
     u32 *a_icnt;               // [items + 1] bits sweep 2 set per item (zeroed by sweep 1), then their exclusive prefix (k_a1_item_scan): [items] = total
     uint2 *a_rec;              // the flat record list {pair slot, position in the index} in item order (k_a1_records), a_rec_cap entries
     u32 a_rec_cap;
+    u32 a_icnt_sat;            // where the prefix of a_icnt saturates (0xFFFFFFFF; option "passa_mfma_icnt_sat" lowers it): an item whose end reaches it overflowed
     double *a_rows;            // [pair slot][D] the pairs' exact residuals c - q (k_a1_rows; rotation: = R)
     int4 *a_meta;              // [pair slot] {query, probe rank, list start (low, high word)}
     u64 *a_metaT;              // [pair slot] the query's threshold as k_a1_select left it

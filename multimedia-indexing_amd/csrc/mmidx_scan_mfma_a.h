@@ -109,11 +109,12 @@ __global__ __launch_bounds__(1024) void k_a1_item_scan(const MfmaParams P) {
         if (lane == 63) s_wave[wv] = incl;
         __syncthreads();
         // (saturating: duplicate-heavy long lists with many queries per list can set more than 2^32 bits in one call; a wrapped prefix
-        //  would let items write overlapping record ranges.  Past the cap every item goes to the redo)
+        //  would let items write overlapping record ranges.  Past the cap every item goes to the redo, ADVICE r5.  The point is
+        //  P.a_icnt_sat: 0xFFFFFFFF, lowered by option "passa_mfma_icnt_sat" in the tests.)
         unsigned long long before = s_carry;
 #pragma unroll
         for (int j = 0; j < 16; j++) before += (j < wv) ? s_wave[j] : 0u;
-        const unsigned long long sat = 0xFFFFFFFFull;
+        const unsigned long long sat = P.a_icnt_sat;
         const unsigned long long mine = before + incl - c;
         if (i < nv) P.a_icnt[i] = (u32)(mine < sat ? mine : sat);
         __syncthreads();
@@ -169,13 +170,15 @@ __global__ __launch_bounds__(A1R_NT) void k_a1_records(const MfmaParams P) {
         const int ntiles = (int)((c1 - c0 + 15) >> 4), npt = (ntiles + 1) >> 1;
         const int ntl = (np + 15) >> 4;
         const unsigned char *bm = P.a_bm + (size_t)v * P.a_bm_stride;
-        const u32 off0 = P.a_icnt[v], cnt = P.a_icnt[v + 1] - off0;
-        if (cnt == 0) continue;  // (block-uniform)
-        if ((unsigned long long)off0 + cnt > (unsigned long long)P.a_rec_cap) {  // the list is full: the item's queries go to the exact kernels
+        const u32 off0 = P.a_icnt[v], end = P.a_icnt[v + 1], cnt = end - off0;
+        // Overflowed: the prefix saturated at or before the item's end (every item past that point reads cnt = 0, the one that straddles
+        // it a count short of its bits), or the range runs past the list's capacity.  Decided BEFORE the empty-item exit below.
+        if (end == P.a_icnt_sat || (unsigned long long)end > (unsigned long long)P.a_rec_cap) {  // the item's queries go to the exact kernels
             for (int r = tid; r < np; r += A1R_NT) P.redo[P.S.order[first + r] / P.S.w] = 1;
-            for (u32 i = off0 + (u32)tid; i < off0 + cnt && i < P.a_rec_cap; i += A1R_NT) P.a_rec[i] = make_uint2(0xFFFFFFFFu, 0u);
+            for (u32 i = off0 + (u32)tid; i < end && i < P.a_rec_cap; i += A1R_NT) P.a_rec[i] = make_uint2(0xFFFFFFFFu, 0u);
             continue;
         }
+        if (cnt == 0) continue;  // (block-uniform)
         const u32 posb = (u32)(beg + c0);  // (an index holds fewer than 2^31 codes)
         if (tid == 0) {  // the rounds this item's records fall into take in its slot range (two atomics per round and item)
             const u32 rsh = (u32)__builtin_ctz((unsigned)P.a_rnd_size);

@@ -237,12 +237,15 @@ __device__ __forceinline__ void q_scan_group(const QParams &QP, const int4 gd, u
     constexpr int G = MMIDX_Q_G, NT = 256, WV = 4, U = MMIDX_Q_U, HKQ = MMIDX_Q_HKQ, NS = MMIDX_Q_SLOTS;
     static_assert(G == WV, "wave i takes query i in the selection");
     static_assert(M * 2048 >= G * MMIDX_Q_HKQ * 8, "the candidates' exact sums re-use the table");
+    // a code's sum a(c) lives in 16 bits, where 0xFFFF marks an empty slot, and the halves of an accumulator must never carry: at most
+    // sixteen entries of <= 4095.  (A wider instantiation would lose neighbours silently: it must not compile.)
+    static_assert(M <= 16 && M * 4095 < 65535, "K3q's 16-bit sums hold at most sixteen saturated entries");
     const ScanParams &P = QP.S;
     const int D = P.D;
     const QLds L(M, D);
     double *s_r = (double *)(smem + L.res);        // [G][D]
     // misc (64 x 8 bytes): words [0..3] a* per query (int; -1: no evidence), [4..7] hand-back flags, [8..11] candidates, [12..15] entries to emit,
-    // [16..19] pool bases, [24..27] a* + 17; doubles [16..19] 4000 / qr; u64 [20..23] largest evidence sum
+    // [16..19] pool bases, [24..27] a* + M + 1; doubles [16..19] 4000 / qr; u64 [20..23] largest evidence sum
     int *s_astar = (int *)(smem + L.misc);
     u32 *s_flag = (u32 *)(smem + L.misc) + 4;
     u32 *s_kept = (u32 *)(smem + L.misc) + 8;
@@ -250,7 +253,7 @@ __device__ __forceinline__ void q_scan_group(const QParams &QP, const int4 gd, u
     u32 *s_base = (u32 *)(smem + L.misc) + 16;
     double *s_inv = (double *)(smem + L.misc) + 16;
     u64 *s_max = (u64 *)(smem + L.misc) + 20;
-    u32 *s_cut = (u32 *)(smem + L.misc) + 24;      // [24..27]: a* + 17 per query
+    u32 *s_cut = (u32 *)(smem + L.misc) + 24;      // [24..27]: a* + M + 1 per query (17 at M = 16)
     u32 *cent = (u32 *)(smem + L.cent);            // [G][HKQ]
 
     const int cell = gd.x, ng = gd.z;
@@ -529,7 +532,7 @@ __device__ __forceinline__ void q_scan_group(const QParams &QP, const int4 gd, u
             }
             if (lo_a >= 4095u) bad = true;  // the evidence would include saturated codes: the scale was too small
             astar = (int)lo_a;
-            cut = lo_a + 17u;
+            cut = lo_a + (u32)(M + 1);  // (floor() loses < 1 per entry: a code with a >= a* + M + 2 is strictly farther, header comment)
         }
         if (lane == 0) {
             s_astar[i] = astar;

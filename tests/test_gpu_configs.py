@@ -15,6 +15,7 @@ import ctypes as C
 import importlib
 import os
 import sys
+import time
 
 import numpy as np
 import pytest
@@ -51,7 +52,9 @@ def test_cfg3_ivfpq_1m(small_configs):
 
 @pytest.mark.parametrize("sigma", [0.15, 1.0])
 def test_cfg4_ivfpq_100m_single_gpu(sigma):
-    """the bench's own builders (bench.py), 100M vectors, oracle on 512 queries of a 4096-query batch"""
+    """the bench's own builders (bench.py), 100M vectors, queries for the headline batch of 16384: oracle on 512 queries of a
+    4096-query call (K3h: fewer than 1.25 queries per list) and on 512 queries drawn over the whole 16384-query call (K3q, the
+    headline's pass A); batch-wide properties of both"""
     import argparse
 
     import torch
@@ -68,19 +71,42 @@ def test_cfg4_ivfpq_100m_single_gpu(sigma):
     cx.world, cx.rank, cx.local, cx.dist = 1, 0, 0, None
     cx.dev = torch.device("cuda", 0)
     cx.stream = torch.cuda.current_stream().cuda_stream
-    k, B, ns = 100, 4096, 512
+    k, B, BH, ns, N = 100, 4096, 16384, 512, 100_000_000
     mu, coarse_h, pq_h = bench.learn_codebooks(cx, sigma)
-    h, Q = bench.build_index(cx, mu, sigma, coarse_h, pq_h, B, sharded_build=False)
-    try:
-        iid = torch.empty(B, k, dtype=torch.int32, device=cx.dev)
-        dd = torch.empty(B, k, dtype=torch.float64, device=cx.dev)
-        cc = torch.empty(B, dtype=torch.int32, device=cx.dev)
-        cx.chk(cx.L.mmidx_set_profiling(h, 1))
-        cx.chk(cx.L.mmidx_search_device(h, k, B, Q.data_ptr(), iid.data_ptr(), dd.data_ptr(), cc.data_ptr(), cx.stream))
+    h, Q = bench.build_index(cx, mu, sigma, coarse_h, pq_h, BH, sharded_build=False)
+    # (the vector each query perturbs: build_index's own draw)
+    gq = torch.Generator(device=cx.dev)
+    gq.manual_seed(4321)
+    qsrc = torch.randint(0, N, (BH,), generator=gq, device=cx.dev).cpu().numpy()
+
+    def search(nq):
+        iid = torch.empty(nq, k, dtype=torch.int32, device=cx.dev)
+        dd = torch.empty(nq, k, dtype=torch.float64, device=cx.dev)
+        cc = torch.empty(nq, dtype=torch.int32, device=cx.dev)
+        cx.chk(cx.L.mmidx_search_device(h, k, nq, Q.data_ptr(), iid.data_ptr(), dd.data_ptr(), cc.data_ptr(), cx.stream))
         torch.cuda.synchronize()
+        buf = C.create_string_buffer(512)
+        cx.chk(cx.L.mmidx_get_dispatch(h, buf, 512))
+        disp = dict(kv.split("=", 1) for kv in buf.value.decode().split(";"))
+        return iid.cpu().numpy(), dd.cpu().numpy(), cc.cpu().numpy(), disp
+
+    hits = []
+
+    def batch_props(i_all, d_all, nq):
+        # size-independent properties on the whole batch: ascending distances, ids inside the index, self hit (asserted at the end)
+        assert np.all(np.diff(d_all, axis=1) >= 0.0)
+        assert i_all.min() >= 0 and i_all.max() < N
+        hits.append(float(np.mean((i_all == qsrc[:nq, None]).any(axis=1))))
+        print(f"cfg4 sigma {sigma}: self hit in the top {k} of {nq} queries: {hits[-1]:.4f}")
+
+    try:
+        cx.chk(cx.L.mmidx_set_profiling(h, 1))
+        i4, d4, c4, disp4 = search(B)
         st = cx.nat.Stats()
         cx.chk(cx.L.mmidx_get_stats(h, C.byref(st)))
         cx.chk(cx.L.mmidx_set_profiling(h, 0))
+        print(f"cfg4 sigma {sigma}: dispatch of {B} queries: {disp4}")
+        assert disp4["pass_a"] == "K3h", disp4  # (4096 queries on 8192 lists: below K3q's gate)
         pairs_per_query = st.passb_items_last / B
         if sigma >= 1.0:
             assert pairs_per_query > 0.5 * 31, "the hard workload must defeat the coarse bound"
@@ -88,14 +114,26 @@ def test_cfg4_ivfpq_100m_single_gpu(sigma):
             assert pairs_per_query < 1.0
         ref = bench.oracle_of_index(cx, h, coarse_h, pq_h)
         rid, rd, rc = ref.search_batch(Q[:ns].cpu().numpy(), k, nthreads=bench.usable_cpus()[0])
-        assert np.array_equal(cc.cpu().numpy()[:ns], rc)
-        assert np.array_equal(iid.cpu().numpy()[:ns], rid), "neighbour ids differ from the oracle at 100M"
-        assert np.array_equal(dd.cpu().numpy()[:ns], rd), "distances are not bit-equal at 100M"
-        # size-independent properties on the whole batch: ascending distances, ids inside the index, self hit
-        d_all = dd.cpu().numpy()
-        assert np.all(np.diff(d_all, axis=1) >= 0.0)
-        i_all = iid.cpu().numpy()
-        assert i_all.min() >= 0 and i_all.max() < 100_000_000
+        assert np.array_equal(c4[:ns], rc)
+        assert np.array_equal(i4[:ns], rid), "neighbour ids differ from the oracle at 100M"
+        assert np.array_equal(d4[:ns], rd), "distances are not bit-equal at 100M"
+        batch_props(i4, d4, B)
+        # the headline batch through the default dispatch: K3q
+        t_head = time.time()
+        ih, dh, ch, disph = search(BH)
+        print(f"cfg4 sigma {sigma}: dispatch of {BH} queries: {disph}")
+        assert disph["pass_a"] == "K3q", disph
+        # a sample over the WHOLE batch (not a prefix): many nearest lists, every position of a K3q group of four
+        sel = np.sort(np.random.default_rng(16384).choice(BH, ns, replace=False))
+        rid, rd, rc = ref.search_batch(Q[torch.as_tensor(sel, device=cx.dev)].cpu().numpy(), k, nthreads=bench.usable_cpus()[0])
+        assert np.array_equal(ch[sel], rc)
+        assert np.array_equal(ih[sel], rid), "neighbour ids of the headline batch differ from the oracle at 100M"
+        assert np.array_equal(dh[sel], rd), "distances of the headline batch are not bit-equal at 100M"
+        batch_props(ih, dh, BH)
+        # the first 4096 queries: K3q's answers are K3h's
+        assert np.array_equal(ch[:B], c4) and np.array_equal(ih[:B], i4) and np.array_equal(dh[:B], d4)
+        print(f"cfg4 sigma {sigma}: the headline batch's call and checks took {time.time() - t_head:.1f} s")
+        assert min(hits) >= 0.9, hits
         del ref
     finally:
         cx.chk(cx.L.mmidx_destroy(h))

@@ -155,3 +155,97 @@ def test_passa_mfma_default_gate(mi, oracle):
         assert st["passa_mfma_launches"] == ran
         assert ix.get_dispatch()["pass_a"] == name
     ix.close()
+
+
+def _overflow_queries(rng, base, nq, D):
+    """midpoints between vectors and self-perturbed vectors: every nearest list is long, no query needs the redo of its own accord"""
+    h = nq // 3
+    return np.concatenate([0.5 * (base[:h] + base[1000:1000 + h]), base[3000:3000 + nq - h] + 0.01 * rng.standard_normal((nq - h, D))])
+
+
+@pytest.mark.parametrize("D,m,C,n,w,k,tr,dup,nq", [
+    (128, 16, 6, 30000, 3, 100, 0, 1, 120),    # <NJ 4, dsub 8>, the headline's shape
+    (128, 16, 5, 24000, 5, 50, 2, 3, 200),     # <4, 8>, RandomPermutation; every vector three times (ties, long runs of equal codes)
+    (128, 8, 6, 24000, 2, 30, 0, 2, 150),      # <4, 16>, every vector twice
+])
+def test_passa_mfma_record_overflow(mi, oracle, D, m, C, n, w, k, tr, dup, nq):
+    """K3ma's flat record list (k_a1_item_scan -> k_a1_records) when it overflows: at the list's capacity (`mfma_qcap`) and where the
+    item prefix saturates (`passa_mfma_icnt_sat`, 0xFFFFFFFF unless a test lowers it).  An item past either point -- and the one
+    that straddles it -- must send its queries to the redo (K3f, exactly from T = +inf) instead of dropping its survivors.  The
+    uncapped run gives the total: verified_codes >= the records, and every pair has at least k + 1 records (K1 codes with acc >= a*),
+    so nq (k + 1) <= records <= total.  Every run returns the oracle's ids and distance bits; the redo runs exactly where a list
+    overflowed.  (Without the saturation rule of k_a1_records the saturated runs dropped neighbours and redid nothing.)"""
+    ks = 256
+    rng = np.random.default_rng(31 * D + m + k)
+    mu, base, pq = _problem(rng, D, m, C, n, dup)
+    n = len(base)
+    ix = mi.IVFPQ(D, n, False, "", m, ks, tr, C, 512)
+    ix.loadCoarseQuantizer(mu)
+    ix.loadProductQuantizer(pq)
+    ix.setW(w)
+    ref = oracle_ivfpq(oracle, {"coarse": mu, "pq": pq}, D, m, ks, C, w, tr=tr, perm=oracle.random_permutation(1, D) if tr == 2 else None)
+    ix.indexVectors([str(i) for i in range(n)], base)
+    ref.add_vectors(base)
+    Q = _overflow_queries(rng, base, nq, D)
+    want = ref.search_batch(Q, k)
+    ix.set_option("passa_mfma", 1)
+
+    def run(qcap, sat, blocks=0):
+        ix.set_option("mfma_qcap", qcap)
+        ix.set_option("passa_mfma_icnt_sat", sat)
+        ix.set_option("mfma_blocks", blocks)
+        ix.set_profiling(True)
+        got = ix.search_batch(k, Q)
+        st = ix.get_stats()
+        ix.set_option("mfma_qcap", 0)
+        ix.set_option("passa_mfma_icnt_sat", 0)
+        ix.set_option("mfma_blocks", 0)
+        assert_same(got, want)
+        assert st["passa_mfma_launches"] == 1
+        return st
+
+    st0 = run(0, 0)
+    total = st0["verified_codes"]
+    lo = nq * (k + 1)  # (<= K3ma's records)
+    assert st0["mfma_redo_queries"] == 0 and total >= lo, st0
+    # (pass B's K3m shares `mfma_qcap` and reserves its survivor slots 512 per wave at a time: the run that must not overflow bounds
+    #  the persistent blocks -- 16, of up to eight waves -- and leaves room for K3m's survivors, their padding and K3ma's records)
+    big = 2 * (total + st0["mfma_survivors"]) + 16 * 8 * 512
+    for qcap, sat, blocks, over in ((0, lo // 3, 0, True),      # the prefix saturates a third of the way in
+                                    (0, 1, 0, True),           # ... after the first record
+                                    (1, 0, 0, True),           # the list is full after the first record
+                                    (lo // 2, 0, 0, True),     # one item straddles the capacity
+                                    (big, 0, 16, False)):      # nothing overflows
+        st = run(qcap, sat, blocks)
+        if over:
+            assert st["mfma_redo_queries"] > 0, (qcap, sat, st)
+        else:
+            assert st["mfma_redo_queries"] == 0, (qcap, sat, st)
+    ix.close()
+
+
+def test_passa_mfma_record_overflow_sharded(mi, oracle):
+    """The same on a handle of two virtual shards on one device (mmidx_create_sharded, devices [0, 0]): the option reaches every shard
+    (mmidx_set_option forwards it), each shard's K3ma saturates its own prefix after 64 records and redoes what lies past it."""
+    D, m, C, n, w, k, ks, nq = 128, 16, 6, 30000, 3, 100, 256, 120
+    rng = np.random.default_rng(91)
+    mu, base, pq = _problem(rng, D, m, C, n)
+    ix = mi.IVFPQ(D, n, False, "", m, ks, 0, C, 512, devices=[0, 0])
+    ix.loadCoarseQuantizer(mu)
+    ix.loadProductQuantizer(pq)
+    ix.setW(w)
+    ref = oracle_ivfpq(oracle, {"coarse": mu, "pq": pq}, D, m, ks, C, w)
+    ix.indexVectors([str(i) for i in range(n)], base)
+    ref.add_vectors(base)
+    Q = _overflow_queries(rng, base, nq, D)
+    want = ref.search_batch(Q, k)
+    ix.set_option("passa_mfma", 1)
+    for sat, over in ((0, False), (64, True), (0, False)):
+        ix.set_option("passa_mfma_icnt_sat", sat)
+        ix.set_profiling(True)
+        got = ix.search_batch(k, Q)
+        st = ix.get_stats()
+        assert_same(got, want)
+        assert st["passa_mfma_launches"] == 1
+        assert (st["mfma_redo_queries"] > 0) == over, (sat, st)
+    ix.close()
