@@ -278,10 +278,13 @@ int mmidx_linear_search(mmidx_linear *l, int k, int64_t nq, const double *Q, int
 /* ---- codebook learning (J/visual/quantization/AbstractQuantizerLearning.java:39-81) ------
  * k-means on the GPU in place of Weka's SimpleKMeans, which the reference calls with setSeed(seed),
  * setNumClusters(k), setMaxIterations(max_iter) and, optionally, k-means++ seeding.  flags:
- *   MMIDX_KMEANS_PLUS_PLUS  k-means++ seeding (else SimpleKMeans' default random seeding),
+ *   MMIDX_KMEANS_PLUS_PLUS  k-means++ seeding (else SimpleKMeans' default random seeding, which skips a drawn
+ *                           instance equal to a centre already taken: fewer than k centres when X has fewer
+ *                           than k distinct rows),
  *   MMIDX_KMEANS_NORMALIZE  min-max attribute normalisation inside the distance (Weka's default).
  * init_centroids (host, [k][d], may be NULL) overrides the seeding.  Empty clusters are dropped as Weka does:
  * *k_out <= k centroids are written to centroids_out (host, room for [k][d]); assign_out[i] indexes them.
+ * 1 <= k <= n < 2^31, else MMIDX_ERR_INVALID_ARG.
  * sse = squared error in the space the clustering ran in.  Weka is an absent third-party dependency: the
  * algorithm is restated, its random stream and summation order are not reproduced (parity unpinned). */
 enum mmidx_kmeans_flags { MMIDX_KMEANS_PLUS_PLUS = 1, MMIDX_KMEANS_NORMALIZE = 2 };

@@ -21,6 +21,7 @@
 #include <cstdio>
 #include <cstring>
 #include <limits>
+#include <set>
 #include <vector>
 
 #include "mmidx.h"
@@ -50,7 +51,8 @@ struct JavaRandom {
         int r = next(31);
         const int m = bound - 1;
         if ((bound & m) == 0) return (int)(((long long)bound * (long long)r) >> 31);
-        for (int u = r; u - (r = u % bound) + m < 0; u = next(31)) {
+        // Java's `u - r + m < 0` relies on int wrap-around (undefined in C++): the same test without overflow
+        for (int u = r; (long long)u - (r = u % bound) + m >= (1LL << 31); u = next(31)) {
         }
         return r;
     }
@@ -117,6 +119,14 @@ __global__ void k_pp_pick(const double *__restrict__ cum, long long n, double r,
     *out = lo;
 }
 
+// rows idx[0 .. m) of X[][d] -> out[m][d] (candidate seeds, compared on the host)
+__global__ void k_gather_rows_ll(const double *__restrict__ X, const long long *__restrict__ idx, double *__restrict__ out, long long m, int d) {
+    const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= m * d) return;
+    const long long r = e / d;
+    out[e] = X[(size_t)idx[r] * d + (size_t)(e - r * d)];
+}
+
 __global__ void k_iota(int32_t *__restrict__ v, long long n) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) v[i] = (int32_t)i;
@@ -176,6 +186,7 @@ int mmidx_kmeans_device(int device, int64_t n, int d, int k, int max_iter, int64
                         const double *init_centroids, double *centroids_out, int32_t *d_assign_out, double *sse_out, int32_t *iters_out,
                         int32_t *k_out, void *stream) {
     if (n < 1 || d < 1 || k < 1 || max_iter < 1 || !dX || !centroids_out) return MMIDX_ERR_INVALID_ARG;
+    if (n > (int64_t)INT32_MAX) return MMIDX_ERR_INVALID_ARG;  // point indices, hipcub's item counts and the JDK draws are 32-bit
     if ((int64_t)k > n) return MMIDX_ERR_INVALID_ARG;  // Weka would stop seeding at n centroids; a codebook needs k <= n
     if (mmidx_device_count() < 1) return MMIDX_ERR_NO_DEVICE;
     LCK(hipSetDevice(device));
@@ -202,6 +213,7 @@ int mmidx_kmeans_device(int device, int64_t n, int d, int k, int max_iter, int64
 
     // ---- seeding ----------------------------------------------------------------------------------------
     std::vector<double> Ch((size_t)k * d);
+    int k_seed = k;  // centres seeded: fewer than k when default seeding runs out of distinct rows
     Buf<double> dC;
     LCK(dC.alloc((size_t)k * d));
     if (init_centroids) {
@@ -215,13 +227,36 @@ int mmidx_kmeans_device(int device, int64_t n, int d, int k, int max_iter, int64
         std::vector<long long> pick;
         pick.reserve((size_t)k);
         if (!plus_plus) {
-            // SimpleKMeans' default seeding: walk j = n-1 .. 0, draw nextInt(j + 1), take that instance, swap it out of range
+            // SimpleKMeans' default seeding: walk j = n-1 .. 0, draw nextInt(j + 1), take that instance unless its (original,
+            // un-normalised) row equals a centre already taken, swap it out of range either way; stop at k centres or when
+            // the walk ends.  The draws do not depend on what is taken, so they are made in batches and the batch's rows
+            // fetched in one gather to be compared here.
             std::vector<int32_t> perm((size_t)n);
             for (int64_t i = 0; i < n; i++) perm[(size_t)i] = (int32_t)i;
-            for (int64_t j = n - 1; j >= 0 && (int)pick.size() < k; j--) {
-                const int r = rnd.nextInt((int)(j + 1));
-                pick.push_back(perm[(size_t)r]);
-                std::swap(perm[(size_t)j], perm[(size_t)r]);
+            const int64_t B = std::min<int64_t>(n, std::max<int64_t>(2 * (int64_t)k, 64));
+            Buf<long long> didx;
+            Buf<double> drows;
+            LCK(didx.alloc((size_t)B));
+            LCK(drows.alloc((size_t)B * d));
+            std::vector<long long> cand;
+            std::vector<double> rows;
+            std::set<std::vector<double>> taken;  // (operator< on the values: -0.0 and 0.0 are one row, as in a == comparison)
+            for (int64_t j = n - 1; j >= 0 && (int)pick.size() < k;) {
+                const int64_t nb = std::min<int64_t>(j + 1, std::max<int64_t>(2 * (k - (int64_t)pick.size()), 64));
+                cand.clear();
+                for (int64_t t = 0; t < nb; t++, j--) {
+                    const int r = rnd.nextInt((int)(j + 1));
+                    cand.push_back(perm[(size_t)r]);
+                    std::swap(perm[(size_t)j], perm[(size_t)r]);
+                }
+                rows.resize((size_t)nb * d);
+                LCK(hipMemcpyAsync(didx.p, cand.data(), (size_t)nb * sizeof(long long), hipMemcpyHostToDevice, st));
+                hipLaunchKernelGGL(k_gather_rows_ll, dim3((unsigned)((nb * d + 255) / 256)), dim3(256), 0, st, dX, didx.p, drows.p, (long long)nb, d);
+                LCK(hipGetLastError());
+                LCK(hipMemcpyAsync(rows.data(), drows.p, (size_t)nb * d * 8, hipMemcpyDeviceToHost, st));
+                LCK(hipStreamSynchronize(st));
+                for (int64_t t = 0; t < nb && (int)pick.size() < k; t++)
+                    if (taken.emplace(rows.begin() + t * d, rows.begin() + (t + 1) * d).second) pick.push_back(cand[(size_t)t]);
             }
         } else {
             // k-means++ (Arthur & Vassilvitskii): first centre uniform, the others with probability ~ D^2
@@ -254,6 +289,7 @@ int mmidx_kmeans_device(int device, int64_t n, int d, int k, int max_iter, int64
         for (size_t c = 0; c < pick.size(); c++)
             LCK(hipMemcpyAsync(Ch.data() + c * d, W + (size_t)pick[c] * d, (size_t)d * 8, hipMemcpyDeviceToHost, st));
         LCK(hipStreamSynchronize(st));
+        k_seed = (int)pick.size();
     }
 
     // ---- Lloyd iterations -------------------------------------------------------------------------------
@@ -277,7 +313,7 @@ int mmidx_kmeans_device(int device, int64_t n, int d, int k, int max_iter, int64
     LCK(hipcub::DeviceRadixSort::SortPairs(nullptr, sb, a_new.p, keys_out.p, iota.p, sorted_idx.p, (int)n, 0, kbits, st));
     LCK(stmp.alloc(sb));
 
-    int k_eff = k, iters = 0;
+    int k_eff = k_seed, iters = 0;
     std::vector<int32_t> h_counts((size_t)k);
     std::vector<long long> h_off((size_t)k + 1);
     mmidx_index *h = nullptr;
@@ -334,6 +370,7 @@ int mmidx_kmeans_device(int device, int64_t n, int d, int k, int max_iter, int64
                 LCK(hipStreamSynchronize(st));
                 for (int64_t i = 0; i < n; i++) ha[(size_t)i] = remap[(size_t)ha[(size_t)i]];
                 LCK(hipMemcpyAsync(a_new.p, ha.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
+                LCK(hipStreamSynchronize(st));  // (ha is freed at the end of this block)
                 // offsets of the compacted numbering
                 int t2 = 0;
                 h_off[0] = 0;
@@ -386,7 +423,7 @@ int mmidx_kmeans_device(int device, int64_t n, int d, int k, int max_iter, int64
 
 int mmidx_kmeans(int device, int64_t n, int d, int k, int max_iter, int64_t seed, int flags, const double *X, const double *init_centroids,
                  double *centroids_out, int32_t *assign_out, double *sse_out, int32_t *iters_out, int32_t *k_out) {
-    if (n < 1 || d < 1 || !X) return MMIDX_ERR_INVALID_ARG;
+    if (n < 1 || d < 1 || !X || n > (int64_t)INT32_MAX) return MMIDX_ERR_INVALID_ARG;
     if (mmidx_device_count() < 1) return MMIDX_ERR_NO_DEVICE;
     LCK(hipSetDevice(device));
     Buf<double> dX;

@@ -62,12 +62,14 @@ def seq_sqdist(x, c):
 
 
 def random_seeding(X, k, seed):
-    """SimpleKMeans' default initialisation (indices of the picked instances)"""
+    """SimpleKMeans' default initialisation (indices of the picked instances): an instance equal to a centre already
+    picked is skipped, the swap and the walk go on; fewer than k picks when X has fewer than k distinct rows"""
     r = JavaRandom(seed)
     perm, picks = list(range(len(X))), []
     for j in range(len(X) - 1, -1, -1):
         i = r.nextInt(j + 1)
-        picks.append(perm[i])
+        if not any(np.array_equal(X[perm[i]], X[p]) for p in picks):
+            picks.append(perm[i])
         perm[j], perm[i] = perm[i], perm[j]
         if len(picks) == k:
             break
@@ -120,7 +122,155 @@ def lloyd(X, C0, max_iter):
         a_old = np.full(len(X), -1) if dropped else a
 
 
-def minmax_normalise(X):
-    """EuclideanDistance's default attribute normalisation (the clustering then runs in this space)"""
+def minmax_normalise(X, ref=None):
+    """EuclideanDistance's default attribute normalisation (the clustering then runs in this space): (x - min) / (max - min),
+    0 for a constant attribute (NormalizableDistance.norm).  ref: the data whose min / max are used (default X itself)"""
     X = np.asarray(X, np.float64)
-    return (X - X.min(0)) / (X.max(0) - X.min(0))
+    R = X if ref is None else np.asarray(ref, np.float64)
+    mn, mx = R.min(0), R.max(0)
+    r = mx - mn
+    return np.divide(X - mn, r, out=np.zeros_like(X), where=r > 0.0)
+
+
+# ---- vectorised twins ---------------------------------------------------------------------------------------------------
+# The same fp64 operations in the same order as the loop versions above (which stay the specification), with numpy doing
+# the loops: bit-identical results at the shapes the GPU learner runs at.  numpy never contracts a * b + c to an FMA, and
+# every sum below is an explicit sequential accumulation (no np.sum / reduceat, whose order is pairwise).
+
+_CHUNK_ELEMS = 1 << 22  # (n_chunk, k) distance block: 32 MB of fp64
+
+
+def sqdist_np(X, C):
+    """yields (i0, D) with D[i, c] = seq_sqdist(X[i0 + i], C[c]) for row chunks of X: dimension ascending, one fp64 add each"""
+    X, C = np.asarray(X, np.float64), np.asarray(C, np.float64)
+    n, d = X.shape
+    step = max(1, _CHUNK_ELEMS // max(1, len(C)))
+    for i0 in range(0, n, step):
+        xb = X[i0:i0 + step]
+        acc = np.zeros((len(xb), len(C)))
+        for j in range(d):
+            df = xb[:, j:j + 1] - C[None, :, j]
+            acc += df * df
+        yield i0, acc
+
+
+def nearest_np(X, C):
+    """index of the nearest centre, first index wins ties (np.argmin)"""
+    out = np.empty(len(X), np.int64)
+    for i0, D in sqdist_np(X, C):
+        out[i0:i0 + len(D)] = np.argmin(D, 1)
+    return out
+
+
+def point_sqerr_np(X, C, a):
+    """|x_i - C[a_i]|^2 per point, dimension ascending"""
+    X, C = np.asarray(X, np.float64), np.asarray(C, np.float64)
+    acc = np.zeros(len(X))
+    for j in range(X.shape[1]):
+        df = X[:, j] - C[a, j]
+        acc += df * df
+    return acc
+
+
+def seq_total(v):
+    """v[0] + v[1] + ... in index order (np.add.accumulate is sequential)"""
+    v = np.asarray(v, np.float64)
+    return float(np.add.accumulate(v)[-1]) if len(v) else 0.0
+
+
+def cluster_sums_np(X, a, k):
+    """(sums [k][d], counts [k]): the members of every cluster added up in ascending index order, starting from 0.0 --
+    one step per member rank r (the r-th member of every cluster that has one), not one per cluster"""
+    X = np.asarray(X, np.float64)
+    a = np.asarray(a, np.int64)
+    counts = np.bincount(a, minlength=k)
+    order = np.argsort(a, kind="stable")  # grouped by cluster, ascending index inside a cluster
+    starts = np.concatenate([[0], np.cumsum(counts)[:-1]])
+    by_size = np.argsort(-counts, kind="stable")  # clusters with more than r members form a prefix of by_size
+    sizes = counts[by_size]
+    acc = np.zeros((k, X.shape[1]))
+    for r in range(int(counts.max()) if k else 0):
+        cl = by_size[:int(np.searchsorted(-sizes, -r, side="left"))]
+        acc[cl] = acc[cl] + X[order[starts[cl] + r]]
+    return acc, counts
+
+
+def lloyd_np(X, C0, max_iter):
+    """lloyd() vectorised (same results bit for bit)"""
+    X = np.asarray(X, np.float64)
+    C = np.array(C0, dtype=np.float64).copy()
+    a_old = np.full(len(X), -1)
+    iters = 0
+    while True:
+        iters += 1
+        a = nearest_np(X, C)
+        changed = int((a != a_old).sum())
+        sums, counts = cluster_sums_np(X, a, len(C))
+        keep = np.nonzero(counts)[0]
+        newC = sums[keep] / counts[keep].astype(np.float64)[:, None]
+        done = changed == 0 or iters >= max_iter
+        dropped = len(keep) != len(C)
+        remap = np.full(len(C), -1)
+        remap[keep] = np.arange(len(keep))
+        C = newC
+        if done:
+            return C, remap[a], iters
+        a_old = np.full(len(X), -1) if dropped else a
+
+
+def random_seeding_np(X, k, seed):
+    """random_seeding() with a hash set of the picked rows in place of the pairwise comparison (same picks)"""
+    X = np.asarray(X, np.float64)
+    r = JavaRandom(seed)
+    n = len(X)
+    perm, picks, seen = np.arange(n), [], set()
+    for j in range(n - 1, -1, -1):
+        i = r.nextInt(j + 1)
+        key = tuple(X[perm[i]].tolist())  # (float ==: -0.0 and 0.0 are one key, as with np.array_equal)
+        if key not in seen:
+            seen.add(key)
+            picks.append(int(perm[i]))
+        perm[j], perm[i] = perm[i], perm[j]
+        if len(picks) == k:
+            break
+    return picks
+
+
+def plus_plus_seeding_np(X, k, seed, margin=1e-9):
+    """plus_plus_seeding() vectorised (same picks, same bucket-edge check)"""
+    X = np.asarray(X, np.float64)
+    n = len(X)
+    r = JavaRandom(seed)
+    picks = [r.nextInt(n)]
+    d2 = None
+    for _ in range(1, k):
+        nd = point_sqerr_np(X, X[picks[-1]][None, :], np.zeros(n, np.int64))
+        d2 = nd if d2 is None else np.minimum(d2, nd)
+        cum = np.cumsum(d2)
+        target = r.nextDouble() * cum[-1]
+        idx = int(np.searchsorted(cum, target, side="right"))
+        if abs(cum[min(idx, n - 1)] - target) <= margin * cum[-1]:
+            raise ValueError("fixture too close to a bucket edge")
+        picks.append(min(idx, n - 1))
+    return picks
+
+
+def kmeans_np(X, k, max_iter, seed=1, plus_plus=False, normalize=True, init=None):
+    """the whole of mmidx_kmeans restated: (centroids [k_eff][d], assignment, squared error, iterations).
+    normalize: the clustering runs on minmax_normalise(X) (given centres normalised with the data's min / max), the squared
+    error is measured there, and the centroids reported are the means of the ORIGINAL members of the final clusters.
+    Default seeding compares original rows; k-means++ draws in the space the clustering runs in."""
+    X = np.asarray(X, np.float64)
+    W = minmax_normalise(X) if normalize else X
+    if init is not None:
+        C0 = minmax_normalise(init, ref=X) if normalize else np.asarray(init, np.float64)
+    elif plus_plus:
+        C0 = W[plus_plus_seeding_np(W, k, seed)]
+    else:
+        C0 = W[random_seeding_np(X, k, seed)]
+    C, a, iters = lloyd_np(W, C0, max_iter)
+    sse = seq_total(point_sqerr_np(W, C, a))
+    if normalize:
+        sums, counts = cluster_sums_np(X, a, len(C))
+        C = sums / counts.astype(np.float64)[:, None]
+    return C, a, sse, iters

@@ -47,6 +47,15 @@ def test_argument_errors_without_touching_the_gpu(mi):
     assert L.mmidx_create(2, 8, 2, 256, 16, 0, None, None, 0, None) == 6
     assert L.mmidx_set_w(None, 3) == 6
     assert L.mmidx_destroy(None) == 0
+    # k-means: point indices, hipcub's item counts and the JDK draws are 32-bit -- n >= 2^31 is refused before any device
+    # call (dummy non-null buffers: nothing may be read or written through them)
+    buf = (C.c_double * 64)()
+    p = C.addressof(buf)
+    for n in (1 << 31, (1 << 31) + 5, 1 << 40):
+        assert L.mmidx_kmeans_device(0, n, 8, 16, 4, 1, 1, p, None, p, None, None, None, None, None) == 6
+        assert L.mmidx_kmeans(0, n, 8, 16, 4, 1, 0, p, None, p, None, None, None, None) == 6
+    assert L.mmidx_kmeans_device(0, 8, 2, 9, 4, 1, 0, p, None, p, None, None, None, None, None) == 6  # k > n
+    assert all(v == 0.0 for v in buf)
 
 
 @pytest.mark.skipif(importlib.import_module("multimedia-indexing_amd").lib().mmidx_device_count() > 0,

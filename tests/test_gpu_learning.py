@@ -4,6 +4,7 @@ Weka's SimpleKMeans is an absent third-party dependency (parity with the referen
 what IS pinned here: from identical seeds the GPU path and the numpy restatement below produce bit-identical
 centroids (exact fp64 argmin with first-index ties, means as index-ordered sums), the JDK random stream of the
 seeding, the dropping of empty clusters, and the file formats the reference's loaders read."""
+import ctypes as _C
 import importlib
 
 import numpy as np
@@ -109,3 +110,211 @@ def test_learned_quantizers_feed_the_index(mi, tmp_path):
         hits += str(i) in ans.getIds()
     assert hits >= 150
     ix.close()
+
+
+# ---- codebook shapes against the vectorised twin ---------------------------------------------------------------------------
+# oracle/kmeans_oracle.py's *_np functions make the loop twin's fp64 operations in the same order (tests/test_kmeans_twin_cpu.py
+# pins the two to each other), so everything below is compared with ==: centroids, assignment, iterations, k_eff and the
+# squared error (per-point sequential sums, added up in index order on the host by the library and by the twin alike).
+
+
+def _twin(X, k, it, seed=1, pp=False, normalize=False, init=None):
+    """(seed actually used, twin result).  A k-means++ draw within 1e-9 of a bucket edge (where the GPU's parallel prefix
+    sum may legitimately pick the neighbour) makes the twin raise; the next seed is then taken -- decided here on the CPU,
+    never by running anything on the GPU again"""
+    for s in range(seed, seed + 50):
+        try:
+            return s, ko.kmeans_np(X, k, it, seed=s, plus_plus=pp, normalize=normalize, init=init)
+        except ValueError:
+            assert pp
+    raise AssertionError("no usable k-means++ seed")
+
+
+def _host(mi, X, k, it, seed=1, pp=False, normalize=False, init=None):
+    return mi.quantization.kmeans(X, k, maxIterations=it, seed=seed, kMeansPlusPlus=pp, normalize=normalize, init=init)
+
+
+def _device(mi, X, k, it, seed=1, pp=False, normalize=False, init=None):
+    """mmidx_kmeans_device exactly as bench.py::gpu_kmeans calls it: fp64 CUDA tensor, null d_assign_out and sse_out,
+    null stream; rows past k_eff stay at 1000.0.  Returns (centroids [k][d], iterations, k_eff)"""
+    import torch
+
+    Xt = torch.from_numpy(np.ascontiguousarray(X, np.float64)).cuda()
+    n, d = X.shape
+    out = np.full((k, d), 1000.0)
+    kout, its = _C.c_int32(0), _C.c_int32(0)
+    ini = None if init is None else np.ascontiguousarray(init, np.float64)
+    flags = (1 if pp else 0) | (2 if normalize else 0)
+    st = mi.lib().mmidx_kmeans_device(0, n, d, k, it, seed, flags, Xt.data_ptr(), ini.ctypes.data if ini is not None else None,
+                                      out.ctypes.data, None, None, _C.addressof(its), _C.addressof(kout), None)
+    torch.cuda.synchronize()
+    assert st == 0
+    return out, its.value, kout.value
+
+
+def _check(got, twin):
+    cent, assign, sse, iters = got
+    tC, tA, tS, tI = twin
+    assert iters == tI
+    assert cent.shape == tC.shape  # (k_eff)
+    assert np.array_equal(assign, tA)
+    assert np.array_equal(cent, tC)
+    assert sse == tS
+
+
+def _check_device(dev, host, k):
+    cent, iters, k_eff = dev
+    hC, _, _, hI = host
+    assert iters == hI and k_eff == len(hC)
+    assert np.array_equal(cent[:k_eff], hC) and np.all(cent[k_eff:] == 1000.0)
+
+
+def _mixture(rng, n, d, comps, sigma):
+    """every component gets members (labels are a shuffled arange), so no cluster empties by accident"""
+    mu = rng.standard_normal((comps, d))
+    lab = rng.permutation(np.arange(n) % comps)
+    return mu, mu[lab] + sigma * rng.standard_normal((n, d))
+
+
+def _case(name):
+    """(X, kwargs of the k-means call); the comment of each case names the path it is meant to reach (a kernel trace of
+    these tests, rocprofv3 --kernel-trace --stats, lists every kernel named here)"""
+    rng = np.random.default_rng(sum(map(ord, name)))
+    if name == "pq_shape":  # bench's PQ learning scaled down (2^18 x 8, ks 256): FROMX K6a' over 2 tiles, radix sort kbits 8
+        X = rng.standard_normal((50_000, 8)) * [1.0, 0.5, 2.0, 1.0, 0.25, 1.0, 1.5, 0.75]
+        return X, dict(k=256, it=8, pp=True)
+    if name == "split_d4":  # d not a multiple of 8: k_split_bf16 + K6a'<false>
+        return rng.standard_normal((30_000, 4)), dict(k=256, it=5, pp=True)
+    if name == "dp_pad":  # d = 130: Dp = 160 (two k chunks), C = 300 -> Cp = 384 with padding rows; default seeding, normalised
+        return rng.standard_normal((5_000, 130)), dict(k=300, it=4, normalize=True)
+    if name == "wide_d300":  # d > 256: a k_centroid_mean thread loops over dimensions; three k chunks
+        return rng.standard_normal((3_000, 300)) * np.linspace(0.5, 2.0, 300), dict(k=40, it=5, pp=True)
+    if name == "pp_multitile":  # n = 300 001: multi-tile hipcub scan + k_pp_pick; clusters of thousands of members
+        return rng.standard_normal((300_001, 8)), dict(k=64, it=3, pp=True)
+    if name == "const_col":  # k_col_minmax with n not a multiple of 256 and a constant column; k_normalize's r = 0 branch
+        X = rng.standard_normal((1_000, 6)) * [1.0, 10.0, 0.1, 1.0, 3.0, 1.0]
+        X[:, 3] = -7.25
+        return X, dict(k=12, it=20, normalize=True)
+    if name == "final_drop":  # a far centre + maxIterations = 1, normalised: dropped on the last iteration -> remap, then
+        X = rng.standard_normal((2_000, 5)) * [1.0, 2.0, 3.0, 4.0, 5.0]  # the final means over the ORIGINAL rows
+        init = np.concatenate([X[:3], [[900.0, -900.0, 900.0, 900.0, 900.0]], X[3:7]])
+        return X, dict(k=8, it=1, normalize=True, init=init)
+    if name == "k1":  # k_eff = 1: C >= 2 fails, the exact k_assign_coarse does the whole assignment
+        return rng.standard_normal((500, 3)), dict(k=1, it=10)
+    if name == "k_eq_n":  # one point per cluster (default seeding takes every row), normalised
+        return rng.standard_normal((200, 4)), dict(k=200, it=10, normalize=True)
+    if name == "d1":  # d = 1: Dp = 32, k_split_bf16 path
+        return rng.standard_normal((2_000, 1)), dict(k=10, it=10, pp=True)
+    raise KeyError(name)
+
+
+@pytest.mark.parametrize("name", ["split_d4", "dp_pad", "wide_d300", "pp_multitile", "const_col", "final_drop", "k1", "k_eq_n", "d1"])
+def test_kmeans_shapes_match_the_twin(mi, name):
+    X, kw = _case(name)
+    k, it = kw.pop("k"), kw.pop("it")
+    seed, twin = _twin(X, k, it, **kw)
+    got = _host(mi, X, k, it, seed=seed, **kw)
+    _check(got, twin)
+    if name == "final_drop":
+        assert len(twin[0]) == 7  # (the far centre really is dropped on the final iteration)
+    if name == "const_col":
+        assert np.all(twin[0][:, 3] == -7.25)
+    if name == "k_eq_n":
+        assert len(twin[0]) == 200 and np.array_equal(np.sort(twin[1]), np.arange(200))
+
+
+@pytest.mark.parametrize("normalize", [False, True])
+def test_kmeans_pq_shape_device_entry(mi, normalize):
+    """bench's PQ codebook call (k-means++, 256 centres, 8-d sub-vectors, 8 iterations) through mmidx_kmeans_device as the
+    bench makes it, and through the host entry, against the twin"""
+    X, kw = _case("pq_shape")
+    k, it = kw.pop("k"), kw.pop("it")
+    seed, twin = _twin(X, k, it, normalize=normalize, **kw)
+    got = _host(mi, X, k, it, seed=seed, normalize=normalize, **kw)
+    _check(got, twin)
+    _check_device(_device(mi, X, k, it, seed=seed, normalize=normalize, **kw), got, k)
+
+
+def test_kmeans_coarse_shape_device_entry(mi):
+    """bench's coarse quantizer call (Lloyd from given centres, no normalisation) at d = 128, k = 512 (Cp = 512: 4 tiles of
+    FROMX K6a'): the given centres are 509 mixture means plus copies of three of them at the end.  The copies lose every tie,
+    empty on iteration 1 and are dropped mid-run; the survivors keep their numbers, so the iteration count shows whether the
+    previous assignment was forgotten after the drop (twin: everything counts as moved on iteration 2, stop on 3)"""
+    rng = np.random.default_rng(128)
+    mu, X = _mixture(rng, 8_000, 128, 509, 0.5)
+    init = np.concatenate([mu, mu[[17, 200, 400]]])
+    seed, twin = _twin(X, 512, 3, init=init)
+    assert len(twin[0]) == 509 and twin[3] == 3
+    assert np.array_equal(ko.nearest_np(X, twin[0]), twin[1])  # (stable after the drop: an early stop would show in iters)
+    got = _host(mi, X, 512, 3, init=init)
+    _check(got, twin)
+    _check_device(_device(mi, X, 512, 3, init=init), got, 512)
+
+
+def test_kmeans_ties_and_duplicate_seeds(mi):
+    """lattice rows (small integers: every squared distance is an integer, exact ties between centres everywhere -> K6a'
+    flags them, the exact redo must keep the first index) with 20 % of the rows copies of 40 others, default seeding at
+    d = 16, k = 256: the draws repeat rows, and SimpleKMeans' rule skips an instance equal to a centre already taken"""
+    rng = np.random.default_rng(16)
+    n, d, k = 10_000, 16, 256
+    X = rng.integers(0, 4, (n, d)).astype(np.float64)
+    dup = rng.choice(n, n // 5, replace=False)
+    X[dup] = X[rng.choice(np.setdiff1d(np.arange(n), dup), 40, replace=False)][rng.integers(0, 40, len(dup))]
+    # the fixture does what it claims: without the rule the first k draws would hold repeated rows, and the first
+    # assignment has points with two or more nearest centres
+    r, perm, naive = ko.JavaRandom(1), np.arange(n), []
+    for j in range(n - 1, n - 1 - k, -1):
+        i = r.nextInt(j + 1)
+        naive.append(int(perm[i]))
+        perm[j], perm[i] = perm[i], perm[j]
+    assert len({tuple(X[p]) for p in naive}) < k
+    picks = ko.random_seeding_np(X, k, 1)
+    assert len(picks) == k and len({tuple(X[p]) for p in picks}) == k
+    _, D0 = next(ko.sqdist_np(X, X[picks]))
+    assert np.sum((D0 == D0.min(1, keepdims=True)).sum(1) > 1) > 100
+    seed, twin = _twin(X, k, 4)
+    _check(_host(mi, X, k, 4), twin)
+
+
+def test_kmeans_default_seeding_runs_out_of_distinct_rows(mi):
+    """fewer distinct rows than k: seeding stops short and k_eff reports it (no failure, no empty duplicate centres)"""
+    X = np.repeat(np.arange(30, dtype=np.float64).reshape(10, 3), 7, 0)
+    twin = ko.kmeans_np(X, 16, 5, normalize=False)
+    assert len(twin[0]) == 10
+    _check(_host(mi, X, 16, 5), twin)
+
+
+def test_pq_learning_end_to_end_matches_the_twin(mi):
+    """ProductQuantizationLearning.learn with a coarse quantizer, a RandomPermutation transform and two k-means repeats,
+    against the same steps assembled from the twin in the Java order (ProductQuantizationLearning.java): residual =
+    centroid - vector, transform after the residual, seeds 1..R keeping the lowest squared error, 1000.0 rows for the
+    centres that are missing"""
+    import np_twin
+
+    q = mi.quantization
+    D, Cc, m, ks, n, R = 16, 8, 4, 64, 3_000, 2
+    perm = np_twin.random_permutation(1, D)
+    for data_seed in range(40, 90):  # the first data set whose k-means++ draws all sit clear of bucket edges (CPU only)
+        rng = np.random.default_rng(data_seed)
+        coarse = 3.0 * rng.standard_normal((Cc, D))
+        X = coarse[rng.integers(0, Cc, n)] + rng.standard_normal((n, D))
+        X[:50] = X[50:100]  # repeated vectors
+        resid = (coarse[ko.nearest_np(X, coarse)] - X)[:, perm]
+        want = np.full((m, ks, D // m), 1000.0)
+        try:
+            for s in range(m):
+                sub = np.ascontiguousarray(resid[:, s * (D // m):(s + 1) * (D // m)])
+                best = None
+                for seed in range(1, R + 1):
+                    C, _, sse, _ = ko.kmeans_np(sub, ks, 15, seed=seed, plus_plus=True, normalize=True)
+                    if best is None or sse < best[1]:
+                        best = (C, sse)
+                want[s, :len(best[0])] = best[0]
+        except ValueError:
+            continue
+        break
+    else:
+        raise AssertionError("no data set without a bucket-edge draw")
+    got = q.ProductQuantizationLearning.learn(X, m, ks, maxIterations=15, numKmeansRepeats=R, coarseQuantizer=coarse,
+                                              transform=q.RandomPermutation(1, D).permute)
+    assert np.array_equal(got, want)
