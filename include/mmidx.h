@@ -54,7 +54,8 @@ enum mmidx_status {
     MMIDX_ERR_NOT_READY = 7,          /* quantizers not loaded (NullPointerException in the reference) */
     MMIDX_ERR_NO_DEVICE = 8,          /* no usable MI355X / HIP runtime: the product path has NO CPU fallback */
     MMIDX_ERR_HIP = 9,                /* HIP runtime error; message carries hipGetErrorString */
-    MMIDX_ERR_UNSUPPORTED = 10        /* configuration outside the kernel envelope (see DESIGN.md limits) */
+    MMIDX_ERR_UNSUPPORTED = 10,       /* configuration outside the kernel envelope (see DESIGN.md limits) */
+    MMIDX_ERR_NOT_CONVERGED = 11      /* mmidx_pca_learn_compute: max_iter reached above tol; the message carries the residual */
 };
 
 enum mmidx_kind { MMIDX_KIND_PQ = 1, MMIDX_KIND_IVFPQ = 2 };
@@ -406,6 +407,34 @@ int mmidx_pca_destroy(mmidx_pca *p);
 int mmidx_pca_get_dims(const mmidx_pca *p, int *nc_out, int *ss_out); /* numComponents, sampleSize of the handle */
 int mmidx_pca_project(mmidx_pca *p, int64_t n, const double *X, double *Y);
 int mmidx_pca_project_device(mmidx_pca *p, int64_t n, const double *dX, double *dY, void *stream);
+
+/* Learning the PCA basis: PCA.addSample / computeBasis (J/dimreduction/PCA.java:120-177; driver PCALearningExample.java:36-55).
+ * create = the constructor (:101-111): room for num_samples rows of ss doubles in HBM, where the samples stay until destroy, as
+ * the reference keeps them in A (:109).  add = addSample for n rows at once, in arrival order (host rows, or rows already in the
+ * HBM of the learner's device; the _device form is asynchronous on `stream`).  compute = computeBasis:
+ *   means_out[ss]   the reference's loop (:142-153): every column summed in arrival order into a zero-initialised double, one
+ *                   division by num_samples -- BIT-EXACT, also when the samples arrived in several add calls;
+ *   sv_out[nc]      the largest nc SINGULAR VALUES OF THE CENTRED SAMPLE MATRIX, descending, NOT divided by n or n - 1: this is what
+ *                   savePCAToFile writes on line 2 (W.get(i, i), :234-237) and what the loader whitens with value^-0.5 (:283-285);
+ *   Vt_out[nc][ss]  the matching orthonormal right singular vectors, one per row.  Sign: in every row the entry of largest
+ *                   magnitude (lowest index on a tie) is positive.  EJML's SVD is an absent third-party dependency whose
+ *                   arithmetic and row signs cannot be reproduced (assumption A2): the contract is mathematical.
+ * Method: Gram matrix of the centred samples on the f64 matrix cores, then blocked subspace iteration with Rayleigh-Ritz (block
+ * nc + 32) until max_i ||G v_i - sv_i^2 v_i||_2 <= tol * sv_1^2 over the nc components; *iters_out = iterations run,
+ * *residual_out = the achieved value of that ratio.  Not converged within max_iter: MMIDX_ERR_NOT_CONVERGED, the message carries the
+ * residual, all outputs are still written.  The Gram route squares the condition number: components with sv below ~1e-8 sv_1 are
+ * not resolved.  Deterministic (fixed start block, no atomics).  Any output pointer may be NULL.
+ * Envelope: 1 <= nc <= ss <= 16384, nc <= 1024, num_samples < 2^31 (else MMIDX_ERR_UNSUPPORTED).  Errors as the reference's, all
+ * MMIDX_ERR_INVALID_ARG and raised before any device call: nc > ss "More components requested than the data's length." (:102-104);
+ * more than num_samples rows "Too many samples" (:121-122); compute before all rows "Not all the data has been added" (:136-137);
+ * nc > num_samples "More data needed to compute the desired number of components" (:138-140). */
+typedef struct mmidx_pca_learner mmidx_pca_learner;
+int mmidx_pca_learn_create(int nc, int64_t num_samples, int ss, int device, mmidx_pca_learner **out);
+int mmidx_pca_learn_add(mmidx_pca_learner *l, int64_t n, const double *X);
+int mmidx_pca_learn_add_device(mmidx_pca_learner *l, int64_t n, const double *dX, void *stream);
+int mmidx_pca_learn_compute(mmidx_pca_learner *l, double tol, int max_iter, double *means_out, double *sv_out,
+                            double *Vt_out, int32_t *iters_out, double *residual_out);
+int mmidx_pca_learn_destroy(mmidx_pca_learner *l);
 
 /* VLAD aggregation: VladAggregator.aggregateInternal (J/aggregation/VladAggregator.java:56-70) with
  * computeNearestCentroid (AbstractFeatureAggregator.java:136-155), and the multi-vocabulary wrapper

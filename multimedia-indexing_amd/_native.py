@@ -16,10 +16,11 @@ SO_PATH = os.environ.get("MMIDX_LIB") or os.path.join(CSRC, "libmmidx_hip.so")
 OK = 0
 STATUS_NAMES = {
     1: "INVALID_SUBVECTORS", 2: "WRONG_DIM", 3: "NOT_IN_MEMORY", 4: "BYTE_OVERFLOW", 5: "CAPACITY",
-    6: "INVALID_ARG", 7: "NOT_READY", 8: "NO_DEVICE", 9: "HIP", 10: "UNSUPPORTED",
+    6: "INVALID_ARG", 7: "NOT_READY", 8: "NO_DEVICE", 9: "HIP", 10: "UNSUPPORTED", 11: "NOT_CONVERGED",
 }
 ERR_INVALID_SUBVECTORS, ERR_WRONG_DIM, ERR_NOT_IN_MEMORY, ERR_BYTE_OVERFLOW = 1, 2, 3, 4
 ERR_CAPACITY, ERR_INVALID_ARG, ERR_NOT_READY, ERR_NO_DEVICE, ERR_HIP, ERR_UNSUPPORTED = 5, 6, 7, 8, 9, 10
+ERR_NOT_CONVERGED = 11
 
 KIND_PQ, KIND_IVFPQ = 1, 2
 TR_NONE, TR_ROTATION, TR_PERMUTATION = 0, 1, 2
@@ -46,7 +47,7 @@ class Stats(C.Structure):
 
 def build(force=False):
     """Compile the HIP library for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
-    srcs = [os.path.join(CSRC, f) for f in ("mmidx_api.hip", "mmidx_learn.hip", "mmidx_probe.hip", "mmidx_kernels.h", "mmidx_scan_grp.h", "mmidx_frontend.h", "mmidx_sharded.h")]
+    srcs = [os.path.join(CSRC, f) for f in ("mmidx_api.hip", "mmidx_learn.hip", "mmidx_pca_learn.hip", "mmidx_small_solve.h", "mmidx_probe.hip", "mmidx_kernels.h", "mmidx_scan_grp.h", "mmidx_frontend.h", "mmidx_sharded.h")]
     srcs.append(os.path.join(os.path.dirname(_HERE), "include", "mmidx.h"))
     stale = not os.path.exists(SO_PATH) or any(os.path.getmtime(s) > os.path.getmtime(SO_PATH) for s in srcs)
     if force or stale:
@@ -97,6 +98,11 @@ SIGNATURES = {
     "mmidx_pca_destroy": (C.c_int, [_vp]),
     "mmidx_pca_project": (C.c_int, [_vp, C.c_int64, _dp, _dp]),
     "mmidx_pca_project_device": (C.c_int, [_vp, C.c_int64, _dp, _dp, _vp]),
+    "mmidx_pca_learn_create": (C.c_int, [C.c_int, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "mmidx_pca_learn_add": (C.c_int, [_vp, C.c_int64, _dp]),
+    "mmidx_pca_learn_add_device": (C.c_int, [_vp, C.c_int64, _dp, _vp]),
+    "mmidx_pca_learn_compute": (C.c_int, [_vp, C.c_double, C.c_int, _dp, _dp, _dp, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
+    "mmidx_pca_learn_destroy": (C.c_int, [_vp]),
     "mmidx_vlad_create": (C.c_int, [C.c_int, _i32p, C.c_int, _dp, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "mmidx_vlad_destroy": (C.c_int, [_vp]),
     "mmidx_vlad_set_option": (C.c_int, [_vp, C.c_char_p, C.c_int]),

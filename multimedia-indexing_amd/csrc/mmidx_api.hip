@@ -4465,6 +4465,18 @@ int mmidx_pca_project_device(mmidx_pca *p, int64_t n, const double *dX, double *
     return MMIDX_OK;
 }
 
+// for mmidx_pca_learn.hip (same library, not exported): the calling thread's error text, and K7 on plain device pointers --
+// Y[n][nc] = (X[n][ss] - mu[ss]) Vt[nc][ss]^T, the tall products of the PCA learner's subspace iteration
+__attribute__((visibility("hidden"))) int mmidx_internal_fail(int code, const char *msg) { return fail(code, "%s", msg); }
+__attribute__((visibility("hidden"))) int mmidx_internal_gemm_nt(const double *X, const double *mu, const double *Vt, double *Y, long long n,
+                                                                  int nc, int ss, void *stream) {
+    dim3 grid((unsigned)((n + PCA_BM - 1) / PCA_BM), (unsigned)((nc + PCA_BN - 1) / PCA_BN));
+    static_assert(PCA_LDS_BYTES <= 64 * 1024, "K7's tiles fit the default dynamic LDS limit: no attribute to raise per launch");
+    hipLaunchKernelGGL(k_pca_project, grid, dim3(PCA_NT), PCA_LDS_BYTES, (hipStream_t)stream, X, mu, Vt, Y, n, nc, ss);
+    HIPCK(hipGetLastError());
+    return MMIDX_OK;
+}
+
 int mmidx_pca_project(mmidx_pca *p, int64_t n, const double *X, double *Y) {
     if (!p) return fail(MMIDX_ERR_INVALID_ARG, "null handle");
     if (n < 0 || (n > 0 && (!X || !Y))) return fail(MMIDX_ERR_INVALID_ARG, "null argument");

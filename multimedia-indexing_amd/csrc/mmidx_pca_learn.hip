@@ -1,0 +1,574 @@
+// mmidx_pca_learn.hip -- learning the PCA basis on the GPU: PCA.addSample / computeBasis (J/dimreduction/PCA.java:120-177).
+//
+// The reference keeps the samples in A[numSamples][sampleSize], computes the column means with a sequential loop, centres A and
+// takes V_t and W from EJML's dense SVD, sorted descending, first numComponents rows.  Here:
+//   means       k_pca_colsum: a thread per column adds the rows in arrival order into a running fp64 sum (the reference's loop,
+//               :142-153, continued across add calls), one division by numSamples on the host -- BIT-EXACT.
+//   Gram        k_pca_gram: G = (A - mu)^T (A - mu) on v_mfma_f64_16x16x4_f64, lower-triangle tiles, mirrored.
+//   eigenpairs  top-nc of G by blocked subspace iteration with Rayleigh-Ritz, block width b = min(ss, nc + 32): Z = G Q (K7,
+//               k_pca_project with a zero mean), T = Q^T Z (k_pca_gram with two operands), eigen-solve of the b x b matrix T on the
+//               host, V = Q W, residuals ||G v_i - lambda_i v_i|| = ||Z w_i - lambda_i v_i||, Q <- CholeskyQR2(Z W).
+//   finish      k_pca_finish: sv = sqrt(max(lambda, 0)), the sign rule (largest-magnitude entry of a row positive, lowest index on
+//               a tie), transpose to Vt[nc][ss].
+// EJML is absent from the reference tree and its SVD cannot be reproduced bit for bit (assumption A2): components and singular
+// values are right singular vectors / values of A - mu in the mathematical sense, row signs by the rule above (EJML's are
+// arbitrary).  sv are the singular values of the CENTRED SAMPLE MATRIX, not divided by n or n - 1: what PCA.savePCAToFile writes on
+// line 2 (W.get(i, i), :234-237) and the loader whitens with value^-0.5 (:283-285).
+// Everything is deterministic: fixed start block, no atomics, no split reductions whose order depends on scheduling.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <mutex>
+#include <vector>
+
+#include "mmidx.h"
+#include "mmidx_small_solve.h"
+
+// defined in mmidx_api.hip: the calling thread's last-error text, and the launch of K7 (k_pca_project) as a plain
+// Y[n][nc] = (X[n][ss] - mu[ss]) Vt[nc][ss]^T on device pointers
+extern "C" {
+__attribute__((visibility("hidden"))) int mmidx_internal_fail(int code, const char *msg);
+__attribute__((visibility("hidden"))) int mmidx_internal_gemm_nt(const double *X, const double *mu, const double *Vt, double *Y, long long n,
+                                                                  int nc, int ss, void *stream);
+}
+
+namespace {
+
+typedef __attribute__((ext_vector_type(4))) double f64x4;
+
+#define PLCK(expr)                                                                                          \
+    do {                                                                                                    \
+        hipError_t e__ = (expr);                                                                            \
+        if (e__ != hipSuccess) {                                                                            \
+            char b__[384];                                                                                  \
+            snprintf(b__, sizeof(b__), "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e__), __FILE__, __LINE__); \
+            return mmidx_internal_fail(MMIDX_ERR_HIP, b__);                                                 \
+        }                                                                                                   \
+    } while (0)
+
+// ------------------------------------------------------------------------------------------------
+// column sums: sum[c] += X[r][c], r = 0 .. n-1 in order (PCA.java:144-149).  A thread per column, a wave reads 512 contiguous
+// bytes of a row; eight rows are requested together and added one after the other (the additions stay sequential).
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void k_pca_colsum(const double *__restrict__ X, long long n, int ss, double *__restrict__ sum) {
+    const int c = blockIdx.x * 64 + threadIdx.x;
+    if (c >= ss) return;
+    double s = sum[c];
+    const double *x = X + c;
+    long long r = 0;
+    for (; r + 8 <= n; r += 8) {
+        double v[8];
+#pragma unroll
+        for (int u = 0; u < 8; u++) v[u] = x[(size_t)(r + u) * ss];
+#pragma unroll
+        for (int u = 0; u < 8; u++) s += v[u];
+    }
+    for (; r < n; r++) s += x[(size_t)r * ss];
+    sum[c] = s;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Gram: C[sa][sb] = (A[n][sa] - muA)^T (B[n][sb] - muB), the contraction runs over the n ROWS.  The transposed-operand
+// counterpart of K7: both operands are read along their rows (contiguous) for GR_BK consecutive samples, the mean is subtracted
+// while staging, tiles go through LDS as [k][column] with a row stride of 16 doubles past a multiple of 32 -- a fragment read is
+// 16 consecutive doubles per k (lane & 15) for four k (lane >> 4), and with that stride the two k of a 32-lane half fall on
+// disjoint halves of the 64 banks (ds_read_b64: bank = (addr / 4) mod 64).  Block = 4 waves, tile 64 x 128: wave w owns rows
+// 16w .. 16w+15 of the tile and its 8 column tiles, as K7 (64 accumulator registers, four waves per SIMD).
+// A operand: one f64 per lane, A[i = lane & 15][k = lane >> 4]; B[k = lane >> 4][j = lane & 15]; C/D: col = lane & 15,
+// row = (lane >> 4) + 4 * reg.
+// SYM (A == B): only tiles that touch the lower triangle run; an element (i >= j) is written to C[i][j] and C[j][i] by the one
+// tile that owns it, so the matrix is exactly symmetric and no element is written twice.
+// ------------------------------------------------------------------------------------------------
+#define GR_BM 64
+#define GR_BN 128
+#ifndef GR_BK
+#define GR_BK 8
+#endif
+#define GR_NT 256
+#define GR_LDA (GR_BM + 16)
+#define GR_LDB (GR_BN + 16)
+#define GR_NA (GR_BK * GR_BM / 2 / GR_NT)  // pairs of doubles per thread: A tile
+#define GR_NB (GR_BK * GR_BN / 2 / GR_NT)  // ... B tile
+
+template <bool SYM>
+__global__ __launch_bounds__(GR_NT, 4) void k_pca_gram(const double *__restrict__ A, const double *__restrict__ B, const double *__restrict__ muA,
+                                                       const double *__restrict__ muB, double *__restrict__ Cm, long long n, int sa, int sb) {
+    __shared__ __attribute__((aligned(16))) double As[GR_BK * GR_LDA];
+    __shared__ __attribute__((aligned(16))) double Bs[GR_BK * GR_LDB];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int i0 = blockIdx.y * GR_BM, j0 = blockIdx.x * GR_BN;
+    if (SYM && i0 + GR_BM - 1 < j0) return;  // strictly above the diagonal (block-uniform)
+    f64x4 acc[8];
+#pragma unroll
+    for (int t = 0; t < 8; t++) acc[t] = f64x4{0.0, 0.0, 0.0, 0.0};
+    // staging: thread <-> (k, pair of columns); the means of its columns stay in registers
+    double2 ra[GR_NA], rb[GR_NB], ma[GR_NA], mb[GR_NB];
+#pragma unroll
+    for (int u = 0; u < GR_NA; u++) {
+        const int c = i0 + ((tid + u * GR_NT) % (GR_BM / 2)) * 2;
+        ma[u] = make_double2(c < sa ? muA[c] : 0.0, c + 1 < sa ? muA[c + 1] : 0.0);
+    }
+#pragma unroll
+    for (int u = 0; u < GR_NB; u++) {
+        const int c = j0 + ((tid + u * GR_NT) % (GR_BN / 2)) * 2;
+        mb[u] = make_double2(c < sb ? muB[c] : 0.0, c + 1 < sb ? muB[c + 1] : 0.0);
+    }
+    auto load_tiles = [&](long long k0) {
+#pragma unroll
+        for (int u = 0; u < GR_NA; u++) {
+            const int p = tid + u * GR_NT, k = p / (GR_BM / 2), c = i0 + (p % (GR_BM / 2)) * 2;
+            const long long gr = k0 + k;
+            double2 v = make_double2(0.0, 0.0);  // rows past n and columns past sa contribute nothing
+            if (gr < n) {
+                const double *src = A + (size_t)gr * sa + c;
+                if (c < sa) v.x = src[0] - ma[u].x;
+                if (c + 1 < sa) v.y = src[1] - ma[u].y;
+            }
+            ra[u] = v;
+        }
+#pragma unroll
+        for (int u = 0; u < GR_NB; u++) {
+            const int p = tid + u * GR_NT, k = p / (GR_BN / 2), c = j0 + (p % (GR_BN / 2)) * 2;
+            const long long gr = k0 + k;
+            double2 v = make_double2(0.0, 0.0);
+            if (gr < n) {
+                const double *src = B + (size_t)gr * sb + c;
+                if (c < sb) v.x = src[0] - mb[u].x;
+                if (c + 1 < sb) v.y = src[1] - mb[u].y;
+            }
+            rb[u] = v;
+        }
+    };
+    auto store_tiles = [&]() {
+#pragma unroll
+        for (int u = 0; u < GR_NA; u++) {
+            const int p = tid + u * GR_NT, k = p / (GR_BM / 2), c = (p % (GR_BM / 2)) * 2;
+            *(double2 *)(As + k * GR_LDA + c) = ra[u];
+        }
+#pragma unroll
+        for (int u = 0; u < GR_NB; u++) {
+            const int p = tid + u * GR_NT, k = p / (GR_BN / 2), c = (p % (GR_BN / 2)) * 2;
+            *(double2 *)(Bs + k * GR_LDB + c) = rb[u];
+        }
+    };
+    const int fr = lane & 15, fk = lane >> 4;
+    load_tiles(0);
+    for (long long k0 = 0; k0 < n; k0 += GR_BK) {
+        __syncthreads();
+        store_tiles();
+        __syncthreads();
+        if (k0 + GR_BK < n) load_tiles(k0 + GR_BK);
+#pragma unroll
+        for (int kk = 0; kk < GR_BK / 4; kk++) {
+            const double a = As[(kk * 4 + fk) * GR_LDA + wave * 16 + fr];
+#pragma unroll
+            for (int t = 0; t < 8; t++) {
+                const double b = Bs[(kk * 4 + fk) * GR_LDB + t * 16 + fr];
+                acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc[t], 0, 0, 0);
+            }
+        }
+    }
+#pragma unroll
+    for (int t = 0; t < 8; t++) {
+        const int j = j0 + t * 16 + (lane & 15);
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            const int i = i0 + wave * 16 + (lane >> 4) + 4 * r;
+            if (i < sa && j < sb) {
+                if (SYM) {
+                    if (i >= j) {
+                        Cm[(size_t)i * sb + j] = acc[t][r];
+                        Cm[(size_t)j * sb + i] = acc[t][r];
+                    }
+                } else {
+                    Cm[(size_t)i * sb + j] = acc[t][r];
+                }
+            }
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// small kernels of the iteration
+// ------------------------------------------------------------------------------------------------
+__device__ inline double unit_hash(unsigned long long x) {  // splitmix64 -> [-1, 1)
+    x += 0x9E3779B97F4A7C15ull;
+    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+    x ^= x >> 31;
+    return (double)(long long)(x >> 11) * 0x1p-52 - 1.0;
+}
+// the fixed start block Q[ss][b] (col < 0: all columns), or one fresh column for a deficient direction
+__global__ void k_pca_fill(double *__restrict__ Q, int ss, int b, int col, unsigned long long salt) {
+    const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (col < 0) {
+        if (e < (long long)ss * b) Q[e] = unit_hash((unsigned long long)e);
+    } else if (e < ss) {
+        Q[(size_t)e * b + col] = unit_hash(salt * 0x100000000ull + (unsigned long long)e * 4099ull + (unsigned long long)col);
+    }
+}
+// out[c][r] = in[r][c]
+__global__ __launch_bounds__(256) void k_pca_transpose(const double *__restrict__ in, double *__restrict__ out, int rows, int cols) {
+    __shared__ double tile[32][33];
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    const int r0 = blockIdx.y * 32, c0 = blockIdx.x * 32;
+    for (int y = ty; y < 32; y += 8)
+        if (r0 + y < rows && c0 + tx < cols) tile[y][tx] = in[(size_t)(r0 + y) * cols + c0 + tx];
+    __syncthreads();
+    for (int y = ty; y < 32; y += 8)
+        if (c0 + y < cols && r0 + tx < rows) out[(size_t)(c0 + y) * rows + r0 + tx] = tile[tx][y];
+}
+// res[i] = || ZW[:, i] - lam[i] V[:, i] ||_2 : a block per column, fixed tree
+__global__ __launch_bounds__(256) void k_pca_resid(const double *__restrict__ ZW, const double *__restrict__ V, const double *__restrict__ lam, int ss,
+                                                   int b, double *__restrict__ res) {
+    __shared__ double red[256];
+    const int i = blockIdx.x;
+    const double l = lam[i];
+    double s = 0.0;
+    for (int k = threadIdx.x; k < ss; k += 256) {
+        const double d = ZW[(size_t)k * b + i] - l * V[(size_t)k * b + i];
+        s += d * d;
+    }
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int off = 128; off > 0; off >>= 1) {
+        if ((int)threadIdx.x < off) red[threadIdx.x] += red[threadIdx.x + off];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) res[i] = sqrt(red[0]);
+}
+// component i: sign rule, transpose, singular value
+__global__ __launch_bounds__(256) void k_pca_finish(const double *__restrict__ V, const double *__restrict__ lam, int ss, int b, double *__restrict__ Vt,
+                                                    double *__restrict__ sv) {
+    __shared__ double bv[256];
+    __shared__ int bi[256];
+    const int i = blockIdx.x;
+    double best = -1.0;
+    int idx = (int)threadIdx.x < ss ? (int)threadIdx.x : 0;  // always a valid row, whatever the values (a NaN compares false)
+    for (int k = threadIdx.x; k < ss; k += 256) {
+        const double a = fabs(V[(size_t)k * b + i]);
+        if (a > best) {  // ascending k inside a thread: the first maximum stays
+            best = a;
+            idx = k;
+        }
+    }
+    bv[threadIdx.x] = best;
+    bi[threadIdx.x] = idx;
+    __syncthreads();
+    for (int off = 128; off > 0; off >>= 1) {
+        if ((int)threadIdx.x < off) {
+            const double ov = bv[threadIdx.x + off];
+            const int oi = bi[threadIdx.x + off];
+            if (ov > bv[threadIdx.x] || (ov == bv[threadIdx.x] && oi < bi[threadIdx.x])) {
+                bv[threadIdx.x] = ov;
+                bi[threadIdx.x] = oi;
+            }
+        }
+        __syncthreads();
+    }
+    const double sgn = V[(size_t)bi[0] * b + i] < 0.0 ? -1.0 : 1.0;
+    for (int k = threadIdx.x; k < ss; k += 256) Vt[(size_t)i * ss + k] = sgn * V[(size_t)k * b + i];
+    if (threadIdx.x == 0) sv[i] = sqrt(lam[i] > 0.0 ? lam[i] : 0.0);
+}
+
+template <typename T>
+struct Buf {
+    T *p = nullptr;
+    ~Buf() {
+        if (p) (void)hipFree(p);
+    }
+    hipError_t alloc(size_t n) { return hipMalloc((void **)&p, std::max<size_t>(n, 1) * sizeof(T)); }
+};
+
+struct Ev {  // a timing event that is destroyed on every return path
+    hipEvent_t e = nullptr;
+    ~Ev() {
+        if (e) (void)hipEventDestroy(e);
+    }
+};
+
+const char *const NONFINITE = "PCA learning: the samples hold non-finite values, or their Gram matrix overflows";
+
+double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+int launch_gram(bool sym, const double *A, const double *B, const double *muA, const double *muB, double *Cm, long long n, int sa, int sb,
+                hipStream_t st) {
+    dim3 grid((unsigned)((sb + GR_BN - 1) / GR_BN), (unsigned)((sa + GR_BM - 1) / GR_BM));
+    if (sym)
+        hipLaunchKernelGGL(k_pca_gram<true>, grid, dim3(GR_NT), 0, st, A, B, muA, muB, Cm, n, sa, sb);
+    else
+        hipLaunchKernelGGL(k_pca_gram<false>, grid, dim3(GR_NT), 0, st, A, B, muA, muB, Cm, n, sa, sb);
+    PLCK(hipGetLastError());
+    return MMIDX_OK;
+}
+
+}  // namespace
+
+struct mmidx_pca_learner {
+    std::mutex mu;
+    int nc = 0, ss = 0, device = 0;
+    int64_t num = 0, count = 0;
+    double *dA = nullptr, *dsum = nullptr;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev_own = nullptr, ev_ext = nullptr;  // order the library's stream and a caller's stream (add_device) on the running sums
+};
+
+namespace {
+
+// rows [count, count + n) <- src (host or device), then the running sums; `st` = the stream the copy and the sums run on
+int add_rows(mmidx_pca_learner *l, int64_t n, const double *src, hipMemcpyKind kind, hipStream_t st) {
+    if (n == 0) return MMIDX_OK;
+    PLCK(hipSetDevice(l->device));
+    double *dst = l->dA + (size_t)l->count * l->ss;
+    if (st != l->stream) PLCK(hipStreamWaitEvent(st, l->ev_own, 0));
+    PLCK(hipMemcpyAsync(dst, src, (size_t)n * l->ss * 8, kind, st));
+    hipLaunchKernelGGL(k_pca_colsum, dim3((unsigned)((l->ss + 63) / 64)), dim3(64), 0, st, dst, (long long)n, l->ss, l->dsum);
+    PLCK(hipGetLastError());
+    if (st != l->stream) {
+        PLCK(hipEventRecord(l->ev_ext, st));
+        PLCK(hipStreamWaitEvent(l->stream, l->ev_ext, 0));
+    } else {
+        PLCK(hipStreamSynchronize(st));  // host rows: the caller may reuse its buffer
+    }
+    PLCK(hipEventRecord(l->ev_own, l->stream));
+    l->count += n;
+    return MMIDX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mmidx_pca_learn_create(int nc, int64_t num_samples, int ss, int device, mmidx_pca_learner **out) {
+    if (!out) return mmidx_internal_fail(MMIDX_ERR_INVALID_ARG, "null out pointer");
+    *out = nullptr;
+    if (nc < 1 || ss < 1 || num_samples < 0) return mmidx_internal_fail(MMIDX_ERR_INVALID_ARG, "bad PCA shape");
+    if (nc > ss) return mmidx_internal_fail(MMIDX_ERR_INVALID_ARG, "More components requested than the data's length.");  // PCA.java:102-104
+    if (ss > 16384 || nc > 1024 || num_samples > (int64_t)INT32_MAX)
+        return mmidx_internal_fail(MMIDX_ERR_UNSUPPORTED, "PCA learning: sampleSize <= 16384, numComponents <= 1024, numSamples < 2^31");
+    const int ndev = mmidx_device_count();
+    if (ndev < 1) return mmidx_internal_fail(MMIDX_ERR_NO_DEVICE, "no HIP device: libmmidx_hip has no CPU fallback");
+    if (device < 0 || device >= ndev) return mmidx_internal_fail(MMIDX_ERR_NO_DEVICE, "device outside the visible range");
+    PLCK(hipSetDevice(device));
+    mmidx_pca_learner *l = new mmidx_pca_learner();
+    l->nc = nc;
+    l->ss = ss;
+    l->num = num_samples;
+    l->device = device;
+    hipError_t e = hipStreamCreateWithFlags(&l->stream, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&l->ev_own, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&l->ev_ext, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipMalloc((void **)&l->dA, std::max<size_t>((size_t)num_samples * ss, 1) * 8);  // the samples stay resident (A, :109)
+    if (e == hipSuccess) e = hipMalloc((void **)&l->dsum, (size_t)ss * 8);
+    if (e == hipSuccess) e = hipMemsetAsync(l->dsum, 0, (size_t)ss * 8, l->stream);
+    if (e == hipSuccess) e = hipEventRecord(l->ev_own, l->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(l->stream);
+    if (e != hipSuccess) {
+        char b[256];
+        snprintf(b, sizeof(b), "PCA learner: allocation of %lld x %d samples failed: %s", (long long)num_samples, ss, hipGetErrorString(e));
+        mmidx_pca_learn_destroy(l);
+        return mmidx_internal_fail(MMIDX_ERR_HIP, b);
+    }
+    *out = l;
+    return MMIDX_OK;
+}
+
+int mmidx_pca_learn_destroy(mmidx_pca_learner *l) {
+    if (!l) return MMIDX_OK;
+    (void)hipSetDevice(l->device);
+    if (l->stream) (void)hipStreamSynchronize(l->stream);
+    if (l->dA) (void)hipFree(l->dA);
+    if (l->dsum) (void)hipFree(l->dsum);
+    if (l->ev_own) (void)hipEventDestroy(l->ev_own);
+    if (l->ev_ext) (void)hipEventDestroy(l->ev_ext);
+    if (l->stream) (void)hipStreamDestroy(l->stream);
+    delete l;
+    return MMIDX_OK;
+}
+
+int mmidx_pca_learn_add(mmidx_pca_learner *l, int64_t n, const double *X) {
+    if (!l) return mmidx_internal_fail(MMIDX_ERR_INVALID_ARG, "null handle");
+    if (n < 0 || (n > 0 && !X)) return mmidx_internal_fail(MMIDX_ERR_INVALID_ARG, "null argument");
+    std::lock_guard<std::mutex> lk(l->mu);
+    if (l->count + n > l->num) return mmidx_internal_fail(MMIDX_ERR_INVALID_ARG, "Too many samples");  // PCA.java:121-122
+    return add_rows(l, n, X, hipMemcpyHostToDevice, l->stream);
+}
+
+int mmidx_pca_learn_add_device(mmidx_pca_learner *l, int64_t n, const double *dX, void *stream) {
+    if (!l) return mmidx_internal_fail(MMIDX_ERR_INVALID_ARG, "null handle");
+    if (n < 0 || (n > 0 && !dX)) return mmidx_internal_fail(MMIDX_ERR_INVALID_ARG, "null argument");
+    std::lock_guard<std::mutex> lk(l->mu);
+    if (l->count + n > l->num) return mmidx_internal_fail(MMIDX_ERR_INVALID_ARG, "Too many samples");
+    return add_rows(l, n, dX, hipMemcpyDeviceToDevice, (hipStream_t)stream);
+}
+
+int mmidx_pca_learn_compute(mmidx_pca_learner *l, double tol, int max_iter, double *means_out, double *sv_out, double *Vt_out,
+                            int32_t *iters_out, double *residual_out) {
+    if (!l) return mmidx_internal_fail(MMIDX_ERR_INVALID_ARG, "null handle");
+    std::lock_guard<std::mutex> lk(l->mu);
+    if (l->count != l->num) return mmidx_internal_fail(MMIDX_ERR_INVALID_ARG, "Not all the data has been added");  // PCA.java:136-137
+    if ((int64_t)l->nc > l->num)
+        return mmidx_internal_fail(MMIDX_ERR_INVALID_ARG, "More data needed to compute the desired number of components");  // :138-140
+    if (!(tol >= 0.0) || max_iter < 1) return mmidx_internal_fail(MMIDX_ERR_INVALID_ARG, "tol must be >= 0 and max_iter >= 1");
+    PLCK(hipSetDevice(l->device));
+    hipStream_t st = l->stream;
+    const int ss = l->ss, nc = l->nc, b = std::min(ss, nc + 32);
+    const long long n = (long long)l->num;
+    const bool trace = getenv("MMIDX_PCA_LEARN_TRACE") != nullptr;
+    const double t_begin = now_s();
+
+    // ---- means (PCA.java:150-153) ----
+    std::vector<double> h_mu((size_t)ss);
+    PLCK(hipMemcpyAsync(h_mu.data(), l->dsum, (size_t)ss * 8, hipMemcpyDeviceToHost, st));
+    PLCK(hipStreamSynchronize(st));
+    for (int j = 0; j < ss; j++) h_mu[(size_t)j] = h_mu[(size_t)j] / (double)n;
+    if (means_out) memcpy(means_out, h_mu.data(), (size_t)ss * 8);
+
+    Buf<double> d_mu, d_zero, G, Q, Z, V, ZW, Qt, S, Wd, d_lam, d_res, d_Vt, d_sv;
+    const size_t sb = (size_t)ss * b, bb = (size_t)b * b;
+    PLCK(d_mu.alloc((size_t)ss));
+    PLCK(d_zero.alloc((size_t)ss));
+    PLCK(G.alloc((size_t)ss * ss));
+    PLCK(Q.alloc(sb));
+    PLCK(Z.alloc(sb));
+    PLCK(V.alloc(sb));
+    PLCK(ZW.alloc(sb));
+    PLCK(Qt.alloc(sb));
+    PLCK(S.alloc(bb));
+    PLCK(Wd.alloc(bb));
+    PLCK(d_lam.alloc((size_t)b));
+    PLCK(d_res.alloc((size_t)b));
+    PLCK(d_Vt.alloc((size_t)nc * ss));
+    PLCK(d_sv.alloc((size_t)nc));
+    PLCK(hipMemcpyAsync(d_mu.p, h_mu.data(), (size_t)ss * 8, hipMemcpyHostToDevice, st));
+    PLCK(hipMemsetAsync(d_zero.p, 0, (size_t)ss * 8, st));
+
+    // ---- Gram matrix of the centred samples ----
+    Ev e0, e1;
+    PLCK(hipEventCreate(&e0.e));
+    PLCK(hipEventCreate(&e1.e));
+    PLCK(hipEventRecord(e0.e, st));
+    int rc = launch_gram(true, l->dA, l->dA, d_mu.p, d_mu.p, G.p, n, ss, ss, st);
+    if (rc) return rc;
+    PLCK(hipEventRecord(e1.e, st));
+    PLCK(hipStreamSynchronize(st));
+    float gram_ms = 0.f;
+    PLCK(hipEventElapsedTime(&gram_ms, e0.e, e1.e));
+
+    double t_small = 0.0;  // host time in the b x b solves
+    std::vector<double> hS(bb), Linv, lam, Wt;
+    std::vector<int> deficient;
+    unsigned long long salt = 1;
+    // CholeskyQR until two passes in a row met no deficient direction (normally the first two): *src <- orthonormal basis of span(*src)
+    auto orth = [&](double *&src, double *&tmp) -> int {
+        for (int pass = 0, clean = 0; pass < 6; pass++) {
+            int r = launch_gram(true, src, src, d_zero.p, d_zero.p, S.p, ss, b, b, st);
+            if (r) return r;
+            PLCK(hipMemcpyAsync(hS.data(), S.p, bb * 8, hipMemcpyDeviceToHost, st));
+            PLCK(hipStreamSynchronize(st));
+            const double t0 = now_s();
+            if (!mmidx_small::chol_inverse(hS.data(), b, (double)b * 0x1p-52, Linv, deficient))
+                return mmidx_internal_fail(MMIDX_ERR_INVALID_ARG, NONFINITE);
+            t_small += now_s() - t0;
+            PLCK(hipMemcpyAsync(Wd.p, Linv.data(), bb * 8, hipMemcpyHostToDevice, st));
+            r = mmidx_internal_gemm_nt(src, d_zero.p, Wd.p, tmp, ss, b, b, st);  // tmp = src L^-T
+            if (r) return r;
+            for (int j : deficient)
+                hipLaunchKernelGGL(k_pca_fill, dim3((unsigned)((ss + 255) / 256)), dim3(256), 0, st, tmp, ss, b, j, salt++);
+            PLCK(hipGetLastError());
+            PLCK(hipStreamSynchronize(st));  // (Linv is rewritten by the next pass)
+            std::swap(src, tmp);
+            clean = deficient.empty() ? clean + 1 : 0;
+            if (clean >= 2) return MMIDX_OK;
+        }
+        return mmidx_internal_fail(MMIDX_ERR_UNSUPPORTED, "PCA learning: the block could not be orthonormalised in 6 CholeskyQR passes");
+    };
+
+    double *q = Q.p, *z = Z.p, *zw = ZW.p;
+    hipLaunchKernelGGL(k_pca_fill, dim3((unsigned)((sb + 255) / 256)), dim3(256), 0, st, q, ss, b, -1, 0ull);
+    PLCK(hipGetLastError());
+    rc = orth(q, z);
+    if (rc) return rc;
+
+    const double t_iter0 = now_s();
+    int iters = 0;
+    double residual = 0.0;
+    bool converged = false;
+    std::vector<double> h_res((size_t)b);
+    for (;;) {
+        iters++;
+        hipLaunchKernelGGL(k_pca_transpose, dim3((unsigned)((b + 31) / 32), (unsigned)((ss + 31) / 32)), dim3(256), 0, st, q, Qt.p, ss, b);
+        PLCK(hipGetLastError());
+        rc = mmidx_internal_gemm_nt(G.p, d_zero.p, Qt.p, z, ss, b, ss, st);  // Z = G Q
+        if (rc) return rc;
+        rc = launch_gram(false, q, z, d_zero.p, d_zero.p, S.p, ss, b, b, st);  // T = Q^T Z
+        if (rc) return rc;
+        PLCK(hipMemcpyAsync(hS.data(), S.p, bb * 8, hipMemcpyDeviceToHost, st));
+        PLCK(hipStreamSynchronize(st));
+        {
+            const double t0 = now_s();
+            for (int i = 0; i < b; i++)
+                for (int j = 0; j < i; j++) {
+                    const double m = 0.5 * (hS[(size_t)i * b + j] + hS[(size_t)j * b + i]);
+                    hS[(size_t)i * b + j] = m;
+                    hS[(size_t)j * b + i] = m;
+                }
+            if (!mmidx_small::sym_eig(hS.data(), b, lam, Wt)) return mmidx_internal_fail(MMIDX_ERR_INVALID_ARG, NONFINITE);
+            t_small += now_s() - t0;
+        }
+        PLCK(hipMemcpyAsync(Wd.p, Wt.data(), bb * 8, hipMemcpyHostToDevice, st));
+        PLCK(hipMemcpyAsync(d_lam.p, lam.data(), (size_t)b * 8, hipMemcpyHostToDevice, st));
+        rc = mmidx_internal_gemm_nt(q, d_zero.p, Wd.p, V.p, ss, b, b, st);  // V = Q W (Ritz vectors)
+        if (rc) return rc;
+        rc = mmidx_internal_gemm_nt(z, d_zero.p, Wd.p, zw, ss, b, b, st);  // Z W = G V
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_pca_resid, dim3((unsigned)nc), dim3(256), 0, st, zw, V.p, d_lam.p, ss, b, d_res.p);
+        PLCK(hipGetLastError());
+        PLCK(hipMemcpyAsync(h_res.data(), d_res.p, (size_t)nc * 8, hipMemcpyDeviceToHost, st));
+        PLCK(hipStreamSynchronize(st));
+        double mr = 0.0;
+        for (int i = 0; i < nc; i++) mr = std::max(mr, h_res[(size_t)i]);
+        residual = lam[0] > 0.0 ? mr / lam[0] : (mr == 0.0 ? 0.0 : HUGE_VAL);
+        if (!(mr == mr)) residual = HUGE_VAL;  // NaN
+        if (trace) fprintf(stderr, "[mmidx] pca_learn: iteration %d residual %.3e\n", iters, residual);
+        if (residual <= tol) {
+            converged = true;
+            break;
+        }
+        if (iters >= max_iter) break;
+        std::swap(q, zw);  // next block: an orthonormal basis of span(Z W)
+        rc = orth(q, z);
+        if (rc) return rc;
+    }
+    const double t_iter1 = now_s();
+
+    // ---- singular values, sign rule, transpose ----
+    hipLaunchKernelGGL(k_pca_finish, dim3((unsigned)nc), dim3(256), 0, st, V.p, d_lam.p, ss, b, d_Vt.p, d_sv.p);
+    PLCK(hipGetLastError());
+    if (Vt_out) PLCK(hipMemcpyAsync(Vt_out, d_Vt.p, (size_t)nc * ss * 8, hipMemcpyDeviceToHost, st));
+    if (sv_out) PLCK(hipMemcpyAsync(sv_out, d_sv.p, (size_t)nc * 8, hipMemcpyDeviceToHost, st));
+    PLCK(hipStreamSynchronize(st));
+    if (iters_out) *iters_out = iters;
+    if (residual_out) *residual_out = residual;
+    if (trace) {
+        long long tiles = 0;  // tiles k_pca_gram ran (lower triangle + the diagonal's): the TF/s figure counts what was executed
+        for (int i0 = 0; i0 < ss; i0 += GR_BM)
+            for (int j0 = 0; j0 < ss; j0 += GR_BN) tiles += i0 + GR_BM - 1 >= j0;
+        fprintf(stderr, "[mmidx] pca_learn: n %lld ss %d nc %d b %d: gram %.3f ms (%.2f TF/s executed), %d iterations %.3f s, host solves %.3f s (start block included), total %.3f s\n",
+                n, ss, nc, b, gram_ms, 2.0 * (double)n * (double)tiles * GR_BM * GR_BN / (gram_ms * 1e-3) * 1e-12, iters, t_iter1 - t_iter0, t_small, now_s() - t_begin);
+    }
+    if (!converged) {
+        char msg[256];
+        snprintf(msg, sizeof(msg), "PCA basis not converged: residual %.3e > tol %.3e after %d iterations", residual, tol, iters);
+        return mmidx_internal_fail(MMIDX_ERR_NOT_CONVERGED, msg);
+    }
+    return MMIDX_OK;
+}
+
+}  // extern "C"

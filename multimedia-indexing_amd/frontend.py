@@ -4,8 +4,9 @@
   gr.iti.mklab.visual.aggregation.VladAggregator              (J/aggregation/VladAggregator.java)
   gr.iti.mklab.visual.aggregation.VladAggregatorMultipleVocabularies
 
-Only the apply side is native (projection = one batched f64-MFMA GEMM, aggregation = one block per
-image); learning the PCA basis / the codebooks stays offline, as in the reference (EJML SVD, Weka).
+Projection = one batched f64-MFMA GEMM, aggregation = one block per image.  The PCA basis is learned on the
+GPU as well (addSample / addSamples, computeBasis, savePCAToFile: `mmidx_pca_learn_*`, a Gram matrix on the f64
+matrix cores and a blocked subspace iteration in place of EJML's SVD); codebooks: quantization.py.
 """
 import ctypes as C
 
@@ -28,6 +29,80 @@ class PCA:
         self.device = device
         self._h = None
         self.isPcaInitialized = False
+        if numComponents > sampleSize:  # IllegalArgumentException, PCA.java:102-104
+            raise MmidxError(N.ERR_INVALID_ARG, "More components requested than the data's length.")
+        # learning side (PCA.java:109-110, :135-177): the samples live in the learner's HBM, the results here
+        self._learner = None
+        self.sampleIndex = 0
+        self.means = self.singularValues = self.V_t = None
+        self.iterations = self.residual = None
+
+    # ---- learning: addSample / computeBasis / savePCAToFile (PCA.java:120-177, :219-247) ----
+    def addSamples(self, X):
+        """Batch form of addSample: rows of X [n][sampleSize] in arrival order."""
+        X = _f64(X)
+        if X.ndim != 2:
+            raise MmidxError(N.ERR_WRONG_DIM, "Unexpected sample size")
+        if self.sampleIndex + X.shape[0] > self.numTrainingSamples:
+            raise MmidxError(N.ERR_INVALID_ARG, "Too many samples")  # PCA.java:121-122
+        if X.shape[1] != self.sampleSize:
+            raise MmidxError(N.ERR_WRONG_DIM, "Unexpected sample size")  # PCA.java:123-124
+        if X.shape[0] == 0:
+            return
+        self._ensure_learner()
+        N.check(N.lib().mmidx_pca_learn_add(self._learner, X.shape[0], X.ctypes.data))
+        self.sampleIndex += X.shape[0]
+
+    def addSample(self, sampleData):
+        """PCA.java:120-130"""
+        if self.sampleIndex >= self.numTrainingSamples:
+            raise MmidxError(N.ERR_INVALID_ARG, "Too many samples")
+        x = _f64(sampleData)
+        if x.ndim != 1 or x.shape[0] != self.sampleSize:
+            raise MmidxError(N.ERR_WRONG_DIM, "Unexpected sample size")
+        self.addSamples(x.reshape(1, -1))
+
+    def _ensure_learner(self):
+        if self._learner is None:
+            h = C.c_void_p()
+            N.check(N.lib().mmidx_pca_learn_create(self.numComponents, self.numTrainingSamples, self.sampleSize, self.device, C.byref(h)))
+            self._learner = h
+
+    def computeBasis(self, tol=1e-12, max_iter=200):
+        """PCA.java:135-177 on the GPU.  Fills .means [sampleSize], .singularValues [numComponents] (singular values of the centred
+        sample matrix, descending -- NOT divided by n: the reference's line 2, W.get(i, i)) and .V_t [numComponents][sampleSize]
+        (in every row the entry of largest magnitude is positive; EJML's row signs are arbitrary), .iterations, .residual.
+        Raises MmidxError(status NOT_CONVERGED) when max_iter is reached above tol; the fields are filled all the same."""
+        if self.sampleIndex != self.numTrainingSamples:
+            raise MmidxError(N.ERR_INVALID_ARG, "Not all the data has been added")  # PCA.java:136-137
+        if self.numComponents > self.numTrainingSamples:
+            raise MmidxError(N.ERR_INVALID_ARG, "More data needed to compute the desired number of components")  # :138-140
+        self._ensure_learner()
+        means, sv = np.zeros(self.sampleSize), np.zeros(self.numComponents)
+        Vt = np.zeros((self.numComponents, self.sampleSize))
+        it, res = C.c_int32(0), C.c_double(0.0)
+        st = N.lib().mmidx_pca_learn_compute(self._learner, float(tol), int(max_iter), means.ctypes.data, sv.ctypes.data, Vt.ctypes.data,
+                                             C.byref(it), C.byref(res))
+        if st in (N.OK, N.ERR_NOT_CONVERGED):
+            self.means, self.singularValues, self.V_t = means, sv, Vt
+            self.iterations, self.residual = int(it.value), float(res.value)
+        N.check(st)
+
+    def setCompact(self, compact):
+        """PCA.java:320-322 chooses between EJML's two SVD forms; there is one method here: a no-op kept for drop-in callers."""
+
+    def savePCAToFile(self, PCAFileName):
+        """PCA.java:219-247: line 1 means, line 2 singular values, then one component per line, space separated; repr(float)
+        is the shortest text that parses back to the same double (as Java's Double.toString round-trips)."""
+        if self.isPcaInitialized:
+            raise MmidxError(N.ERR_INVALID_ARG, "Cannot save, PCA is initialized!")  # :220-222
+        if self.V_t is None:
+            raise MmidxError(N.ERR_NOT_READY, "Cannot save to file, PCA matrix is null!")  # :223-225
+        with open(PCAFileName, "w") as f:
+            f.write(" ".join(repr(float(v)) for v in self.means) + "\n")
+            f.write(" ".join(repr(float(v)) for v in self.singularValues) + "\n")
+            for row in self.V_t:
+                f.write(" ".join(repr(float(v)) for v in row) + "\n")
 
     def loadPCAFromFile(self, filename):
         """PCA.java:257-318: line 1 means, line 2 eigenvalues, then one component per line (space separated)."""
@@ -53,7 +128,8 @@ class PCA:
         h = C.c_void_p()
         N.check(N.lib().mmidx_pca_create(self.numComponents, self.sampleSize, int(self.doWhitening), means.ctypes.data,
                                          eig.ctypes.data if eig is not None else None, Vt.ctypes.data, self.device, C.byref(h)))
-        self.close()
+        if self._h:  # (a learner in progress is left alone)
+            N.lib().mmidx_pca_destroy(self._h)
         self._h = h
         self.isPcaInitialized = True
 
@@ -79,6 +155,9 @@ class PCA:
         if self._h:
             N.lib().mmidx_pca_destroy(self._h)
             self._h = None
+        if getattr(self, "_learner", None):
+            N.lib().mmidx_pca_learn_destroy(self._learner)
+            self._learner = None
 
     def __del__(self):
         try:

@@ -91,6 +91,18 @@ public final class MmidxNative {
 	public static native void pcaProject(long pca, int n, int sampleSize, int numComponents, double[] samples,
 			double[] projected) throws Exception;
 
+	/* ---- learning the PCA basis (mmidx_pca_learn_*): PCA.addSample / computeBasis ---- */
+	public static native long pcaLearnCreate(int numComponents, int numSamples, int sampleSize, int device)
+			throws Exception;
+
+	public static native void pcaLearnDestroy(long learner);
+
+	public static native void pcaLearnAdd(long learner, int n, int sampleSize, double[] samples) throws Exception;
+
+	/** returns the iterations run; residualOut[0] = achieved residual; throws when maxIter is reached above tol */
+	public static native int pcaLearnCompute(long learner, int numComponents, int sampleSize, double tol, int maxIter,
+			double[] means, double[] singularValues, double[] components, double[] residualOut) throws Exception;
+
 	public static native long vladCreate(int[] numCentroids, int descriptorLength, double[] codebooks,
 			boolean normalizationsOn, int device) throws Exception;
 

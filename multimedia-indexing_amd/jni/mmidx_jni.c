@@ -472,6 +472,52 @@ done:
     (*env)->ReleaseDoubleArrayElements(env, x, x_, JNI_ABORT);
     (*env)->ReleaseDoubleArrayElements(env, y, y_, 0);
 }
+/* ---- learning the PCA basis: PCA.addSample / computeBasis (PCA.java:120-177) -> mmidx_pca_learn_*.  The learner has no
+ *      dimension getter: numComponents / sampleSize come from GpuPCA's final fields, the values the learner was created with. */
+JNIEXPORT jlong JNICALL JFN(pcaLearnCreate)(JNIEnv *env, jclass c, jint nc, jint numSamples, jint ss, jint device) {
+    mmidx_pca_learner *l = NULL;
+    (void)c;
+    CHECK(mmidx_pca_learn_create(nc, numSamples, ss, device, &l));
+done:
+    return (jlong)(intptr_t)l;
+}
+JNIEXPORT void JNICALL JFN(pcaLearnDestroy)(JNIEnv *env, jclass c, jlong l) {
+    (void)env;
+    (void)c;
+    mmidx_pca_learn_destroy((mmidx_pca_learner *)(intptr_t)l);
+}
+/* addSample for n samples: x[n][ss], arrival order */
+JNIEXPORT void JNICALL JFN(pcaLearnAdd)(JNIEnv *env, jclass c, jlong l, jint n, jint ss, jdoubleArray x) {
+    jdouble *x_;
+    (void)c;
+    if (n < 0 || ss < 1 || bad_len(env, x, (int64_t)n * ss, 0, "samples")) return;
+    x_ = (*env)->GetDoubleArrayElements(env, x, NULL);
+    CHECK(mmidx_pca_learn_add((mmidx_pca_learner *)(intptr_t)l, n, x_));
+done:
+    (*env)->ReleaseDoubleArrayElements(env, x, x_, JNI_ABORT);
+}
+/* computeBasis: means[ss], singular values[nc], components[nc][ss], residualOut[1]; returns the iterations.  Not converged within
+ * maxIter: throws with the residual in the message; the arrays are written all the same. */
+JNIEXPORT jint JNICALL JFN(pcaLearnCompute)(JNIEnv *env, jclass c, jlong l, jint nc, jint ss, jdouble tol, jint maxIter, jdoubleArray means,
+                                            jdoubleArray sv, jdoubleArray vt, jdoubleArray residualOut) {
+    jdouble *m_, *s_, *v_, *r_;
+    int32_t iters = 0;
+    (void)c;
+    if (nc < 1 || ss < 1 || bad_len(env, means, ss, 0, "means") || bad_len(env, sv, nc, 0, "singular values") ||
+        bad_len(env, vt, (int64_t)nc * ss, 0, "components") || bad_len(env, residualOut, 1, 0, "residual"))
+        return 0;
+    m_ = (*env)->GetDoubleArrayElements(env, means, NULL);
+    s_ = (*env)->GetDoubleArrayElements(env, sv, NULL);
+    v_ = (*env)->GetDoubleArrayElements(env, vt, NULL);
+    r_ = (*env)->GetDoubleArrayElements(env, residualOut, NULL);
+    CHECK(mmidx_pca_learn_compute((mmidx_pca_learner *)(intptr_t)l, tol, maxIter, m_, s_, v_, &iters, r_));
+done:
+    (*env)->ReleaseDoubleArrayElements(env, means, m_, 0);
+    (*env)->ReleaseDoubleArrayElements(env, sv, s_, 0);
+    (*env)->ReleaseDoubleArrayElements(env, vt, v_, 0);
+    (*env)->ReleaseDoubleArrayElements(env, residualOut, r_, 0);
+    return (jint)iters;
+}
 JNIEXPORT jlong JNICALL JFN(vladCreate)(JNIEnv *env, jclass c, jintArray ncent, jint dl, jdoubleArray codebooks, jboolean normalizationsOn,
                                         jint device) {
     mmidx_vlad *v = NULL;
