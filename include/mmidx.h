@@ -467,6 +467,41 @@ int mmidx_vectorize(mmidx_vlad *v, mmidx_pca *p, int64_t nimg, const int64_t *de
 int mmidx_vectorize_device(mmidx_vlad *v, mmidx_pca *p, int64_t nimg, const int64_t *d_desc_off,
                            const double *d_descs, int max_desc, double *d_out, void *stream);
 
+/* Bag-of-words aggregation: BowAggregator.aggregateInternal (J/aggregation/BowAggregator.java:39-74) for a batch of images.
+ * codebook[nc][dl] = the vocabulary; desc_off[nimg+1] delimits each image's descriptors in descs[total][dl], exactly as for
+ * mmidx_vlad_aggregate; out[nimg][nc] (getVectorLength() == numCentroids), raw counts, no normalisation.
+ *   k == 1 (hard)  bow[computeNearestCentroid(d)]++ per descriptor (AbstractFeatureAggregator.java:136-155; strict `<`: the first
+ *                  of several equally near centroids wins).
+ *   k  > 1 (soft)  nn = computeKNearestCentroids(d, k) (AFA:193-220), then bow[nn[j]]++ descriptorLength TIMES for each of the k
+ *                  indices (the inner loop BowAggregator.java:47-51, sic): every (descriptor, neighbour) hit adds dl -- reproduced,
+ *                  not "fixed".  Only the set of the k indices matters; which of several centroids tied at the k-th position
+ *                  belongs to it follows the bounded queue, i.e. assumption A1, as in mmidx_coarse_device (whose loop,
+ *                  IVFPQ.java:575-601, is AFA:193-220 line for line and which serves this path).
+ * All values are integers far below 2^53: the output is BIT-EXACT.  Counters are 32-bit hit counts (the x dl weight is applied once
+ * at the end): one word may take up to 2^32 - 1 hits of one image.
+ * create: MMIDX_ERR_INVALID_ARG, raised before any device call, for a null pointer, nc < 1, dl < 1, k < 1 (the LingPipe queue
+ * constructor throws) and k > nc (AFA:214-217 polls an emptied queue: NullPointerException); k > 5459 is MMIDX_ERR_UNSUPPORTED, also
+ * before any device call (the coarse stage's exact selection keeps k + 1 entries of 12 bytes in a 64 KiB LDS block); a null handle is refused the same way
+ * by every call but destroy.  The descriptor-length check of aggregate (AFA:72-79, "Descriptor length is incompatible with codebook centroid
+ * length!") belongs to the binding, which sees the arrays: mmidx_bow_get_dims (any pointer may be NULL) gives it the lengths.
+ * set_option: "exact" = 1: the assignment through the hidden handle's "exact_coarse" (fp64, no matrix-core bound); "hist_global" = 1:
+ * the global-memory histogram also where the LDS form applies (up to 40960 words); "chunk_images" = n: the host form takes n images
+ * per round (0 = automatic: the dense [chunk][nc] workspace stays under 1 GiB).  None of them changes a result.
+ * aggregate_device: asynchronous on `stream` except for two read-backs: the descriptor range of the call (desc_off[0],
+ * desc_off[nimg]: 16 bytes into pinned memory, one wait) and, for k == 1, the count inside mmidx_assign_device.
+ * threading: every call on a handle takes the handle's mutex, so calls from several threads are served one after the other; a
+ * _device call holds it while its work is enqueued, and a call on another stream than the one before first waits for that stream
+ * (the workspaces are shared).  max_desc (largest descriptor count of an image) is
+ * accepted for symmetry with mmidx_vlad_aggregate_device; no workspace is sized by it. */
+typedef struct mmidx_bow mmidx_bow;
+int mmidx_bow_create(int nc, int dl, int k, const double *codebook, int device, mmidx_bow **out);
+int mmidx_bow_destroy(mmidx_bow *b);
+int mmidx_bow_get_dims(const mmidx_bow *b, int *nc, int *dl, int *k);
+int mmidx_bow_set_option(mmidx_bow *b, const char *name, int value);
+int mmidx_bow_aggregate(mmidx_bow *b, int64_t nimg, const int64_t *desc_off, const double *descs, double *out);
+int mmidx_bow_aggregate_device(mmidx_bow *b, int64_t nimg, const int64_t *d_desc_off, const double *d_descs, int max_desc,
+                               double *d_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -47,7 +47,7 @@ class Stats(C.Structure):
 
 def build(force=False):
     """Compile the HIP library for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
-    srcs = [os.path.join(CSRC, f) for f in ("mmidx_api.hip", "mmidx_learn.hip", "mmidx_pca_learn.hip", "mmidx_small_solve.h", "mmidx_probe.hip", "mmidx_kernels.h", "mmidx_scan_grp.h", "mmidx_frontend.h", "mmidx_sharded.h")]
+    srcs = [os.path.join(CSRC, f) for f in ("mmidx_api.hip", "mmidx_bow.hip", "mmidx_learn.hip", "mmidx_pca_learn.hip", "mmidx_small_solve.h", "mmidx_probe.hip", "mmidx_kernels.h", "mmidx_scan_grp.h", "mmidx_frontend.h", "mmidx_sharded.h")]
     srcs.append(os.path.join(os.path.dirname(_HERE), "include", "mmidx.h"))
     stale = not os.path.exists(SO_PATH) or any(os.path.getmtime(s) > os.path.getmtime(SO_PATH) for s in srcs)
     if force or stale:
@@ -109,6 +109,12 @@ SIGNATURES = {
     "mmidx_vlad_vector_length": (C.c_int, [_vp, C.POINTER(C.c_int)]),
     "mmidx_vlad_aggregate": (C.c_int, [_vp, C.c_int64, _vp, _dp, _dp]),
     "mmidx_vlad_aggregate_device": (C.c_int, [_vp, C.c_int64, _vp, _dp, C.c_int, _dp, _vp]),
+    "mmidx_bow_create": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.POINTER(C.c_void_p)]),
+    "mmidx_bow_destroy": (C.c_int, [_vp]),
+    "mmidx_bow_get_dims": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "mmidx_bow_set_option": (C.c_int, [_vp, C.c_char_p, C.c_int]),
+    "mmidx_bow_aggregate": (C.c_int, [_vp, C.c_int64, _vp, _dp, _dp]),
+    "mmidx_bow_aggregate_device": (C.c_int, [_vp, C.c_int64, _vp, _dp, C.c_int, _dp, _vp]),
     "mmidx_linear_create": (C.c_int, [C.c_int, C.c_int64, C.c_int, C.POINTER(C.c_void_p)]),
     "mmidx_linear_destroy": (C.c_int, [_vp]),
     "mmidx_linear_add": (C.c_int, [_vp, C.c_int64, _dp]),

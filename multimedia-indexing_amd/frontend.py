@@ -3,6 +3,7 @@
   gr.iti.mklab.visual.dimreduction.PCA                        (J/dimreduction/PCA.java)
   gr.iti.mklab.visual.aggregation.VladAggregator              (J/aggregation/VladAggregator.java)
   gr.iti.mklab.visual.aggregation.VladAggregatorMultipleVocabularies
+  gr.iti.mklab.visual.aggregation.BowAggregator               (J/aggregation/BowAggregator.java)
 
 Projection = one batched f64-MFMA GEMM, aggregation = one block per image.  The PCA basis is learned on the
 GPU as well (addSample / addSamples, computeBasis, savePCAToFile: `mmidx_pca_learn_*`, a Gram matrix on the f64
@@ -227,12 +228,83 @@ class VladAggregator(VladAggregatorMultipleVocabularies):
         super().__init__([codebook], normalizationsOn=False, device=device)
 
 
+class BowAggregator:
+    """BowAggregator(double[][] codebook) / BowAggregator(double[][] codebook, int k), BowAggregator.java:24-37: raw bag-of-words
+    counts, hard (k = 1) or soft over the k nearest centroids -- where every (descriptor, neighbour) hit adds descriptorLength, as
+    the reference's inner loop does (:47-51).  Bit-exact; no normalisation."""
+
+    def __init__(self, codebook, k=1, device=0):
+        cb = _f64(codebook)
+        if cb.ndim != 2:
+            raise MmidxError(N.ERR_INVALID_ARG, "the codebook is a [numCentroids][descriptorLength] array")
+        self.numCentroids, self.descriptorLength, self.k = int(cb.shape[0]), int(cb.shape[1]), int(k)
+        h = C.c_void_p()
+        N.check(N.lib().mmidx_bow_create(self.numCentroids, self.descriptorLength, self.k, cb.ctypes.data, device, C.byref(h)))
+        self._h = h
+
+    def getVectorLength(self):
+        return self.numCentroids
+
+    def getNumCentroids(self):
+        return self.numCentroids
+
+    def getDescriptorLength(self):
+        return self.descriptorLength
+
+    def _rows(self, d):
+        """one image's descriptors as [n][descriptorLength]; AbstractFeatureAggregator.aggregate's check, AFA:72-79"""
+        if d is None or len(d) == 0:
+            return None
+        a = _f64(d)
+        if a.ndim != 2 or a.shape[1] != self.descriptorLength:
+            raise MmidxError(N.ERR_WRONG_DIM, "Descriptor length is incompatible with codebook centroid length!")
+        return a
+
+    def aggregate_batch(self, descriptor_sets):
+        """descriptor_sets: list of [n_i][descriptorLength] arrays (n_i may be 0) -> [nimg][numCentroids]."""
+        rows = [self._rows(d) for d in descriptor_sets]
+        nimg = len(rows)
+        off = np.zeros(nimg + 1, np.int64)
+        for i, a in enumerate(rows):
+            off[i + 1] = off[i] + (0 if a is None else a.shape[0])
+        descs = np.zeros((max(int(off[-1]), 1), self.descriptorLength))
+        for i, a in enumerate(rows):
+            if a is not None:
+                descs[off[i]:off[i + 1]] = a
+        out = np.zeros((nimg, self.numCentroids))
+        N.check(N.lib().mmidx_bow_aggregate(self._h, nimg, off.ctypes.data, descs.ctypes.data, out.ctypes.data))
+        return out
+
+    def aggregate(self, descriptors):
+        """BowAggregator.aggregateInternal(double[][]), :39-74"""
+        return self.aggregate_batch([descriptors])[0]
+
+    def set_option(self, name, value):
+        """measurement / test switches, none changes a result: "exact" = 1 (fp64 assignment), "hist_global" = 1 (the global-memory
+        histogram also where the LDS form applies), "chunk_images" = n (images per round of the host form, 0 = automatic)"""
+        N.check(N.lib().mmidx_bow_set_option(self._h, name.encode(), int(value)))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            N.lib().mmidx_bow_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class ImageVectorizer:
     """Batch form of ImageVectorization.transformToVector (J/vectorization/ImageVectorization.java:169-208):
     descriptors -> VLAD -> PCA projection in one native call (`mmidx_vectorize`), replacing the reference's
     per-image thread pool (ImageVectorizer.java:123-126); the 8192-d VLAD vectors never leave the GPU."""
 
     def __init__(self, aggregator, pca):
+        if not isinstance(aggregator, VladAggregatorMultipleVocabularies):  # (mmidx_vectorize takes a mmidx_vlad handle and nothing else)
+            raise MmidxError(N.ERR_INVALID_ARG, "ImageVectorizer needs a VLAD aggregator (ImageVectorization is VLAD-only), got "
+                             + type(aggregator).__name__)
         if aggregator.getVectorLength() != pca.sampleSize:
             raise MmidxError(N.ERR_WRONG_DIM, "aggregator vector length does not match the PCA sample size")
         self.aggregator, self.pca = aggregator, pca

@@ -114,6 +114,16 @@ public final class MmidxNative {
 	public static native void vladAggregate(long vlad, long pca, int descriptorLength, int outLen, long[] descOff,
 			double[] descriptors, double[] out) throws Exception;
 
+	/* ---- bag of words (mmidx_bow_*): BowAggregator.aggregateInternal, k = 1 hard, k > 1 soft ---- */
+	public static native long bowCreate(int numCentroids, int descriptorLength, int k, double[] codebook, int device)
+			throws Exception;
+
+	public static native void bowDestroy(long bow);
+
+	/** out[nimg][numCentroids]; descriptorLength and outLen are checked against the native object */
+	public static native void bowAggregate(long bow, int descriptorLength, int outLen, long[] descOff,
+			double[] descriptors, double[] out) throws Exception;
+
 	private MmidxNative() {
 	}
 }

@@ -14,7 +14,7 @@
  *   gcc -shared -fPIC -I$JAVA_HOME/include -I$JAVA_HOME/include/linux -I../../include \
  *       mmidx_jni.c -o libmmidx_jni.so -L../csrc -lmmidx_hip
  * Java side: java/gr/iti/mklab/visual/datastructures/{MmidxNative,GpuIVFPQ,GpuPQ,GpuLinear}.java,
- *            java/gr/iti/mklab/visual/dimreduction/GpuPCA.java, java/gr/iti/mklab/visual/aggregation/GpuVladAggregator.java
+ *            java/gr/iti/mklab/visual/dimreduction/GpuPCA.java, java/gr/iti/mklab/visual/aggregation/{GpuVladAggregator,GpuBowAggregator}.java
  */
 #include <jni.h>
 #include <stdint.h>
@@ -589,6 +589,66 @@ JNIEXPORT void JNICALL JFN(vladAggregate)(JNIEnv *env, jclass c, jlong v, jlong 
     o_ = (*env)->GetDoubleArrayElements(env, out, NULL);
     if (pca) CHECK(mmidx_vectorize((mmidx_vlad *)(intptr_t)v, (mmidx_pca *)(intptr_t)pca, nimg, (const int64_t *)off_, d_, o_));
     else CHECK(mmidx_vlad_aggregate((mmidx_vlad *)(intptr_t)v, nimg, (const int64_t *)off_, d_, o_));
+done:
+    (*env)->ReleaseLongArrayElements(env, descOff, off_, JNI_ABORT);
+    (*env)->ReleaseDoubleArrayElements(env, descs, d_, JNI_ABORT);
+    (*env)->ReleaseDoubleArrayElements(env, out, o_, 0);
+}
+
+/* ---- bag of words: BowAggregator.aggregateInternal (BowAggregator.java:39-74), hard (k = 1) and soft ---------------- */
+JNIEXPORT jlong JNICALL JFN(bowCreate)(JNIEnv *env, jclass c, jint nc, jint dl, jint k, jdoubleArray codebook, jint device) {
+    mmidx_bow *b = NULL;
+    jdouble *cb_;
+    (void)c;
+    if (nc < 1 || dl < 1) { /* (the library says so as well; the array check below needs a sane product first) */
+        throw_msg(env, "java/lang/IllegalArgumentException", "the codebook is empty");
+        return 0;
+    }
+    if (bad_len(env, codebook, (int64_t)nc * dl, 0, "codebook")) return 0;
+    cb_ = (*env)->GetDoubleArrayElements(env, codebook, NULL);
+    CHECK(mmidx_bow_create(nc, dl, k, cb_, device, &b));
+done:
+    (*env)->ReleaseDoubleArrayElements(env, codebook, cb_, JNI_ABORT);
+    return (jlong)(intptr_t)b;
+}
+JNIEXPORT void JNICALL JFN(bowDestroy)(JNIEnv *env, jclass c, jlong b) {
+    (void)env;
+    (void)c;
+    mmidx_bow_destroy((mmidx_bow *)(intptr_t)b);
+}
+/* aggregate for nimg images: descOff[nimg + 1] delimits each image's descriptors in descs[total][dl]; out[nimg][numCentroids].
+ * dl and outLen are what the Java wrapper believes: both are checked against mmidx_bow_get_dims. */
+JNIEXPORT void JNICALL JFN(bowAggregate)(JNIEnv *env, jclass c, jlong b, jint dl, jint outLen, jlongArray descOff, jdoubleArray descs,
+                                         jdoubleArray out) {
+    jint nimg;
+    jlong *off_;
+    jdouble *d_, *o_;
+    (void)c;
+    if (bad_len(env, descOff, 1, 0, "descOff")) return;
+    nimg = (*env)->GetArrayLength(env, descOff) - 1;
+    off_ = (*env)->GetLongArrayElements(env, descOff, NULL);
+    {   /* descriptor length and output length from the native object; the offsets must be non-decreasing from 0 */
+        int nn = 0, dn = 0, bad = 0;
+        jint i;
+        if (mmidx_bow_get_dims((const mmidx_bow *)(intptr_t)b, &nn, &dn, NULL) != MMIDX_OK) bad = 1;
+        if (!bad && (dn != dl || nn != outLen)) bad = 1;
+        if (!bad && off_[0] != 0) bad = 2;
+        for (i = 0; !bad && i < nimg; i++)
+            if (off_[i + 1] < off_[i]) bad = 2;
+        if (bad) {
+            throw_msg(env, "java/lang/IllegalArgumentException",
+                      bad == 2 ? "descOff must start at 0 and be non-decreasing" : "descriptor / output lengths differ from the native object's");
+            (*env)->ReleaseLongArrayElements(env, descOff, off_, JNI_ABORT);
+            return;
+        }
+    }
+    if (bad_len(env, descs, (int64_t)off_[nimg] * dl, 0, "descriptors") || bad_len(env, out, (int64_t)nimg * outLen, 0, "out")) {
+        (*env)->ReleaseLongArrayElements(env, descOff, off_, JNI_ABORT);
+        return;
+    }
+    d_ = (*env)->GetDoubleArrayElements(env, descs, NULL);
+    o_ = (*env)->GetDoubleArrayElements(env, out, NULL);
+    CHECK(mmidx_bow_aggregate((mmidx_bow *)(intptr_t)b, nimg, (const int64_t *)off_, d_, o_));
 done:
     (*env)->ReleaseLongArrayElements(env, descOff, off_, JNI_ABORT);
     (*env)->ReleaseDoubleArrayElements(env, descs, d_, JNI_ABORT);
