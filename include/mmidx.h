@@ -339,40 +339,50 @@ typedef struct mmidx_stats {
  * events around pass A: passa_ms / passa_launches -- an event record is a ~5 us bubble in the stream, so a throughput
  * run carries as few as its roofline figure needs) */
 int mmidx_set_profiling(mmidx_index *h, int enabled);
-/* measurement switches; results are identical in every setting.  "exhaustive" = 1: every probed
- * code is read and summed in fp64 (no lower-bound filter, no coarse-bound probe pruning) -- the
- * configuration the HBM roofline of the scan kernel is quoted on; "no_filter", "no_bound",
- * "exact_coarse" switch the individual devices (DESIGN.md sections 5.2, 5.4, 5.5); "combine" = 0:
- * concurrent mmidx_search callers are served one at a time instead of together (section 5.11).
- * A/B and test switches: "coarse_v1" (K1c/K1d instead of K1e/K1f), "coarse_fused" (K1f as one kernel instead of
- * front end + selection), "coarse_nodma" (K1e with register staging
- * instead of the LDS-DMA kernel), "passa_hist" (1 / 0 / -1: K3h always / never / for long lists), "passa_wide" (K3h with
- * 512-thread blocks), "passa_prefix", "no_grp" (pass B through K3f only), "grp_blocks",
- * "passb_main_grid", "no_item_compaction", "passa_item_min", "passa_item_margin" (a shard's pass-A item list,
- * section 6), "smin_pre" (K3s, the certified Smin of every far pair in front of pass B's sort, section 5.15: 1 always, 0 never,
- * -1 = default: by the figures the device reported for the call before), "smin_valu" (1: K3s with packed VALU FMAs instead of
- * the matrix cores), "smin_bf16" (0: without K3s's bf16 first stage), "coarse_dma_kc" (0: long vectors through K1e's register staging instead of the
- * LDS-DMA kernel), "no_union" (K3g's instances that rank the union of the verified candidates: -1 always, 1 never, 0 hint).  On a sharded handle: "shard_exchange" (0: partial lists stored into the owners' buffers over xGMI, 1: ncclSend /
- * ncclRecv), "tie_slots" (flagged queries per owner and replay round, 0 = no replay), "shard_max_round"; every other option goes
- * to every shard.  Round 5: "no_split_table" (1: an exact table of twice the LDS -- m = 128 byte codes -- stays in global scratch instead
- * of being taken in two sweeps with half of it in LDS, k_scan_split).  Round 4: "no_mfma" (1: pass B through K3g / K3f instead of the matrix-core bound K3m / K3mk), "mfma_sub" (codes per
- * work item of K3m / K3mk, 0 = sized from the call), "mfma_qcap" (survivor records per launch, K3ma's record list included; a small value sends queries through the
- * redo path), "passa_mfma_icnt_sat" (test switch: the point where K3ma's per-item record prefix saturates, 0 = default 0xFFFFFFFF;
- * every item that reaches it sends its queries through the redo path), "mfma_blocks", "mfma_kc_v1" (1: K3mk without LDS-DMA, k_scan_mfma_kc, also where k_scan_mfma_kc2 applies),
- * "mfma_kc_tpw" (8 / 16 code tiles per wave of k_scan_mfma_kc), "lut_pre" (pass A's tables built by their own kernel),
- * "coarse_wave_sel" (0: the coarse stage's exact selection always by a block per query instead of k_coarse_front_sel),
- * "passb_small" (0: pass B through K3m / K3g also when the call before kept at most 64 pairs; default 1: K3f's looping kernel alone,
- * one launch), "passa_mfma" (round 5, K3ma: pass A through the matrix-core bound in two sweeps -- 1 wherever the shape allows, 0 never,
- * -1 = default: from 8 queries per list of a long-list index),
- * "shard_route_host" (round 5; 1: mmidx_add_vectors_sliced_device sends its records through the host as before round 5 instead of routing
- * them between the devices),
- * "shard_pipeline" (1: the query exchange of a sharded handle on a second stream / communicator; the default for in-process shards, off
- * by default on two or more physical devices until a multi-device run has passed).  Round 6: "passa_q" (K3q, pass A decided on packed
- * integer table sums with four queries of a nearest list per block, mmidx_scan_q.h: 1 wherever the shape allows -- IVFPQ, byte codes,
- * ks = 256, m = 16, dsub in {4, 8, 16}, k <= 151 --, 0 never, -1 = default: from 1.25 queries per non-empty list of a long-list index),
- * "host_slots" (default 1: host-pointer searches of more than 4096 queries from several threads take one of three slots -- own copy
- * stream and buffers -- and hold the handle's lock only while their kernels are enqueued; 0: one request at a time).
- * None of them changes a result. */
+/* Runtime switches for measurements and tests, by name.  None of them changes a result (DESIGN.md section 5 describes the
+ * devices they switch).  An unknown name is MMIDX_ERR_INVALID_ARG.  One line per name, the text of the table kOptions of
+ * csrc/mmidx_api.hip; "(env MMIDX_X)" marks the ones mmidx_create also reads from the environment.
+ *   "exhaustive": sets no_filter and no_bound together: every probed code is read and summed in fp64
+ *   "no_filter": exact scan only, no lower-bound filter (from the environment it also sets no_bound) (env MMIDX_NO_FILTER)
+ *   "no_bound": no coarse-bound pruning of probes (env MMIDX_NO_BOUND)
+ *   "exact_coarse": coarse stage and assignment by fp64 distances to every centroid (K1a/K1b) (env MMIDX_EXACT_COARSE)
+ *   "debug_sync": synchronise after every stage, report the first failing one and per-stage figures on stderr (env MMIDX_DEBUG_SYNC)
+ *   "combine": concurrent mmidx_search callers are served together (default 1)
+ *   "host_slots": large host-pointer requests: up to three callers in flight (default 1); 0 = one at a time through the combiner's queue
+ *   "coarse_v1": coarse stage by K1c/K1d (fp32 MFMA, full distance matrix) instead of K1e/K1f (env MMIDX_COARSE_V1)
+ *   "coarse_fused": K1f as one kernel (front end + selection)
+ *   "coarse_dma_kc": K1e with LDS-DMA also for vectors of several k chunks, Dp a multiple of 128 (default 1)
+ *   "coarse_wave_sel": the coarse stage's exact selection by one wave per query where its tile applies (default 1); 0 = always a block per query
+ *   "passa_q": pass A by K3q: 1 always (where the shape allows), 0 never, -1 = from 1.25 queries per non-empty list of a long-list index (default); K3q is tested before passa_hist, so passa_q = 0 is needed for passa_hist to take effect on long-list m = 16 indexes
+ *   "passa_mfma": pass A by K3ma: 1 always (where the shape allows), 0 never, -1 = from 8 queries per list of a long-list index (default)
+ *   "passa_mfma_wide": K3ma's small items through the eight-wave instance (default 1); 0 = the four-wave instance alone
+ *   "passa_mfma_icnt_sat": where K3ma's record prefix saturates (0 = 0xFFFFFFFF); tests force the overflow path
+ *   "passa_hist": pass A by K3h: 1 always, 0 never, -1 = lists of >= 4096 codes on average (default) (env MMIDX_PASSA_HIST)
+ *   "passa_wide": K3h with 512-thread blocks (env MMIDX_PASSA_WIDE)
+ *   "passa_item_min": fewest queries per call for a shard's pass A to launch over the queries with a non-empty nearest list only (default 4096)
+ *   "passa_item_margin": blocks that launch takes beyond 1.15 x the expected count (default 1024; tests: 0)
+ *   "smin_pre": K3s (k_pair_smin) in front of pass B's counting sort: 1 always, 0 never, -1 = by the device-reported figures of the call before (default)
+ *   "smin_bf16": K3s's bf16 first stage for 16-dimensional sub-quantizers (default 1); 0 = fp32 only
+ *   "smin_valu": K3s with packed VALU FMAs instead of the matrix cores
+ *   "no_mfma": no matrix-core bounds: pass B through K3g / K3f instead of K3m, and no K3ma in pass A
+ *   "no_grp": pass B through K3f (one block per query and list) instead of the grouped K3g
+ *   "no_union": K3g without the per-query histogram that lowers thresholds from the union over lists; -1 = with it always
+ *   "no_split_table": m = 128: the table-in-global-scratch kernels instead of k_scan_split
+ *   "passb_small": pass B through K3f when the like call before kept at most 64 pairs (default 1)
+ *   "passb_main_grid": > 0: fixed size of K3f's main launch (tests force the looping tail kernel)
+ *   "mfma_sub": codes per K3m item (0 = sized from the call)
+ *   "mfma_qcap": survivor records per K3m launch (0 = sized from the call); tests force the redo path
+ *   "mfma_blocks": persistent blocks of K3m (0 = occupancy x CUs)
+ *   "mfma_kc_v1": K3mk without LDS-DMA (k_scan_mfma_kc) also where k_scan_mfma_kc2 applies
+ *   "mfma_kc_tpw": code tiles per wave of K3mk: 8 (default) or 16
+ *   "flat_chunk": codes per chunk of a flat PQ list, from 4096 (0 = sized from the batch)
+ * A sharded handle passes these on to every shard and has options of its own (csrc/mmidx_sharded.h):
+ *   "shard_exchange": 0 = partial lists stored into the owners' buffers over xGMI, 1 = ncclSend / ncclRecv
+ *   "tie_slots": flagged queries per owner and replay round (0 = no replay)
+ *   "shard_max_round": queries per collective round
+ *   "combine": as above, for the group's own combiner
+ *   "shard_route_host": 1 = mmidx_add_vectors_sliced_device sends its records through the host instead of routing them between the devices
+ *   "shard_pipeline": 1 = the query exchange on a second stream / communicator (the default for in-process shards; off by default on two or more physical devices) */
 int mmidx_set_option(mmidx_index *h, const char *name, int value);
 int mmidx_get_stats(mmidx_index *h, mmidx_stats *out);
 /* Which kernel family served each stage of the most recent search sub-batch of this handle (ABI version 7), as text:

@@ -173,6 +173,75 @@ int combiner_submit(Combiner &c, SearchReq &me, int64_t max_q, Serve serve) {
 
 }  // namespace
 
+// ---- runtime switches ------------------------------------------------------------------------------------------------------
+// A/B and test switches of a handle, set by name through mmidx_set_option; a few are also read from the environment by
+// mmidx_create.  kOptions is the one description of each: name, field, how a value is normalised, environment twin, meaning
+// (include/mmidx.h lists the same names).
+struct Switches {
+    int no_filter = 0, no_bound = 0, exact_coarse = 0, debug_sync = 0;
+    int coarse_v1 = 0, coarse_fused = 0, coarse_dma_kc = 1, coarse_wave_sel = 1;
+    int passa_q = -1, passa_mfma = -1, passa_mfma_wide = 1, passa_mfma_icnt_sat = 0, passa_hist = -1, passa_wide = 0;
+    int passa_item_min = 4096, passa_item_margin = 1024;
+    int smin_pre = -1, smin_bf16 = 1, smin_valu = 0;
+    int no_mfma = 0, no_grp = 0, no_union = 0, no_split_table = 0, passb_small = 1, passb_main_grid = 0;
+    int mfma_sub = 0, mfma_qcap = 0, mfma_blocks = 0, mfma_kc_v1 = 0, mfma_kc_tpw = 8;
+    int flat_chunk = 0, host_slots = 1;
+};
+
+enum OptNorm {
+    OPT_BOOL,     // value != 0
+    OPT_TRI,      // -1 (negative), 0 or 1
+    OPT_MIN0,     // max(0, value)
+    OPT_RAW,      // as given
+    OPT_8_OR_16,  // 16 or, for anything else, 8
+};
+
+struct OptionRow {
+    const char *name;
+    int Switches::*field;  // null: mmidx_set_option places the value itself ("exhaustive", "combine")
+    OptNorm norm;
+    const char *env;       // environment variable read at create, or null
+    const char *what;
+};
+
+const OptionRow kOptions[] = {
+    {"exhaustive", nullptr, OPT_BOOL, nullptr, "sets no_filter and no_bound together: every probed code is read and summed in fp64"},
+    {"no_filter", &Switches::no_filter, OPT_BOOL, "MMIDX_NO_FILTER", "exact scan only, no lower-bound filter (from the environment it also sets no_bound)"},
+    {"no_bound", &Switches::no_bound, OPT_BOOL, "MMIDX_NO_BOUND", "no coarse-bound pruning of probes"},
+    {"exact_coarse", &Switches::exact_coarse, OPT_BOOL, "MMIDX_EXACT_COARSE", "coarse stage and assignment by fp64 distances to every centroid (K1a/K1b)"},
+    {"debug_sync", &Switches::debug_sync, OPT_BOOL, "MMIDX_DEBUG_SYNC", "synchronise after every stage, report the first failing one and per-stage figures on stderr"},
+    {"combine", nullptr, OPT_BOOL, nullptr, "concurrent mmidx_search callers are served together (default 1)"},
+    {"host_slots", &Switches::host_slots, OPT_BOOL, nullptr, "large host-pointer requests: up to three callers in flight (default 1); 0 = one at a time through the combiner's queue"},
+    {"coarse_v1", &Switches::coarse_v1, OPT_BOOL, "MMIDX_COARSE_V1", "coarse stage by K1c/K1d (fp32 MFMA, full distance matrix) instead of K1e/K1f"},
+    {"coarse_fused", &Switches::coarse_fused, OPT_BOOL, nullptr, "K1f as one kernel (front end + selection)"},
+    {"coarse_dma_kc", &Switches::coarse_dma_kc, OPT_BOOL, nullptr, "K1e with LDS-DMA also for vectors of several k chunks, Dp a multiple of 128 (default 1)"},
+    {"coarse_wave_sel", &Switches::coarse_wave_sel, OPT_BOOL, nullptr, "the coarse stage's exact selection by one wave per query where its tile applies (default 1); 0 = always a block per query"},
+    {"passa_q", &Switches::passa_q, OPT_RAW, nullptr, "pass A by K3q: 1 always (where the shape allows), 0 never, -1 = from 1.25 queries per non-empty list of a long-list index (default); "
+     "K3q is tested before passa_hist, so passa_q = 0 is needed for passa_hist to take effect on long-list m = 16 indexes"},
+    {"passa_mfma", &Switches::passa_mfma, OPT_RAW, nullptr, "pass A by K3ma: 1 always (where the shape allows), 0 never, -1 = from 8 queries per list of a long-list index (default)"},
+    {"passa_mfma_wide", &Switches::passa_mfma_wide, OPT_BOOL, nullptr, "K3ma's small items through the eight-wave instance (default 1); 0 = the four-wave instance alone"},
+    {"passa_mfma_icnt_sat", &Switches::passa_mfma_icnt_sat, OPT_MIN0, nullptr, "where K3ma's record prefix saturates (0 = 0xFFFFFFFF); tests force the overflow path"},
+    {"passa_hist", &Switches::passa_hist, OPT_RAW, "MMIDX_PASSA_HIST", "pass A by K3h: 1 always, 0 never, -1 = lists of >= 4096 codes on average (default)"},
+    {"passa_wide", &Switches::passa_wide, OPT_RAW, "MMIDX_PASSA_WIDE", "K3h with 512-thread blocks"},
+    {"passa_item_min", &Switches::passa_item_min, OPT_RAW, nullptr, "fewest queries per call for a shard's pass A to launch over the queries with a non-empty nearest list only (default 4096)"},
+    {"passa_item_margin", &Switches::passa_item_margin, OPT_RAW, nullptr, "blocks that launch takes beyond 1.15 x the expected count (default 1024; tests: 0)"},
+    {"smin_pre", &Switches::smin_pre, OPT_TRI, nullptr, "K3s (k_pair_smin) in front of pass B's counting sort: 1 always, 0 never, -1 = by the device-reported figures of the call before (default)"},
+    {"smin_bf16", &Switches::smin_bf16, OPT_BOOL, nullptr, "K3s's bf16 first stage for 16-dimensional sub-quantizers (default 1); 0 = fp32 only"},
+    {"smin_valu", &Switches::smin_valu, OPT_BOOL, nullptr, "K3s with packed VALU FMAs instead of the matrix cores"},
+    {"no_mfma", &Switches::no_mfma, OPT_BOOL, nullptr, "no matrix-core bounds: pass B through K3g / K3f instead of K3m, and no K3ma in pass A"},
+    {"no_grp", &Switches::no_grp, OPT_BOOL, nullptr, "pass B through K3f (one block per query and list) instead of the grouped K3g"},
+    {"no_union", &Switches::no_union, OPT_TRI, nullptr, "K3g without the per-query histogram that lowers thresholds from the union over lists; -1 = with it always"},
+    {"no_split_table", &Switches::no_split_table, OPT_BOOL, nullptr, "m = 128: the table-in-global-scratch kernels instead of k_scan_split"},
+    {"passb_small", &Switches::passb_small, OPT_BOOL, nullptr, "pass B through K3f when the like call before kept at most 64 pairs (default 1)"},
+    {"passb_main_grid", &Switches::passb_main_grid, OPT_RAW, nullptr, "> 0: fixed size of K3f's main launch (tests force the looping tail kernel)"},
+    {"mfma_sub", &Switches::mfma_sub, OPT_MIN0, nullptr, "codes per K3m item (0 = sized from the call)"},
+    {"mfma_qcap", &Switches::mfma_qcap, OPT_MIN0, nullptr, "survivor records per K3m launch (0 = sized from the call); tests force the redo path"},
+    {"mfma_blocks", &Switches::mfma_blocks, OPT_MIN0, nullptr, "persistent blocks of K3m (0 = occupancy x CUs)"},
+    {"mfma_kc_v1", &Switches::mfma_kc_v1, OPT_BOOL, nullptr, "K3mk without LDS-DMA (k_scan_mfma_kc) also where k_scan_mfma_kc2 applies"},
+    {"mfma_kc_tpw", &Switches::mfma_kc_tpw, OPT_8_OR_16, nullptr, "code tiles per wave of K3mk: 8 (default) or 16"},
+    {"flat_chunk", &Switches::flat_chunk, OPT_RAW, nullptr, "codes per chunk of a flat PQ list, from 4096 (0 = sized from the batch)"},
+};
+
 struct ShardGroup;  // mmidx_sharded.h
 
 struct mmidx_index {
@@ -185,27 +254,14 @@ struct mmidx_index {
     int nlists = 1;
     size_t code_bytes = 1;  // per sub-quantizer
     bool coarse_set = false, pq_set = false;
-    bool no_filter = false;  // MMIDX_NO_FILTER=1: exact scan only (A/B switch for measurements)
-    bool no_bound = false;   // MMIDX_NO_BOUND=1: no coarse-bound pruning of probes
-    bool debug_sync = false; // MMIDX_DEBUG_SYNC=1
-    bool passa_512 = false;  // MMIDX_PASSA_512=1: pass A with 512-thread blocks
+    Switches sw;  // every runtime switch (kOptions above)
     int32_t *pin_hint = nullptr;  // pinned host word: pass B's item count of the previous call (launch sizing hint)
-    int passb_main_grid = 0;      // > 0: fixed size of pass B's main launch (tests: force the looping tail kernel)
-    int passa_hist = -1;     // MMIDX_PASSA_HIST: 1 = always use K3h in pass A, 0 = never, -1 = lists of >= 4096 codes on average
-    int passa_wide = 0;      // option "passa_wide" / MMIDX_PASSA_WIDE=1: K3h with 512-thread blocks
-    int passa_prefix = 0;    // MMIDX_PASSA_PREFIX=n: pass A scans n codes exactly, the rest of the list filtered
-    bool passa_su2 = false;  // MMIDX_PASSA_SU2=1: pass A with 2 codes per thread per segment (A/B switch)
-    bool passa_filter = false;  // MMIDX_PASSA_FILTER=1
-    bool no_seed = true;        // MMIDX_SEED=1: pass A with the seeded scan K3s (measured slower than K3: 1.45 vs 1.22 ms
-                                // per 8192 queries -- one block per query is latency-bound, not LDS-bound; kept for study)
     double rmax = 0.0;       // sqrt(sum_s max_j ||pq[s][j]||^2) * (1 + 1e-12)
     double rot_shrink = 0.0; // RandomRotation: |v R| >= rot_shrink |v| for every v (0: the matrix is too far from orthogonal to say)
     // K3g (grouped pass B, mmidx_scan_grp.h): fp32 copy of the codebook (entry index innermost), ||p||^2 and their maxima
     float *d_pq32T = nullptr, *d_pn32 = nullptr;
     double *d_pnmax = nullptr;
     bool grp_valid = false;  // tables match the current quantizers
-    int no_grp = 0;          // option "no_grp" = 1: pass B through K3f only (A/B switch)
-    int grp_blocks = 0;      // option "grp_blocks": persistent blocks of K3g (0 = occupancy x CUs)
     int num_cus = 0;
     hipStream_t stream = nullptr;
     std::mutex mu;
@@ -228,7 +284,6 @@ struct mmidx_index {
         bool busy = false;
     };
     static constexpr int N_HOST_SLOTS = 3;
-    int host_slots_on = 1;  // option "host_slots": 0 = large requests through the combiner's queue, one at a time (rounds 1-5)
     HostSlot host_slot[N_HOST_SLOTS];
     std::mutex slot_mu;
     std::condition_variable slot_cv;
@@ -241,15 +296,7 @@ struct mmidx_index {
     unsigned short *d_Ch = nullptr, *d_Cl = nullptr;
     double *d_cn_pad = nullptr;  // [Cp] |c|^2, +inf on the padding rows
     int Cp = 0, Dp = 0;          // C rounded up to 128, D rounded up to 32
-    bool coarse_v1 = false;      // MMIDX_COARSE_V1=1: K1c/K1d (fp32 MFMA, full d~ matrix) instead
-    bool coarse_fused = false;   // option "coarse_fused": K1f as one kernel (front end + selection), as in round 1 (A/B switch)
-    int coarse_dma_kc = 1;       // option "coarse_dma_kc": K1e' with LDS-DMA also for vectors of several k chunks (Dp a multiple of 128)
-    bool coarse_nodma = false;   // option "coarse_nodma": K1e with register staging also when Dp == 128 (A/B switch)
-    bool no_item_compaction = false;  // option "no_item_compaction": a shard's pass A over every query (A/B switch)
-    int passa_item_min = 4096;        // option "passa_item_min": fewest queries per call for that compaction
-    int passa_item_margin = 1024;     // option "passa_item_margin": blocks launched beyond 1.15 x the expected count (tests: 0)
     double cn_max = 0.0, cnorm_max = 0.0;
-    bool exact_coarse = false;  // MMIDX_EXACT_COARSE=1: fp64 distances to every centroid (K1a/K1b)
     bool cdsel_valid = false;   // ws_cdsel holds the selected cells' exact distances for the current batch
     int32_t *d_perm = nullptr;
 
@@ -297,14 +344,8 @@ struct mmidx_index {
     DevBuf<double> ws_flatlut;   // ... and the queries' exact lookup tables [nq][m][256] (k_flat_lut)
     DevBuf<u32> ws_ghist;        // K3g: per-query histogram of accepted candidates [nq][256] (thresholds from the union over lists)
     DevBuf<u64> ws_T0;           // ... and pass A's thresholds as the launch found them
-    int no_union = 0;            // option "no_union": K3g without that histogram (A/B switch)
-    int smin_pre = -1;           // option "smin_pre": K3s (k_pair_smin) in front of pass B's counting sort: 1 always, 0 never, -1 when the
-                                 // device-reported figures of the call before say that at least half of the pairs end at Smin >= T
-    int smin_bf16 = 1;           // option "smin_bf16": K3s's bf16 first stage for 16-dimensional sub-quantizers (0: fp32 only)
-    int smin_valu = 0;           // option "smin_valu": K3s with packed VALU FMAs instead of the matrix cores (A/B)
     bool pre_on = false;         // the call before ran K3s (which pair of hint words describes it)
     int pre_skip = 0;            // calls K3s still sits out in front of K3mk (it removed next to nothing the last time)
-    int flat_chunk = 0;          // option "flat_chunk": codes per chunk of a flat PQ list (0 = sized from the batch)
     // K3m (mmidx_scan_mfma.h): pass B as a certified lower bound on the matrix cores
     unsigned short *d_pq16 = nullptr;  // fp16 codebook [D / 8][256][8], scaled by 2^pq_ep
     double *d_pn64 = nullptr;          // [m][256] ||p_sj||^2
@@ -312,27 +353,16 @@ struct mmidx_index {
     bool xn_valid = false, mfma_valid = false, mfma_ok = false;
     int pq_ep = 0;
     double pq_maxabs = 0.0;            // largest |codebook element| (set_pq)
-    int no_mfma = 0;                   // option "no_mfma" = 1: pass B through K3g / K3f (A/B switch)
-    int no_split_table = 0;            // option "no_split_table" = 1: a table of twice the LDS (m = 128) stays in global scratch (A/B switch)
-    int mfma_sub = 0;                  // option "mfma_sub": codes per K3m item (0 = sized from the call)
-    int mfma_qcap = 0;                 // option "mfma_qcap": survivor records per launch (0 = sized from the call; tests force the redo path)
-    int passa_mfma_icnt_sat = 0;       // option "passa_mfma_icnt_sat": where K3ma's record prefix saturates (0 = 0xFFFFFFFF; tests force the overflow path)
-    int mfma_blocks = 0;               // option "mfma_blocks": persistent blocks (0 = occupancy x CUs)
-    int lut_pre = -1;                  // option "lut_pre": pass A's tables built ahead of K3h by k_lut_pre: 1 always, 0 never, -1 = where it pays (m >= 32)
     DevBuf<double> ws_lutpre;
     DevBuf<uint4> ws_surv;
     DevBuf<double> ws_R;               // RandomRotation: the kept pairs' exact rotated residuals [pairs][D]
     DevBuf<u32> ws_defer;              // k_coarse_front_sel: count + list of the queries left to k_coarse_select_defer
-    int passb_small = 1;               // option "passb_small": 0 = pass B through K3m / K3g also when the call before kept at most 64 pairs
     int hint_calls = 0;                // IVF pass-B stages launched so far (pin_hint[0] describes the last one)
     int64_t hint_last_nq = -1, hint_prev_nq = -1;  // batch size and probes of the stage launched last / the one before it (whose count pin_hint[0] holds
     int hint_last_w = -1, hint_prev_w = -1;        //  while the current call is being enqueued): "passb_small" trusts the hint for a like call only
     DevBuf<unsigned short> ws_R16;     // K3mk: the kept pairs' fp16 residuals [pairs][D]
     DevBuf<double> ws_nrow;            // ... and ||r||^2
     double coarse_maxabs = 0.0;        // largest |centroid element| (set_coarse)
-    int coarse_wave_sel = 1;           // option "coarse_wave_sel": 0 = the coarse stage's exact selection always by k_coarse_select_list (a block per query)
-    int mfma_kc_v1 = 0;                // option "mfma_kc_v1": 1 = K3mk without LDS-DMA (k_scan_mfma_kc) also where k_scan_mfma_kc2 applies
-    int mfma_kc_tpw = 8;               // option "mfma_kc_tpw": code tiles per wave of K3mk (8 or 16)
     DevBuf<u32> ws_mfctl, ws_psnap;
     DevBuf<unsigned char> ws_redo;
     void *d_grpx = nullptr, *pin_grpx = nullptr;  // K3g's GrpExtra on the device and its pinned mirror
@@ -349,11 +379,8 @@ struct mmidx_index {
     const char *disp_coarse = "-", *disp_passa = "-", *disp_passb = "-", *disp_pre = "-";
     // K3ma (pass A on the matrix cores, mmidx_scan_mfma_a.h)
     hipEvent_t host_ev[4] = {nullptr, nullptr, nullptr, nullptr};  // mmidx_search (host buffers): the answers' slices on their way back
-    int passa_q = -1;                  // option "passa_q": K3q (mmidx_scan_q.h) 1 always (where the shape allows), 0 never, -1 = from 1.25 queries per non-empty list of a long-list index
     double *d_pqstat = nullptr;        // K3q: [m * dsub] mean_j p_sj[t], then [m] mean_j ||p_sj||^2
     float *d_pqT32 = nullptr;          // K3q: the transposed codebook in fp32, dimension pairs side by side [m][dsub / 2][256][2] (ks = 256, even dsub)
-    int passa_mfma = -1;               // option "passa_mfma": 1 always (where the shape allows), 0 never, -1 = from 8 queries per list of a long-list index
-    int a_wide = 1;                    // option "passa_mfma_wide": 0 = K3ma's sweeps by the four-wave instance alone (A/B switch)
     DevBuf<float> ws_acand;            // [pairs][pieces][256] sweep 1's kept accumulator values
     DevBuf<double2> ws_arowc;          // [pairs] upper-bound maps
     DevBuf<unsigned char> ws_abm;      // [items][stride] sweep 2's compare masks
@@ -565,8 +592,8 @@ int assign_device(mmidx_index *h, int64_t n, const double *dX, int32_t *d_cell, 
     if (n == 0) return MMIDX_OK;
     const int ivf = h->kind == MMIDX_KIND_IVFPQ;
     const size_t asg_lds = (size_t)((ASG_BM * (h->D + 2) + 3) & ~3) * 4 + (size_t)ASG_BK * ASG_BN * 4;
-    const bool split16 = h->d_Ch && !h->coarse_v1;  // (K6a' stages centroid tiles only: any vector length; K6a holds whole vectors in LDS)
-    if (ivf && !h->exact_coarse && (split16 || asg_lds <= 160 * 1024) && h->C >= 2) {
+    const bool split16 = h->d_Ch && !h->sw.coarse_v1;  // (K6a' stages centroid tiles only: any vector length; K6a holds whole vectors in LDS)
+    if (ivf && !h->sw.exact_coarse && (split16 || asg_lds <= 160 * 1024) && h->C >= 2) {
         // certified approximate assignment (bf16-split or fp32 MFMA) + exact redo of the flagged vectors
         constexpr int QT = 16;
         if (!split16) HIPCK(h->ws_Q32.reserve((size_t)n * h->D));
@@ -577,7 +604,7 @@ int assign_device(mmidx_index *h, int64_t n, const double *dX, int32_t *d_cell, 
         if (split16) {
             // bf16-split dot products on the matrix cores (K6a'), 5x the rate of the fp32 MFMA
             const size_t l16 = 2 * (size_t)G16_BC * G16_STRIDE;
-            const bool fromx = h->Dp <= G16_KC && (h->D % 8) == 0 && ((uintptr_t)dX & 15) == 0 && !getenv("MMIDX_ASSIGN_SPLIT");
+            const bool fromx = h->Dp <= G16_KC && (h->D % 8) == 0 && ((uintptr_t)dX & 15) == 0;
             if (fromx) {  // one k chunk: the kernel splits the fp64 rows itself (no k_split_bf16 round trip through HBM)
                 HIPCK(hipFuncSetAttribute((const void *)k_assign_gmin16_t<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l16));
                 hipLaunchKernelGGL(k_assign_gmin16_t<true>, dim3((unsigned)((n + G16_BQ - 1) / G16_BQ)), dim3(MMIDX_BLOCK), l16, st, (const __bf16 *)nullptr,
@@ -686,7 +713,7 @@ int launch_scan_t(const ScanParams &P, dim3 grid, size_t lds, hipStream_t st) {
     return MMIDX_OK;
 }
 
-// su = codes per thread per segment (1 or 2; 11 = 1 with 512-thread blocks); P.cap and lds sized for it
+// su = codes per thread per segment (1 or 2); P.cap and lds sized for it
 int launch_scan(const mmidx_index *h, const ScanParams &P, dim3 grid, size_t lds, hipStream_t st, int su = 2) {
     if (P.glut) {  // the table lives in global scratch (make_plan: it does not fit the LDS): generic kernels, LDS = vectors + candidates
         if ((size_t)grid.x * grid.y > h->glut_slots) return fail(MMIDX_ERR_UNSUPPORTED, "lookup-table scratch too small for %u x %u blocks", grid.x, grid.y);
@@ -694,7 +721,7 @@ int launch_scan(const mmidx_index *h, const ScanParams &P, dim3 grid, size_t lds
         const size_t l = lds - (size_t)h->m * h->ks * 8;
         // twice the LDS (m = 128 byte codes): two sweeps with half the table in LDS each (k_scan_split); cap >= K1 + 512 covers its
         // 512-code segments, a chunk's partial sums fit the block's table slot
-        if (!P.sdc_tt && !h->no_split_table && h->code_bytes == 1 && h->ks == 256 && h->m == 128 && P.chunk <= h->m * h->ks &&
+        if (!P.sdc_tt && !h->sw.no_split_table && h->code_bytes == 1 && h->ks == 256 && h->m == 128 && P.chunk <= h->m * h->ks &&
             l + (size_t)64 * 256 * 8 <= 160 * 1024) {
             const size_t sl = l + (size_t)64 * 256 * 8;
             HIPCK(hipFuncSetAttribute((const void *)k_scan_split<128, 512>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sl));
@@ -714,14 +741,6 @@ int launch_scan(const mmidx_index *h, const ScanParams &P, dim3 grid, size_t lds
         }
     }
     if (h->code_bytes == 1) {
-        if (su == 11) {  // one code per thread, 512-thread blocks
-            switch (h->m) {
-                case 8: return launch_scan_t<8, unsigned char, 1, 512>(P, grid, lds, st);
-                case 16: return launch_scan_t<16, unsigned char, 1, 512>(P, grid, lds, st);
-                case 32: return launch_scan_t<32, unsigned char, 1, 512>(P, grid, lds, st);
-                default: break;
-            }
-        }
         if (su == 1) {
             switch (h->m) {
                 case 8: return launch_scan_t<8, unsigned char, 1>(P, grid, lds, st);
@@ -755,11 +774,10 @@ bool coarse_certified(const mmidx_index *h, size_t *alds_out = nullptr, int *cch
     const size_t alds = sel_fixed + (size_t)std::max(cch, 1) * row_bytes;
     if (alds_out) *alds_out = alds;
     if (cch_out) *cch_out = cch;
-    return !h->exact_coarse && h->C >= MMIDX_BLOCK && h->w + 1 <= MMIDX_BLOCK && h->C <= 64 * MMIDX_BLOCK && h->w >= 1 && cch >= 1 && alds <= 64 * 1024;
+    return !h->sw.exact_coarse && h->C >= MMIDX_BLOCK && h->w + 1 <= MMIDX_BLOCK && h->C <= 64 * MMIDX_BLOCK && h->w >= 1 && cch >= 1 && alds <= 64 * 1024;
 }
 
 struct SearchPlan;
-int launch_scan_seeded(const mmidx_index *h, ScanParams P, const SearchPlan &pl, dim3 grid, hipStream_t st);
 int launch_scan_filtered(const mmidx_index *h, ScanParams P, const SearchPlan &pl, dim3 grid, hipStream_t st, int main_grid = 0);
 
 struct SearchPlan {
@@ -792,8 +810,8 @@ int make_plan(mmidx_index *h, int k, int64_t nq, SearchPlan &pl, bool need_coars
         chunk = nq >= 512 ? 65536 : 32768;
         // (with K3m behind it -- thresholds tighten from the survivors' upper bounds as the scan goes -- the exact, LDS-bound pass over
         //  chunk 0 can be half as long: cfg2 2.06 -> 1.93 ms per 4096 queries; 16384 and 8192 measure the same)
-        if (h->mfma_ok && !h->no_mfma) chunk = 32768;
-        if (h->flat_chunk >= 4096) chunk = std::min<int64_t>(h->flat_chunk, 1 << 23);  // option "flat_chunk" (A/B)
+        if (h->mfma_ok && !h->sw.no_mfma) chunk = 32768;
+        if (h->sw.flat_chunk >= 4096) chunk = std::min<int64_t>(h->sw.flat_chunk, 1 << 23);  // option "flat_chunk" (A/B)
     }
     const int64_t maxlen = std::max<int64_t>(h->max_list_len, 1);
     pl.chunk = (int)chunk;
@@ -847,7 +865,7 @@ int launch_filt_t(const mmidx_index *h, ScanParams P, dim3 grid, size_t lds, hip
         const int32_t seen = h->pin_hint ? *(volatile int32_t *)h->pin_hint : -1;
         const unsigned hint = seen >= 0 ? (unsigned)seen : worst;
         const unsigned want = main_grid > 0 ? (unsigned)main_grid
-                                            : (h->passb_main_grid > 0 ? (unsigned)h->passb_main_grid : 2u * hint + 2048u);
+                                            : (h->sw.passb_main_grid > 0 ? (unsigned)h->sw.passb_main_grid : 2u * hint + 2048u);
         g1 = std::min(worst, (want + 7u) & ~7u);
     }
     if (P.order && main_grid < 0) g1 = 0;  // (the looping kernel alone: what K3g hands back is normally nothing)
@@ -865,7 +883,7 @@ int launch_filt_t(const mmidx_index *h, ScanParams P, dim3 grid, size_t lds, hip
 
 // pass B: lower-bound filtered scan where it applies (byte codes, templated m), else the exact scan
 int launch_scan_filtered(const mmidx_index *h, ScanParams P, const SearchPlan &pl, dim3 grid, hipStream_t st, int main_grid) {
-    const bool ok = h->code_bytes == 1 && h->ks <= 256 && (h->m == 8 || h->m == 16 || h->m == 32) && !h->no_filter && !P.sdc_tt;
+    const bool ok = h->code_bytes == 1 && h->ks <= 256 && (h->m == 8 || h->m == 16 || h->m == 32) && !h->sw.no_filter && !P.sdc_tt;
     if (!ok) return launch_scan(h, P, grid, pl.lds, st);
     int cap = 1;
     while (cap < pl.K1 + MMIDX_VROUND) cap <<= 1;
@@ -878,14 +896,6 @@ int launch_scan_filtered(const mmidx_index *h, ScanParams P, const SearchPlan &p
         case 16: return launch_filt_t<16>(h, P, grid, lds, st, main_grid);
         default: return launch_filt_t<32>(h, P, grid, lds, st, main_grid);
     }
-}
-
-template <int M>
-int launch_seed_t(const ScanParams &P, dim3 grid, size_t lds, hipStream_t st) {
-    HIPCK(hipFuncSetAttribute((const void *)k_scan_seed<M>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL((k_scan_seed<M>), grid, dim3(MMIDX_BLOCK), lds, st, P);
-    HIPCK(hipGetLastError());
-    return MMIDX_OK;
 }
 
 template <int M, int KS, int NT>
@@ -925,13 +935,13 @@ int launch_scan_hist(mmidx_index *h, ScanParams P, const SearchPlan &pl, dim3 gr
                     !P.order && !P.xcd_remap && pl.chunk <= (1 << 24);
     if (!ok) return 1;
     // a shard (at most half of the lists live here): launch over the queries whose nearest list is non-empty only
-    const bool compact_items = P.ivf && P.nrank == 1 && P.rank_lo == 0 && grid.y == 1 && !h->no_item_compaction &&
-                               h->nonempty_lists * 2 <= (int64_t)h->C && (int64_t)grid.x >= (int64_t)h->passa_item_min;
+    const bool compact_items = P.ivf && P.nrank == 1 && P.rank_lo == 0 && grid.y == 1 &&
+                               h->nonempty_lists * 2 <= (int64_t)h->C && (int64_t)grid.x >= (int64_t)h->sw.passa_item_min;
     const size_t fixed = (size_t)h->m * h->ks * 8 + (h->transform ? 2 : 1) * (size_t)h->D * 8 + 2 * MMIDX_HWV * 8 + 16 + MMIDX_HB * 4 + MMIDX_HCNT * 4;
     // 256 threads: four blocks per CU; 512 threads (option "passa_wide"): three, six waves per SIMD; m = 64 (the reference's
     // flagship shape, YFCC100MExample.java:85-90: 64 x 256 doubles = 128 KiB of table): ONE block of 1024 threads per CU --
     // the same sixteen waves per CU over one table instead of four
-    const bool wide = h->passa_wide != 0;
+    const bool wide = h->sw.passa_wide != 0;
     const bool whole_cu = h->m == 64;
     // position buffer: what is left of the block's share of the CU's LDS, within [768, 4096] entries
     int64_t room = (int64_t)(160 * 1024 / (whole_cu ? 1 : (wide ? 3 : 4))) - 256 - (int64_t)fixed;
@@ -946,7 +956,7 @@ int launch_scan_hist(mmidx_index *h, ScanParams P, const SearchPlan &pl, dim3 gr
     P.cap = cap;
     // the queries' exact tables ahead of the scan (k_lut_pre: a codebook row read once per 64 queries instead of once per query)
     {
-        const bool want = h->lut_pre > 0 || (h->lut_pre < 0 && h->m >= 32);
+        const bool want = h->m >= 32;  // (where it pays)
         const long long nqa = (long long)grid.x;  // (pass A: one item per query)
         const size_t tab = (size_t)h->m * h->ks;
         if (want && P.nrank == 1 && P.rank_lo == 0 && grid.y == 1 && h->transform != MMIDX_TR_ROTATION && (tab & 1) == 0 && (h->dsub == 8 || h->dsub == 16 || h->dsub == 4) &&
@@ -968,7 +978,7 @@ int launch_scan_hist(mmidx_index *h, ScanParams P, const SearchPlan &pl, dim3 gr
     if (compact_items) {
         const long long nq_items = (long long)grid.x;
         const double share = (double)h->nonempty_lists / (double)h->C;  // expected fraction of queries served here
-        long long gm = (long long)(1.15 * share * (double)nq_items) + h->passa_item_margin;
+        long long gm = (long long)(1.15 * share * (double)nq_items) + h->sw.passa_item_margin;
         if (gm < 1) gm = 1;
         if (gm > nq_items) gm = nq_items;
         HIPCK(h->ws_order.reserve((size_t)nq_items * (size_t)P.w));  // (pass B's size: its reserve later must not reallocate under this launch)
@@ -988,7 +998,7 @@ int launch_scan_hist(mmidx_index *h, ScanParams P, const SearchPlan &pl, dim3 gr
         default: rc = launch_hist_t<32>(P, grid, lds, st, wide); break;
     }
     if (rc) return rc;
-    if (h->debug_sync) {
+    if (h->sw.debug_sync) {
         int32_t c4[4];
         (void)hipStreamSynchronize(st);
         (void)hipMemcpy(c4, h->ws_fb.p, sizeof(c4), hipMemcpyDeviceToHost);
@@ -1006,28 +1016,10 @@ int launch_scan_hist(mmidx_index *h, ScanParams P, const SearchPlan &pl, dim3 gr
     return launch_scan(h, F, dim3((unsigned)nfb, 1), pl.lds, st);
 }
 
-// pass A: seeded scan (exact sample -> histogram of u8 lower bounds -> exact verify) where it applies
-int launch_scan_seeded(const mmidx_index *h, ScanParams P, const SearchPlan &pl, dim3 grid, hipStream_t st) {
-    const bool ok = h->code_bytes == 1 && h->ks <= 256 && (h->m == 8 || h->m == 16 || h->m == 32) && !h->no_filter &&
-                    !h->no_seed && !P.sdc_tt;
-    if (!ok) return launch_scan(h, P, grid, pl.lds, st);
-    int cap = 1;
-    while (cap < pl.K1 + MMIDX_SEED_N0) cap <<= 1;
-    P.cap = cap;
-    const size_t lds = (size_t)h->m * h->ks * 8 + 2 * (size_t)h->D * 8 + (size_t)cap * 12 + 4 * (size_t)h->m * 8 + 16 +
-                       (size_t)MMIDX_SURV_CAP * 4 + 256 * 4 + 16 + (size_t)h->m * 256 + (size_t)((pl.chunk + 15) & ~15);
-    if (lds > 160 * 1024) return launch_scan(h, P, grid, pl.lds, st);
-    switch (h->m) {
-        case 8: return launch_seed_t<8>(P, grid, lds, st);
-        case 16: return launch_seed_t<16>(P, grid, lds, st);
-        default: return launch_seed_t<32>(P, grid, lds, st);
-    }
-}
-
 // MMIDX_DEBUG_SYNC=1: synchronise after every stage and report the first failing one
 #define DBG_SYNC(name)                                                                        \
     do {                                                                                      \
-        if (h->debug_sync) {                                                                  \
+        if (h->sw.debug_sync) {                                                                  \
             hipError_t e__ = hipStreamSynchronize(st);                                        \
             fprintf(stderr, "[mmidx] %s: %s\n", name, hipGetErrorString(e__));               \
             if (e__ != hipSuccess) return fail(MMIDX_ERR_HIP, "%s failed: %s", name, hipGetErrorString(e__)); \
@@ -1070,16 +1062,12 @@ int launch_grp_t(mmidx_index *h, const GrpParams &GP, size_t lds, hipStream_t st
         if (static_lds != 0) return 1;  // (K3f takes the pairs)
     }
     HIPCK(hipFuncSetAttribute((const void *)k_scan_grp<M, G, DSUB, FLAT, UNION>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    int blocks = h->grp_blocks;
-    if (blocks <= 0) {
-        int occ = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void *)k_scan_grp<M, G, DSUB, FLAT, UNION>, GRP_NT, lds) != hipSuccess || occ < 1) {
-            (void)hipGetLastError();
-            occ = 1;
-        }
-        blocks = occ * std::max(h->num_cus, 8);
+    int occ = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void *)k_scan_grp<M, G, DSUB, FLAT, UNION>, GRP_NT, lds) != hipSuccess || occ < 1) {
+        (void)hipGetLastError();
+        occ = 1;
     }
-    blocks = std::max(8, (blocks + 7) & ~7);
+    const int blocks = std::max(8, (occ * std::max(h->num_cus, 8) + 7) & ~7);
     hipLaunchKernelGGL((k_scan_grp<M, G, DSUB, FLAT, UNION>), dim3((unsigned)blocks), dim3(GRP_NT), lds, st, GP);
     HIPCK(hipGetLastError());
     return MMIDX_OK;
@@ -1089,7 +1077,7 @@ int launch_grp_t(mmidx_index *h, const GrpParams &GP, size_t lds, hipStream_t st
 template <int NJ, int DSUB, int MODE, int NWV>
 int launch_mfma_a_scan_w(mmidx_index *h, const MfmaParams &MP, size_t lds, hipStream_t st) {
     HIPCK(hipFuncSetAttribute((const void *)k_scan_mfma<NJ, DSUB, MODE, NWV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    int blocks = h->mfma_blocks;
+    int blocks = h->sw.mfma_blocks;
     if (blocks <= 0) {
         int occ = 0;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void *)k_scan_mfma<NJ, DSUB, MODE, NWV>, NWV * 64, lds) != hipSuccess || occ < 1) {
@@ -1137,13 +1125,13 @@ int launch_a1_verify_t(mmidx_index *h, const MfmaParams &MP, hipStream_t st) {
 // ---- K3q (mmidx_scan_q.h): pass A on integers, up to four queries of a nearest list per block -----------------------------------
 // does pass A of this call go through K3q?
 bool passa_q_applies(const mmidx_index *h, const ScanParams &P, const SearchPlan &pl, long long nq) {
-    if (h->passa_q == 0 || !P.ivf || P.sdc_tt || nq <= 0 || !h->d_pqstat || !h->d_pqT32) return false;
+    if (h->sw.passa_q == 0 || !P.ivf || P.sdc_tt || nq <= 0 || !h->d_pqstat || !h->d_pqT32) return false;
     if (h->code_bytes != 1 || h->ks != 256 || h->m != 16 || (h->dsub != 4 && h->dsub != 8 && h->dsub != 16)) return false;
     if (pl.K1 + 40 > MMIDX_Q_HKQ) return false;  // (~K1 + 10 candidates per query, and room for ties)
     if (h->max_list_len >= (1ll << 24) || nq * (long long)P.w >= 0x7fffff00ll) return false;
     if (h->transform == MMIDX_TR_ROTATION && !h->d_rot) return false;
     if (h->transform == MMIDX_TR_PERMUTATION && !h->d_perm) return false;
-    if (h->passa_q > 0) return true;
+    if (h->sw.passa_q > 0) return true;
     // a block costs the same for one query as for four: from ~1.25 queries per non-empty list the shared scan beats K3h's one block per
     // query; long lists only (K3h's gate)
     return 4 * nq >= 5 * std::max<int64_t>(1, h->nonempty_lists) && h->n_csr / std::max<int64_t>(1, h->nonempty_lists) >= 4096;
@@ -1214,7 +1202,7 @@ int launch_passa_q(mmidx_index *h, const ScanParams &P, const SearchPlan &pl, lo
         default: rc = launch_q_t<16, 16>(QP, grid, L.total, st); break;
     }
     if (rc) return rc;
-    if (h->debug_sync) {
+    if (h->sw.debug_sync) {
         int32_t c4[4], ng = 0;
         (void)hipStreamSynchronize(st);
         (void)hipMemcpy(c4, h->ws_fb.p, sizeof(c4), hipMemcpyDeviceToHost);
@@ -1247,7 +1235,7 @@ PassaMfmaShape passa_mfma_shape(const mmidx_index *h, long long npairs) {
     constexpr int G = MF_QG;
     PassaMfmaShape S{};
     const long long maxlen = std::max<long long>(h->max_list_len, 1);
-    int sub = h->mfma_sub;
+    int sub = h->sw.mfma_sub;
     if (sub <= 0) {
         const long long est_groups = npairs / G + std::min<long long>(npairs, std::max<int64_t>(1, h->nonempty_lists));
         const long long want = 4ll * 2 * std::max(h->num_cus, 8);
@@ -1268,13 +1256,13 @@ PassaMfmaShape passa_mfma_shape(const mmidx_index *h, long long npairs) {
 
 // does pass A of this call go through K3ma?  (all the applicability checks: launch_passa_mfma itself must not fall back after its first launch)
 bool passa_mfma_applies(const mmidx_index *h, const ScanParams &P, const SearchPlan &pl, long long nq) {
-    if (h->passa_mfma == 0 || !P.ivf || h->no_mfma || !h->mfma_ok || !h->xn_valid || h->no_filter || P.sdc_tt || nq <= 0 || h->D > 128) return false;
+    if (h->sw.passa_mfma == 0 || !P.ivf || h->sw.no_mfma || !h->mfma_ok || !h->xn_valid || h->sw.no_filter || P.sdc_tt || nq <= 0 || h->D > 128) return false;
     if (pl.K1 > 128) return false;                                             // (a pair keeps 256 values per piece: K1 of them must be there)
     if (h->max_list_len >= (1ll << 24) || nq * (long long)P.w >= 0x7fffff00ll || ((uintptr_t)P.Q & 15) != 0) return false;
     if (h->d_perm && !h->d_coarseP) return false;
     if (h->transform == MMIDX_TR_ROTATION && (!h->d_rot || (size_t)nq * h->D * 8 > ((size_t)8 << 30))) return false;
     if (!passa_mfma_shape(h, nq).fits) return false;  // (the sweep-2 bitmap would exceed 32 GiB: one very long list)
-    if (h->passa_mfma > 0) return true;
+    if (h->sw.passa_mfma > 0) return true;
     // from ~8 queries per nearest list, on an index of long lists (where K3h would run): a shard holding a part of the
     // lists sees the same number of queries per LOCAL list
     return nq >= 8ll * h->C && h->n_csr / std::max<int64_t>(1, h->nonempty_lists) >= 4096;
@@ -1307,7 +1295,7 @@ int launch_passa_mfma(mmidx_index *h, const ScanParams &P, const SearchPlan &pl,
     HIPCK(h->ws_abm.reserve(max_groups * (size_t)nsub * bm_stride));
     HIPCK(h->ws_aicnt.reserve(max_groups * (size_t)nsub + 1));
     // (about K1 + 10 % records per pair; the list holds 512 per pair -- what does not fit sends its queries to the exact kernels)
-    const size_t rec_cap = h->mfma_qcap > 0 ? (size_t)h->mfma_qcap : std::min<size_t>((size_t)0xFFFFF000u, std::max<size_t>((size_t)1 << 20, (size_t)npairs * 512));
+    const size_t rec_cap = h->sw.mfma_qcap > 0 ? (size_t)h->sw.mfma_qcap : std::min<size_t>((size_t)0xFFFFF000u, std::max<size_t>((size_t)1 << 20, (size_t)npairs * 512));
     HIPCK(h->ws_arec.reserve(rec_cap));
     const int rnd_size = A1V_RND(h->dsub);
     HIPCK(h->ws_arnd.reserve(rec_cap / (size_t)rnd_size + 2));
@@ -1372,7 +1360,7 @@ int launch_passa_mfma(mmidx_index *h, const ScanParams &P, const SearchPlan &pl,
     MP.fb_chunk = pl.chunk;
     MP.fb_nchunks = std::max(pl.nchunks, 1);
     MP.npairs_flat = npairs;
-    MP.stat = (h->profiling == 1 || h->debug_sync) ? (unsigned long long *)(h->d_counters + 3) : nullptr;
+    MP.stat = (h->profiling == 1 || h->sw.debug_sync) ? (unsigned long long *)(h->d_counters + 3) : nullptr;
     MP.nver = (unsigned long long *)(h->d_counters + 7);
     MP.a_cand = h->ws_acand.p;
     MP.a_rowc = h->ws_arowc.p;
@@ -1381,7 +1369,7 @@ int launch_passa_mfma(mmidx_index *h, const ScanParams &P, const SearchPlan &pl,
     MP.a_icnt = h->ws_aicnt.p;
     MP.a_rec = h->ws_arec.p;
     MP.a_rec_cap = (u32)rec_cap;
-    MP.a_icnt_sat = h->passa_mfma_icnt_sat > 0 ? (u32)h->passa_mfma_icnt_sat : 0xFFFFFFFFu;
+    MP.a_icnt_sat = h->sw.passa_mfma_icnt_sat > 0 ? (u32)h->sw.passa_mfma_icnt_sat : 0xFFFFFFFFu;
     MP.a_rows = h->transform == MMIDX_TR_ROTATION ? h->ws_R.p : h->ws_arows.p;
     MP.a_meta = h->ws_ameta.p;
     MP.a_metaT = h->ws_ametaT.p;
@@ -1415,8 +1403,8 @@ int launch_passa_mfma(mmidx_index *h, const ScanParams &P, const SearchPlan &pl,
     }
     if (aev) HIPCK(hipEventRecord(aev[2], st));
     DBG_SYNC("K3ma select");
-    if (h->debug_sync) HIPCK(hipMemsetAsync(h->ws_abm.p, 0, max_groups * (size_t)nsub * bm_stride, st));  // (the debug report below counts bits)
-    MP.a_wide = h->a_wide ? 1 : 0;
+    if (h->sw.debug_sync) HIPCK(hipMemsetAsync(h->ws_abm.p, 0, max_groups * (size_t)nsub * bm_stride, st));  // (the debug report below counts bits)
+    MP.a_wide = h->sw.passa_mfma_wide ? 1 : 0;
     rc = launch_mfma_a_scan<2>(h, MP, L.total, st);  // sweep 2: compare masks
     if (rc) return rc;
     if (aev) HIPCK(hipEventRecord(aev[3], st));
@@ -1440,7 +1428,7 @@ int launch_passa_mfma(mmidx_index *h, const ScanParams &P, const SearchPlan &pl,
     hipLaunchKernelGGL(k_mfma_redo, dim3((unsigned)((span + 255) / 256)), dim3(256), 0, st, MP, (long long)nq);
     HIPCK(hipGetLastError());
     DBG_SYNC("K3ma redo");
-    if (h->debug_sync) {
+    if (h->sw.debug_sync) {
         int32_t g2[2], np1 = 0;
         (void)hipStreamSynchronize(st);
         (void)hipMemcpy(g2, h->ws_gfb.p, sizeof(g2), hipMemcpyDeviceToHost);
@@ -1501,7 +1489,7 @@ int launch_grouped_common(mmidx_index *h, const ScanParams &S, ScanParams F, con
     const size_t nfb = (size_t)npairs * (size_t)nchunks;
     HIPCK(h->ws_gdesc.reserve((size_t)npairs / G + (size_t)nlists + 8));
     HIPCK(h->ws_gfb.reserve(4 + 2 * nfb + 16));
-    if (h->debug_sync) HIPCK(hipMemsetAsync(h->ws_gfb.p, 0, (4 + 2 * nfb + 16) * sizeof(int32_t), st));
+    if (h->sw.debug_sync) HIPCK(hipMemsetAsync(h->ws_gfb.p, 0, (4 + 2 * nfb + 16) * sizeof(int32_t), st));
     hipLaunchKernelGGL(k_group_build, dim3(1), dim3(1024), 0, st, h->ws_pcount.p, h->ws_pstart.p, nlists, G, h->ws_gdesc.p, h->ws_gfb.p,
                        (u32 *)(h->ws_gfb.p + 1), (unsigned long long *)(h->d_counters + 7), h->pin_hint ? h->pin_hint + 1 : nullptr);
     HIPCK(hipGetLastError());
@@ -1526,7 +1514,7 @@ int launch_grouped_common(mmidx_index *h, const ScanParams &S, ScanParams F, con
     //  separable benchmark, whose far probes all fall to the coarse bound, would pay for nothing; a stale hint costs speed, never results)
     // ... and the UNION instance only when the call before verified more than a few codes per query (k_group_build reports it)
     const bool union_worth = !S.ivf || (h->pin_hint && *(volatile int32_t *)h->pin_hint > 0 && (long long)*(volatile int32_t *)(h->pin_hint + 1) > 8 * nq);
-    if ((h->no_union < 0 || (!h->no_union && union_worth)) && nq > 0 && nq * 256 * 4 <= (1ll << 31)) {  // (no_union = -1: always, A/B)
+    if ((h->sw.no_union < 0 || (!h->sw.no_union && union_worth)) && nq > 0 && nq * 256 * 4 <= (1ll << 31)) {  // (no_union = -1: always, A/B)
         HIPCK(h->ws_ghist.reserve((size_t)nq * 256));
         HIPCK(h->ws_T0.reserve((size_t)nq));
         HIPCK(hipMemsetAsync(h->ws_ghist.p, 0, (size_t)nq * 256 * sizeof(u32), st));
@@ -1534,7 +1522,7 @@ int launch_grouped_common(mmidx_index *h, const ScanParams &S, ScanParams F, con
         GX.ghist = h->ws_ghist.p;
         GX.T0 = h->ws_T0.p;
     }
-    GP.stat = (h->profiling == 1 || h->debug_sync) ? (unsigned long long *)(h->d_counters + 3) : nullptr;  // [0] verified, [1] flag (adds), [2..3] item statistics
+    GP.stat = (h->profiling == 1 || h->sw.debug_sync) ? (unsigned long long *)(h->d_counters + 3) : nullptr;  // [0] verified, [1] flag (adds), [2..3] item statistics
     int rc;
     const int ds = h->dsub;
     // flat PQ with the queries' exact tables: its own instances (m = 8, 16 -- the others verify from the codebook as IVF does)
@@ -1589,7 +1577,7 @@ int launch_grouped_common(mmidx_index *h, const ScanParams &S, ScanParams F, con
 #undef GRP_GO
     if (rc) return rc;
     DBG_SYNC("K3g scan");
-    if (h->debug_sync) {
+    if (h->sw.debug_sync) {
         int32_t c4[2];
         (void)hipStreamSynchronize(st);
         (void)hipMemcpy(c4, h->ws_gfb.p, sizeof(c4), hipMemcpyDeviceToHost);
@@ -1653,7 +1641,7 @@ int build_mfma_tables(mmidx_index *h) {
 template <int NJ, int DSUB>
 int launch_mfma_scan_t(mmidx_index *h, const MfmaParams &MP, size_t lds, hipStream_t st) {
     HIPCK(hipFuncSetAttribute((const void *)k_scan_mfma<NJ, DSUB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    int blocks = h->mfma_blocks;
+    int blocks = h->sw.mfma_blocks;
     if (blocks <= 0) {
         int occ = 0;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void *)k_scan_mfma<NJ, DSUB>, MF_NT, lds) != hipSuccess || occ < 1) {
@@ -1679,7 +1667,7 @@ int launch_mfma_verify_t(mmidx_index *h, const MfmaParams &MP, hipStream_t st) {
 template <int DSUB, int TPW>
 int launch_mfma_kc_scan_t(mmidx_index *h, const MfmaKcParams &KP, size_t lds, hipStream_t st) {
     HIPCK(hipFuncSetAttribute((const void *)k_scan_mfma_kc<DSUB, TPW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    int blocks = h->mfma_blocks;
+    int blocks = h->sw.mfma_blocks;
     if (blocks <= 0) {
         int occ = 0;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void *)k_scan_mfma_kc<DSUB, TPW>, MF_NT, lds) != hipSuccess || occ < 1) {
@@ -1696,7 +1684,7 @@ int launch_mfma_kc_scan_t(mmidx_index *h, const MfmaKcParams &KP, size_t lds, hi
 
 template <int DSUB, int CG>
 int launch_mfma_kc2_scan_t(mmidx_index *h, const MfmaKcParams &KP, hipStream_t st) {
-    int blocks = h->mfma_blocks > 0 ? h->mfma_blocks : std::max(h->num_cus, 8);  // one block of 512 threads per CU (156 KiB of LDS)
+    int blocks = h->sw.mfma_blocks > 0 ? h->sw.mfma_blocks : std::max(h->num_cus, 8);  // one block of 512 threads per CU (156 KiB of LDS)
     blocks = std::max(8, (blocks + 7) & ~7);
     hipLaunchKernelGGL((k_scan_mfma_kc2<DSUB, CG>), dim3((unsigned)blocks), dim3(MFK2_NT), 0, st, KP);
     HIPCK(hipGetLastError());
@@ -1716,12 +1704,12 @@ int launch_mfma_kc(mmidx_index *h, const ScanParams &S, ScanParams F, const Sear
     // the DMA form (k_scan_mfma_kc2) where the lanes' code bytes come in aligned words: D a multiple of 256
     const int nb = 32 / h->dsub, quarter = h->m / 4;
     int cg = 0;
-    if (!h->mfma_kc_v1 && h->D % 256 == 0 && h->m % 4 == 0)
+    if (!h->sw.mfma_kc_v1 && h->D % 256 == 0 && h->m % 4 == 0)
         for (int c : {8, 4})  // (16 bytes per load would hold 32 registers per wave for the code words: the chunk loop spills)
             if (!cg && quarter % c == 0 && c >= 2 * nb) cg = c;
-    const int tpw = cg ? MFK2_TPW * (MFK2_NT / 64) / 4 : (h->mfma_kc_tpw == 16 ? 16 : 8);  // tiles of a piece / 4
-    int sub = h->mfma_sub > 0 ? ((h->mfma_sub + 63) & ~63) : 64 * tpw;
-    if (cg) sub = h->mfma_sub > 0 ? std::min(sub, 1 << 20) : 8 * MFK2_TPW * (MFK2_NT / 64) * 16;  // k_scan_mfma_kc2 walks an item in passes of 1024 codes
+    const int tpw = cg ? MFK2_TPW * (MFK2_NT / 64) / 4 : (h->sw.mfma_kc_tpw == 16 ? 16 : 8);  // tiles of a piece / 4
+    int sub = h->sw.mfma_sub > 0 ? ((h->sw.mfma_sub + 63) & ~63) : 64 * tpw;
+    if (cg) sub = h->sw.mfma_sub > 0 ? std::min(sub, 1 << 20) : 8 * MFK2_TPW * (MFK2_NT / 64) * 16;  // k_scan_mfma_kc2 walks an item in passes of 1024 codes
     else sub = std::min(sub, 64 * tpw);  // (a wave holds at most TPW tiles' accumulators)
     const int nsub = (int)((maxlen + sub - 1) / sub);
     if ((long long)(npairs / G + nlists) * nsub > 0x7fffff00ll) return 1;
@@ -1733,7 +1721,7 @@ int launch_mfma_kc(mmidx_index *h, const ScanParams &S, ScanParams F, const Sear
     HIPCK(h->ws_redo.reserve((size_t)nq));
     HIPCK(h->ws_psnap.reserve((size_t)nq));
     HIPCK(h->ws_mfctl.reserve(64));
-    size_t qcap = h->mfma_qcap > 0 ? (size_t)h->mfma_qcap : std::min<size_t>((size_t)1 << 28, std::max<size_t>((size_t)1 << 20, (size_t)nq * 4096));
+    size_t qcap = h->sw.mfma_qcap > 0 ? (size_t)h->sw.mfma_qcap : std::min<size_t>((size_t)1 << 28, std::max<size_t>((size_t)1 << 20, (size_t)nq * 4096));
     HIPCK(h->ws_surv.reserve(qcap));
     HIPCK(h->ws_R16.reserve((size_t)npairs * h->D));
     HIPCK(h->ws_nrow.reserve((size_t)npairs));
@@ -1788,7 +1776,7 @@ int launch_mfma_kc(mmidx_index *h, const ScanParams &S, ScanParams F, const Sear
     MP.fb_chunk = pl.chunk;
     MP.fb_nchunks = std::max(nchunks_f, 1);
     MP.npairs_flat = npairs;
-    MP.stat = (h->profiling == 1 || h->debug_sync) ? (unsigned long long *)(h->d_counters + 3) : nullptr;
+    MP.stat = (h->profiling == 1 || h->sw.debug_sync) ? (unsigned long long *)(h->d_counters + 3) : nullptr;
     MP.nver = (unsigned long long *)(h->d_counters + 7);
     KP.R16 = h->ws_R16.p;
     KP.nrow = h->ws_nrow.p;
@@ -1829,7 +1817,7 @@ int launch_mfma_kc(mmidx_index *h, const ScanParams &S, ScanParams F, const Sear
     const long long span = std::max<long long>(npairs, nq);
     hipLaunchKernelGGL(k_mfma_redo, dim3((unsigned)((span + 255) / 256)), dim3(256), 0, st, MP, (long long)nq);
     HIPCK(hipGetLastError());
-    if (h->debug_sync) {
+    if (h->sw.debug_sync) {
         u32 c16[16];
         int32_t g2[2], sc[2];
         (void)hipStreamSynchronize(st);
@@ -1851,7 +1839,7 @@ int launch_mfma_kc(mmidx_index *h, const ScanParams &S, ScanParams F, const Sear
 // IVF or the flat-PQ form); F: those of the K3f launch that redoes the queries K3m hands back.  Returns 1 when K3m does not apply.
 int launch_mfma_common(mmidx_index *h, const ScanParams &S, ScanParams F, const SearchPlan &pl, int nlists, int nchunks_f, long long npairs,
                        long long maxlen, hipStream_t st, long long nq, const double *flat_lut) {
-    if (h->no_mfma || !h->mfma_ok || !h->xn_valid || h->no_filter || S.sdc_tt || nq <= 0 || npairs <= 0 || maxlen >= (1ll << 31) ||
+    if (h->sw.no_mfma || !h->mfma_ok || !h->xn_valid || h->sw.no_filter || S.sdc_tt || nq <= 0 || npairs <= 0 || maxlen >= (1ll << 31) ||
         nq * 256 * 4 > (1ll << 31) || npairs >= 0x7fffff00ll || ((uintptr_t)S.Q & 15) != 0)
         return 1;
     if (h->D > 128) return launch_mfma_kc(h, S, F, pl, nlists, nchunks_f, npairs, maxlen, st, nq, flat_lut);
@@ -1869,7 +1857,7 @@ int launch_mfma_common(mmidx_index *h, const ScanParams &S, ScanParams F, const 
     DBG_SYNC("K3m group build");
     // items: (group, piece of `sub` codes).  One piece per list where the batch fills the chip anyway; shorter pieces when there
     // are few groups (small calls, flat PQ's long chunks), so that the persistent blocks all find work
-    int sub = h->mfma_sub;
+    int sub = h->sw.mfma_sub;
     if (sub <= 0) {
         const long long est_groups = npairs / G + std::min<long long>(npairs, nlists);
         const long long want = 4ll * 2 * std::max(h->num_cus, 8);  // (four items per resident block; eight cost cfg2 a third piece per chunk: 1.31 -> 1.21 ms)
@@ -1885,7 +1873,7 @@ int launch_mfma_common(mmidx_index *h, const ScanParams &S, ScanParams F, const 
     HIPCK(h->ws_redo.reserve((size_t)nq));
     HIPCK(h->ws_psnap.reserve((size_t)nq));
     HIPCK(h->ws_mfctl.reserve(64));
-    size_t qcap = h->mfma_qcap > 0 ? (size_t)h->mfma_qcap : std::min<size_t>((size_t)1 << 28, std::max<size_t>((size_t)1 << 20, (size_t)nq * 2048));
+    size_t qcap = h->sw.mfma_qcap > 0 ? (size_t)h->sw.mfma_qcap : std::min<size_t>((size_t)1 << 28, std::max<size_t>((size_t)1 << 20, (size_t)nq * 2048));
     HIPCK(h->ws_surv.reserve(qcap));
     hipLaunchKernelGGL(k_mfma_prep, dim3((unsigned)std::min<long long>(4096, (nq * 64 + 255) / 256)), dim3(256), 0, st, (const int32_t *)h->ws_gfb.p, h->ws_ghist.p,
                        h->ws_redo.p, h->ws_mfctl.p, S.T, h->ws_T0.p, S.pool_cnt, h->ws_psnap.p, (long long)nq);
@@ -1934,7 +1922,7 @@ int launch_mfma_common(mmidx_index *h, const ScanParams &S, ScanParams F, const 
     MP.fb_chunk = pl.chunk;
     MP.fb_nchunks = std::max(nchunks_f, 1);
     MP.npairs_flat = npairs;
-    MP.stat = (h->profiling == 1 || h->debug_sync) ? (unsigned long long *)(h->d_counters + 3) : nullptr;
+    MP.stat = (h->profiling == 1 || h->sw.debug_sync) ? (unsigned long long *)(h->d_counters + 3) : nullptr;
     MP.nver = (unsigned long long *)(h->d_counters + 7);
     const MfmaLds L(h->D);
     int rc;
@@ -1967,7 +1955,7 @@ int launch_mfma_common(mmidx_index *h, const ScanParams &S, ScanParams F, const 
     hipLaunchKernelGGL(k_mfma_redo, dim3((unsigned)((span + 255) / 256)), dim3(256), 0, st, MP, (long long)nq);
     HIPCK(hipGetLastError());
     DBG_SYNC("K3m redo");
-    if (h->debug_sync) {
+    if (h->sw.debug_sync) {
         u32 c16[16];
         int32_t g2[2];
         (void)hipStreamSynchronize(st);
@@ -1992,8 +1980,8 @@ int launch_scan_grouped(mmidx_index *h, const ScanParams &P, const SearchPlan &p
     // pass B in six launches of ~5 us (group build, prep, scan, verification, redo, K3f tail: the host cannot know the count); K3f's
     // looping kernel alone serves whatever the count turns out to be in ONE launch -- exactly, if slowly should the guess be wrong
     // (the next call sees the real count).  Option "passb_small" = 0: off.
-    if (P.ivf && h->passb_small && h->pin_hint && h->hint_calls > 1 && h->code_bytes == 1 && h->ks <= 256 && (h->m == 8 || h->m == 16 || h->m == 32) &&
-        !h->no_filter && !P.sdc_tt && !h->debug_sync && h->hint_prev_nq == (int64_t)nq && h->hint_prev_w == P.w) {
+    if (P.ivf && h->sw.passb_small && h->pin_hint && h->hint_calls > 1 && h->code_bytes == 1 && h->ks <= 256 && (h->m == 8 || h->m == 16 || h->m == 32) &&
+        !h->sw.no_filter && !P.sdc_tt && !h->sw.debug_sync && h->hint_prev_nq == (int64_t)nq && h->hint_prev_w == P.w) {
         const int32_t seen = *(volatile int32_t *)h->pin_hint;
         if (seen >= 0 && seen <= 64) {
             const unsigned gx = (unsigned)(((P.n_items + 7) / 8) * 8);
@@ -2007,7 +1995,7 @@ int launch_scan_grouped(mmidx_index *h, const ScanParams &P, const SearchPlan &p
         if (rcm != 1) return rcm;
     }
     h->disp_passb = "K3f";
-    if (h->no_grp || !h->grp_valid || !h->d_pq32T || h->no_filter || P.sdc_tt || !P.ivf || h->max_list_len >= (1 << 24)) return 1;
+    if (h->sw.no_grp || !h->grp_valid || !h->d_pq32T || h->sw.no_filter || P.sdc_tt || !P.ivf || h->max_list_len >= (1 << 24)) return 1;
     h->disp_passb = "K3g";
     return launch_grouped_common(h, P, P, pl, h->C, pl.nchunks, npairs, st, nq);
 }
@@ -2017,9 +2005,9 @@ int launch_scan_grouped(mmidx_index *h, const ScanParams &P, const SearchPlan &p
 int launch_scan_grouped_flat(mmidx_index *h, const ScanParams &P, const SearchPlan &pl, long long nq, hipStream_t st) {
     const int nch = P.w;
     const long long npairs = nq * (long long)(nch - 1);
-    if (h->no_filter || P.sdc_tt || P.ivf || nch < 2 || pl.chunk >= (1 << 24) || npairs >= 0x7fffff00ll || nq * (long long)nch >= 0x7fffff00ll) return 1;
-    const bool grp_ok = !h->no_grp && h->grp_valid && h->d_pq32T;
-    const bool mf_ok = !h->no_mfma && h->mfma_ok && h->xn_valid;
+    if (h->sw.no_filter || P.sdc_tt || P.ivf || nch < 2 || pl.chunk >= (1 << 24) || npairs >= 0x7fffff00ll || nq * (long long)nch >= 0x7fffff00ll) return 1;
+    const bool grp_ok = !h->sw.no_grp && h->grp_valid && h->d_pq32T;
+    const bool mf_ok = !h->sw.no_mfma && h->mfma_ok && h->xn_valid;
     if (!grp_ok && !mf_ok) return 1;
     HIPCK(h->ws_pcount.reserve((size_t)nch + 1));
     HIPCK(h->ws_pstart.reserve((size_t)nch + 1));
@@ -2081,7 +2069,7 @@ int run_coarse(mmidx_index *h, int64_t nq, const double *dQ, int32_t *d_cells, h
     const bool approx = coarse_certified(h, &alds, &cch);
     const size_t glds = sel_fixed + std::max<size_t>((size_t)std::max(cch, 1) * row_bytes, (size_t)MMIDX_BLOCK * 4);
     const int G = h->Cp / 8;
-    if (approx && !h->coarse_v1 && h->d_Ch && G >= 4 * (h->w + 1) && glds <= 64 * 1024) {
+    if (approx && !h->sw.coarse_v1 && h->d_Ch && G >= 4 * (h->w + 1) && glds <= 64 * 1024) {
         // K1e + K1f: bf16-split dot products on the matrix cores, group minima only, certified candidates in fp64
         HIPCK(h->ws_qn.reserve((size_t)nq));
         HIPCK(h->ws_Qh.reserve((size_t)nq * h->Dp));
@@ -2094,12 +2082,12 @@ int run_coarse(mmidx_index *h, int64_t nq, const double *dQ, int32_t *d_cells, h
         const int ntiles = h->Cp / G16_BC;
         const int qblocks = (int)((nq + G16_BQ - 1) / G16_BQ);
         const int csplit = std::max(1, std::min(ntiles, (512 + qblocks - 1) / qblocks));
-        if (h->Dp == G16_KC && !h->coarse_nodma) {
+        if (h->Dp == G16_KC) {
             // one k chunk: centroid tiles by LDS-DMA into two half-tile buffers (static LDS)
             hipLaunchKernelGGL(k_coarse_gmin16_dma, dim3((unsigned)qblocks, (unsigned)csplit), dim3(MMIDX_BLOCK), 0, st, (const __bf16 *)h->ws_Qh.p,
                                (const __bf16 *)h->ws_Ql.p, (const __bf16 *)h->d_Ch, (const __bf16 *)h->d_Cl, h->d_cn_pad, h->ws_qn.p,
                                (float2 *)h->ws_gmin.p, h->Cp, (int)nq, G);
-        } else if (h->Dp > G16_KC && h->Dp % G16_KC == 0 && h->coarse_dma_kc) {
+        } else if (h->Dp > G16_KC && h->Dp % G16_KC == 0 && h->sw.coarse_dma_kc) {
             // several k chunks (long vectors): the same double buffering, (chunk, half tile) after (chunk, half tile)
             hipLaunchKernelGGL(k_coarse_gmin16_dma_kc, dim3((unsigned)qblocks, (unsigned)csplit), dim3(MMIDX_BLOCK), 0, st, (const __bf16 *)h->ws_Qh.p,
                                (const __bf16 *)h->ws_Ql.p, (const __bf16 *)h->d_Ch, (const __bf16 *)h->d_Cl, h->d_cn_pad, h->ws_qn.p,
@@ -2131,14 +2119,14 @@ int run_coarse(mmidx_index *h, int64_t nq, const double *dQ, int32_t *d_cells, h
         A.Dp = h->Dp;
         A.nq = (int)nq;
         // front end and selection as two kernels where a query's candidates fit the list between them (about 1.3 (w + 1))
-        const bool split = !h->coarse_fused && G <= 1024 && 2 * (h->w + 1) + 32 < MMIDX_CLIST;
+        const bool split = !h->sw.coarse_fused && G <= 1024 && 2 * (h->w + 1) + 32 < MMIDX_CLIST;
         if (split) {
             HIPCK(h->ws_clist.reserve((size_t)nq * MMIDX_CLIST));
             A.clist = (u32 *)h->ws_clist.p;
             // front end + exact stage by one wave per query where its LDS tile applies (option "coarse_wave_sel", default on); what it
             // leaves (more than 64 candidates) goes through the block-per-query form
             A.defer = h->ws_defer.p;
-            const bool wave_sel = h->coarse_wave_sel && h->w < 64 && (h->D == 64 || h->D == 128 || h->D == 256);
+            const bool wave_sel = h->sw.coarse_wave_sel && h->w < 64 && (h->D == 64 || h->D == 128 || h->D == 256);
             const unsigned fgrid = (unsigned)((nq + 3) / 4);
             h->disp_coarse = wave_sel ? "K1e'+K1f(front_sel)" : "K1e'+K1f(front+select_list)";
             if (wave_sel && h->D == 128) hipLaunchKernelGGL((k_coarse_front_sel<8>), dim3((unsigned)nq), dim3(64), 0, st, A);  // (a wave a block)
@@ -2310,8 +2298,6 @@ int search_batch_device(mmidx_index *h, const SearchPlan &pl, int k, int64_t nq,
     P.ivf = ivf;
     P.glut = pl.glut ? h->ws_glut.p : nullptr;
     P.chunk = pl.chunk;
-    P.code_lo = 0;
-    P.code_hi = 0x7fffffff;
     P.K1 = pl.K1;
     P.cap = pl.cap;
     P.poolq = pl.poolq;
@@ -2333,14 +2319,14 @@ int search_batch_device(mmidx_index *h, const SearchPlan &pl, int k, int64_t nq,
         P.nrank = two_pass ? 1 : P.w;
         P.n_items = (int)(nq * P.nrank);
         P.xcd_remap = 0;
-        // (the adaptive filter also works from T = +inf, but for one list per query the exact scan
-        //  measured faster: 1.23 vs ~1.4 ms per 8192 queries; MMIDX_PASSA_FILTER=1 switches)
+        // the ladder: K3q -> K3ma -> K3h -> K3, the first whose gate holds.  (The adaptive filter K3f also works from T = +inf, but
+        //  for one list per query the exact scan measured faster -- 1.23 vs ~1.4 ms per 8192 queries -- so pass A never takes it.)
         int rc = MMIDX_OK;
         if (phase != 2) {
             h->disp_passb = "-";
             h->disp_pre = "-";
             if (!ivf) h->disp_coarse = "-";
-            if (two_pass && passa_q_applies(h, P, pl, (long long)nq) && !(h->passa_mfma > 0 && passa_mfma_applies(h, P, pl, (long long)nq))) {
+            if (two_pass && passa_q_applies(h, P, pl, (long long)nq) && !(h->sw.passa_mfma > 0 && passa_mfma_applies(h, P, pl, (long long)nq))) {
                 // K3q: the queries of a nearest list four to a block, decided on integers (mmidx_scan_q.h)
                 h->disp_passa = "K3q";
                 rc = launch_passa_q(h, P, pl, (long long)nq, st);
@@ -2350,46 +2336,27 @@ int search_batch_device(mmidx_index *h, const SearchPlan &pl, int k, int64_t nq,
                 h->disp_passa = "K3ma";
                 rc = launch_passa_mfma(h, P, pl, (long long)nq, st);
                 pcount_zeroed = false;  // (its pair sort counted in ws_pcount)
-            } else if (h->passa_filter) {
-                h->disp_passa = "K3f";
-                rc = launch_scan_filtered(h, P, pl, dim3((unsigned)P.n_items, (unsigned)grid_chunks), st);
-            } else if (!h->no_seed) {
-                h->disp_passa = "K3seed";
-                rc = launch_scan_seeded(h, P, pl, dim3((unsigned)P.n_items, (unsigned)grid_chunks), st);
-            } else if (two_pass && !sdc_tt && h->passa_hist != 0 &&
-                       (h->passa_hist > 0 || h->n_csr / std::max<int64_t>(1, ivf ? h->nonempty_lists : 1) >= 4096) &&
+            } else if (two_pass && !sdc_tt && h->sw.passa_hist != 0 &&
+                       (h->sw.passa_hist > 0 || h->n_csr / std::max<int64_t>(1, ivf ? h->nonempty_lists : 1) >= 4096) &&
                        (rc = launch_scan_hist(h, P, pl, dim3((unsigned)P.n_items, (unsigned)grid_chunks), st)) != 1) {
                 // (K3h ran -- its empty fallback launch is not counted as a scan launch -- or failed with rc > 1)
                 h->disp_passa = "K3h";
             } else {
-                h->disp_passa = pl.glut ? ((!h->no_split_table && h->code_bytes == 1 && h->ks == 256 && h->m == 128) ? "K3(table in two halves)" : "K3(table in global scratch)")
+                h->disp_passa = pl.glut ? ((!h->sw.no_split_table && h->code_bytes == 1 && h->ks == 256 && h->m == 128) ? "K3(table in two halves)" : "K3(table in global scratch)")
                                         : (two_pass ? "K3" : "K3(single pass)");
                 rc = MMIDX_OK;
                 // one code per thread per segment: smaller candidate buffer -> a fourth block per CU
                 ScanParams PA = P;
                 int su = 2;
                 size_t lds_a = pl.lds;
-                if (two_pass && ivf && !h->passa_su2 && !pl.glut && h->code_bytes == 1 && (h->m == 8 || h->m == 16 || h->m == 32)) {  // (the GLUT kernels are SU = 2 only: their buffer keeps pl.cap)
-                    const int nt = h->passa_512 ? 512 : MMIDX_BLOCK;
+                if (two_pass && ivf && !pl.glut && h->code_bytes == 1 && (h->m == 8 || h->m == 16 || h->m == 32)) {  // (the GLUT kernels are SU = 2 only: their buffer keeps pl.cap)
                     int cap1 = 1;
-                    while (cap1 < pl.K1 + nt) cap1 <<= 1;
+                    while (cap1 < pl.K1 + MMIDX_BLOCK) cap1 <<= 1;
                     PA.cap = cap1;
                     lds_a = scan_lds_bytes(h, cap1);
-                    su = h->passa_512 ? 11 : 1;
+                    su = 1;
                 }
-                // prefix mode: the exact scan (LDS-bound fp64 gather) covers only the first passa_prefix
-                // codes of the nearest list -- enough for a useful threshold -- and the rest of that
-                // list goes through the filtered scan under it
-                const bool prefix = two_pass && ivf && h->passa_prefix > 0 && !sdc_tt;
-                if (prefix) PA.code_hi = h->passa_prefix;
                 rc = launch_scan(h, PA, dim3((unsigned)P.n_items, (unsigned)grid_chunks), lds_a, st, su);
-                if (rc) return rc;
-                if (prefix) {
-                    ScanParams PR = P;
-                    PR.code_lo = h->passa_prefix;
-                    rc = launch_scan_filtered(h, PR, pl, dim3((unsigned)P.n_items, (unsigned)grid_chunks), st);
-                    if (prof) h->launches += 1;
-                }
             }
             if (rc) return rc;
             DBG_SYNC("pass A scan");
@@ -2445,11 +2412,11 @@ int search_batch_device(mmidx_index *h, const SearchPlan &pl, int k, int64_t nq,
             PB.rmax = h->rmax;
             PB.D = h->D;
             PB.C = h->C;
-            PB.enabled = ((h->transform != MMIDX_TR_ROTATION || h->rot_shrink > 0.0) && !h->no_bound) ? 1 : 0;
+            PB.enabled = ((h->transform != MMIDX_TR_ROTATION || h->rot_shrink > 0.0) && !h->sw.no_bound) ? 1 : 0;
             PB.shrink = h->transform == MMIDX_TR_ROTATION ? h->rot_shrink : 1.0;
             const unsigned g = (unsigned)((npairs + 255) / 256);
             DBG_SYNC("pair memset");
-            if (h->debug_sync) {
+            if (h->sw.debug_sync) {
                 std::vector<u64> ht((size_t)nq);
                 std::vector<int32_t> hc((size_t)npairs);
                 (void)hipMemcpy(ht.data(), h->ws_T.p, (size_t)nq * 8, hipMemcpyDeviceToHost);
@@ -2462,11 +2429,11 @@ int search_batch_device(mmidx_index *h, const SearchPlan &pl, int k, int64_t nq,
             }
             // K3s: pairs whose certified Smin reaches the threshold leave before the sort (only where K3g would run, and only when
             // the figures the device reported for the call before say it pays; a stale figure costs speed, never results)
-            const bool pre_ok = !h->no_grp && h->grp_valid && h->d_pq32T && !h->no_filter && !P.sdc_tt && h->max_list_len < (1 << 24) &&
+            const bool pre_ok = !h->sw.no_grp && h->grp_valid && h->d_pq32T && !h->sw.no_filter && !P.sdc_tt && h->max_list_len < (1 << 24) &&
                                 (h->dsub == 4 || h->dsub == 8 || h->dsub == 16) && npairs < 0x7fffff00ll && ((uintptr_t)dQ & 15) == 0;  // (16-byte loads of the query rows)
             bool use_pre = false;
-            if (pre_ok && h->smin_pre > 0) use_pre = true;
-            else if (pre_ok && h->smin_pre < 0 && h->D > 128 && h->mfma_ok && !h->no_mfma && h->xn_valid) {
+            if (pre_ok && h->sw.smin_pre > 0) use_pre = true;
+            else if (pre_ok && h->sw.smin_pre < 0 && h->D > 128 && h->mfma_ok && !h->sw.no_mfma && h->xn_valid) {
                 // in front of K3mk: the bound costs a tenth of the scan it can save, and there are no K3g figures to go by -- on, unless
                 // the last run removed less than an eighth of the pairs it looked at ([2] in, [0] left): then seven calls go without
                 use_pre = true;
@@ -2483,7 +2450,7 @@ int search_batch_device(mmidx_index *h, const SearchPlan &pl, int k, int64_t nq,
                         }
                     }
                 }
-            } else if (pre_ok && h->smin_pre < 0 && h->pin_hint) {
+            } else if (pre_ok && h->sw.smin_pre < 0 && h->pin_hint) {
                 volatile int32_t *ph = (volatile int32_t *)h->pin_hint;
                 if (h->pre_on) {  // [2] pairs K3s looked at, [0] pairs it left: it stays while it removes a quarter
                     const long long in = ph[2], left = ph[0];
@@ -2509,7 +2476,7 @@ int search_batch_device(mmidx_index *h, const SearchPlan &pl, int k, int64_t nq,
                 SP.Q = dQ;
                 SP.coarse = h->d_coarse;
                 SP.perm = h->d_perm;
-                if (h->d_perm && h->d_coarseP && !h->smin_valu) {  // transformed copies: contiguous loads instead of 8-byte gathers
+                if (h->d_perm && h->d_coarseP && !h->sw.smin_valu) {  // transformed copies: contiguous loads instead of 8-byte gathers
                     HIPCK(h->ws_Qp.reserve((size_t)nq * h->D));
                     const long long tot = (long long)nq * h->D;
                     hipLaunchKernelGGL(k_permute_cols, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, dQ, h->d_perm, h->ws_Qp.p, h->D, (long long)nq);
@@ -2531,7 +2498,7 @@ int search_batch_device(mmidx_index *h, const SearchPlan &pl, int k, int64_t nq,
                 const long long nbatch = (npairs + 31) / 32;
                 const dim3 sg((unsigned)sgroups, (unsigned)std::max<long long>(1, std::min<long long>(2 * std::max(h->num_cus, 8) / sgroups, nbatch)));
                 int32_t *hint_cand = h->pin_hint ? h->pin_hint + 2 : nullptr;
-                if (h->dsub == 16 && h->smin_bf16 && !h->smin_valu) {
+                if (h->dsub == 16 && h->sw.smin_bf16 && !h->sw.smin_valu) {
                     // first stage: the bf16 bound over every candidate; what it cannot drop becomes the fp32 stage's candidate list
                     HIPCK(h->ws_cand2.reserve((size_t)npairs + 4));
                     HIPCK(h->ws_smin1.reserve((size_t)npairs));
@@ -2551,7 +2518,7 @@ int search_batch_device(mmidx_index *h, const SearchPlan &pl, int k, int64_t nq,
                     cand_list = h->ws_cand2.p;
                     hint_cand = nullptr;  // (the figure the host steers by is the first stage's input)
                 }
-                if (h->smin_valu) {  // (A/B: the packed-FMA form)
+                if (h->sw.smin_valu) {  // (A/B: the packed-FMA form)
                     if (h->dsub == 16) hipLaunchKernelGGL(k_pair_smin<16>, sg, dim3(SMIN_NW * 64), 0, st, SP);
                     else if (h->dsub == 8) hipLaunchKernelGGL(k_pair_smin<8>, sg, dim3(SMIN_NW * 64), 0, st, SP);
                     else hipLaunchKernelGGL(k_pair_smin<4>, sg, dim3(SMIN_NW * 64), 0, st, SP);
@@ -2602,7 +2569,7 @@ int search_batch_device(mmidx_index *h, const SearchPlan &pl, int k, int64_t nq,
                                h->ws_order.p, h->ws_keep.p);
             HIPCK(hipGetLastError());
             DBG_SYNC("pair sort");
-            if (h->debug_sync) {
+            if (h->sw.debug_sync) {
                 int32_t nsurv = 0;
                 (void)hipMemcpy(&nsurv, h->ws_pstart.p + h->C, 4, hipMemcpyDeviceToHost);
                 fprintf(stderr, "[mmidx] pass B: %d of %lld (query, probe) pairs survive the coarse bound (rmax %.4f)\n", nsurv,
@@ -2878,30 +2845,12 @@ int mmidx_create(int kind, int D, int m, int ks, int C, int transform, const int
     }
     h->h_off.assign((size_t)h->nlists + 1, 0);
     {
-        const char *nf = getenv("MMIDX_NO_FILTER");
-        h->no_filter = nf && nf[0] == '1';
-        const char *nb = getenv("MMIDX_NO_BOUND");
-        h->no_bound = (nb && nb[0] == '1') || h->no_filter;
-        const char *ds = getenv("MMIDX_DEBUG_SYNC");
-        h->debug_sync = ds && ds[0] == '1';
-        const char *ec = getenv("MMIDX_EXACT_COARSE");
-        h->exact_coarse = ec && ec[0] == '1';
-        const char *p5 = getenv("MMIDX_PASSA_512");
-        h->passa_512 = p5 && p5[0] == '1';
-        const char *p2 = getenv("MMIDX_PASSA_SU2");
-        h->passa_su2 = p2 && p2[0] == '1';
-        const char *cv1 = getenv("MMIDX_COARSE_V1");
-        h->coarse_v1 = cv1 && cv1[0] == '1';
-        const char *ph = getenv("MMIDX_PASSA_HIST");
-        if (ph) h->passa_hist = atoi(ph);
-        const char *pw = getenv("MMIDX_PASSA_WIDE");
-        if (pw) h->passa_wide = atoi(pw);
-        const char *pp = getenv("MMIDX_PASSA_PREFIX");
-        if (pp) h->passa_prefix = atoi(pp);
-        const char *pf = getenv("MMIDX_PASSA_FILTER");
-        h->passa_filter = pf && pf[0] == '1';
-        const char *nsd = getenv("MMIDX_SEED");
-        h->no_seed = !(nsd && nsd[0] == '1');
+        // the switches with an environment twin: a flag is on when the variable starts with '1', a number is taken as written
+        for (const OptionRow &o : kOptions) {
+            const char *e = o.env ? getenv(o.env) : nullptr;
+            if (e) h->sw.*o.field = o.norm == OPT_BOOL ? e[0] == '1' : atoi(e);
+        }
+        if (h->sw.no_filter) h->sw.no_bound = 1;
     }
     *out = h;
     return MMIDX_OK;
@@ -3613,7 +3562,7 @@ int mmidx_search(mmidx_index *h, int k, int64_t nq, const double *Q, int32_t *ii
     me.iid = iid_out;
     me.dist = dist_out;
     me.cnt = count_out;
-    if (nq > MMIDX_COMB_MAX_Q && h->host_slots_on) return search_host_big(h, me);
+    if (nq > MMIDX_COMB_MAX_Q && h->sw.host_slots) return search_host_big(h, me);
     return combiner_submit(h->comb, me, MMIDX_COMB_MAX_Q, [h](SearchReq *const *batch, size_t nb) {
         std::lock_guard<std::recursive_mutex> slk(h->search_mu);  // (id queries use the same workspaces and stream)
         return search_host_batch(h, batch, nb);
@@ -3862,92 +3811,27 @@ int mmidx_compact_partials_device(int device, int k, int64_t nq, const double *d
     return MMIDX_OK;
 }
 
-// runtime switches for measurements (same meaning as the MMIDX_* environment variables read at create)
+// runtime switches for measurements and tests: the rows of kOptions
 int mmidx_set_option(mmidx_index *h, const char *name, int value) {
     if (!h || !name) return fail(MMIDX_ERR_INVALID_ARG, "null argument");
     if (h->grp) return sharded_set_option(h, name, value);
     const std::string n(name);
-    if (n == "exhaustive") {  // every probed code is read and summed in fp64: no filter, no coarse bound
-        h->no_filter = value != 0;
-        h->no_bound = value != 0;
-    } else if (n == "no_filter") {
-        h->no_filter = value != 0;
-    } else if (n == "no_bound") {
-        h->no_bound = value != 0;
-    } else if (n == "exact_coarse") {
-        h->exact_coarse = value != 0;
-    } else if (n == "combine") {
-        h->comb.enabled = value != 0;
-    } else if (n == "passb_main_grid") {
-        h->passb_main_grid = value;
-    } else if (n == "coarse_v1") {
-        h->coarse_v1 = value != 0;
-    } else if (n == "coarse_fused") {
-        h->coarse_fused = value != 0;
-    } else if (n == "coarse_dma_kc") {
-        h->coarse_dma_kc = value != 0;
-    } else if (n == "coarse_nodma") {
-        h->coarse_nodma = value != 0;
-    } else if (n == "no_item_compaction") {
-        h->no_item_compaction = value != 0;
-    } else if (n == "passa_item_min") {
-        h->passa_item_min = value;
-    } else if (n == "passa_item_margin") {
-        h->passa_item_margin = value;
-    } else if (n == "passa_hist") {
-        h->passa_hist = value;
-    } else if (n == "passa_wide") {
-        h->passa_wide = value;
-    } else if (n == "no_grp") {  // pass B through K3f (one block per (query, list)) instead of the grouped K3g
-        h->no_grp = value != 0;
-    } else if (n == "flat_chunk") {
-        h->flat_chunk = value;
-    } else if (n == "smin_bf16") {
-        h->smin_bf16 = value != 0;
-    } else if (n == "smin_valu") {
-        h->smin_valu = value != 0;
-    } else if (n == "smin_pre") {  // K3s in front of pass B: 1 always, 0 never, -1 by the device's figures of the call before
-        h->smin_pre = value < 0 ? -1 : (value != 0);
-    } else if (n == "no_union") {  // K3g without the per-query histogram that lowers thresholds from the union over lists
-        h->no_union = value < 0 ? -1 : (value != 0);
-    } else if (n == "host_slots") {  // large host-pointer requests: 1 = up to three callers in flight (default), 0 = one at a time
-        h->host_slots_on = value != 0;
-    } else if (n == "passa_q") {  // K3q: 1 always, 0 never, -1 by the batch (default)
-        h->passa_q = value;
-    } else if (n == "passa_mfma") {  // K3ma: 1 always, 0 never, -1 by the batch (default)
-        h->passa_mfma = value;
-    } else if (n == "passa_mfma_wide") {
-        h->a_wide = value != 0;
-    } else if (n == "no_split_table") {  // m = 128: the table-in-global kernels instead of k_scan_split
-        h->no_split_table = value != 0;
-    } else if (n == "no_mfma") {  // pass B through K3g / K3f instead of the matrix-core bound K3m
-        h->no_mfma = value != 0;
-    } else if (n == "mfma_sub") {
-        h->mfma_sub = value > 0 ? value : 0;
-    } else if (n == "mfma_qcap") {
-        h->mfma_qcap = value > 0 ? value : 0;
-    } else if (n == "passa_mfma_icnt_sat") {  // K3ma's record prefix saturates here (0: at 0xFFFFFFFF); a small value sends its items to the redo
-        h->passa_mfma_icnt_sat = value > 0 ? value : 0;
-    } else if (n == "coarse_wave_sel") {
-        h->coarse_wave_sel = value != 0;
-    } else if (n == "passb_small") {
-        h->passb_small = value != 0;
-    } else if (n == "mfma_kc_v1") {
-        h->mfma_kc_v1 = value != 0;
-    } else if (n == "mfma_kc_tpw") {
-        h->mfma_kc_tpw = value == 16 ? 16 : 8;
-    } else if (n == "lut_pre") {
-        h->lut_pre = value < 0 ? -1 : (value != 0);
-    } else if (n == "mfma_blocks") {
-        h->mfma_blocks = value > 0 ? value : 0;
-    } else if (n == "grp_blocks") {
-        h->grp_blocks = value > 0 ? value : 0;
-    } else if (n == "passa_prefix") {
-        h->passa_prefix = value > 0 ? value : 0;
-    } else {
-        return fail(MMIDX_ERR_INVALID_ARG, "unknown option '%s'", name);
+    for (const OptionRow &o : kOptions) {
+        if (n != o.name) continue;
+        int v = value;
+        switch (o.norm) {
+            case OPT_BOOL: v = value != 0; break;
+            case OPT_TRI: v = value < 0 ? -1 : (value != 0); break;
+            case OPT_MIN0: v = std::max(0, value); break;
+            case OPT_8_OR_16: v = value == 16 ? 16 : 8; break;
+            case OPT_RAW: break;
+        }
+        if (o.field) h->sw.*o.field = v;
+        else if (n == "combine") h->comb.enabled = v != 0;
+        else h->sw.no_filter = h->sw.no_bound = v;  // "exhaustive"
+        return MMIDX_OK;
     }
-    return MMIDX_OK;
+    return fail(MMIDX_ERR_INVALID_ARG, "unknown option '%s'", name);
 }
 
 int mmidx_set_profiling(mmidx_index *h, int enabled) {
@@ -4040,7 +3924,7 @@ int mmidx_get_stats(mmidx_index *h, mmidx_stats *out) {
         s.mfma_survivors = (int64_t)c2[0];
         s.mfma_redo_queries = (int64_t)c2[1];
     }
-    if (h->debug_sync || getenv("MMIDX_GRP_STATS"))
+    if (h->sw.debug_sync || getenv("MMIDX_GRP_STATS"))
     {
         fprintf(stderr, "[mmidx] K3g: %llu pairs in groups, %llu alive after the table build (Smin < T), %llu codes verified\n", (unsigned long long)cnt[5],
                 (unsigned long long)cnt[6], (unsigned long long)cnt[3]);
@@ -4148,7 +4032,7 @@ int mmidx_get_dispatch(mmidx_index *h, char *out, int cap) {
     if (!h || !out || cap < 1) return fail(MMIDX_ERR_INVALID_ARG, "null argument");
     const mmidx_index *s = h->grp ? sharded_first(h) : h;
     // (launch_scan_filtered / launch_scan: K3f falls back to the exact scan K3 for shapes it has no instance of)
-    const bool k3f_ok = s->code_bytes == 1 && s->ks <= 256 && (s->m == 8 || s->m == 16 || s->m == 32) && !s->no_filter;
+    const bool k3f_ok = s->code_bytes == 1 && s->ks <= 256 && (s->m == 8 || s->m == 16 || s->m == 32) && !s->sw.no_filter;
     const char *pb = s->disp_passb;
     if (!k3f_ok && pb[0] == 'K' && pb[1] == '3' && pb[2] == 'f') pb = "K3(exact scan: no K3f instance for this shape)";
     snprintf(out, (size_t)cap, "coarse=%s;pass_a=%s;pre=%s;pass_b=%s", s->disp_coarse, s->disp_passa, s->disp_pre, pb);
@@ -4395,7 +4279,7 @@ struct mmidx_vlad {
     // per vocabulary whose "coarse quantizer" is the vocabulary
     std::vector<mmidx_index *> asg;
     DevBuf<int32_t> ws_nn;
-    int exact = 0;  // option "exact" / MMIDX_VLAD_EXACT=1: the one-kernel form (k_vlad: fp64 brute-force assignment inside the block)
+    int exact = 0;  // option "exact": the one-kernel form (k_vlad: fp64 brute-force assignment inside the block)
     int two_pass = 0;  // option "two_pass": K8' also where K8'' (k_vlad_fused) applies
 };
 
@@ -4524,7 +4408,6 @@ int mmidx_vlad_create(int nvocab, const int32_t *ncent, int dl, const double *co
     HIPCK(hipStreamCreateWithFlags(&v->stream, hipStreamNonBlocking));
     HIPCK(hipMalloc((void **)&v->d_cb, tot * 8));
     HIPCK(hipMemcpy(v->d_cb, codebooks, tot * 8, hipMemcpyHostToDevice));
-    v->exact = getenv("MMIDX_VLAD_EXACT") ? 1 : 0;
     for (int i = 0; i < nvocab; i++) {  // (a vocabulary the assignment kernels cannot take leaves its slot empty: k_vlad serves it)
         mmidx_index *a = nullptr;
         if (ncent[i] >= 2) {

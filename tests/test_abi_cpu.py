@@ -77,3 +77,62 @@ def test_product_does_not_reference_the_oracle():
             if f.endswith((".py", ".hip", ".h", ".cpp", "Makefile")):
                 txt = open(os.path.join(dirpath, f), errors="replace").read()
                 assert "mmidx_oracle" not in txt and "from oracle" not in txt and "import oracle" not in txt, f
+
+
+def _read(*parts):
+    return open(os.path.join(ROOT, *parts), errors="replace").read()
+
+
+def option_table_names():
+    """the names in the rows of kOptions (csrc/mmidx_api.hip)"""
+    src = _read("multimedia-indexing_amd", "csrc", "mmidx_api.hip")
+    table = src[src.index("const OptionRow kOptions[] = {"):]
+    return re.findall(r'^    \{"(\w+)",', table[:table.index("\n};")], flags=re.M)
+
+
+def test_option_table_matches_header_and_callers():
+    """The switch surface is one table: include/mmidx.h lists exactly its names, every caller in the tree passes a name that
+    exists, and nothing of the retired switches is left in the product."""
+    names = option_table_names()
+    assert len(names) >= 30 and len(set(names)) == len(names)
+    # (a) the header's list: the lines `"name": text` between the list's opening sentence and the sharded handle's own options
+    hdr = _read("include", "mmidx.h")
+    lst = hdr[hdr.index("/* Runtime switches for measurements and tests"):hdr.index("int mmidx_set_option(")]
+    own, shard = lst.split(" * A sharded handle passes these on")
+    assert sorted(re.findall(r'^ \*   "(\w+)":', own, flags=re.M)) == sorted(names)
+    # ... and the group-level ones are those of sharded_set_option
+    sh = _read("multimedia-indexing_amd", "csrc", "mmidx_sharded.h")
+    sh = sh[sh.index("int sharded_set_option("):]
+    shard_names = set(re.findall(r'n == "(\w+)"', sh[:sh.index("\n}\n")]))
+    assert set(re.findall(r'^ \*   "(\w+)":', shard, flags=re.M)) == shard_names and len(shard_names) == 6
+    # (b) every literal option name a caller passes is known.  The VLAD and bag-of-words aggregators have set_option entry
+    # points of their own (mmidx_vlad_set_option, mmidx_bow_set_option): their names are read from the sources the same way;
+    # "no_such_option" is what tests pass to see the refusal.
+    api = _read("multimedia-indexing_amd", "csrc", "mmidx_api.hip")
+    vlad = api[api.index("int mmidx_vlad_set_option("):]
+    aggregator = set(re.findall(r'== "(\w+)"', vlad[:vlad.index("\n}\n")] + _read("multimedia-indexing_amd", "csrc", "mmidx_bow.hip")))
+    known = set(names) | shard_names | aggregator | {"no_such_option"}
+    files = [os.path.join(ROOT, "bench.py"), os.path.join(ROOT, "multimedia-indexing_amd", "csrc", "mmidx_bow.hip")]
+    for top in ("tests", "tools", "examples", "multimedia-indexing_amd"):
+        for dirpath, dirs, fs in os.walk(os.path.join(ROOT, top)):
+            dirs[:] = [d for d in dirs if not (top == "tools" and d == "dbg") and d != "__pycache__"]
+            files += [os.path.join(dirpath, f) for f in fs if f.endswith((".py", ".java", ".c"))]
+    seen = set()
+    for f in files:
+        for n in re.findall(r'set_option\(\s*(?:[\w.>\-]+\s*,\s*)?b?["\'](\w+)["\']', open(f, errors="replace").read()):
+            assert n in known, f"{f} passes option '{n}', which no set_option knows"
+            seen.add(n)
+    assert {"exhaustive", "exact_coarse", "passa_q", "tie_slots"} <= seen  # (the scan does find the callers)
+    # (c) the retired switches and the code only they reached are gone from the product
+    retired = ["k_scan_seed", "launch_scan_seeded", "passa_512", "passa_su2", "passa_filter", "passa_prefix", "no_seed", "code_lo", "code_hi",
+               "coarse_nodma", "no_item_compaction", "grp_blocks", "MMIDX_ASSIGN_SPLIT", "MMIDX_VLAD_EXACT"]
+    for top in ("multimedia-indexing_amd", "include"):
+        for dirpath, dirs, fs in os.walk(os.path.join(ROOT, top)):
+            dirs[:] = [d for d in dirs if d != "__pycache__"]
+            for f in fs:
+                if f.endswith((".so", ".o", ".pyc")):
+                    continue
+                txt = open(os.path.join(dirpath, f), errors="replace").read()
+                for r in retired:
+                    assert not re.search(r"\b" + r + r"\b", txt), f"{os.path.join(dirpath, f)} still names {r}"
+    assert '"lut_pre"' not in api  # (the ScanParams field and the kernel keep the name; only the option went)

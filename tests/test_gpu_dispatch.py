@@ -78,3 +78,76 @@ def test_dispatch_table(mi, oracle, row):
     npar = min(nq, 6)
     ref.add_vectors(base)
     assert_same(tuple(a[:npar] for a in got), ref.search_batch(Q[:npar], k))
+
+
+RETIRED_OPTIONS = ["no_seed", "passa_filter", "passa_512", "passa_su2", "passa_prefix", "coarse_nodma", "no_item_compaction", "lut_pre", "grp_blocks"]
+
+
+def option_defaults():
+    """name -> default of every row of kOptions (csrc/mmidx_api.hip): the initialisers of struct Switches, plus the two rows
+    that have no field of their own ("exhaustive" off, "combine" on)."""
+    import os
+    import re
+
+    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "multimedia-indexing_amd", "csrc", "mmidx_api.hip")).read()
+    body = src[src.index("struct Switches {"):]
+    body = body[:body.index("};")]
+    dflt = {n: int(v) for n, v in re.findall(r"\b(\w+) = (-?\d+)", body)}
+    table = src[src.index("const OptionRow kOptions[] = {"):]
+    names = re.findall(r'^    \{"(\w+)",', table[:table.index("\n};")], flags=re.M)
+    dflt.update(exhaustive=0, combine=1)
+    assert sorted(names) == sorted(dflt) and len(names) >= 30
+    return dflt
+
+
+def small_ivfpq(mi, oracle):
+    D, C, m, ks, n, w = 128, 8, 16, 256, 40000, 4
+    rng = np.random.default_rng(77)
+    mu = 0.5 * rng.standard_normal((C, D))
+    base = mu[rng.integers(0, C, n)] + rng.standard_normal((n, D))
+    ds = D // m
+    pq = np.stack([synth.kmeans((mu[rng.integers(0, C, 2 * ks + 500)] - base[:2 * ks + 500])[:, s * ds:(s + 1) * ds], ks, iters=1, seed=s) for s in range(m)])
+    Q = base[:30] + 0.01 * rng.standard_normal((30, D))
+
+    def make():
+        ix = mi.IVFPQ(D, n, False, "", m, ks, 0, C, 512)
+        ix.loadCoarseQuantizer(mu)
+        ix.loadProductQuantizer(pq)
+        ix.setW(w)
+        return ix
+
+    ref = oracle_ivfpq(oracle, {"coarse": mu, "pq": pq}, D, m, ks, C, w)
+    ref.add_vectors(base)
+    return make, base, Q, ref
+
+
+def test_retired_options_are_unknown(mi, oracle):
+    """A retired option name is refused like any unknown one (MMIDX_ERR_INVALID_ARG = 6), and the handle serves a search afterwards."""
+    make, base, Q, ref = small_ivfpq(mi, oracle)
+    ix = make()
+    for name in RETIRED_OPTIONS + ["no_such_option"]:
+        with pytest.raises(mi.MmidxError) as ei:
+            ix.set_option(name, 1)
+        assert ei.value.status == 6 and "unknown option" in str(ei.value), name
+    ix.indexVectors([str(i) for i in range(len(base))], base)
+    got = ix.search_batch(100, Q)
+    ix.close()
+    assert_same(tuple(a[:6] for a in got), ref.search_batch(Q[:6], 100))
+
+
+def test_options_at_their_defaults_change_nothing(mi, oracle):
+    """Every surviving option set to its default value: the same kernels and the same answers as a fresh handle."""
+    make, base, Q, ref = small_ivfpq(mi, oracle)
+    res = []
+    for set_all in (False, True):
+        ix = make()
+        if set_all:
+            for name, v in option_defaults().items():
+                ix.set_option(name, v)
+        ix.indexVectors([str(i) for i in range(len(base))], base)
+        res.append((ix.search_batch(100, Q), ix.get_dispatch()))
+        ix.close()
+    (fresh, d0), (again, d1) = res
+    assert d0 == d1, (d0, d1)
+    assert_same(again, fresh)
+    assert_same(tuple(a[:6] for a in fresh), ref.search_batch(Q[:6], 100))

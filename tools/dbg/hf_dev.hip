@@ -111,8 +111,6 @@ int main(int argc, char **argv) {
     P.fb_count = (u32 *)d_fb;
     P.fb_items = d_fb + 4;
     P.fb_ch = d_fb + 4 + nq;
-    P.code_lo = 0;
-    P.code_hi = 0x7fffffff;
     P.K1 = K1;
     P.poolq = poolq;
 
