@@ -17,7 +17,7 @@
 #include "mmidx_scan_mfma_kc.h"
 #include "mmidx_scan_mfma_a.h"
 #include "mmidx_scan_q.h"
-#include "mmidx_frontend.h"
+#include "mmidx_host.h"
 
 #include <algorithm>
 #include <cmath>
@@ -34,25 +34,7 @@
 
 namespace {
 
-thread_local std::string g_err;
-
-int fail(int code, const char *fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    g_err = buf;
-    return code;
-}
-
-#define HIPCK(expr)                                                                          \
-    do {                                                                                     \
-        hipError_t e__ = (expr);                                                             \
-        if (e__ != hipSuccess)                                                               \
-            return fail(MMIDX_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e__), \
-                        __FILE__, __LINE__);                                                 \
-    } while (0)
+thread_local std::string g_err;  // mmidx_last_error: written by mmidx_fail
 
 // ---- java.util.Random + Collections.shuffle (RandomPermutation.java:29-40) --------------------
 struct JRandom {
@@ -78,100 +60,19 @@ void jdk_random_permutation(int64_t seed, int dim, int32_t *perm) {
     for (int i = dim; i > 1; i--) std::swap(perm[i - 1], perm[r.nextInt(i)]);
 }
 
-template <typename T>
-struct DevBuf {
-    T *p = nullptr;
-    size_t cap = 0;  // elements
-    hipError_t reserve(size_t n) {
-        if (n <= cap) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        size_t want = n + n / 8 + 64;
-        hipError_t e = hipMalloc((void **)&p, want * sizeof(T));
-        if (e == hipSuccess) cap = want;
-        return e;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-};
+}  // namespace
 
-// one host-pointer search call waiting to be served (see mmidx_search)
-struct SearchReq {
-    int k;
-    int64_t nq;
-    const double *Q;
-    int32_t *iid;
-    double *dist;
-    int32_t *cnt;
-    int rc = MMIDX_OK;
-    bool done = false;
-    std::string err;
-    std::condition_variable cv;  // its caller sleeps here: woken when served, or when it is the oldest and nobody leads
-};
-
-// Concurrent callers of a host-pointer search are combined into one device batch (the reference's API is one query
-// per call, from many reader threads): requests queue here, one caller at a time leads and serves the queue.
-struct Combiner {
-    std::mutex mu;
-    std::deque<SearchReq *> q;
-    bool busy = false;
-    int enabled = 1;  // 0 = every call runs on its own
-};
-
-// Queues `me`, leads batches (serve(requests, count) -> status) until `me` has been served, returns its status.
-template <class Serve>
-int combiner_submit(Combiner &c, SearchReq &me, int64_t max_q, Serve serve) {
-    std::unique_lock<std::mutex> lk(c.mu);
-    c.q.push_back(&me);
-    while (!me.done) {
-        if (c.busy) {
-            me.cv.wait(lk);
-            continue;
-        }
-        // lead: the oldest request and everything behind it with the same k, up to the batch limit
-        c.busy = true;
-        std::vector<SearchReq *> batch;
-        {
-            SearchReq *first = c.q.front();
-            c.q.pop_front();
-            batch.push_back(first);
-            int64_t tot = first->nq;
-            if (c.enabled && tot <= max_q) {
-                for (auto it = c.q.begin(); it != c.q.end();) {
-                    if ((*it)->k == first->k && tot + (*it)->nq <= max_q) {
-                        tot += (*it)->nq;
-                        batch.push_back(*it);
-                        it = c.q.erase(it);
-                    } else {
-                        ++it;
-                    }
-                }
-            }
-        }
-        lk.unlock();
-        const int brc = serve(batch.data(), batch.size());
-        lk.lock();
-        for (SearchReq *r : batch) {
-            r->rc = brc;
-            if (brc && r != &me) r->err = g_err;  // the message lives in the leader's thread
-            r->done = true;
-            if (r != &me) r->cv.notify_one();
-        }
-        c.busy = false;
-        // hand the lead to the oldest waiting caller (only that thread is woken); if this call is still unserved
-        // -- the batch was another k's -- it leads again itself
-        if (me.done && !c.q.empty()) c.q.front()->cv.notify_one();
-    }
-    lk.unlock();
-    if (me.rc && !me.err.empty()) g_err = me.err;
-    return me.rc;
+int mmidx_fail(int code, const char *fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof(buf), fmt, ap);
+    va_end(ap);
+    g_err = buf;
+    return code;
 }
 
-}  // namespace
+void mmidx_clear_error() { g_err.clear(); }
 
 // ---- runtime switches ------------------------------------------------------------------------------------------------------
 // A/B and test switches of a handle, set by name through mmidx_set_option; a few are also read from the environment by
@@ -423,7 +324,7 @@ void sharded_destroy(mmidx_index *h);
 #define NOT_ON_SHARDED(h, name)                                                                                              \
     do {                                                                                                                     \
         if ((h) && (h)->grp)                                                                                                 \
-            return fail(MMIDX_ERR_UNSUPPORTED, name " takes a plain handle: a sharded handle has one device per shard (use the " \
+            return mmidx_fail(MMIDX_ERR_UNSUPPORTED, name " takes a plain handle: a sharded handle has one device per shard (use the " \
                                                     "host-pointer entry points or the _sliced_device forms)");              \
     } while (0)
 
@@ -500,7 +401,7 @@ int build_csr(mmidx_index *h) {
         int c = pcell[(size_t)i];
         if (c < 0 || c >= nl) {
             h->n_pend = 0;  // (drop the pending batch rather than fail every later call on this handle)
-            return fail(MMIDX_ERR_INVALID_ARG, "list id %d outside 0..%d: %lld pending records dropped", c, nl - 1, (long long)np);
+            return mmidx_fail(MMIDX_ERR_INVALID_ARG, "list id %d outside 0..%d: %lld pending records dropped", c, nl - 1, (long long)np);
         }
         cnt[(size_t)c]++;
     }
@@ -574,10 +475,10 @@ int build_csr(mmidx_index *h) {
 }
 
 int check_ready(const mmidx_index *h) {
-    if (!h) return fail(MMIDX_ERR_INVALID_ARG, "null handle");
-    if (!h->pq_set) return fail(MMIDX_ERR_NOT_READY, "product quantizer not loaded (loadProductQuantizer)");
+    if (!h) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null handle");
+    if (!h->pq_set) return mmidx_fail(MMIDX_ERR_NOT_READY, "product quantizer not loaded (loadProductQuantizer)");
     if (h->kind == MMIDX_KIND_IVFPQ && !h->coarse_set)
-        return fail(MMIDX_ERR_NOT_READY, "coarse quantizer not loaded (loadCoarseQuantizer)");
+        return mmidx_fail(MMIDX_ERR_NOT_READY, "coarse quantizer not loaded (loadCoarseQuantizer)");
     return MMIDX_OK;
 }
 
@@ -690,7 +591,7 @@ int encode_device(mmidx_index *h, int64_t n, const double *dX, int32_t *d_cell, 
     }
     constexpr int VT = 8;
     const size_t lds = 2 * (size_t)VT * h->D * 8 + (size_t)h->m * VT * 4 * 12;
-    if (lds > 160 * 1024) return fail(MMIDX_ERR_UNSUPPORTED, "vector length %d too large for the encode kernel", h->D);
+    if (lds > 160 * 1024) return mmidx_fail(MMIDX_ERR_UNSUPPORTED, "vector length %d too large for the encode kernel", h->D);
     const unsigned grid = (unsigned)((n + VT - 1) / VT);
     if (h->code_bytes == 1) {
         HIPCK(hipFuncSetAttribute((const void *)k_encode_pq<VT, unsigned char>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -716,8 +617,8 @@ int launch_scan_t(const ScanParams &P, dim3 grid, size_t lds, hipStream_t st) {
 // su = codes per thread per segment (1 or 2); P.cap and lds sized for it
 int launch_scan(const mmidx_index *h, const ScanParams &P, dim3 grid, size_t lds, hipStream_t st, int su = 2) {
     if (P.glut) {  // the table lives in global scratch (make_plan: it does not fit the LDS): generic kernels, LDS = vectors + candidates
-        if ((size_t)grid.x * grid.y > h->glut_slots) return fail(MMIDX_ERR_UNSUPPORTED, "lookup-table scratch too small for %u x %u blocks", grid.x, grid.y);
-        if (P.cap < P.K1 + MMIDX_SEG) return fail(MMIDX_ERR_UNSUPPORTED, "candidate buffer of %d entries too small for k + 1 = %d and a %d-code segment", P.cap, P.K1, MMIDX_SEG);
+        if ((size_t)grid.x * grid.y > h->glut_slots) return mmidx_fail(MMIDX_ERR_UNSUPPORTED, "lookup-table scratch too small for %u x %u blocks", grid.x, grid.y);
+        if (P.cap < P.K1 + MMIDX_SEG) return mmidx_fail(MMIDX_ERR_UNSUPPORTED, "candidate buffer of %d entries too small for k + 1 = %d and a %d-code segment", P.cap, P.K1, MMIDX_SEG);
         const size_t l = lds - (size_t)h->m * h->ks * 8;
         // twice the LDS (m = 128 byte codes): two sweeps with half the table in LDS each (k_scan_split); cap >= K1 + 512 covers its
         // 512-code segments, a chunk's partial sums fit the block's table slot
@@ -788,7 +689,7 @@ struct SearchPlan {
 };
 
 int make_plan(mmidx_index *h, int k, int64_t nq, SearchPlan &pl, bool need_coarse = true) {
-    if (k < 1 || k > MMIDX_K_MAX) return fail(MMIDX_ERR_INVALID_ARG, "k must be in 1..%d (got %d)", MMIDX_K_MAX, k);
+    if (k < 1 || k > MMIDX_K_MAX) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "k must be in 1..%d (got %d)", MMIDX_K_MAX, k);
     pl.K1 = k + 1;
     int cap = 1;
     while (cap < pl.K1 + MMIDX_SEG) cap <<= 1;
@@ -796,7 +697,7 @@ int make_plan(mmidx_index *h, int k, int64_t nq, SearchPlan &pl, bool need_coars
     pl.lds = scan_lds_bytes(h, cap);
     pl.glut = pl.lds > 160 * 1024;  // table in global scratch, the generic exact-scan kernels only (IVFPQ.java has no such limit)
     if (pl.glut && pl.lds - (size_t)h->m * h->ks * 8 > 160 * 1024)
-        return fail(MMIDX_ERR_UNSUPPORTED, "vectors and candidate buffer of k = %d do not fit the 160 KiB LDS", k);
+        return mmidx_fail(MMIDX_ERR_UNSUPPORTED, "vectors and candidate buffer of k = %d do not fit the 160 KiB LDS", k);
     const int ivf = h->kind == MMIDX_KIND_IVFPQ;
     const int nprobe = ivf ? h->w : 1;
     int64_t chunk = 16384;
@@ -909,7 +810,7 @@ int launch_hist_nt(const ScanParams &P, dim3 grid, size_t lds, hipStream_t st) {
             static_lds = (int)fa.sharedSizeBytes;
         }
         if (static_lds != 0)
-            return fail(MMIDX_ERR_UNSUPPORTED, "k_scan_hist owns %d bytes of static LDS: its table is not at LDS address 0", static_lds);
+            return mmidx_fail(MMIDX_ERR_UNSUPPORTED, "k_scan_hist owns %d bytes of static LDS: its table is not at LDS address 0", static_lds);
     }
     HIPCK(hipFuncSetAttribute((const void *)k_scan_hist<M, KS, NT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL((k_scan_hist<M, KS, NT>), grid, dim3(NT), lds, st, P);
@@ -1022,7 +923,7 @@ int launch_scan_hist(mmidx_index *h, ScanParams P, const SearchPlan &pl, dim3 gr
         if (h->sw.debug_sync) {                                                                  \
             hipError_t e__ = hipStreamSynchronize(st);                                        \
             fprintf(stderr, "[mmidx] %s: %s\n", name, hipGetErrorString(e__));               \
-            if (e__ != hipSuccess) return fail(MMIDX_ERR_HIP, "%s failed: %s", name, hipGetErrorString(e__)); \
+            if (e__ != hipSuccess) return mmidx_fail(MMIDX_ERR_HIP, "%s failed: %s", name, hipGetErrorString(e__)); \
         }                                                                                     \
     } while (0)
 
@@ -1145,7 +1046,7 @@ int launch_q_t(const QParams &QP, unsigned grid, size_t lds, hipStream_t st) {
         HIPCK(hipFuncGetAttributes(&fa, (const void *)k_scan_q<M, DSUB>));
         static_lds = (int)fa.sharedSizeBytes;
     }
-    if (static_lds != 0) return fail(MMIDX_ERR_UNSUPPORTED, "k_scan_q owns %d bytes of static LDS: its table is not at LDS address 0", static_lds);
+    if (static_lds != 0) return mmidx_fail(MMIDX_ERR_UNSUPPORTED, "k_scan_q owns %d bytes of static LDS: its table is not at LDS address 0", static_lds);
     HIPCK(hipFuncSetAttribute((const void *)k_scan_q<M, DSUB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL((k_scan_q<M, DSUB>), dim3(grid), dim3(256), lds, st, QP);
     HIPCK(hipGetLastError());
@@ -1282,7 +1183,7 @@ int launch_passa_mfma(mmidx_index *h, const ScanParams &P, const SearchPlan &pl,
     HIPCK(h->ws_gdesc.reserve((size_t)npairs / G + (size_t)C + 8));
     HIPCK(h->ws_gfb.reserve(4 + 2 * nfb + 16));
     const PassaMfmaShape SH = passa_mfma_shape(h, npairs);
-    if (!SH.fits) return fail(MMIDX_ERR_UNSUPPORTED, "K3ma's bitmap does not fit (passa_mfma_applies must have said so)");
+    if (!SH.fits) return mmidx_fail(MMIDX_ERR_UNSUPPORTED, "K3ma's bitmap does not fit (passa_mfma_applies must have said so)");
     const int sub = SH.sub, nsub = SH.nsub;
     const size_t max_groups = SH.max_groups, bm_stride = SH.bm_stride;
     HIPCK(h->ws_T0.reserve((size_t)nq));
@@ -1810,7 +1711,7 @@ int launch_mfma_kc(mmidx_index *h, const ScanParams &S, ScanParams F, const Sear
         default: break;
     }
 #undef KC_VER
-    if (rc) return rc < 0 ? rc : fail(MMIDX_ERR_UNSUPPORTED, "K3mk: no verification instance for m = %d", h->m);
+    if (rc) return rc < 0 ? rc : mmidx_fail(MMIDX_ERR_UNSUPPORTED, "K3mk: no verification instance for m = %d", h->m);
     if (mev) HIPCK(hipEventRecord(mev[2], st));
     if (MP.stat) hipLaunchKernelGGL(k_mfma_count, dim3(1024), dim3(256), 0, st, MP);
     DBG_SYNC("K3mk verify");
@@ -2199,7 +2100,7 @@ int run_coarse(mmidx_index *h, int64_t nq, const double *dQ, int32_t *d_cells, h
     } else
         hipLaunchKernelGGL(k_coarse_dist<QT>, g1, dim3(MMIDX_BLOCK), 0, st, h->d_coarseT, dQ, h->ws_cdist.p, h->C, h->D, (int)nq);
     const size_t lds = (size_t)(h->w + 1) * 12 + 16;
-    if (lds > 64 * 1024) return fail(MMIDX_ERR_UNSUPPORTED, "w = %d too large", h->w);
+    if (lds > 64 * 1024) return mmidx_fail(MMIDX_ERR_UNSUPPORTED, "w = %d too large", h->w);
     const bool fast = h->C >= MMIDX_BLOCK && h->w + 1 <= MMIDX_BLOCK && h->C <= 64 * MMIDX_BLOCK;
     const size_t flds = (size_t)MMIDX_CSEL_CAP * 12 + (size_t)(h->w + 1) * 12 + 16;
     if (fast && h->C <= 8 * MMIDX_BLOCK)
@@ -2658,7 +2559,7 @@ int search_batch_device(mmidx_index *h, const SearchPlan &pl, int k, int64_t nq,
         const unsigned tgrid = (unsigned)std::min<int64_t>((nq + MMIDX_BLOCK - 1) / MMIDX_BLOCK, 4096);  // (a block reads MMIDX_BLOCK flags at once; flagged queries are rare)
         const size_t tlds = (P.glut ? 0 : (size_t)h->m * h->ks * 8) + 2 * (size_t)h->D * 8;
         if (P.glut) {  // (the table in global scratch: one slot per query of the sub-batch)
-            if ((size_t)nq > h->glut_slots) return fail(MMIDX_ERR_UNSUPPORTED, "lookup-table scratch too small for the tie replay");
+            if ((size_t)nq > h->glut_slots) return mmidx_fail(MMIDX_ERR_UNSUPPORTED, "lookup-table scratch too small for the tie replay");
             if (sdc_tt) {
                 hipLaunchKernelGGL((k_tie_resolve<unsigned char, true, true>), dim3(tgrid), dim3(MMIDX_BLOCK), tlds, st, TP);
             } else if (h->code_bytes == 1) {
@@ -2696,10 +2597,10 @@ int search_common(mmidx_index *h, int k, int64_t nq, const double *dQ, const int
                   const double *sdc_tt = nullptr) {
     int rc = check_ready(h);
     if (rc) return rc;
-    if (nq < 0) return fail(MMIDX_ERR_INVALID_ARG, "nq < 0");
+    if (nq < 0) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "nq < 0");
     const int ivf = h->kind == MMIDX_KIND_IVFPQ;
     if (ivf && (h->w < 1 || h->w > h->C))
-        return fail(MMIDX_ERR_INVALID_ARG, "w = %d outside 1..%d (setW)", h->w, h->C);
+        return mmidx_fail(MMIDX_ERR_INVALID_ARG, "w = %d outside 1..%d (setW)", h->w, h->C);
     rc = set_device(h);
     if (rc) return rc;
     {
@@ -2765,18 +2666,18 @@ int mmidx_device_count(void) {
 
 int mmidx_create(int kind, int D, int m, int ks, int C, int transform, const int32_t *perm, const double *rot, int device,
                  mmidx_index **out) {
-    if (!out) return fail(MMIDX_ERR_INVALID_ARG, "null out pointer");
+    if (!out) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null out pointer");
     *out = nullptr;
-    if (kind != MMIDX_KIND_PQ && kind != MMIDX_KIND_IVFPQ) return fail(MMIDX_ERR_INVALID_ARG, "unknown index kind %d", kind);
-    if (D < 1 || m < 1 || D % m > 0) return fail(MMIDX_ERR_INVALID_SUBVECTORS, "The given number of subvectors is not valid!");
-    if (ks < 1 || ks > 65536) return fail(MMIDX_ERR_UNSUPPORTED, "numProductCentroids %d outside 1..65536", ks);
-    if (kind == MMIDX_KIND_IVFPQ && C < 1) return fail(MMIDX_ERR_INVALID_ARG, "numCoarseCentroids must be >= 1");
-    if (transform < 0 || transform > 2) return fail(MMIDX_ERR_INVALID_ARG, "unknown transformation %d", transform);
+    if (kind != MMIDX_KIND_PQ && kind != MMIDX_KIND_IVFPQ) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "unknown index kind %d", kind);
+    if (D < 1 || m < 1 || D % m > 0) return mmidx_fail(MMIDX_ERR_INVALID_SUBVECTORS, "The given number of subvectors is not valid!");
+    if (ks < 1 || ks > 65536) return mmidx_fail(MMIDX_ERR_UNSUPPORTED, "numProductCentroids %d outside 1..65536", ks);
+    if (kind == MMIDX_KIND_IVFPQ && C < 1) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "numCoarseCentroids must be >= 1");
+    if (transform < 0 || transform > 2) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "unknown transformation %d", transform);
     if (transform == MMIDX_TR_ROTATION && !rot)
-        return fail(MMIDX_ERR_INVALID_ARG, "RandomRotation needs the D x D matrix computed by the Java side");
+        return mmidx_fail(MMIDX_ERR_INVALID_ARG, "RandomRotation needs the D x D matrix computed by the Java side");
     const int ndev = mmidx_device_count();
-    if (ndev < 1) return fail(MMIDX_ERR_NO_DEVICE, "no HIP device: libmmidx_hip has no CPU fallback");
-    if (device < 0 || device >= ndev) return fail(MMIDX_ERR_NO_DEVICE, "device %d outside 0..%d", device, ndev - 1);
+    if (ndev < 1) return mmidx_fail(MMIDX_ERR_NO_DEVICE, "no HIP device: libmmidx_hip has no CPU fallback");
+    if (device < 0 || device >= ndev) return mmidx_fail(MMIDX_ERR_NO_DEVICE, "device %d outside 0..%d", device, ndev - 1);
     HIPCK(hipSetDevice(device));
     mmidx_index *h = new mmidx_index();
     h->kind = kind;
@@ -2804,11 +2705,11 @@ int mmidx_create(int kind, int D, int m, int ks, int C, int transform, const int
     hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
     if (e != hipSuccess) {
         delete h;
-        return fail(MMIDX_ERR_HIP, "hipStreamCreate failed: %s", hipGetErrorString(e));
+        return mmidx_fail(MMIDX_ERR_HIP, "hipStreamCreate failed: %s", hipGetErrorString(e));
     }
     if (hipMalloc((void **)&h->d_counters, 16 * sizeof(u64)) != hipSuccess || hipMemset(h->d_counters, 0, 16 * sizeof(u64)) != hipSuccess) {
         delete h;
-        return fail(MMIDX_ERR_HIP, "hipMalloc failed");
+        return mmidx_fail(MMIDX_ERR_HIP, "hipMalloc failed");
     }
     if (transform == MMIDX_TR_PERMUTATION) {
         std::vector<int32_t> p((size_t)D);
@@ -2816,7 +2717,7 @@ int mmidx_create(int kind, int D, int m, int ks, int C, int transform, const int
             for (int i = 0; i < D; i++) {
                 if (perm[i] < 0 || perm[i] >= D) {
                     mmidx_destroy(h);
-                    return fail(MMIDX_ERR_INVALID_ARG, "permutation index out of range");
+                    return mmidx_fail(MMIDX_ERR_INVALID_ARG, "permutation index out of range");
                 }
                 p[(size_t)i] = perm[i];
             }
@@ -2975,8 +2876,8 @@ int mmidx_destroy(mmidx_index *h) {
 }
 
 int mmidx_set_coarse(mmidx_index *h, const double *coarse) {
-    if (!h || !coarse) return fail(MMIDX_ERR_INVALID_ARG, "null argument");
-    if (h->kind != MMIDX_KIND_IVFPQ) return fail(MMIDX_ERR_INVALID_ARG, "PQ index has no coarse quantizer");
+    if (!h || !coarse) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null argument");
+    if (h->kind != MMIDX_KIND_IVFPQ) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "PQ index has no coarse quantizer");
     if (h->grp) {  // codebooks are replicated on every shard
         int rcs = sharded_for_each(h, [&](mmidx_index *s) { return mmidx_set_coarse(s, coarse); });
         if (!rcs) h->coarse_set = true;
@@ -3046,7 +2947,7 @@ int mmidx_set_coarse(mmidx_index *h, const double *coarse) {
 }
 
 int mmidx_set_pq(mmidx_index *h, const double *pq) {
-    if (!h || !pq) return fail(MMIDX_ERR_INVALID_ARG, "null argument");
+    if (!h || !pq) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null argument");
     if (h->grp) {
         int rcs = sharded_for_each(h, [&](mmidx_index *s) { return mmidx_set_pq(s, pq); });
         if (!rcs) h->pq_set = true;
@@ -3115,24 +3016,24 @@ int mmidx_set_pq(mmidx_index *h, const double *pq) {
 }
 
 int mmidx_set_w(mmidx_index *h, int w) {
-    if (!h) return fail(MMIDX_ERR_INVALID_ARG, "null handle");
+    if (!h) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null handle");
     h->w = w;  // validated at search time, as the reference does (IVFPQ.java:95-97)
     if (h->grp) return sharded_for_each(h, [&](mmidx_index *s) { return mmidx_set_w(s, w); });
     return MMIDX_OK;
 }
 int mmidx_get_w(const mmidx_index *h, int *w_out) {
-    if (!h || !w_out) return fail(MMIDX_ERR_INVALID_ARG, "null argument");
+    if (!h || !w_out) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null argument");
     *w_out = h->w;
     return MMIDX_OK;
 }
 int mmidx_size(const mmidx_index *h, int64_t *n_out) {
-    if (!h || !n_out) return fail(MMIDX_ERR_INVALID_ARG, "null argument");
+    if (!h || !n_out) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null argument");
     *n_out = h->grp ? sharded_total(h) : total_size(h);
     return MMIDX_OK;
 }
 
 int mmidx_sync_index(mmidx_index *h) {
-    if (!h) return fail(MMIDX_ERR_INVALID_ARG, "null handle");
+    if (!h) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null handle");
     if (h->grp) return sharded_sync(h);
     int rc = set_device(h);
     if (rc) return rc;
@@ -3141,7 +3042,7 @@ int mmidx_sync_index(mmidx_index *h) {
 }
 
 int mmidx_list_sizes(mmidx_index *h, int32_t *sizes_out) {
-    if (!h || !sizes_out) return fail(MMIDX_ERR_INVALID_ARG, "null argument");
+    if (!h || !sizes_out) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null argument");
     if (h->grp) return sharded_list_sizes(h, sizes_out);
     int rc = mmidx_sync_index(h);
     if (rc) return rc;
@@ -3153,7 +3054,7 @@ int mmidx_encode_device(mmidx_index *h, int64_t n, const double *dX, int32_t *d_
     NOT_ON_SHARDED(h, "mmidx_encode_device");
     int rc = check_ready(h);
     if (rc) return rc;
-    if (n < 0 || (n > 0 && (!dX || !d_cell_out || !d_code_out))) return fail(MMIDX_ERR_INVALID_ARG, "null argument");
+    if (n < 0 || (n > 0 && (!dX || !d_cell_out || !d_code_out))) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null argument");
     rc = set_device(h);
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
@@ -3174,12 +3075,12 @@ int mmidx_encode_device(mmidx_index *h, int64_t n, const double *dX, int32_t *d_
 
 int mmidx_encode(mmidx_index *h, int64_t n, const double *X, int32_t *cell_out, void *code_out) {
     if (h && h->grp) {
-        if (n < 0 || (n > 0 && (!X || !code_out))) return fail(MMIDX_ERR_INVALID_ARG, "null argument");
+        if (n < 0 || (n > 0 && (!X || !code_out))) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null argument");
         return sharded_encode(h, n, X, cell_out, code_out);
     }
     int rc = check_ready(h);
     if (rc) return rc;
-    if (n < 0 || (n > 0 && (!X || !code_out))) return fail(MMIDX_ERR_INVALID_ARG, "null argument");
+    if (n < 0 || (n > 0 && (!X || !code_out))) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null argument");
     if (n == 0) return MMIDX_OK;
     rc = set_device(h);
     if (rc) return rc;
@@ -3203,12 +3104,12 @@ int mmidx_encode(mmidx_index *h, int64_t n, const double *X, int32_t *cell_out, 
 
 // append n device-resident records; codes in stored form (int8 biased / int16)
 int mmidx_add_codes_device(mmidx_index *h, int64_t n, const int32_t *d_iids, const int32_t *d_cells, const void *d_codes, void *stream) {
-    if (!h) return fail(MMIDX_ERR_INVALID_ARG, "null handle");
+    if (!h) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null handle");
     NOT_ON_SHARDED(h, "mmidx_add_codes_device");
-    if (n < 0 || (n > 0 && (!d_iids || !d_codes))) return fail(MMIDX_ERR_INVALID_ARG, "null argument");
-    if (h->kind == MMIDX_KIND_IVFPQ && n > 0 && !d_cells) return fail(MMIDX_ERR_INVALID_ARG, "IVFPQ needs list ids");
+    if (n < 0 || (n > 0 && (!d_iids || !d_codes))) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null argument");
+    if (h->kind == MMIDX_KIND_IVFPQ && n > 0 && !d_cells) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "IVFPQ needs list ids");
     if (n == 0) return MMIDX_OK;
-    if (total_size(h) + n > 2147483647LL) return fail(MMIDX_ERR_CAPACITY, "Maximum index capacity reached, no more vectors can be indexed!");
+    if (total_size(h) + n > 2147483647LL) return mmidx_fail(MMIDX_ERR_CAPACITY, "Maximum index capacity reached, no more vectors can be indexed!");
     int rc = set_device(h);
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
@@ -3248,21 +3149,21 @@ int mmidx_add_codes_device(mmidx_index *h, int64_t n, const int32_t *d_iids, con
     int32_t bad = 0;
     HIPCK(hipMemcpyAsync(&bad, h->d_counters + 4, sizeof(bad), hipMemcpyDeviceToHost, h->stream));
     HIPCK(hipStreamSynchronize(h->stream));
-    if (bad & 1) return fail(MMIDX_ERR_INVALID_ARG, "list id outside 0..%d: the batch was not added", h->nlists - 1);
-    if (bad & 2) return fail(MMIDX_ERR_INVALID_ARG, "code value outside 0..%d (numProductCentroids): the batch was not added", h->ks - 1);
+    if (bad & 1) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "list id outside 0..%d: the batch was not added", h->nlists - 1);
+    if (bad & 2) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "code value outside 0..%d (numProductCentroids): the batch was not added", h->ks - 1);
     h->n_pend += n;
     return MMIDX_OK;
 }
 
 int mmidx_add_codes(mmidx_index *h, int64_t n, const int32_t *iids, const int32_t *cells, const void *codes) {
-    if (!h) return fail(MMIDX_ERR_INVALID_ARG, "null handle");
-    if (n < 0 || (n > 0 && (!iids || !codes))) return fail(MMIDX_ERR_INVALID_ARG, "null argument");
-    if (h->kind == MMIDX_KIND_IVFPQ && n > 0 && !cells) return fail(MMIDX_ERR_INVALID_ARG, "IVFPQ needs list ids");
+    if (!h) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null handle");
+    if (n < 0 || (n > 0 && (!iids || !codes))) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null argument");
+    if (h->kind == MMIDX_KIND_IVFPQ && n > 0 && !cells) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "IVFPQ needs list ids");
     if (n == 0) return MMIDX_OK;
     if (h->grp) return sharded_add_codes(h, n, iids, cells, codes);
     if (h->kind == MMIDX_KIND_IVFPQ)
         for (int64_t i = 0; i < n; i++)
-            if (cells[i] < 0 || cells[i] >= h->C) return fail(MMIDX_ERR_INVALID_ARG, "list id %d outside 0..%d", cells[i], h->C - 1);
+            if (cells[i] < 0 || cells[i] >= h->C) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "list id %d outside 0..%d", cells[i], h->C - 1);
     int rc = set_device(h);
     if (rc) return rc;
     const size_t cb = (size_t)h->m * h->code_bytes;
@@ -3285,9 +3186,9 @@ int mmidx_add_vectors_device(mmidx_index *h, int64_t n, const double *dX, const 
     NOT_ON_SHARDED(h, "mmidx_add_vectors_device");
     int rc = check_ready(h);
     if (rc) return rc;
-    if (n < 0 || (n > 0 && !dX)) return fail(MMIDX_ERR_INVALID_ARG, "null argument");
+    if (n < 0 || (n > 0 && !dX)) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null argument");
     if (n == 0) return MMIDX_OK;
-    if (total_size(h) + n > 2147483647LL) return fail(MMIDX_ERR_CAPACITY, "Maximum index capacity reached, no more vectors can be indexed!");
+    if (total_size(h) + n > 2147483647LL) return mmidx_fail(MMIDX_ERR_CAPACITY, "Maximum index capacity reached, no more vectors can be indexed!");
     rc = set_device(h);
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
@@ -3313,12 +3214,12 @@ int mmidx_add_vectors_device(mmidx_index *h, int64_t n, const double *dX, const 
 
 int mmidx_add_vectors(mmidx_index *h, int64_t n, const double *X, const int32_t *iids, int32_t *cell_out, void *code_out) {
     if (h && h->grp) {
-        if (n < 0 || (n > 0 && !X)) return fail(MMIDX_ERR_INVALID_ARG, "null argument");
+        if (n < 0 || (n > 0 && !X)) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null argument");
         return sharded_add_vectors(h, n, X, nullptr, nullptr, iids, MMIDX_IID_AUTO, cell_out, code_out);
     }
     int rc = check_ready(h);
     if (rc) return rc;
-    if (n < 0 || (n > 0 && !X)) return fail(MMIDX_ERR_INVALID_ARG, "null argument");
+    if (n < 0 || (n > 0 && !X)) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null argument");
     if (n == 0) return MMIDX_OK;
     rc = set_device(h);
     if (rc) return rc;
@@ -3357,8 +3258,8 @@ int mmidx_add_vectors(mmidx_index *h, int64_t n, const double *X, const int32_t 
 
 int mmidx_search_device(mmidx_index *h, int k, int64_t nq, const double *dQ, int32_t *d_iid_out, double *d_dist_out,
                         int32_t *d_count_out, void *stream) {
-    if (!h) return fail(MMIDX_ERR_INVALID_ARG, "null handle");
-    if (nq > 0 && (!dQ || !d_iid_out || !d_dist_out || !d_count_out)) return fail(MMIDX_ERR_INVALID_ARG, "null argument");
+    if (!h) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null handle");
+    if (nq > 0 && (!dQ || !d_iid_out || !d_dist_out || !d_count_out)) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null argument");
     NOT_ON_SHARDED(h, "mmidx_search_device");
     hipStream_t st = (hipStream_t)stream;
     DeviceCall call(h, st);
@@ -3371,7 +3272,6 @@ int mmidx_search_device(mmidx_index *h, int k, int64_t nq, const double *dQ, int
 // TOGETHER by the next leader: queries staged in pinned memory (one H2D), one search, one D2H of
 // (distances | ids | counts), results scattered to the callers' buffers.  Every query's answer is the one it
 // would get alone (queries of a batch are independent in every kernel).
-#define MMIDX_COMB_MAX_Q 4096   // queries per combined batch; larger requests run alone with direct copies
 static int search_host_direct(mmidx_index *h, const SearchReq &r) {
     const int k = r.k;
     const int64_t nq = r.nq;
@@ -3548,9 +3448,9 @@ static int search_host_batch(mmidx_index *h, SearchReq *const *batch, size_t nb)
 }
 
 int mmidx_search(mmidx_index *h, int k, int64_t nq, const double *Q, int32_t *iid_out, double *dist_out, int32_t *count_out) {
-    if (!h) return fail(MMIDX_ERR_INVALID_ARG, "null handle");
-    if (nq > 0 && (!Q || !iid_out || !dist_out || !count_out)) return fail(MMIDX_ERR_INVALID_ARG, "null argument");
-    if (k < 1 || k > MMIDX_K_MAX) return fail(MMIDX_ERR_INVALID_ARG, "k must be in 1..%d (got %d)", MMIDX_K_MAX, k);
+    if (!h) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null handle");
+    if (nq > 0 && (!Q || !iid_out || !dist_out || !count_out)) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null argument");
+    if (k < 1 || k > MMIDX_K_MAX) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "k must be in 1..%d (got %d)", MMIDX_K_MAX, k);
     if (h->grp) return sharded_search(h, k, nq, Q, iid_out, dist_out, count_out);
     int rc = check_ready(h);
     if (rc) return rc;
@@ -3571,12 +3471,12 @@ int mmidx_search(mmidx_index *h, int k, int64_t nq, const double *Q, int32_t *ii
 
 // computeNearestNeighborsInternal(k, iid) for PQ: computeKnnSDC, PQ.java:334-374
 int mmidx_search_sdc(mmidx_index *h, int k, int64_t nq, const int32_t *iids, int32_t *iid_out, double *dist_out, int32_t *count_out) {
-    if (!h) return fail(MMIDX_ERR_INVALID_ARG, "null handle");
-    if (nq > 0 && (!iids || !iid_out || !dist_out || !count_out)) return fail(MMIDX_ERR_INVALID_ARG, "null argument");
+    if (!h) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null handle");
+    if (nq > 0 && (!iids || !iid_out || !dist_out || !count_out)) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null argument");
     NOT_ON_SHARDED(h, "mmidx_search_sdc");
-    if (h->kind != MMIDX_KIND_PQ) return fail(MMIDX_ERR_UNSUPPORTED, "id queries: IVFPQ.computeKnnIVFSDC is unimplemented in the reference (IVFPQ.java:509-511)");
-    if (h->code_bytes != 1) return fail(MMIDX_ERR_UNSUPPORTED, "SDC needs byte codes (the reference dereferences pqByteCodes unconditionally, PQ.java:350)");
-    if (k < 1 || k > MMIDX_K_MAX) return fail(MMIDX_ERR_INVALID_ARG, "k must be in 1..%d (got %d)", MMIDX_K_MAX, k);
+    if (h->kind != MMIDX_KIND_PQ) return mmidx_fail(MMIDX_ERR_UNSUPPORTED, "id queries: IVFPQ.computeKnnIVFSDC is unimplemented in the reference (IVFPQ.java:509-511)");
+    if (h->code_bytes != 1) return mmidx_fail(MMIDX_ERR_UNSUPPORTED, "SDC needs byte codes (the reference dereferences pqByteCodes unconditionally, PQ.java:350)");
+    if (k < 1 || k > MMIDX_K_MAX) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "k must be in 1..%d (got %d)", MMIDX_K_MAX, k);
     int rc = check_ready(h);
     if (rc) return rc;
     if (nq == 0) return MMIDX_OK;
@@ -3589,7 +3489,7 @@ int mmidx_search_sdc(mmidx_index *h, int k, int64_t nq, const int32_t *iids, int
         if (rc) return rc;
     }
     for (int64_t i = 0; i < nq; i++)
-        if (iids[i] < 0 || iids[i] >= h->n_csr) return fail(MMIDX_ERR_INVALID_ARG, "internal id %d outside 0..%lld", iids[i], (long long)h->n_csr - 1);
+        if (iids[i] < 0 || iids[i] >= h->n_csr) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "internal id %d outside 0..%lld", iids[i], (long long)h->n_csr - 1);
     const size_t per = (size_t)h->m * h->ks * h->dsub;
     const int64_t QB = std::max<int64_t>(1, (int64_t)((1ull << 30) / (per * 8)));  // <= 1 GiB of term tables per round
     for (int64_t q0 = 0; q0 < nq; q0 += QB) {
@@ -3619,39 +3519,20 @@ int mmidx_coarse_device(mmidx_index *h, int64_t nq, const double *dQ, int32_t *d
     NOT_ON_SHARDED(h, "mmidx_coarse_device");
     int rc = check_ready(h);
     if (rc) return rc;
-    if (h->kind != MMIDX_KIND_IVFPQ) return fail(MMIDX_ERR_INVALID_ARG, "PQ index has no coarse quantizer");
-    if (h->w < 1 || h->w > h->C) return fail(MMIDX_ERR_INVALID_ARG, "w = %d outside 1..%d (setW)", h->w, h->C);
-    if (nq > 0 && (!dQ || !d_cells_out)) return fail(MMIDX_ERR_INVALID_ARG, "null argument");
+    if (h->kind != MMIDX_KIND_IVFPQ) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "PQ index has no coarse quantizer");
+    if (h->w < 1 || h->w > h->C) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "w = %d outside 1..%d (setW)", h->w, h->C);
+    if (nq > 0 && (!dQ || !d_cells_out)) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null argument");
     rc = set_device(h);
     if (rc) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    DeviceCall call(h, st);
-    const int64_t qb = std::max<int64_t>(1, (2ll << 30) / ((int64_t)h->C * 8));
-    for (int64_t q0 = 0; q0 < nq; q0 += qb) {
-        const int64_t nb = std::min(qb, nq - q0);
-        rc = run_coarse(h, nb, dQ + (size_t)q0 * h->D, d_cells_out + (size_t)q0 * h->w, st);
-        if (rc) return rc;
-        if (d_cdist_out) {
-            double *dst = d_cdist_out + (size_t)q0 * h->w;
-            if (h->cdsel_valid) {
-                HIPCK(hipMemcpyAsync(dst, h->ws_cdsel.p, (size_t)nb * h->w * 8, hipMemcpyDeviceToDevice, st));
-            } else {
-                const long long tot = (long long)nb * h->w;
-                hipLaunchKernelGGL(k_gather_cdist, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, h->ws_cdist.p,
-                                   d_cells_out + (size_t)q0 * h->w, dst, h->C, h->w, tot);
-                HIPCK(hipGetLastError());
-            }
-        }
-    }
-    return MMIDX_OK;
+    return mmidx_internal_coarse_topw(h, h->w, nq, dQ, d_cells_out, d_cdist_out, (hipStream_t)stream);
 }
 
 int mmidx_search_partial_device(mmidx_index *h, int k, int64_t nq, const double *dQ, const int32_t *d_cells, double *d_pdist,
                                 int64_t *d_pkey, int32_t *d_pcount, void *stream) {
-    if (!h) return fail(MMIDX_ERR_INVALID_ARG, "null handle");
+    if (!h) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null handle");
     NOT_ON_SHARDED(h, "mmidx_search_partial_device");
-    if (nq > 0 && (!dQ || !d_pdist || !d_pkey || !d_pcount)) return fail(MMIDX_ERR_INVALID_ARG, "null argument");
-    if (h->kind == MMIDX_KIND_IVFPQ && nq > 0 && !d_cells) return fail(MMIDX_ERR_INVALID_ARG, "IVFPQ partial search needs the probe cells");
+    if (nq > 0 && (!dQ || !d_pdist || !d_pkey || !d_pcount)) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null argument");
+    if (h->kind == MMIDX_KIND_IVFPQ && nq > 0 && !d_cells) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "IVFPQ partial search needs the probe cells");
     hipStream_t st = (hipStream_t)stream;
     DeviceCall call(h, st);
     return search_common(h, k, nq, dQ, h->kind == MMIDX_KIND_IVFPQ ? d_cells : nullptr, 1, nullptr, nullptr, d_pcount, d_pdist,
@@ -3661,15 +3542,15 @@ int mmidx_search_partial_device(mmidx_index *h, int k, int64_t nq, const double 
 // two-phase sharded search: thresholds are exchanged between the phases (MIN all-reduce)
 static int shard_phase(mmidx_index *h, int k, int64_t nq, const double *dQ, const int32_t *d_cells, const double *d_cdist, int phase,
                        double *d_T, double *d_pdist, int64_t *d_pkey, int32_t *d_pcount, void *stream) {
-    if (!h) return fail(MMIDX_ERR_INVALID_ARG, "null handle");
+    if (!h) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null handle");
     NOT_ON_SHARDED(h, "the shard phases");
-    if (nq > 0 && (!dQ || !d_T)) return fail(MMIDX_ERR_INVALID_ARG, "null argument");
-    if (phase == 2 && nq > 0 && (!d_pdist || !d_pkey || !d_pcount)) return fail(MMIDX_ERR_INVALID_ARG, "null argument");
+    if (nq > 0 && (!dQ || !d_T)) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null argument");
+    if (phase == 2 && nq > 0 && (!d_pdist || !d_pkey || !d_pcount)) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null argument");
     int rc = check_ready(h);
     if (rc) return rc;
     const int ivf = h->kind == MMIDX_KIND_IVFPQ;
-    if (ivf && nq > 0 && !d_cells) return fail(MMIDX_ERR_INVALID_ARG, "IVFPQ shard search needs the probe cells");
-    if (ivf && (h->w < 1 || h->w > h->C)) return fail(MMIDX_ERR_INVALID_ARG, "w = %d outside 1..%d (setW)", h->w, h->C);
+    if (ivf && nq > 0 && !d_cells) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "IVFPQ shard search needs the probe cells");
+    if (ivf && (h->w < 1 || h->w > h->C)) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "w = %d outside 1..%d (setW)", h->w, h->C);
     if (nq == 0) return MMIDX_OK;
     rc = set_device(h);
     if (rc) return rc;
@@ -3686,7 +3567,7 @@ static int shard_phase(mmidx_index *h, int k, int64_t nq, const double *dQ, cons
     SearchPlan pl;
     rc = make_plan(h, k, nq, pl, false);
     if (rc) return rc;
-    if (nq > pl.qb) return fail(MMIDX_ERR_UNSUPPORTED, "shard phases take at most %lld queries per call for this index", (long long)pl.qb);
+    if (nq > pl.qb) return mmidx_fail(MMIDX_ERR_UNSUPPORTED, "shard phases take at most %lld queries per call for this index", (long long)pl.qb);
     return search_batch_device(h, pl, k, nq, dQ, ivf ? d_cells : nullptr, 1, nullptr, nullptr, d_pcount, d_pdist, (long long *)d_pkey, phase,
                                d_T, (hipStream_t)stream, nullptr, ivf ? d_cdist : nullptr);
 }
@@ -3703,11 +3584,11 @@ int mmidx_shard_pass_b_device(mmidx_index *h, int k, int64_t nq, const double *d
 int mmidx_merge_partials_device(int device, int k, int64_t nq, int nshards, const double *d_pdist, const int64_t *d_pkey,
                                 const int32_t *d_pcount, const int64_t *d_poff, int32_t *d_iid_out, double *d_dist_out,
                                 int32_t *d_count_out, int32_t *d_flag_out, void *stream) {
-    if (k < 1 || k > MMIDX_K_MAX) return fail(MMIDX_ERR_INVALID_ARG, "k must be in 1..%d (got %d)", MMIDX_K_MAX, k);
-    if (nshards < 1 || nq < 0) return fail(MMIDX_ERR_INVALID_ARG, "bad shard / query count");
+    if (k < 1 || k > MMIDX_K_MAX) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "k must be in 1..%d (got %d)", MMIDX_K_MAX, k);
+    if (nshards < 1 || nq < 0) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "bad shard / query count");
     if (nq > 0 && (!d_pdist || !d_pkey || !d_pcount || !d_iid_out || !d_dist_out || !d_count_out))
-        return fail(MMIDX_ERR_INVALID_ARG, "null argument");
-    if (mmidx_device_count() < 1) return fail(MMIDX_ERR_NO_DEVICE, "no HIP device: libmmidx_hip has no CPU fallback");
+        return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null argument");
+    if (mmidx_device_count() < 1) return mmidx_fail(MMIDX_ERR_NO_DEVICE, "no HIP device: libmmidx_hip has no CPU fallback");
     if (nq == 0) return MMIDX_OK;
     HIPCK(hipSetDevice(device));
     return launch_merge_partials(k, nq, nshards, d_pdist, d_pkey, d_pcount, d_poff, d_iid_out, d_dist_out, d_count_out, d_flag_out, nullptr,
@@ -3717,14 +3598,14 @@ int mmidx_merge_partials_device(int device, int k, int64_t nq, int nshards, cons
 // one pass of the cross-shard tie replay (k_shard_tie); counts / pB / tie_iids are reduced over ranks by the caller in between
 int mmidx_shard_tie_phase_device(mmidx_index *h, int phase, int k, int64_t nf, const double *dQ, const int32_t *d_cells, const int32_t *d_fq,
                                  const double *d_tau, int32_t *d_counts, int32_t *d_pB, int32_t *d_tie_iids, void *stream) {
-    if (!h) return fail(MMIDX_ERR_INVALID_ARG, "null handle");
+    if (!h) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null handle");
     NOT_ON_SHARDED(h, "mmidx_shard_tie_phase_device");
-    if (phase < 0 || phase > 2 || k < 1 || nf < 0) return fail(MMIDX_ERR_INVALID_ARG, "bad phase / k / count");
+    if (phase < 0 || phase > 2 || k < 1 || nf < 0) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "bad phase / k / count");
     if (nf > 0 && (!dQ || !d_cells || !d_fq || !d_tau || !d_counts || (phase >= 1 && !d_pB) || (phase == 2 && !d_tie_iids)))
-        return fail(MMIDX_ERR_INVALID_ARG, "null argument");
+        return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null argument");
     int rc = check_ready(h);
     if (rc) return rc;
-    if (h->kind != MMIDX_KIND_IVFPQ) return fail(MMIDX_ERR_INVALID_ARG, "sharded search needs an IVFPQ index");
+    if (h->kind != MMIDX_KIND_IVFPQ) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "sharded search needs an IVFPQ index");
     if (nf == 0) return MMIDX_OK;
     rc = set_device(h);
     if (rc) return rc;
@@ -3779,11 +3660,11 @@ int mmidx_shard_tie_phase_device(mmidx_index *h, int phase, int k, int64_t nf, c
 }
 
 int mmidx_assign_device(mmidx_index *h, int64_t n, const double *dX, int32_t *d_cell_out, void *stream) {
-    if (!h) return fail(MMIDX_ERR_INVALID_ARG, "null handle");
+    if (!h) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null handle");
     NOT_ON_SHARDED(h, "mmidx_assign_device");
-    if (h->kind != MMIDX_KIND_IVFPQ) return fail(MMIDX_ERR_INVALID_ARG, "PQ index has no coarse quantizer");
-    if (!h->coarse_set) return fail(MMIDX_ERR_NOT_READY, "coarse quantizer not loaded (loadCoarseQuantizer)");
-    if (n < 0 || (n > 0 && (!dX || !d_cell_out))) return fail(MMIDX_ERR_INVALID_ARG, "null argument");
+    if (h->kind != MMIDX_KIND_IVFPQ) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "PQ index has no coarse quantizer");
+    if (!h->coarse_set) return mmidx_fail(MMIDX_ERR_NOT_READY, "coarse quantizer not loaded (loadCoarseQuantizer)");
+    if (n < 0 || (n > 0 && (!dX || !d_cell_out))) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null argument");
     int rc = set_device(h);
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
@@ -3799,9 +3680,9 @@ int mmidx_assign_device(mmidx_index *h, int64_t n, const double *dX, int32_t *d_
 
 int mmidx_compact_partials_device(int device, int k, int64_t nq, const double *d_pdist, const int64_t *d_pkey, const int32_t *d_pcount,
                                   const int64_t *d_poff, double *d_out_dist, int64_t *d_out_key, void *stream) {
-    if (k < 1 || k > MMIDX_K_MAX || nq < 0) return fail(MMIDX_ERR_INVALID_ARG, "bad k / query count");
-    if (nq > 0 && (!d_pdist || !d_pkey || !d_pcount || !d_poff)) return fail(MMIDX_ERR_INVALID_ARG, "null argument");
-    if (mmidx_device_count() < 1) return fail(MMIDX_ERR_NO_DEVICE, "no HIP device: libmmidx_hip has no CPU fallback");
+    if (k < 1 || k > MMIDX_K_MAX || nq < 0) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "bad k / query count");
+    if (nq > 0 && (!d_pdist || !d_pkey || !d_pcount || !d_poff)) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null argument");
+    if (mmidx_device_count() < 1) return mmidx_fail(MMIDX_ERR_NO_DEVICE, "no HIP device: libmmidx_hip has no CPU fallback");
     if (nq == 0) return MMIDX_OK;
     HIPCK(hipSetDevice(device));
     hipLaunchKernelGGL(k_compact_partials, dim3((unsigned)((nq + 3) / 4)), dim3(MMIDX_BLOCK), 0, (hipStream_t)stream, d_pdist,
@@ -3813,7 +3694,7 @@ int mmidx_compact_partials_device(int device, int k, int64_t nq, const double *d
 
 // runtime switches for measurements and tests: the rows of kOptions
 int mmidx_set_option(mmidx_index *h, const char *name, int value) {
-    if (!h || !name) return fail(MMIDX_ERR_INVALID_ARG, "null argument");
+    if (!h || !name) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null argument");
     if (h->grp) return sharded_set_option(h, name, value);
     const std::string n(name);
     for (const OptionRow &o : kOptions) {
@@ -3831,11 +3712,11 @@ int mmidx_set_option(mmidx_index *h, const char *name, int value) {
         else h->sw.no_filter = h->sw.no_bound = v;  // "exhaustive"
         return MMIDX_OK;
     }
-    return fail(MMIDX_ERR_INVALID_ARG, "unknown option '%s'", name);
+    return mmidx_fail(MMIDX_ERR_INVALID_ARG, "unknown option '%s'", name);
 }
 
 int mmidx_set_profiling(mmidx_index *h, int enabled) {
-    if (!h) return fail(MMIDX_ERR_INVALID_ARG, "null handle");
+    if (!h) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null handle");
     if (h->grp) return sharded_for_each(h, [&](mmidx_index *s) { return mmidx_set_profiling(s, enabled); });
     int rc = set_device(h);
     if (rc) return rc;
@@ -3858,7 +3739,7 @@ int mmidx_set_profiling(mmidx_index *h, int enabled) {
 // Resolves every event recorded since the last call (synchronises with the launch stream) and
 // returns the accumulated statistics; the accumulation restarts afterwards.
 int mmidx_get_stats(mmidx_index *h, mmidx_stats *out) {
-    if (!h || !out) return fail(MMIDX_ERR_INVALID_ARG, "null argument");
+    if (!h || !out) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null argument");
     if (h->grp) return sharded_get_stats(h, out);
     int rc = set_device(h);
     if (rc) return rc;
@@ -3960,7 +3841,7 @@ int ensure_inverse(mmidx_index *h) {
     }
     hipError_t e = hipMemcpy(&mx, d_max, sizeof(mx), hipMemcpyDeviceToHost);
     (void)hipFree(d_max);
-    if (e != hipSuccess) return fail(MMIDX_ERR_HIP, "hipMemcpy failed: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return mmidx_fail(MMIDX_ERR_HIP, "hipMemcpy failed: %s", hipGetErrorString(e));
     h->inv_size = (int64_t)mx + 1;
     HIPCK(h->ws_inv.reserve((size_t)std::max<int64_t>(h->inv_size, 1)));
     HIPCK(hipMemsetAsync(h->ws_inv.p, 0xFF, (size_t)std::max<int64_t>(h->inv_size, 1) * sizeof(int32_t), h->stream));
@@ -3985,7 +3866,7 @@ int lookup_records(mmidx_index *h, int64_t n, const int32_t *iids, int32_t **d_p
     if (hipMalloc((void **)&d_pos, std::max<size_t>((size_t)n * 4, 16)) != hipSuccess || hipMalloc(&d_code, std::max<size_t>(cbytes, 16)) != hipSuccess) {
         (void)hipFree(d_iids);
         if (d_pos) (void)hipFree(d_pos);
-        return fail(MMIDX_ERR_HIP, "hipMalloc failed");
+        return mmidx_fail(MMIDX_ERR_HIP, "hipMalloc failed");
     }
     auto cleanup = [&]() {
         (void)hipFree(d_iids);
@@ -4009,13 +3890,13 @@ int lookup_records(mmidx_index *h, int64_t n, const int32_t *iids, int32_t **d_p
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
     if (e != hipSuccess) {
         cleanup();
-        return fail(MMIDX_ERR_HIP, "record lookup failed: %s", hipGetErrorString(e));
+        return mmidx_fail(MMIDX_ERR_HIP, "record lookup failed: %s", hipGetErrorString(e));
     }
     for (int64_t i = 0; i < n; i++) {
         if (pos[(size_t)i] < 0) {
             if (allow_missing) continue;  // (a shard of a sharded handle: the id lives on another shard)
             cleanup();
-            return fail(MMIDX_ERR_INVALID_ARG, "Id does not exist!");  // IVFPQ.java:803-805, :868-870
+            return mmidx_fail(MMIDX_ERR_INVALID_ARG, "Id does not exist!");  // IVFPQ.java:803-805, :868-870
         }
         // list of a position: the last list whose start is <= pos
         const auto it = std::upper_bound(h->h_off.begin(), h->h_off.end(), (int64_t)pos[(size_t)i]);
@@ -4029,7 +3910,7 @@ int lookup_records(mmidx_index *h, int64_t n, const int32_t *iids, int32_t **d_p
 }  // namespace
 
 int mmidx_get_dispatch(mmidx_index *h, char *out, int cap) {
-    if (!h || !out || cap < 1) return fail(MMIDX_ERR_INVALID_ARG, "null argument");
+    if (!h || !out || cap < 1) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null argument");
     const mmidx_index *s = h->grp ? sharded_first(h) : h;
     // (launch_scan_filtered / launch_scan: K3f falls back to the exact scan K3 for shapes it has no instance of)
     const bool k3f_ok = s->code_bytes == 1 && s->ks <= 256 && (s->m == 8 || s->m == 16 || s->m == 32) && !s->sw.no_filter;
@@ -4040,7 +3921,7 @@ int mmidx_get_dispatch(mmidx_index *h, char *out, int cap) {
 }
 
 int mmidx_get_dims(const mmidx_index *h, int *D, int *m, int *ks, int *C, int *code_bytes) {
-    if (!h) return fail(MMIDX_ERR_INVALID_ARG, "null handle");
+    if (!h) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null handle");
     if (D) *D = h->D;
     if (m) *m = h->m;
     if (ks) *ks = h->ks;
@@ -4050,8 +3931,8 @@ int mmidx_get_dims(const mmidx_index *h, int *D, int *m, int *ks, int *C, int *c
 }
 
 int mmidx_get_codes(mmidx_index *h, int64_t n, const int32_t *iids, int32_t *cell_out, void *code_out) {
-    if (!h || (n > 0 && !iids)) return fail(MMIDX_ERR_INVALID_ARG, "null argument");
-    if (n < 0) return fail(MMIDX_ERR_INVALID_ARG, "n < 0");
+    if (!h || (n > 0 && !iids)) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null argument");
+    if (n < 0) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "n < 0");
     if (n == 0) return MMIDX_OK;
     if (h->grp) return sharded_get_codes(h, n, iids, cell_out, code_out);
     int rc = set_device(h);
@@ -4067,15 +3948,15 @@ int mmidx_get_codes(mmidx_index *h, int64_t n, const int32_t *iids, int32_t *cel
     if (code_out) e = hipMemcpy(code_out, d_code, (size_t)n * h->m * h->code_bytes, hipMemcpyDeviceToHost);
     (void)hipFree(d_pos);
     (void)hipFree(d_code);
-    if (e != hipSuccess) return fail(MMIDX_ERR_HIP, "hipMemcpy failed: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return mmidx_fail(MMIDX_ERR_HIP, "hipMemcpy failed: %s", hipGetErrorString(e));
     if (cell_out)
         for (int64_t i = 0; i < n; i++) cell_out[i] = h->kind == MMIDX_KIND_IVFPQ ? cells[(size_t)i] : -1;
     return MMIDX_OK;
 }
 
 int mmidx_distance(mmidx_index *h, int64_t n, const double *Q, const int32_t *iids, double *dist_out) {
-    if (!h || (n > 0 && (!Q || !iids || !dist_out))) return fail(MMIDX_ERR_INVALID_ARG, "null argument");
-    if (n < 0) return fail(MMIDX_ERR_INVALID_ARG, "n < 0");
+    if (!h || (n > 0 && (!Q || !iids || !dist_out))) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null argument");
+    if (n < 0) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "n < 0");
     if (h->grp) return n == 0 ? MMIDX_OK : sharded_distance(h, n, Q, iids, dist_out);
     int rc = check_ready(h);
     if (rc) return rc;
@@ -4123,13 +4004,13 @@ int mmidx_distance(mmidx_index *h, int64_t n, const double *Q, const int32_t *ii
     if (dQ) (void)hipFree(dQ);
     if (d_out) (void)hipFree(d_out);
     if (d_cell) (void)hipFree(d_cell);
-    if (e != hipSuccess) return fail(MMIDX_ERR_HIP, "mmidx_distance failed: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return mmidx_fail(MMIDX_ERR_HIP, "mmidx_distance failed: %s", hipGetErrorString(e));
     return MMIDX_OK;
 }
 
 /* snapshot of the in-memory index, list-major (the layout loadIndexInMemory builds) */
 int mmidx_export(mmidx_index *h, int64_t *list_off_out, int32_t *iids_out, void *codes_out) {
-    if (!h || !list_off_out) return fail(MMIDX_ERR_INVALID_ARG, "null argument");
+    if (!h || !list_off_out) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null argument");
     if (h->grp) return sharded_export(h, list_off_out, iids_out, codes_out);
     int rc = mmidx_sync_index(h);
     if (rc) return rc;
@@ -4158,7 +4039,7 @@ struct MmidxSnapHeader {
 };
 
 int mmidx_save(mmidx_index *h, const char *path) {
-    if (!h || !path) return fail(MMIDX_ERR_INVALID_ARG, "null argument");
+    if (!h || !path) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null argument");
     int64_t n = 0;
     int rc = mmidx_size(h, &n);
     if (rc) return rc;
@@ -4171,7 +4052,7 @@ int mmidx_save(mmidx_index *h, const char *path) {
     std::vector<unsigned char> codes((size_t)n * m * cb);
     rc = mmidx_export(h, off.data(), n ? iids.data() : nullptr, n ? (void *)codes.data() : nullptr);
     if (rc) return rc;
-    if (off[(size_t)nlists] != n) return fail(MMIDX_ERR_HIP, "export returned %lld records, the index holds %lld", (long long)off[(size_t)nlists], (long long)n);
+    if (off[(size_t)nlists] != n) return mmidx_fail(MMIDX_ERR_HIP, "export returned %lld records, the index holds %lld", (long long)off[(size_t)nlists], (long long)n);
     MmidxSnapHeader hd{};
     memcpy(hd.magic, "MMIDXSN1", 8);
     hd.version = 1;
@@ -4186,42 +4067,42 @@ int mmidx_save(mmidx_index *h, const char *path) {
     hd.nlists = (uint64_t)nlists;
     const std::string tmp = std::string(path) + ".tmp";
     FILE *f = fopen(tmp.c_str(), "wb");
-    if (!f) return fail(MMIDX_ERR_INVALID_ARG, "cannot open %s for writing", tmp.c_str());
+    if (!f) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "cannot open %s for writing", tmp.c_str());
     bool ok = fwrite(&hd, sizeof(hd), 1, f) == 1 && fwrite(off.data(), 8, off.size(), f) == off.size();
     ok = ok && (n == 0 || (fwrite(iids.data(), 4, iids.size(), f) == iids.size() && fwrite(codes.data(), 1, codes.size(), f) == codes.size()));
     ok = (fclose(f) == 0) && ok;
     if (!ok || rename(tmp.c_str(), path) != 0) {
         (void)remove(tmp.c_str());
-        return fail(MMIDX_ERR_INVALID_ARG, "writing the snapshot %s failed", path);
+        return mmidx_fail(MMIDX_ERR_INVALID_ARG, "writing the snapshot %s failed", path);
     }
     return MMIDX_OK;
 }
 
 int mmidx_load(mmidx_index *h, const char *path) {
-    if (!h || !path) return fail(MMIDX_ERR_INVALID_ARG, "null argument");
+    if (!h || !path) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null argument");
     int64_t have = 0;
     int rc = mmidx_size(h, &have);
     if (rc) return rc;
-    if (have != 0) return fail(MMIDX_ERR_INVALID_ARG, "mmidx_load needs an empty index (this one holds %lld records)", (long long)have);
+    if (have != 0) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "mmidx_load needs an empty index (this one holds %lld records)", (long long)have);
     int D = 0, m = 0, ks = 0, C = 0, cb = 0;
     rc = mmidx_get_dims(h, &D, &m, &ks, &C, &cb);
     if (rc) return rc;
     FILE *f = fopen(path, "rb");
-    if (!f) return fail(MMIDX_ERR_INVALID_ARG, "cannot open the snapshot %s", path);
+    if (!f) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "cannot open the snapshot %s", path);
     MmidxSnapHeader hd{};
     const bool hok = fread(&hd, sizeof(hd), 1, f) == 1 && memcmp(hd.magic, "MMIDXSN1", 8) == 0 && hd.version == 1;
     const int64_t nlists = h->kind == MMIDX_KIND_IVFPQ ? C : 1;
     if (!hok || hd.kind != (uint32_t)h->kind || hd.D != (uint32_t)D || hd.m != (uint32_t)m || hd.ks != (uint32_t)ks || hd.C != (uint32_t)C ||
         hd.code_bytes != (uint32_t)cb || hd.transform != (uint32_t)h->transform || hd.nlists != (uint64_t)nlists) {
         fclose(f);
-        return fail(MMIDX_ERR_INVALID_ARG, "%s is not a snapshot of an index of this shape (kind / D / m / ks / C / code width / transform)", path);
+        return mmidx_fail(MMIDX_ERR_INVALID_ARG, "%s is not a snapshot of an index of this shape (kind / D / m / ks / C / code width / transform)", path);
     }
     std::vector<int64_t> off((size_t)nlists + 1);
     bool ok = fread(off.data(), 8, off.size(), f) == off.size() && off[0] == 0 && off[(size_t)nlists] == (int64_t)hd.n;
     for (int64_t c = 0; ok && c < nlists; c++) ok = off[(size_t)c] <= off[(size_t)c + 1];
     if (!ok) {
         fclose(f);
-        return fail(MMIDX_ERR_INVALID_ARG, "%s: damaged list offsets", path);
+        return mmidx_fail(MMIDX_ERR_INVALID_ARG, "%s: damaged list offsets", path);
     }
     const int64_t n = (int64_t)hd.n;
     const size_t rec = (size_t)m * cb;
@@ -4250,541 +4131,40 @@ int mmidx_load(mmidx_index *h, const char *path) {
         }
     }
     fclose(f);
-    if (!ok) return fail(MMIDX_ERR_INVALID_ARG, "%s: truncated snapshot", path);
+    if (!ok) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "%s: truncated snapshot", path);
     return mmidx_sync_index(h);
 }
 
 }  // extern "C"
 
-// =================================================================================================
-// Front end of BASELINE config 5: PCA projection (K7) and VLAD aggregation (K8)
-// =================================================================================================
-struct mmidx_pca {
-    std::mutex mu;  // host-pointer calls share the workspaces
-    int nc = 0, ss = 0, whitening = 0, device = 0;
-    double *d_mu = nullptr, *d_Vt = nullptr;
-    hipStream_t stream = nullptr;
-    DevBuf<double> ws_X, ws_Y;
-};
-struct mmidx_vlad {
-    std::mutex mu;  // host-pointer calls share the workspaces
-    int nvocab = 0, dl = 0, norms = 0, device = 0, veclen = 0;
-    std::vector<int> nc;
-    std::vector<size_t> cb_off;  // element offset of each codebook
-    double *d_cb = nullptr;
-    hipStream_t stream = nullptr;
-    DevBuf<double> ws_desc, ws_out;
-    DevBuf<long long> ws_off;
-    // K8': the assignment of every descriptor of a launch through the encoder's certified MFMA argmin -- one hidden index handle
-    // per vocabulary whose "coarse quantizer" is the vocabulary
-    std::vector<mmidx_index *> asg;
-    DevBuf<int32_t> ws_nn;
-    int exact = 0;  // option "exact": the one-kernel form (k_vlad: fp64 brute-force assignment inside the block)
-    int two_pass = 0;  // option "two_pass": K8' also where K8'' (k_vlad_fused) applies
-};
-
-extern "C" {
-
-int mmidx_pca_create(int nc, int ss, int whitening, const double *means, const double *eig, const double *Vt, int device,
-                     mmidx_pca **out) {
-    if (!out) return fail(MMIDX_ERR_INVALID_ARG, "null out pointer");
-    *out = nullptr;
-    if (nc < 1 || ss < 1 || !means || !Vt) return fail(MMIDX_ERR_INVALID_ARG, "bad PCA shape or null matrix");
-    if (whitening && !eig) return fail(MMIDX_ERR_INVALID_ARG, "whitening needs the eigenvalues line of the PCA file");
-    const int ndev = mmidx_device_count();
-    if (ndev < 1) return fail(MMIDX_ERR_NO_DEVICE, "no HIP device: libmmidx_hip has no CPU fallback");
-    if (device < 0 || device >= ndev) return fail(MMIDX_ERR_NO_DEVICE, "device %d outside 0..%d", device, ndev - 1);
-    HIPCK(hipSetDevice(device));
-    mmidx_pca *p = new mmidx_pca();
-    p->nc = nc;
-    p->ss = ss;
-    p->whitening = whitening ? 1 : 0;
-    p->device = device;
-    std::vector<double> V((size_t)nc * ss);
-    for (int i = 0; i < nc; i++) {
-        // W(i,i) = pow(eig_i, -0.5); V_t <- W * V_t  (PCA.java:283-285, :311): row i scaled by w_ii
-        const double wv = whitening ? std::pow(eig[i], -0.5) : 1.0;
-        for (int j = 0; j < ss; j++) V[(size_t)i * ss + j] = whitening ? wv * Vt[(size_t)i * ss + j] : Vt[(size_t)i * ss + j];
-    }
-    HIPCK(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
-    HIPCK(hipMalloc((void **)&p->d_mu, (size_t)ss * 8));
-    HIPCK(hipMalloc((void **)&p->d_Vt, (size_t)nc * ss * 8));
-    HIPCK(hipMemcpy(p->d_mu, means, (size_t)ss * 8, hipMemcpyHostToDevice));
-    HIPCK(hipMemcpy(p->d_Vt, V.data(), (size_t)nc * ss * 8, hipMemcpyHostToDevice));
-    *out = p;
-    return MMIDX_OK;
-}
-
-int mmidx_pca_get_dims(const mmidx_pca *p, int *nc_out, int *ss_out) {
-    if (!p) return fail(MMIDX_ERR_INVALID_ARG, "null handle");
-    if (nc_out) *nc_out = p->nc;
-    if (ss_out) *ss_out = p->ss;
-    return MMIDX_OK;
-}
-
-int mmidx_pca_destroy(mmidx_pca *p) {
-    if (!p) return MMIDX_OK;
-    (void)hipSetDevice(p->device);
-    if (p->d_mu) (void)hipFree(p->d_mu);
-    if (p->d_Vt) (void)hipFree(p->d_Vt);
-    p->ws_X.release();
-    p->ws_Y.release();
-    if (p->stream) (void)hipStreamDestroy(p->stream);
-    delete p;
-    return MMIDX_OK;
-}
-
-int mmidx_pca_project_device(mmidx_pca *p, int64_t n, const double *dX, double *dY, void *stream) {
-    if (!p) return fail(MMIDX_ERR_INVALID_ARG, "null handle");
-    if (n < 0 || (n > 0 && (!dX || !dY))) return fail(MMIDX_ERR_INVALID_ARG, "null argument");
-    if (n == 0) return MMIDX_OK;
-    HIPCK(hipSetDevice(p->device));
-    hipStream_t st = (hipStream_t)stream;
-    dim3 grid((unsigned)((n + PCA_BM - 1) / PCA_BM), (unsigned)((p->nc + PCA_BN - 1) / PCA_BN));
-    HIPCK(hipFuncSetAttribute((const void *)k_pca_project, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PCA_LDS_BYTES));
-    hipLaunchKernelGGL(k_pca_project, grid, dim3(PCA_NT), PCA_LDS_BYTES, st, dX, p->d_mu, p->d_Vt, dY, (long long)n, p->nc, p->ss);
-    if (p->whitening)
-        hipLaunchKernelGGL(k_rows_normalize_l2, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, dY, (long long)n, p->nc);
-    HIPCK(hipGetLastError());
-    return MMIDX_OK;
-}
-
-// for mmidx_pca_learn.hip (same library, not exported): the calling thread's error text, and K7 on plain device pointers --
-// Y[n][nc] = (X[n][ss] - mu[ss]) Vt[nc][ss]^T, the tall products of the PCA learner's subspace iteration
-__attribute__((visibility("hidden"))) int mmidx_internal_fail(int code, const char *msg) { return fail(code, "%s", msg); }
-__attribute__((visibility("hidden"))) int mmidx_internal_gemm_nt(const double *X, const double *mu, const double *Vt, double *Y, long long n,
-                                                                  int nc, int ss, void *stream) {
-    dim3 grid((unsigned)((n + PCA_BM - 1) / PCA_BM), (unsigned)((nc + PCA_BN - 1) / PCA_BN));
-    static_assert(PCA_LDS_BYTES <= 64 * 1024, "K7's tiles fit the default dynamic LDS limit: no attribute to raise per launch");
-    hipLaunchKernelGGL(k_pca_project, grid, dim3(PCA_NT), PCA_LDS_BYTES, (hipStream_t)stream, X, mu, Vt, Y, n, nc, ss);
-    HIPCK(hipGetLastError());
-    return MMIDX_OK;
-}
-
-int mmidx_pca_project(mmidx_pca *p, int64_t n, const double *X, double *Y) {
-    if (!p) return fail(MMIDX_ERR_INVALID_ARG, "null handle");
-    if (n < 0 || (n > 0 && (!X || !Y))) return fail(MMIDX_ERR_INVALID_ARG, "null argument");
-    std::lock_guard<std::mutex> lk(p->mu);
-    HIPCK(hipSetDevice(p->device));
-    const int64_t B = std::max<int64_t>(1, (int64_t)(1ll << 28) / p->ss);  // <= 2 GiB of samples per round
-    for (int64_t i0 = 0; i0 < n; i0 += B) {
-        const int64_t nb = std::min(B, n - i0);
-        HIPCK(p->ws_X.reserve((size_t)nb * p->ss));
-        HIPCK(p->ws_Y.reserve((size_t)nb * p->nc));
-        HIPCK(hipMemcpyAsync(p->ws_X.p, X + (size_t)i0 * p->ss, (size_t)nb * p->ss * 8, hipMemcpyHostToDevice, p->stream));
-        int rc = mmidx_pca_project_device(p, nb, p->ws_X.p, p->ws_Y.p, p->stream);
-        if (rc) return rc;
-        HIPCK(hipMemcpyAsync(Y + (size_t)i0 * p->nc, p->ws_Y.p, (size_t)nb * p->nc * 8, hipMemcpyDeviceToHost, p->stream));
-        HIPCK(hipStreamSynchronize(p->stream));
-    }
-    return MMIDX_OK;
-}
-
-int mmidx_vlad_create(int nvocab, const int32_t *ncent, int dl, const double *codebooks, int normalizations_on, int device,
-                      mmidx_vlad **out) {
-    if (!out) return fail(MMIDX_ERR_INVALID_ARG, "null out pointer");
-    *out = nullptr;
-    if (nvocab < 1 || !ncent || dl < 1 || !codebooks) return fail(MMIDX_ERR_INVALID_ARG, "bad codebook description");
-    const int ndev = mmidx_device_count();
-    if (ndev < 1) return fail(MMIDX_ERR_NO_DEVICE, "no HIP device: libmmidx_hip has no CPU fallback");
-    if (device < 0 || device >= ndev) return fail(MMIDX_ERR_NO_DEVICE, "device %d outside 0..%d", device, ndev - 1);
-    HIPCK(hipSetDevice(device));
-    mmidx_vlad *v = new mmidx_vlad();
-    v->nvocab = nvocab;
-    v->dl = dl;
-    v->norms = normalizations_on ? 1 : 0;
-    v->device = device;
-    size_t tot = 0;
-    for (int i = 0; i < nvocab; i++) {
-        if (ncent[i] < 1) {
-            delete v;
-            return fail(MMIDX_ERR_INVALID_ARG, "empty codebook");
-        }
-        v->nc.push_back(ncent[i]);
-        v->cb_off.push_back(tot);
-        tot += (size_t)ncent[i] * dl;
-    }
-    v->veclen = (int)tot;
-    HIPCK(hipStreamCreateWithFlags(&v->stream, hipStreamNonBlocking));
-    HIPCK(hipMalloc((void **)&v->d_cb, tot * 8));
-    HIPCK(hipMemcpy(v->d_cb, codebooks, tot * 8, hipMemcpyHostToDevice));
-    for (int i = 0; i < nvocab; i++) {  // (a vocabulary the assignment kernels cannot take leaves its slot empty: k_vlad serves it)
-        mmidx_index *a = nullptr;
-        if (ncent[i] >= 2) {
-            int rca = mmidx_create(MMIDX_KIND_IVFPQ, dl, 1, 2, ncent[i], MMIDX_TR_NONE, nullptr, nullptr, device, &a);
-            if (rca == MMIDX_OK) rca = mmidx_set_coarse(a, codebooks + v->cb_off[(size_t)i]);
-            if (rca != MMIDX_OK) {  // the slot falls back to k_vlad: not an error of this call, so no stale message either
-                if (a) mmidx_destroy(a);
-                a = nullptr;
-                g_err.clear();
-            }
-        }
-        v->asg.push_back(a);
-    }
-    *out = v;
-    return MMIDX_OK;
-}
-
-int mmidx_vlad_set_option(mmidx_vlad *v, const char *name, int value) {
-    if (!v || !name) return fail(MMIDX_ERR_INVALID_ARG, "null argument");
-    if (std::string(name) == "exact") {
-        v->exact = value != 0;
-        return MMIDX_OK;
-    }
-    if (std::string(name) == "two_pass") {  // K8' (assignment kernel + accumulation kernel) also where the one-kernel form K8'' applies (A/B switch)
-        v->two_pass = value != 0;
-        return MMIDX_OK;
-    }
-    return fail(MMIDX_ERR_INVALID_ARG, "unknown option '%s'", name);
-}
-
-int mmidx_vlad_destroy(mmidx_vlad *v) {
-    if (!v) return MMIDX_OK;
-    (void)hipSetDevice(v->device);
-    if (v->d_cb) (void)hipFree(v->d_cb);
-    for (mmidx_index *a : v->asg)
-        if (a) mmidx_destroy(a);
-    v->ws_nn.release();
-    v->ws_desc.release();
-    v->ws_out.release();
-    v->ws_off.release();
-    if (v->stream) (void)hipStreamDestroy(v->stream);
-    delete v;
-    return MMIDX_OK;
-}
-
-int mmidx_vlad_descriptor_length(const mmidx_vlad *v, int *dl_out) {
-    if (!v || !dl_out) return fail(MMIDX_ERR_INVALID_ARG, "null argument");
-    *dl_out = v->dl;
-    return MMIDX_OK;
-}
-
-int mmidx_vlad_vector_length(const mmidx_vlad *v, int *len_out) {
-    if (!v || !len_out) return fail(MMIDX_ERR_INVALID_ARG, "null argument");
-    *len_out = v->veclen;
-    return MMIDX_OK;
-}
-
-// max_desc: largest descriptor count of any image in the batch (sizes the LDS work lists)
-int mmidx_vlad_aggregate_device(mmidx_vlad *v, int64_t nimg, const int64_t *d_desc_off, const double *d_descs, int max_desc,
-                                double *d_out, void *stream) {
-    if (!v) return fail(MMIDX_ERR_INVALID_ARG, "null handle");
-    if (nimg < 0 || (nimg > 0 && (!d_desc_off || !d_out))) return fail(MMIDX_ERR_INVALID_ARG, "null argument");
-    if (nimg == 0) return MMIDX_OK;
-    HIPCK(hipSetDevice(v->device));
-    hipStream_t st = (hipStream_t)stream;
-    const int maxnd = (std::max(max_desc, 2) + 1) & ~1;
-    long long ndesc = -1;  // descriptors of the launch (read back once when the assignment runs as its own stage)
-    for (int i = 0; i < v->nvocab; i++) {
-        const int nc = v->nc[(size_t)i];
-        if (!v->exact && !v->two_pass && v->asg[(size_t)i] && d_descs && v->dl == 64 && nc <= 128) {
-            // K8'': one kernel, one pass over the descriptors in HBM, no host synchronisation (the flagged descriptors are redone by the
-            // image's own block): 64-dimensional descriptors, vocabularies of at most 128 centroids
-            const mmidx_index *a = v->asg[(size_t)i];
-            if (a->d_Ch && a->Cp == G16_BC && a->Dp >= 64 && a->Dp <= G16_KC) {
-                const size_t lf = 2 * (size_t)G16_BC * (64 * 2 + 16) + 2 * (size_t)maxnd * 4 + (size_t)((nc + 2) & ~1) * 4 + (size_t)(VF_FLAG_CAP + 2) * 4 + 32;
-                if (lf <= 160 * 1024 && a->d_coarseT) {
-                    HIPCK(hipFuncSetAttribute((const void *)k_vlad_fused, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lf));
-                    hipLaunchKernelGGL(k_vlad_fused, dim3((unsigned)nimg), dim3(256), lf, st, v->d_cb + v->cb_off[(size_t)i], (const double *)a->d_coarseT, nc, maxnd, (const __bf16 *)a->d_Ch,
-                                       (const __bf16 *)a->d_Cl, a->d_cn_pad, a->cnorm_max, a->cn_max, a->Dp, (const long long *)d_desc_off, d_descs, d_out, v->veclen,
-                                       (int)v->cb_off[(size_t)i], v->norms);
-                    HIPCK(hipGetLastError());
-                    continue;
-                }
-            }
-        }
-        if (!v->exact && v->asg[(size_t)i] && d_descs) {
-            // K8': nearest centroid of EVERY descriptor on the matrix cores (certified, exact redo of the flagged few), then one
-            // block per image for the ordered accumulation
-            if (ndesc < 0) {
-                HIPCK(hipMemcpyAsync(&ndesc, d_desc_off + nimg, sizeof(long long), hipMemcpyDeviceToHost, st));
-                HIPCK(hipStreamSynchronize(st));
-                HIPCK(v->ws_nn.reserve((size_t)std::max<long long>(ndesc, 1)));
-            }
-            if (ndesc > 0) {
-                int rca = mmidx_assign_device(v->asg[(size_t)i], ndesc, d_descs, v->ws_nn.p, st);
-                if (rca) return rca;
-                HIPCK(hipSetDevice(v->device));
-            }
-            const size_t lds2 = 2 * (size_t)maxnd * 4 + (size_t)((nc + 2) & ~1) * 4 + 32;
-            if (lds2 > 64 * 1024) return fail(MMIDX_ERR_UNSUPPORTED, "%d descriptors per image exceed the accumulation kernel's LDS", max_desc);
-            if (v->dl == 64)
-                hipLaunchKernelGGL(k_vlad_accum<64>, dim3((unsigned)nimg), dim3(256), lds2, st, v->d_cb + v->cb_off[(size_t)i], nc, v->dl, maxnd, v->ws_nn.p,
-                                   (const long long *)d_desc_off, d_descs, d_out, v->veclen, (int)v->cb_off[(size_t)i], v->norms);
-            else
-                hipLaunchKernelGGL(k_vlad_accum<0>, dim3((unsigned)nimg), dim3(256), lds2, st, v->d_cb + v->cb_off[(size_t)i], nc, v->dl, maxnd, v->ws_nn.p,
-                                   (const long long *)d_desc_off, d_descs, d_out, v->veclen, (int)v->cb_off[(size_t)i], v->norms);
-            HIPCK(hipGetLastError());
-            continue;
-        }
-        const size_t lds = (size_t)nc * v->dl * 8 + 2 * (size_t)maxnd * 4 + (size_t)((nc + 2) & ~1) * 4 + 32;
-        if (lds > 160 * 1024)
-            return fail(MMIDX_ERR_UNSUPPORTED, "codebook %d x %d plus %d descriptors per image exceed the 160 KiB LDS", nc, v->dl, max_desc);
-        const int norms = v->norms;
-        if (v->dl == 64) {
-            HIPCK(hipFuncSetAttribute((const void *)k_vlad<64>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL(k_vlad<64>, dim3((unsigned)nimg), dim3(256), lds, st, v->d_cb + v->cb_off[(size_t)i], nc, v->dl, maxnd,
-                               (const long long *)d_desc_off, d_descs, d_out, v->veclen, (int)v->cb_off[(size_t)i], norms);
-        } else {
-            HIPCK(hipFuncSetAttribute((const void *)k_vlad<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL(k_vlad<0>, dim3((unsigned)nimg), dim3(256), lds, st, v->d_cb + v->cb_off[(size_t)i], nc, v->dl, maxnd,
-                               (const long long *)d_desc_off, d_descs, d_out, v->veclen, (int)v->cb_off[(size_t)i], norms);
-        }
-    }
-    if (v->nvocab > 1 && v->norms)
-        hipLaunchKernelGGL(k_rows_normalize_l2_block, dim3((unsigned)nimg), dim3(256), 0, st, d_out, v->veclen);
-    HIPCK(hipGetLastError());
-    return MMIDX_OK;
-}
-
-int mmidx_vlad_aggregate(mmidx_vlad *v, int64_t nimg, const int64_t *desc_off, const double *descs, double *out) {
-    if (!v) return fail(MMIDX_ERR_INVALID_ARG, "null handle");
-    if (nimg < 0 || (nimg > 0 && (!desc_off || !out))) return fail(MMIDX_ERR_INVALID_ARG, "null argument");
-    if (nimg == 0) return MMIDX_OK;
-    std::lock_guard<std::mutex> lk(v->mu);
-    HIPCK(hipSetDevice(v->device));
-    const int64_t total = desc_off[nimg] - desc_off[0];
-    if (total > 0 && !descs) return fail(MMIDX_ERR_INVALID_ARG, "null descriptors");
-    int max_desc = 0;
-    std::vector<long long> off((size_t)nimg + 1);
-    for (int64_t i = 0; i <= nimg; i++) off[(size_t)i] = desc_off[i] - desc_off[0];
-    for (int64_t i = 0; i < nimg; i++) max_desc = std::max<int>(max_desc, (int)(off[(size_t)i + 1] - off[(size_t)i]));
-    HIPCK(v->ws_off.reserve((size_t)nimg + 1));
-    HIPCK(v->ws_desc.reserve((size_t)std::max<int64_t>(total, 1) * v->dl));
-    HIPCK(v->ws_out.reserve((size_t)nimg * v->veclen));
-    HIPCK(hipMemcpyAsync(v->ws_off.p, off.data(), ((size_t)nimg + 1) * 8, hipMemcpyHostToDevice, v->stream));
-    if (total > 0)
-        HIPCK(hipMemcpyAsync(v->ws_desc.p, descs + (size_t)desc_off[0] * v->dl, (size_t)total * v->dl * 8, hipMemcpyHostToDevice, v->stream));
-    int rc = mmidx_vlad_aggregate_device(v, nimg, (const int64_t *)v->ws_off.p, v->ws_desc.p, max_desc, v->ws_out.p, v->stream);
-    if (rc) return rc;
-    HIPCK(hipMemcpyAsync(out, v->ws_out.p, (size_t)nimg * v->veclen * 8, hipMemcpyDeviceToHost, v->stream));
-    HIPCK(hipStreamSynchronize(v->stream));
-    return MMIDX_OK;
-}
-
-// ImageVectorization.transformToVector (J/vectorization/ImageVectorization.java:169-208) for a batch: aggregate, then
-// PCA.sampleToEigenSpace -- descriptors in, projected vectors out, the VLAD vectors never leave the device
-int mmidx_vectorize_device(mmidx_vlad *v, mmidx_pca *p, int64_t nimg, const int64_t *d_desc_off, const double *d_descs, int max_desc,
-                           double *d_out, void *stream) {
-    if (!v || !p) return fail(MMIDX_ERR_INVALID_ARG, "null handle");
-    if (v->veclen != p->ss)
-        return fail(MMIDX_ERR_WRONG_DIM, "VLAD vector length %d does not match the PCA sample size %d", v->veclen, p->ss);
-    if (v->device != p->device) return fail(MMIDX_ERR_INVALID_ARG, "aggregator and PCA live on different devices");
-    if (nimg < 0 || (nimg > 0 && (!d_desc_off || !d_out))) return fail(MMIDX_ERR_INVALID_ARG, "null argument");
-    if (nimg == 0) return MMIDX_OK;
-    HIPCK(hipSetDevice(v->device));
-    const int64_t B = std::max<int64_t>(1, (int64_t)(1ll << 28) / v->veclen);  // <= 2 GiB of VLAD vectors per round
-    for (int64_t i0 = 0; i0 < nimg; i0 += B) {
-        const int64_t nb = std::min(B, nimg - i0);
-        HIPCK(v->ws_out.reserve((size_t)nb * v->veclen));
-        // (the offsets are absolute into d_descs: a sub-range of images needs no rebasing)
-        int rc = mmidx_vlad_aggregate_device(v, nb, d_desc_off + i0, d_descs, max_desc, v->ws_out.p, stream);
-        if (rc) return rc;
-        rc = mmidx_pca_project_device(p, nb, v->ws_out.p, d_out + (size_t)i0 * p->nc, stream);
-        if (rc) return rc;
-    }
-    return MMIDX_OK;
-}
-
-int mmidx_vectorize(mmidx_vlad *v, mmidx_pca *p, int64_t nimg, const int64_t *desc_off, const double *descs, double *out) {
-    if (!v || !p) return fail(MMIDX_ERR_INVALID_ARG, "null handle");
-    if (nimg < 0 || (nimg > 0 && (!desc_off || !out))) return fail(MMIDX_ERR_INVALID_ARG, "null argument");
-    if (nimg == 0) return MMIDX_OK;
-    std::lock_guard<std::mutex> lk(v->mu);
-    std::lock_guard<std::mutex> lk2(p->mu);
-    HIPCK(hipSetDevice(v->device));
-    const int64_t total = desc_off[nimg] - desc_off[0];
-    if (total > 0 && !descs) return fail(MMIDX_ERR_INVALID_ARG, "null descriptors");
-    int max_desc = 0;
-    std::vector<long long> off((size_t)nimg + 1);
-    for (int64_t i = 0; i <= nimg; i++) off[(size_t)i] = desc_off[i] - desc_off[0];
-    for (int64_t i = 0; i < nimg; i++) max_desc = std::max<int>(max_desc, (int)(off[(size_t)i + 1] - off[(size_t)i]));
-    HIPCK(v->ws_off.reserve((size_t)nimg + 1));
-    HIPCK(v->ws_desc.reserve((size_t)std::max<int64_t>(total, 1) * v->dl));
-    HIPCK(p->ws_Y.reserve((size_t)nimg * p->nc));
-    HIPCK(hipMemcpyAsync(v->ws_off.p, off.data(), ((size_t)nimg + 1) * 8, hipMemcpyHostToDevice, v->stream));
-    if (total > 0)
-        HIPCK(hipMemcpyAsync(v->ws_desc.p, descs + (size_t)desc_off[0] * v->dl, (size_t)total * v->dl * 8, hipMemcpyHostToDevice, v->stream));
-    int rc = mmidx_vectorize_device(v, p, nimg, (const int64_t *)v->ws_off.p, v->ws_desc.p, max_desc, p->ws_Y.p, v->stream);
-    if (rc) return rc;
-    HIPCK(hipMemcpyAsync(out, p->ws_Y.p, (size_t)nimg * p->nc * 8, hipMemcpyDeviceToHost, v->stream));
-    HIPCK(hipStreamSynchronize(v->stream));
-    return MMIDX_OK;
-}
-
-// ---- Linear (exhaustive exact search, J/datastructures/Linear.java) -----------------------------------------------
-// computeNearestNeighborsInternal (Linear.java:138-163) offers (i, sum_j (q_j - x_ij)^2) for every vector in index order
-// to a bounded queue of size k: exactly what computeNearestCoarseIndices does with the coarse centroids and w, so the
-// indexed vectors are handed to the coarse stage as "centroids" (certified bf16 / fp32 matrix-core filter + exact fp64 for
-// the few candidates while n <= 16384, the plain exact kernels beyond that); (q - x)^2 and (x - q)^2 are the same bits.
-struct mmidx_linear {
-    std::mutex mu;
-    int D = 0, device = 0;
-    int64_t capacity = 0;
-    std::vector<double> X;  // [n][D]; Linear keeps its vectors in memory too (TDoubleArrayList, Linear.java:45)
-    mmidx_index *inner = nullptr;
-    int64_t inner_n = -1;   // number of vectors the inner handle was built for
-    DevBuf<double> ws_Q, ws_d;
-    DevBuf<int32_t> ws_i;
-    Combiner comb;              // concurrent one-query callers are served together, as in mmidx_search
-    std::vector<double> cat_Q;  // their queries, concatenated
-};
-
-int mmidx_linear_create(int D, int64_t capacity, int device, mmidx_linear **out) {
-    if (!out) return fail(MMIDX_ERR_INVALID_ARG, "null out pointer");
-    *out = nullptr;
-    if (D < 1 || capacity < 0) return fail(MMIDX_ERR_INVALID_ARG, "bad vector length / capacity");
-    const int ndev = mmidx_device_count();
-    if (ndev < 1) return fail(MMIDX_ERR_NO_DEVICE, "no HIP device: libmmidx_hip has no CPU fallback");
-    if (device < 0 || device >= ndev) return fail(MMIDX_ERR_NO_DEVICE, "device %d outside 0..%d", device, ndev - 1);
-    mmidx_linear *l = new mmidx_linear();
-    l->D = D;
-    l->device = device;
-    l->capacity = capacity;
-    *out = l;
-    return MMIDX_OK;
-}
-
-int mmidx_linear_destroy(mmidx_linear *l) {
-    if (!l) return MMIDX_OK;
-    (void)hipSetDevice(l->device);
-    if (l->inner) mmidx_destroy(l->inner);
-    l->ws_Q.release();
-    l->ws_d.release();
-    l->ws_i.release();
-    delete l;
-    return MMIDX_OK;
-}
-
-int mmidx_linear_add(mmidx_linear *l, int64_t n, const double *X) {  // indexVectorInternal, Linear.java:111-122
-    if (!l || n < 0 || (n > 0 && !X)) return fail(MMIDX_ERR_INVALID_ARG, "null argument");
-    std::lock_guard<std::mutex> lk(l->mu);
-    const int64_t have = (int64_t)(l->X.size() / (size_t)l->D);
-    if (l->capacity > 0 && have + n > l->capacity) return fail(MMIDX_ERR_CAPACITY, "Maximum index capacity reached, no more vectors can be indexed!");
-    l->X.insert(l->X.end(), X, X + (size_t)n * l->D);
-    return MMIDX_OK;
-}
-
-int mmidx_linear_get_dim(const mmidx_linear *l, int *D_out) {
-    if (!l || !D_out) return fail(MMIDX_ERR_INVALID_ARG, "null argument");
-    *D_out = l->D;
-    return MMIDX_OK;
-}
-
-int mmidx_linear_size(const mmidx_linear *l, int64_t *n_out) {
-    if (!l || !n_out) return fail(MMIDX_ERR_INVALID_ARG, "null argument");
-    *n_out = (int64_t)(l->X.size() / (size_t)l->D);
-    return MMIDX_OK;
-}
-
-int mmidx_linear_get_vector(const mmidx_linear *l, int64_t iid, double *out) {  // Linear.getVector, Linear.java:253-263
-    if (!l || !out) return fail(MMIDX_ERR_INVALID_ARG, "null argument");
-    const int64_t have = (int64_t)(l->X.size() / (size_t)l->D);
-    if (iid < 0 || iid >= have) return fail(MMIDX_ERR_INVALID_ARG, "Internal id %lld is out of range!", (long long)iid);
-    memcpy(out, l->X.data() + (size_t)iid * l->D, (size_t)l->D * 8);
-    return MMIDX_OK;
-}
-
-// serves batch[0..nb) (same k) as one search over the concatenated queries; the caller holds l->mu
-static int linear_search_batch(mmidx_linear *l, SearchReq *const *batch, size_t nb) {
-    const int k = batch[0]->k;
-    const int64_t n = (int64_t)(l->X.size() / (size_t)l->D);
-    if (n > 0x7fffffff) return fail(MMIDX_ERR_CAPACITY, "internal ids are 32-bit, as in the reference");
-    int64_t nq = 0;
-    for (size_t b = 0; b < nb; b++) {
-        SearchReq *r = batch[b];
-        for (int64_t i = 0; i < r->nq * k; i++) {
-            r->iid[i] = -1;
-            r->dist[i] = std::numeric_limits<double>::infinity();
-        }
-        for (int64_t q = 0; q < r->nq; q++) r->cnt[q] = 0;
-        nq += r->nq;
-    }
-    if (nq == 0 || n == 0) return MMIDX_OK;
-    const double *Q = batch[0]->Q;
-    if (nb > 1) {
-        l->cat_Q.resize((size_t)nq * l->D);
-        size_t off = 0;
-        for (size_t b = 0; b < nb; b++) {
-            memcpy(l->cat_Q.data() + off, batch[b]->Q, (size_t)batch[b]->nq * l->D * 8);
-            off += (size_t)batch[b]->nq * l->D;
-        }
-        Q = l->cat_Q.data();
-    }
-    HIPCK(hipSetDevice(l->device));
-    if (l->inner_n != n) {
-        if (l->inner) mmidx_destroy(l->inner);
-        l->inner = nullptr;
-        l->inner_n = -1;
-        int rc = mmidx_create(MMIDX_KIND_IVFPQ, l->D, 1, 2, (int)n, MMIDX_TR_NONE, nullptr, nullptr, l->device, &l->inner);
-        if (rc) return rc;
-        rc = mmidx_set_coarse(l->inner, l->X.data());
-        if (rc) return rc;
-        l->inner_n = n;
-    }
-    mmidx_index *h = l->inner;
-    const int w = (int)std::min<int64_t>(k, n);
+// ---- what the other units of the library call (declared in mmidx_host.h) ------------------------------------------------------
+int mmidx_internal_coarse_topw(mmidx_index *h, int w, int64_t nq, const double *dQ, int32_t *d_cells, double *d_dist_or_null, hipStream_t st) {
+    DeviceCall call(h, st);
     h->w = w;
-    hipStream_t st = h->stream;
-    const int64_t qb = std::max<int64_t>(1, std::min<int64_t>(nq, (2ll << 30) / ((int64_t)n * 8)));
-    HIPCK(l->ws_Q.reserve((size_t)qb * l->D));
-    HIPCK(l->ws_i.reserve((size_t)qb * w));
-    HIPCK(l->ws_d.reserve((size_t)qb * w));
-    std::vector<int32_t> hi((size_t)qb * w);
-    std::vector<double> hd((size_t)qb * w);
-    size_t cur = 0;        // request that holds query q0 + q, and that query's position in it
-    int64_t cur_q = 0;
+    const int64_t qb = std::max<int64_t>(1, (2ll << 30) / ((int64_t)h->C * 8));
     for (int64_t q0 = 0; q0 < nq; q0 += qb) {
-        const int64_t nbq = std::min(qb, nq - q0);
-        HIPCK(hipMemcpyAsync(l->ws_Q.p, Q + (size_t)q0 * l->D, (size_t)nbq * l->D * 8, hipMemcpyHostToDevice, st));
-        int rc = run_coarse(h, nbq, l->ws_Q.p, l->ws_i.p, st);
+        const int64_t nb = std::min(qb, nq - q0);
+        int32_t *cells = d_cells + (size_t)q0 * w;
+        int rc = run_coarse(h, nb, dQ + (size_t)q0 * h->D, cells, st);
         if (rc) return rc;
-        if (h->cdsel_valid) {
-            HIPCK(hipMemcpyAsync(l->ws_d.p, h->ws_cdsel.p, (size_t)nbq * w * 8, hipMemcpyDeviceToDevice, st));
-        } else {
-            const long long tot = (long long)nbq * w;
-            hipLaunchKernelGGL(k_gather_cdist, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, h->ws_cdist.p, l->ws_i.p, l->ws_d.p,
-                               h->C, w, tot);
-            HIPCK(hipGetLastError());
-        }
-        HIPCK(hipMemcpyAsync(hi.data(), l->ws_i.p, (size_t)nbq * w * 4, hipMemcpyDeviceToHost, st));
-        HIPCK(hipMemcpyAsync(hd.data(), l->ws_d.p, (size_t)nbq * w * 8, hipMemcpyDeviceToHost, st));
-        HIPCK(hipStreamSynchronize(st));
-        for (int64_t q = 0; q < nbq; q++) {
-            while (cur_q >= batch[cur]->nq) {
-                cur++;
-                cur_q = 0;
+        if (d_dist_or_null) {
+            double *dst = d_dist_or_null + (size_t)q0 * w;
+            if (h->cdsel_valid) {
+                HIPCK(hipMemcpyAsync(dst, h->ws_cdsel.p, (size_t)nb * w * 8, hipMemcpyDeviceToDevice, st));
+            } else {
+                const long long tot = (long long)nb * w;
+                hipLaunchKernelGGL(k_gather_cdist, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, h->ws_cdist.p, cells, dst, h->C, w, tot);
+                HIPCK(hipGetLastError());
             }
-            SearchReq *r = batch[cur];
-            for (int t = 0; t < w; t++) {
-                r->iid[(size_t)cur_q * k + t] = hi[(size_t)q * w + t];
-                r->dist[(size_t)cur_q * k + t] = hd[(size_t)q * w + t];
-            }
-            r->cnt[cur_q] = w;
-            cur_q++;
         }
     }
     return MMIDX_OK;
 }
 
-int mmidx_linear_search(mmidx_linear *l, int k, int64_t nq, const double *Q, int32_t *iid_out, double *dist_out, int32_t *count_out) {
-    if (!l) return fail(MMIDX_ERR_INVALID_ARG, "null handle");
-    if (k < 1) return fail(MMIDX_ERR_INVALID_ARG, "k must be positive (got %d)", k);
-    if (nq < 0 || (nq > 0 && (!Q || !iid_out || !dist_out || !count_out))) return fail(MMIDX_ERR_INVALID_ARG, "null argument");
-    if (nq == 0) return MMIDX_OK;
-    SearchReq me;
-    me.k = k;
-    me.nq = nq;
-    me.Q = Q;
-    me.iid = iid_out;
-    me.dist = dist_out;
-    me.cnt = count_out;
-    return combiner_submit(l->comb, me, MMIDX_COMB_MAX_Q, [l](SearchReq *const *batch, size_t nb) {
-        std::lock_guard<std::mutex> lk(l->mu);
-        return linear_search_batch(l, batch, nb);
-    });
+int mmidx_internal_coarse_tables(const mmidx_index *h, MmidxCoarseTables *out) {
+    if (!h || !out) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null argument");
+    *out = {h->d_coarseT, h->d_Ch, h->d_Cl, h->d_cn_pad, h->cnorm_max, h->cn_max, h->Cp, h->Dp};
+    return MMIDX_OK;
 }
-
-}  // extern "C"
 
 #include "mmidx_sharded.h"

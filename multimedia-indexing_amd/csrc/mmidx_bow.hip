@@ -24,7 +24,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdarg>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -33,55 +32,9 @@
 #include <string>
 #include <vector>
 
-#include "mmidx.h"
-
-// defined in mmidx_api.hip: the calling thread's last-error text
-extern "C" {
-__attribute__((visibility("hidden"))) int mmidx_internal_fail(int code, const char *msg);
-}
+#include "mmidx_host.h"
 
 namespace {
-
-#define BWCK(expr)                                                                                          \
-    do {                                                                                                    \
-        hipError_t e__ = (expr);                                                                            \
-        if (e__ != hipSuccess) {                                                                            \
-            char b__[384];                                                                                  \
-            snprintf(b__, sizeof(b__), "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e__), __FILE__, __LINE__); \
-            return mmidx_internal_fail(MMIDX_ERR_HIP, b__);                                                 \
-        }                                                                                                   \
-    } while (0)
-
-int bfail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
-int bfail(int code, const char *fmt, ...) {
-    char buf[384];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    return mmidx_internal_fail(code, buf);
-}
-
-template <typename T>
-struct Buf {
-    T *p = nullptr;
-    size_t cap = 0;  // elements
-    hipError_t reserve(size_t n) {
-        if (n <= cap) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        const size_t want = n + n / 8 + 64;
-        hipError_t e = hipMalloc((void **)&p, want * sizeof(T));
-        if (e == hipSuccess) cap = want;
-        return e;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-};
 
 constexpr long long BOW_CELL_BUDGET = 1ll << 25;   // int32 cell entries per assignment chunk (128 MiB)
 constexpr long long BOW_OUT_BUDGET = 1ll << 27;    // doubles of the host form's dense [chunk][nc] workspace (1 GiB)
@@ -159,9 +112,9 @@ struct mmidx_bow {
     int nc = 0, dl = 0, k = 1, device = 0;
     mmidx_index *asg = nullptr;  // the vocabulary as the coarse quantizer of a hidden index (nc >= 2)
     hipStream_t stream = nullptr;
-    Buf<int32_t> ws_cells;
-    Buf<double> ws_desc, ws_out;
-    Buf<long long> ws_off;
+    DevBuf<int32_t> ws_cells;
+    DevBuf<double> ws_desc, ws_out;
+    DevBuf<long long> ws_off;
     int hist_global = 0;   // option "hist_global": K9b also where K9a applies
     int chunk_images = 0;  // option "chunk_images": images per round of the host form (0 = sized from the budgets)
 };
@@ -172,8 +125,8 @@ namespace {
 int bow_run(mmidx_bow *b, int64_t nimg, const long long *d_off, const double *d_descs, long long dlo, long long dhi, double *d_out,
             hipStream_t st) {
     const long long ndesc = dhi - dlo;
-    if (ndesc < 0) return bfail(MMIDX_ERR_INVALID_ARG, "descriptor offsets decrease (%lld .. %lld)", dlo, dhi);
-    if (ndesc > 0 && !d_descs) return bfail(MMIDX_ERR_INVALID_ARG, "null descriptors");
+    if (ndesc < 0) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "descriptor offsets decrease (%lld .. %lld)", dlo, dhi);
+    if (ndesc > 0 && !d_descs) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null descriptors");
     const int nc = b->nc, k = b->k;
     if (b->last_stream_valid && b->last_stream != st) {
         // the cell buffer may still be read by the histogram of the call before, on another stream (which the caller may have
@@ -188,37 +141,37 @@ int bow_run(mmidx_bow *b, int64_t nimg, const long long *d_off, const double *d_
     const unsigned weight = k == 1 ? 1u : (unsigned)b->dl;  // BowAggregator.java:47-51: bow[nn[j]]++ descriptorLength times
     if (nc == 1) {
         hipLaunchKernelGGL(k_bow_single, dim3((unsigned)((nimg + 255) / 256)), dim3(256), 0, st, d_off, (long long)nimg, d_out);
-        BWCK(hipGetLastError());
+        HIPCK(hipGetLastError());
         return MMIDX_OK;
     }
     const long long chunk = std::max<long long>(1, BOW_CELL_BUDGET / k);
     const bool lds_form = !b->hist_global && nc <= BOW_LDS_MAX_NC && ndesc <= chunk;
     const long long slots = (long long)nimg * nc;
-    if (!lds_form) BWCK(hipMemsetAsync(d_out, 0, (size_t)slots * 8, st));
-    BWCK(b->ws_cells.reserve((size_t)std::max<long long>(1, std::min(ndesc, chunk) * k)));
+    if (!lds_form) HIPCK(hipMemsetAsync(d_out, 0, (size_t)slots * 8, st));
+    HIPCK(b->ws_cells.reserve((size_t)std::max<long long>(1, std::min(ndesc, chunk) * k)));
     for (long long c0 = dlo; c0 < dhi; c0 += chunk) {
         const long long n = std::min(chunk, dhi - c0);
         const double *x = d_descs + (size_t)c0 * b->dl;
         int rc = k == 1 ? mmidx_assign_device(b->asg, n, x, b->ws_cells.p, st) : mmidx_coarse_device(b->asg, n, x, b->ws_cells.p, nullptr, st);
         if (rc) return rc;
-        BWCK(hipSetDevice(b->device));
+        HIPCK(hipSetDevice(b->device));
         if (!lds_form) {
             const long long nhits = n * k;
             hipLaunchKernelGGL(k_bow_hist_global, dim3((unsigned)((nhits + 255) / 256)), dim3(256), 0, st, b->ws_cells.p, d_off, (long long)nimg, c0,
                                nhits, nc, k, d_out);
-            BWCK(hipGetLastError());
+            HIPCK(hipGetLastError());
         }
     }
     if (lds_form) {
         const size_t lds = (size_t)nc * 4;
         const int nt = lds <= (size_t)BOW_LDS_SMALL ? 256 : 1024;
         if (lds > 64 * 1024)  // (beyond the default limit of dynamic LDS only)
-            BWCK(hipFuncSetAttribute((const void *)k_bow_hist_lds, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            HIPCK(hipFuncSetAttribute((const void *)k_bow_hist_lds, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         hipLaunchKernelGGL(k_bow_hist_lds, dim3((unsigned)nimg), dim3(nt), lds, st, b->ws_cells.p, d_off, dlo, ndesc * k, nc, k, weight, d_out);
     } else {
         hipLaunchKernelGGL(k_bow_convert, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, st, d_out, slots, weight);
     }
-    BWCK(hipGetLastError());
+    HIPCK(hipGetLastError());
     return MMIDX_OK;
 }
 
@@ -227,19 +180,19 @@ int bow_run(mmidx_bow *b, int64_t nimg, const long long *d_off, const double *d_
 extern "C" {
 
 int mmidx_bow_create(int nc, int dl, int k, const double *codebook, int device, mmidx_bow **out) {
-    if (!out) return bfail(MMIDX_ERR_INVALID_ARG, "null out pointer");
+    if (!out) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null out pointer");
     *out = nullptr;
-    if (!codebook) return bfail(MMIDX_ERR_INVALID_ARG, "null codebook");
-    if (nc < 1) return bfail(MMIDX_ERR_INVALID_ARG, "numCentroids = %d: the codebook is empty", nc);
-    if (dl < 1) return bfail(MMIDX_ERR_INVALID_ARG, "descriptorLength = %d must be >= 1", dl);
-    if (k < 1) return bfail(MMIDX_ERR_INVALID_ARG, "k = %d must be >= 1 (BoundedPriorityQueue constructor)", k);
-    if (k > nc) return bfail(MMIDX_ERR_INVALID_ARG, "k = %d exceeds the %d centroids of the codebook (AFA:214-217 polls an empty queue)", k, nc);
+    if (!codebook) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null codebook");
+    if (nc < 1) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "numCentroids = %d: the codebook is empty", nc);
+    if (dl < 1) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "descriptorLength = %d must be >= 1", dl);
+    if (k < 1) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "k = %d must be >= 1 (BoundedPriorityQueue constructor)", k);
+    if (k > nc) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "k = %d exceeds the %d centroids of the codebook (AFA:214-217 polls an empty queue)", k, nc);
     if (k > BOW_K_MAX)
-        return bfail(MMIDX_ERR_UNSUPPORTED, "k = %d beyond the %d neighbours the coarse stage's selection holds in LDS", k, BOW_K_MAX);
+        return mmidx_fail(MMIDX_ERR_UNSUPPORTED, "k = %d beyond the %d neighbours the coarse stage's selection holds in LDS", k, BOW_K_MAX);
     const int ndev = mmidx_device_count();
-    if (ndev < 1) return bfail(MMIDX_ERR_NO_DEVICE, "no HIP device: libmmidx_hip has no CPU fallback");
-    if (device < 0 || device >= ndev) return bfail(MMIDX_ERR_NO_DEVICE, "device %d outside 0..%d", device, ndev - 1);
-    BWCK(hipSetDevice(device));
+    if (ndev < 1) return mmidx_fail(MMIDX_ERR_NO_DEVICE, "no HIP device: libmmidx_hip has no CPU fallback");
+    if (device < 0 || device >= ndev) return mmidx_fail(MMIDX_ERR_NO_DEVICE, "device %d outside 0..%d", device, ndev - 1);
+    HIPCK(hipSetDevice(device));
     mmidx_bow *b = new mmidx_bow();
     if (hipHostMalloc((void **)&b->pin_ends, 16) != hipSuccess) {  // (the read-back then lands in pageable memory)
         b->pin_ends = nullptr;
@@ -252,7 +205,7 @@ int mmidx_bow_create(int nc, int dl, int k, const double *codebook, int device, 
     hipError_t e = hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking);
     if (e != hipSuccess) {
         delete b;
-        return bfail(MMIDX_ERR_HIP, "hipStreamCreate failed: %s", hipGetErrorString(e));
+        return mmidx_fail(MMIDX_ERR_HIP, "hipStreamCreate failed: %s", hipGetErrorString(e));
     }
     if (nc >= 2) {
         // m = 1, ks = 2 with an all-zero product quantizer: never used, but mmidx_coarse_device wants a complete index
@@ -287,7 +240,7 @@ int mmidx_bow_destroy(mmidx_bow *b) {
 }
 
 int mmidx_bow_get_dims(const mmidx_bow *b, int *nc, int *dl, int *k) {
-    if (!b) return bfail(MMIDX_ERR_INVALID_ARG, "null handle");
+    if (!b) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null handle");
     if (nc) *nc = b->nc;
     if (dl) *dl = b->dl;
     if (k) *k = b->k;
@@ -295,7 +248,7 @@ int mmidx_bow_get_dims(const mmidx_bow *b, int *nc, int *dl, int *k) {
 }
 
 int mmidx_bow_set_option(mmidx_bow *b, const char *name, int value) {
-    if (!b || !name) return bfail(MMIDX_ERR_INVALID_ARG, "null argument");
+    if (!b || !name) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null argument");
     const std::string n(name);
     std::lock_guard<std::mutex> lk(b->mu);
     if (n == "exact") return b->asg ? mmidx_set_option(b->asg, "exact_coarse", value != 0) : MMIDX_OK;
@@ -304,46 +257,46 @@ int mmidx_bow_set_option(mmidx_bow *b, const char *name, int value) {
         return MMIDX_OK;
     }
     if (n == "chunk_images") {
-        if (value < 0) return bfail(MMIDX_ERR_INVALID_ARG, "chunk_images = %d must be >= 0", value);
+        if (value < 0) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "chunk_images = %d must be >= 0", value);
         b->chunk_images = value;
         return MMIDX_OK;
     }
-    return bfail(MMIDX_ERR_INVALID_ARG, "unknown option '%s'", name);
+    return mmidx_fail(MMIDX_ERR_INVALID_ARG, "unknown option '%s'", name);
 }
 
 int mmidx_bow_aggregate_device(mmidx_bow *b, int64_t nimg, const int64_t *d_desc_off, const double *d_descs, int max_desc, double *d_out,
                                void *stream) {
-    if (!b) return bfail(MMIDX_ERR_INVALID_ARG, "null handle");
-    if (nimg < 0 || max_desc < 0 || (nimg > 0 && (!d_desc_off || !d_out))) return bfail(MMIDX_ERR_INVALID_ARG, "null argument");
+    if (!b) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null handle");
+    if (nimg < 0 || max_desc < 0 || (nimg > 0 && (!d_desc_off || !d_out))) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null argument");
     if (nimg == 0) return MMIDX_OK;
     std::lock_guard<std::mutex> lk(b->mu);  // (held while the call is ENQUEUED; bow_run orders the workspaces between streams)
-    BWCK(hipSetDevice(b->device));
+    HIPCK(hipSetDevice(b->device));
     hipStream_t st = (hipStream_t)stream;
     long long stack_ends[2] = {0, 0};
     long long *ends = b->pin_ends ? b->pin_ends : stack_ends;  // the descriptor range of the call: the assignment is sized by it
     ends[0] = ends[1] = 0;
     if (b->nc > 1) {
         if (nimg == 1) {
-            BWCK(hipMemcpyAsync(ends, d_desc_off, 16, hipMemcpyDeviceToHost, st));
+            HIPCK(hipMemcpyAsync(ends, d_desc_off, 16, hipMemcpyDeviceToHost, st));
         } else {
-            BWCK(hipMemcpyAsync(&ends[0], d_desc_off, 8, hipMemcpyDeviceToHost, st));
-            BWCK(hipMemcpyAsync(&ends[1], d_desc_off + nimg, 8, hipMemcpyDeviceToHost, st));
+            HIPCK(hipMemcpyAsync(&ends[0], d_desc_off, 8, hipMemcpyDeviceToHost, st));
+            HIPCK(hipMemcpyAsync(&ends[1], d_desc_off + nimg, 8, hipMemcpyDeviceToHost, st));
         }
-        BWCK(hipStreamSynchronize(st));
+        HIPCK(hipStreamSynchronize(st));
     }
     const long long dlo = ends[0], dhi = ends[1];
     return bow_run(b, nimg, (const long long *)d_desc_off, d_descs, dlo, dhi, d_out, st);
 }
 
 int mmidx_bow_aggregate(mmidx_bow *b, int64_t nimg, const int64_t *desc_off, const double *descs, double *out) {
-    if (!b) return bfail(MMIDX_ERR_INVALID_ARG, "null handle");
-    if (nimg < 0 || (nimg > 0 && (!desc_off || !out))) return bfail(MMIDX_ERR_INVALID_ARG, "null argument");
+    if (!b) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null handle");
+    if (nimg < 0 || (nimg > 0 && (!desc_off || !out))) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null argument");
     if (nimg == 0) return MMIDX_OK;
     for (int64_t i = 0; i < nimg; i++)
-        if (desc_off[i + 1] < desc_off[i]) return bfail(MMIDX_ERR_INVALID_ARG, "desc_off decreases at image %lld", (long long)i);
-    if (desc_off[nimg] > desc_off[0] && !descs) return bfail(MMIDX_ERR_INVALID_ARG, "null descriptors");
+        if (desc_off[i + 1] < desc_off[i]) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "desc_off decreases at image %lld", (long long)i);
+    if (desc_off[nimg] > desc_off[0] && !descs) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null descriptors");
     std::lock_guard<std::mutex> lk(b->mu);
-    BWCK(hipSetDevice(b->device));
+    HIPCK(hipSetDevice(b->device));
     const int64_t by_out = std::max<int64_t>(1, BOW_OUT_BUDGET / b->nc);
     std::vector<long long> off;
     for (int64_t i0 = 0; i0 < nimg;) {
@@ -357,16 +310,16 @@ int mmidx_bow_aggregate(mmidx_bow *b, int64_t nimg, const int64_t *desc_off, con
         const int64_t total = desc_off[i0 + nb] - desc_off[i0];
         off.resize((size_t)nb + 1);
         for (int64_t i = 0; i <= nb; i++) off[(size_t)i] = desc_off[i0 + i] - desc_off[i0];
-        BWCK(b->ws_off.reserve((size_t)nb + 1));
-        BWCK(b->ws_desc.reserve((size_t)std::max<int64_t>(total, 1) * b->dl));
-        BWCK(b->ws_out.reserve((size_t)nb * b->nc));
-        BWCK(hipMemcpyAsync(b->ws_off.p, off.data(), ((size_t)nb + 1) * 8, hipMemcpyHostToDevice, b->stream));
+        HIPCK(b->ws_off.reserve((size_t)nb + 1));
+        HIPCK(b->ws_desc.reserve((size_t)std::max<int64_t>(total, 1) * b->dl));
+        HIPCK(b->ws_out.reserve((size_t)nb * b->nc));
+        HIPCK(hipMemcpyAsync(b->ws_off.p, off.data(), ((size_t)nb + 1) * 8, hipMemcpyHostToDevice, b->stream));
         if (total > 0)
-            BWCK(hipMemcpyAsync(b->ws_desc.p, descs + (size_t)desc_off[i0] * b->dl, (size_t)total * b->dl * 8, hipMemcpyHostToDevice, b->stream));
+            HIPCK(hipMemcpyAsync(b->ws_desc.p, descs + (size_t)desc_off[i0] * b->dl, (size_t)total * b->dl * 8, hipMemcpyHostToDevice, b->stream));
         int rc = bow_run(b, nb, b->ws_off.p, b->ws_desc.p, 0, total, b->ws_out.p, b->stream);
         if (rc) return rc;
-        BWCK(hipMemcpyAsync(out + (size_t)i0 * b->nc, b->ws_out.p, (size_t)nb * b->nc * 8, hipMemcpyDeviceToHost, b->stream));
-        BWCK(hipStreamSynchronize(b->stream));  // (off is reused by the next round)
+        HIPCK(hipMemcpyAsync(out + (size_t)i0 * b->nc, b->ws_out.p, (size_t)nb * b->nc * 8, hipMemcpyDeviceToHost, b->stream));
+        HIPCK(hipStreamSynchronize(b->stream));  // (off is reused by the next round)
         i0 += nb;
     }
     return MMIDX_OK;

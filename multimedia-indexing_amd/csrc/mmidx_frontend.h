@@ -6,6 +6,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "mmidx_device_util.h"
+#include "mmidx_host.h"  // G16_BC, G16_BQ
+
 typedef __attribute__((ext_vector_type(4))) double f64x4;
 
 // ------------------------------------------------------------------------------------------------

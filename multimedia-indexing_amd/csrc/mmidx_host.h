@@ -1,0 +1,170 @@
+// mmidx_host.h -- host plumbing shared by every unit of libmmidx_hip.so: the error text, the HIP-check macro, device buffers,
+// the caller combiner, the tile constants host code sizes launches with, and the hidden functions one unit calls in another.
+//
+// Host only: no __global__ is defined here.  A kernel header defines plain external-linkage kernels, so it is included by
+// exactly one .hip; what another unit needs of it goes through an mmidx_internal_* function declared at the end of this file.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <condition_variable>
+#include <cstddef>
+#include <cstdint>
+#include <deque>
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "../../include/mmidx.h"
+
+#define MMIDX_HIDDEN __attribute__((visibility("hidden")))
+
+// records the calling thread's error text (mmidx_last_error) and returns `code`; defined in mmidx_api.hip
+MMIDX_HIDDEN int mmidx_fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
+// empties that text: for a call that recovered from a failure of its own making
+MMIDX_HIDDEN void mmidx_clear_error();
+
+#define HIPCK(expr)                                                                                \
+    do {                                                                                           \
+        hipError_t e__ = (expr);                                                                   \
+        if (e__ != hipSuccess)                                                                     \
+            return mmidx_fail(MMIDX_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e__), \
+                              __FILE__, __LINE__);                                                 \
+    } while (0)
+
+// (the types below stay inside the library: hidden, so that their instantiations add nothing to the exported symbols)
+#pragma GCC visibility push(hidden)
+
+// a workspace that grows and is released by its owner
+template <typename T>
+struct DevBuf {
+    T *p = nullptr;
+    size_t cap = 0;  // elements
+    hipError_t reserve(size_t n) {
+        if (n <= cap) return hipSuccess;
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        cap = 0;
+        size_t want = n + n / 8 + 64;
+        hipError_t e = hipMalloc((void **)&p, want * sizeof(T));
+        if (e == hipSuccess) cap = want;
+        return e;
+    }
+    void release() {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        cap = 0;
+    }
+};
+
+// a device array of one call: exact size, freed on every return path
+template <typename T>
+struct ScopedBuf {
+    T *p = nullptr;
+    ~ScopedBuf() {
+        if (p) (void)hipFree(p);
+    }
+    hipError_t alloc(size_t n) { return hipMalloc((void **)&p, std::max<size_t>(n, 1) * sizeof(T)); }
+};
+
+#define MMIDX_COMB_MAX_Q 4096   // queries per combined batch; larger requests run alone with direct copies
+
+// one host-pointer search call waiting to be served (see mmidx_search)
+struct SearchReq {
+    int k;
+    int64_t nq;
+    const double *Q;
+    int32_t *iid;
+    double *dist;
+    int32_t *cnt;
+    int rc = MMIDX_OK;
+    bool done = false;
+    std::string err;
+    std::condition_variable cv;  // its caller sleeps here: woken when served, or when it is the oldest and nobody leads
+};
+
+// Concurrent callers of a host-pointer search are combined into one device batch (the reference's API is one query
+// per call, from many reader threads): requests queue here, one caller at a time leads and serves the queue.
+struct Combiner {
+    std::mutex mu;
+    std::deque<SearchReq *> q;
+    bool busy = false;
+    int enabled = 1;  // 0 = every call runs on its own
+};
+
+// Queues `me`, leads batches (serve(requests, count) -> status) until `me` has been served, returns its status.
+template <class Serve>
+int combiner_submit(Combiner &c, SearchReq &me, int64_t max_q, Serve serve) {
+    std::unique_lock<std::mutex> lk(c.mu);
+    c.q.push_back(&me);
+    while (!me.done) {
+        if (c.busy) {
+            me.cv.wait(lk);
+            continue;
+        }
+        // lead: the oldest request and everything behind it with the same k, up to the batch limit
+        c.busy = true;
+        std::vector<SearchReq *> batch;
+        {
+            SearchReq *first = c.q.front();
+            c.q.pop_front();
+            batch.push_back(first);
+            int64_t tot = first->nq;
+            if (c.enabled && tot <= max_q) {
+                for (auto it = c.q.begin(); it != c.q.end();) {
+                    if ((*it)->k == first->k && tot + (*it)->nq <= max_q) {
+                        tot += (*it)->nq;
+                        batch.push_back(*it);
+                        it = c.q.erase(it);
+                    } else {
+                        ++it;
+                    }
+                }
+            }
+        }
+        lk.unlock();
+        const int brc = serve(batch.data(), batch.size());
+        lk.lock();
+        for (SearchReq *r : batch) {
+            r->rc = brc;
+            if (brc && r != &me) r->err = mmidx_last_error();  // the message lives in the leader's thread
+            r->done = true;
+            if (r != &me) r->cv.notify_one();
+        }
+        c.busy = false;
+        // hand the lead to the oldest waiting caller (only that thread is woken); if this call is still unserved
+        // -- the batch was another k's -- it leads again itself
+        if (me.done && !c.q.empty()) c.q.front()->cv.notify_one();
+    }
+    lk.unlock();
+    if (me.rc && !me.err.empty()) return mmidx_fail(me.rc, "%s", me.err.c_str());
+    return me.rc;
+}
+
+#pragma GCC visibility pop
+
+// tiles of the bf16-split coarse kernels (K1e, the encoder's argmin, K8''): host code of more than one unit sizes launches by them
+#define G16_BQ 128     // queries per block (32 per wave)
+#define G16_BC 128     // centroids per tile
+#define G16_KC 128     // k per LDS tile
+#define G16_STRIDE 272 // bytes per LDS row: 256 + 16 (conflict-free 16-byte fragment reads)
+
+// ---- calls across units (hidden: none of these is exported) ----------------------------------------------------------------
+extern "C" {
+// mmidx_api.hip: what K8'' reads of an index handle's coarse quantizer (bf16 head / tail copies padded to Cp x Dp, |c|^2, maxima)
+struct MmidxCoarseTables {
+    const double *coarseT;
+    const unsigned short *Ch, *Cl;
+    const double *cn_pad;
+    double cnorm_max, cn_max;
+    int Cp, Dp;
+};
+MMIDX_HIDDEN int mmidx_internal_coarse_tables(const mmidx_index *h, MmidxCoarseTables *out);
+// mmidx_api.hip: the w nearest centroids of nq queries on device pointers, in rounds of at most 2 GiB of distances: cells
+// [nq][w] and, where asked for, their exact distances.  Sets the handle's w.  mmidx_coarse_device and Linear go through it.
+MMIDX_HIDDEN int mmidx_internal_coarse_topw(mmidx_index *h, int w, int64_t nq, const double *dQ, int32_t *d_cells, double *d_dist_or_null,
+                                            hipStream_t st);
+// mmidx_frontend.hip: K7 on plain device pointers, Y[n][nc] = (X[n][ss] - mu[ss]) Vt[nc][ss]^T
+MMIDX_HIDDEN int mmidx_internal_gemm_nt(const double *X, const double *mu, const double *Vt, double *Y, long long n, int nc, int ss,
+                                        void *stream);
+}  // extern "C"

@@ -10,8 +10,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-typedef unsigned long long u64;
-typedef unsigned int u32;
+#include "mmidx_device_util.h"
+#include "mmidx_host.h"
 
 #define MMIDX_BLOCK 256
 #define MMIDX_KEY_MAX 0xFFFFFFFFFFFFFFFFull
@@ -51,19 +51,7 @@ __device__ __forceinline__ void block_bitonic_sort(u64 *key, V *val, int n) {
     __syncthreads();
 }
 
-// wave64 helpers that stay in the VALU (DPP / readlane): inside K3h's scan loop the LDS pipe is saturated
-// by the table gather, and every ds_bpermute-based __shfl would queue behind it
-__device__ __forceinline__ u32 wave_incl_scan_u32(u32 x) {
-    u32 v = x;  // Hillis-Steele inside each row of 16 lanes, then the row totals (gfx9 row broadcasts)
-    v += (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false);  // row_shr:1
-    v += (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false);  // row_shr:2
-    v += (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false);  // row_shr:4
-    v += (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false);  // row_shr:8
-    v += (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false);  // row_bcast:15 -> rows 1, 3
-    v += (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false);  // row_bcast:31 -> rows 2, 3
-    return v;
-}
-__device__ __forceinline__ u32 wave_read_u32(u32 x, int l) { return (u32)__builtin_amdgcn_readlane((int)x, l); }
+// (wave_incl_scan_u32, wave_read_u32: mmidx_device_util.h)
 // minimum / maximum over the wave (same DPP ladder; lanes a step does not reach keep their own value), wave-uniform result
 __device__ __forceinline__ u32 wave_min_u32(u32 x) {
     u32 v = x;
@@ -429,7 +417,6 @@ __global__ __launch_bounds__(MMIDX_BLOCK) void k_coarse_select_fast(const double
 #define DOT_BN 256
 #define DOT_BK 32
 #define DOT_LDA 34  // padded A row stride (floats): (2*row + k) mod 32 is conflict-free for the fragment read
-typedef __attribute__((ext_vector_type(4))) float f32x4;
 
 __global__ __launch_bounds__(MMIDX_BLOCK) void k_coarse_dot32(const float *__restrict__ CT32, const float *__restrict__ Q32,
                                                               const double *__restrict__ cn, const double *__restrict__ qn,
@@ -1005,11 +992,7 @@ __global__ __launch_bounds__(MMIDX_BLOCK) void k_coarse_select_approx(const Appr
 //                                   <= (3D + 16) 2^-22 |q||c|
 //   d~ = |c|^2 + |q|^2 - 2 S evaluated in fp32 from fp32 copies of the norms: 2^-21 (|c| + |q|)^2
 // ------------------------------------------------------------------------------------------------
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-#define G16_BQ 128     // queries per block (32 per wave)
-#define G16_BC 128     // centroids per tile
-#define G16_KC 128     // k per LDS tile
-#define G16_STRIDE 272 // bytes per LDS row: 256 + 16 (conflict-free 16-byte fragment reads)
+// (tile constants G16_BQ / G16_BC / G16_KC / G16_STRIDE: mmidx_host.h -- host code of several units sizes launches by them)
 
 // one wave per row: X (fp64) -> bf16 head / tail (zero padded to Dp), optional fp32 copy and squared norm
 __global__ __launch_bounds__(MMIDX_BLOCK) void k_split_bf16(const double *__restrict__ X, __bf16 *__restrict__ H,

@@ -24,20 +24,11 @@
 #include <set>
 #include <vector>
 
-#include "mmidx.h"
+#include "mmidx_host.h"
 
 namespace {
 
 typedef unsigned long long u64;
-
-#define LCK(call)                                                     \
-    do {                                                              \
-        hipError_t e_ = (call);                                       \
-        if (e_ != hipSuccess) {                                       \
-            fprintf(stderr, "[mmidx] k-means: %s failed: %s\n", #call, hipGetErrorString(e_)); \
-            return MMIDX_ERR_HIP;                                     \
-        }                                                             \
-    } while (0)
 
 // java.util.Random (the generator Weka seeds with setSeed): 48-bit LCG, JDK javadoc
 struct JavaRandom {
@@ -169,15 +160,6 @@ __global__ void k_point_sqerr(const double *__restrict__ X, const double *__rest
     out[i] = acc;
 }
 
-template <typename T>
-struct Buf {
-    T *p = nullptr;
-    ~Buf() {
-        if (p) (void)hipFree(p);
-    }
-    hipError_t alloc(size_t n) { return hipMalloc((void **)&p, std::max<size_t>(n, 1) * sizeof(T)); }
-};
-
 }  // namespace
 
 extern "C" {
@@ -185,37 +167,38 @@ extern "C" {
 int mmidx_kmeans_device(int device, int64_t n, int d, int k, int max_iter, int64_t seed, int flags, const double *dX,
                         const double *init_centroids, double *centroids_out, int32_t *d_assign_out, double *sse_out, int32_t *iters_out,
                         int32_t *k_out, void *stream) {
-    if (n < 1 || d < 1 || k < 1 || max_iter < 1 || !dX || !centroids_out) return MMIDX_ERR_INVALID_ARG;
-    if (n > (int64_t)INT32_MAX) return MMIDX_ERR_INVALID_ARG;  // point indices, hipcub's item counts and the JDK draws are 32-bit
-    if ((int64_t)k > n) return MMIDX_ERR_INVALID_ARG;  // Weka would stop seeding at n centroids; a codebook needs k <= n
-    if (mmidx_device_count() < 1) return MMIDX_ERR_NO_DEVICE;
-    LCK(hipSetDevice(device));
+    if (n < 1 || d < 1 || k < 1 || max_iter < 1 || !dX || !centroids_out)
+        return mmidx_fail(MMIDX_ERR_INVALID_ARG, "k-means: n, d, k and max_iter must be positive, data and centroids_out non-null");
+    if (n > (int64_t)INT32_MAX) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "k-means: more than 2^31 - 1 points");  // point indices, hipcub's item counts and the JDK draws are 32-bit
+    if ((int64_t)k > n) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "k-means: k = %d exceeds the %lld points", k, (long long)n);  // Weka would stop seeding at n centroids; a codebook needs k <= n
+    if (mmidx_device_count() < 1) return mmidx_fail(MMIDX_ERR_NO_DEVICE, "no HIP device: libmmidx_hip has no CPU fallback");
+    HIPCK(hipSetDevice(device));
     hipStream_t st = (hipStream_t)stream;
     const bool plus_plus = (flags & MMIDX_KMEANS_PLUS_PLUS) != 0, normalize = (flags & MMIDX_KMEANS_NORMALIZE) != 0;
     const size_t nd = (size_t)n * d;
 
     // ---- working copy of the data (normalised attributes: Weka's default distance) --------------------
-    Buf<double> Xn, mn, mx;
+    ScopedBuf<double> Xn, mn, mx;
     const double *W = dX;
     std::vector<double> h_mn((size_t)d, 0.0), h_mx((size_t)d, 1.0);
     if (normalize) {
-        LCK(Xn.alloc(nd));
-        LCK(mn.alloc((size_t)d));
-        LCK(mx.alloc((size_t)d));
+        HIPCK(Xn.alloc(nd));
+        HIPCK(mn.alloc((size_t)d));
+        HIPCK(mx.alloc((size_t)d));
         hipLaunchKernelGGL(k_col_minmax, dim3((unsigned)d), dim3(256), 0, st, dX, (long long)n, d, mn.p, mx.p);
         hipLaunchKernelGGL(k_normalize, dim3((unsigned)((nd + 255) / 256)), dim3(256), 0, st, dX, Xn.p, mn.p, mx.p, (long long)nd, d);
-        LCK(hipGetLastError());
-        LCK(hipMemcpyAsync(h_mn.data(), mn.p, (size_t)d * 8, hipMemcpyDeviceToHost, st));
-        LCK(hipMemcpyAsync(h_mx.data(), mx.p, (size_t)d * 8, hipMemcpyDeviceToHost, st));
-        LCK(hipStreamSynchronize(st));
+        HIPCK(hipGetLastError());
+        HIPCK(hipMemcpyAsync(h_mn.data(), mn.p, (size_t)d * 8, hipMemcpyDeviceToHost, st));
+        HIPCK(hipMemcpyAsync(h_mx.data(), mx.p, (size_t)d * 8, hipMemcpyDeviceToHost, st));
+        HIPCK(hipStreamSynchronize(st));
         W = Xn.p;
     }
 
     // ---- seeding ----------------------------------------------------------------------------------------
     std::vector<double> Ch((size_t)k * d);
     int k_seed = k;  // centres seeded: fewer than k when default seeding runs out of distinct rows
-    Buf<double> dC;
-    LCK(dC.alloc((size_t)k * d));
+    ScopedBuf<double> dC;
+    HIPCK(dC.alloc((size_t)k * d));
     if (init_centroids) {
         for (int c = 0; c < k; c++)
             for (int j = 0; j < d; j++) {
@@ -234,10 +217,10 @@ int mmidx_kmeans_device(int device, int64_t n, int d, int k, int max_iter, int64
             std::vector<int32_t> perm((size_t)n);
             for (int64_t i = 0; i < n; i++) perm[(size_t)i] = (int32_t)i;
             const int64_t B = std::min<int64_t>(n, std::max<int64_t>(2 * (int64_t)k, 64));
-            Buf<long long> didx;
-            Buf<double> drows;
-            LCK(didx.alloc((size_t)B));
-            LCK(drows.alloc((size_t)B * d));
+            ScopedBuf<long long> didx;
+            ScopedBuf<double> drows;
+            HIPCK(didx.alloc((size_t)B));
+            HIPCK(drows.alloc((size_t)B * d));
             std::vector<long long> cand;
             std::vector<double> rows;
             std::set<std::vector<double>> taken;  // (operator< on the values: -0.0 and 0.0 are one row, as in a == comparison)
@@ -250,68 +233,68 @@ int mmidx_kmeans_device(int device, int64_t n, int d, int k, int max_iter, int64
                     std::swap(perm[(size_t)j], perm[(size_t)r]);
                 }
                 rows.resize((size_t)nb * d);
-                LCK(hipMemcpyAsync(didx.p, cand.data(), (size_t)nb * sizeof(long long), hipMemcpyHostToDevice, st));
+                HIPCK(hipMemcpyAsync(didx.p, cand.data(), (size_t)nb * sizeof(long long), hipMemcpyHostToDevice, st));
                 hipLaunchKernelGGL(k_gather_rows_ll, dim3((unsigned)((nb * d + 255) / 256)), dim3(256), 0, st, dX, didx.p, drows.p, (long long)nb, d);
-                LCK(hipGetLastError());
-                LCK(hipMemcpyAsync(rows.data(), drows.p, (size_t)nb * d * 8, hipMemcpyDeviceToHost, st));
-                LCK(hipStreamSynchronize(st));
+                HIPCK(hipGetLastError());
+                HIPCK(hipMemcpyAsync(rows.data(), drows.p, (size_t)nb * d * 8, hipMemcpyDeviceToHost, st));
+                HIPCK(hipStreamSynchronize(st));
                 for (int64_t t = 0; t < nb && (int)pick.size() < k; t++)
                     if (taken.emplace(rows.begin() + t * d, rows.begin() + (t + 1) * d).second) pick.push_back(cand[(size_t)t]);
             }
         } else {
             // k-means++ (Arthur & Vassilvitskii): first centre uniform, the others with probability ~ D^2
-            Buf<double> mind2, cum;
-            Buf<long long> dpick;
-            Buf<unsigned char> tmp;
-            LCK(mind2.alloc((size_t)n));
-            LCK(cum.alloc((size_t)n));
-            LCK(dpick.alloc(1));
+            ScopedBuf<double> mind2, cum;
+            ScopedBuf<long long> dpick;
+            ScopedBuf<unsigned char> tmp;
+            HIPCK(mind2.alloc((size_t)n));
+            HIPCK(cum.alloc((size_t)n));
+            HIPCK(dpick.alloc(1));
             size_t tb = 0;
-            LCK(hipcub::DeviceScan::InclusiveSum(nullptr, tb, mind2.p, cum.p, (int)n, st));
-            LCK(tmp.alloc(tb));
+            HIPCK(hipcub::DeviceScan::InclusiveSum(nullptr, tb, mind2.p, cum.p, (int)n, st));
+            HIPCK(tmp.alloc(tb));
             pick.push_back(rnd.nextInt((int)n));
             for (int c = 1; c < k; c++) {
                 hipLaunchKernelGGL(k_pp_update, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, W, W + (size_t)pick.back() * d, mind2.p,
                                    (long long)n, d, c == 1 ? 1 : 0);
-                LCK(hipcub::DeviceScan::InclusiveSum(tmp.p, tb, mind2.p, cum.p, (int)n, st));
+                HIPCK(hipcub::DeviceScan::InclusiveSum(tmp.p, tb, mind2.p, cum.p, (int)n, st));
                 double total = 0.0;
-                LCK(hipMemcpyAsync(&total, cum.p + (n - 1), 8, hipMemcpyDeviceToHost, st));
-                LCK(hipStreamSynchronize(st));
+                HIPCK(hipMemcpyAsync(&total, cum.p + (n - 1), 8, hipMemcpyDeviceToHost, st));
+                HIPCK(hipStreamSynchronize(st));
                 const double prob = rnd.nextDouble();
                 long long idx = 0;
                 hipLaunchKernelGGL(k_pp_pick, dim3(1), dim3(1), 0, st, cum.p, (long long)n, prob * total, dpick.p);
-                LCK(hipMemcpyAsync(&idx, dpick.p, 8, hipMemcpyDeviceToHost, st));
-                LCK(hipStreamSynchronize(st));
+                HIPCK(hipMemcpyAsync(&idx, dpick.p, 8, hipMemcpyDeviceToHost, st));
+                HIPCK(hipStreamSynchronize(st));
                 pick.push_back(idx);
             }
         }
         // gather the picked rows
         for (size_t c = 0; c < pick.size(); c++)
-            LCK(hipMemcpyAsync(Ch.data() + c * d, W + (size_t)pick[c] * d, (size_t)d * 8, hipMemcpyDeviceToHost, st));
-        LCK(hipStreamSynchronize(st));
+            HIPCK(hipMemcpyAsync(Ch.data() + c * d, W + (size_t)pick[c] * d, (size_t)d * 8, hipMemcpyDeviceToHost, st));
+        HIPCK(hipStreamSynchronize(st));
         k_seed = (int)pick.size();
     }
 
     // ---- Lloyd iterations -------------------------------------------------------------------------------
-    Buf<int32_t> a_old, a_new, iota, sorted_idx, keys_out, counts;
-    Buf<long long> off;
-    Buf<u64> changed;
-    Buf<unsigned char> stmp;
-    LCK(a_old.alloc((size_t)n));
-    LCK(a_new.alloc((size_t)n));
-    LCK(iota.alloc((size_t)n));
-    LCK(sorted_idx.alloc((size_t)n));
-    LCK(keys_out.alloc((size_t)n));
-    LCK(counts.alloc((size_t)k));
-    LCK(off.alloc((size_t)k + 1));
-    LCK(changed.alloc(1));
-    LCK(hipMemsetAsync(a_old.p, 0xFF, (size_t)n * 4, st));
+    ScopedBuf<int32_t> a_old, a_new, iota, sorted_idx, keys_out, counts;
+    ScopedBuf<long long> off;
+    ScopedBuf<u64> changed;
+    ScopedBuf<unsigned char> stmp;
+    HIPCK(a_old.alloc((size_t)n));
+    HIPCK(a_new.alloc((size_t)n));
+    HIPCK(iota.alloc((size_t)n));
+    HIPCK(sorted_idx.alloc((size_t)n));
+    HIPCK(keys_out.alloc((size_t)n));
+    HIPCK(counts.alloc((size_t)k));
+    HIPCK(off.alloc((size_t)k + 1));
+    HIPCK(changed.alloc(1));
+    HIPCK(hipMemsetAsync(a_old.p, 0xFF, (size_t)n * 4, st));
     hipLaunchKernelGGL(k_iota, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, iota.p, (long long)n);
     int kbits = 1;
     while ((1 << kbits) < k) kbits++;
     size_t sb = 0;
-    LCK(hipcub::DeviceRadixSort::SortPairs(nullptr, sb, a_new.p, keys_out.p, iota.p, sorted_idx.p, (int)n, 0, kbits, st));
-    LCK(stmp.alloc(sb));
+    HIPCK(hipcub::DeviceRadixSort::SortPairs(nullptr, sb, a_new.p, keys_out.p, iota.p, sorted_idx.p, (int)n, 0, kbits, st));
+    HIPCK(stmp.alloc(sb));
 
     int k_eff = k_seed, iters = 0;
     std::vector<int32_t> h_counts((size_t)k);
@@ -319,9 +302,9 @@ int mmidx_kmeans_device(int device, int64_t n, int d, int k, int max_iter, int64
     mmidx_index *h = nullptr;
     int rc = MMIDX_OK;
     auto sort_and_mean = [&](const double *data, double *d_out) -> int {
-        LCK(hipcub::DeviceRadixSort::SortPairs(stmp.p, sb, a_new.p, keys_out.p, iota.p, sorted_idx.p, (int)n, 0, kbits, st));
+        HIPCK(hipcub::DeviceRadixSort::SortPairs(stmp.p, sb, a_new.p, keys_out.p, iota.p, sorted_idx.p, (int)n, 0, kbits, st));
         hipLaunchKernelGGL(k_centroid_mean, dim3((unsigned)k_eff), dim3(256), 0, st, data, sorted_idx.p, off.p, d_out, d);
-        LCK(hipGetLastError());
+        HIPCK(hipGetLastError());
         return MMIDX_OK;
     };
     for (;;) {
@@ -334,20 +317,20 @@ int mmidx_kmeans_device(int device, int64_t n, int d, int k, int max_iter, int64
         if (rc) break;
         rc = mmidx_assign_device(h, n, W, a_new.p, st);
         if (rc) break;
-        LCK(hipMemsetAsync(changed.p, 0, 8, st));
-        LCK(hipMemsetAsync(counts.p, 0, (size_t)k_eff * 4, st));
+        HIPCK(hipMemsetAsync(changed.p, 0, 8, st));
+        HIPCK(hipMemsetAsync(counts.p, 0, (size_t)k_eff * 4, st));
         hipLaunchKernelGGL(k_changed_counts, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a_old.p, a_new.p, (long long)n, changed.p, counts.p);
         u64 nchanged = 0;
-        LCK(hipMemcpyAsync(&nchanged, changed.p, 8, hipMemcpyDeviceToHost, st));
-        LCK(hipMemcpyAsync(h_counts.data(), counts.p, (size_t)k_eff * 4, hipMemcpyDeviceToHost, st));
-        LCK(hipStreamSynchronize(st));
+        HIPCK(hipMemcpyAsync(&nchanged, changed.p, 8, hipMemcpyDeviceToHost, st));
+        HIPCK(hipMemcpyAsync(h_counts.data(), counts.p, (size_t)k_eff * 4, hipMemcpyDeviceToHost, st));
+        HIPCK(hipStreamSynchronize(st));
         h_off[0] = 0;
         for (int c = 0; c < k_eff; c++) h_off[(size_t)c + 1] = h_off[(size_t)c] + h_counts[(size_t)c];
-        LCK(hipMemcpyAsync(off.p, h_off.data(), ((size_t)k_eff + 1) * 8, hipMemcpyHostToDevice, st));
+        HIPCK(hipMemcpyAsync(off.p, h_off.data(), ((size_t)k_eff + 1) * 8, hipMemcpyHostToDevice, st));
         rc = sort_and_mean(W, dC.p);
         if (rc) break;
-        LCK(hipMemcpyAsync(Ch.data(), dC.p, (size_t)k_eff * d * 8, hipMemcpyDeviceToHost, st));
-        LCK(hipStreamSynchronize(st));
+        HIPCK(hipMemcpyAsync(Ch.data(), dC.p, (size_t)k_eff * d * 8, hipMemcpyDeviceToHost, st));
+        HIPCK(hipStreamSynchronize(st));
         const bool done = nchanged == 0 || iters >= max_iter;
         // empty clusters are dropped (SimpleKMeans: m_NumClusters -= emptyClusterCount); the survivors keep their order
         int kept = 0;
@@ -366,11 +349,11 @@ int mmidx_kmeans_device(int device, int64_t n, int d, int k, int max_iter, int64
                 for (int c = 0; c < k_eff; c++)
                     if (h_counts[(size_t)c] > 0) remap[(size_t)c] = t++;
                 std::vector<int32_t> ha((size_t)n);
-                LCK(hipMemcpyAsync(ha.data(), a_new.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-                LCK(hipStreamSynchronize(st));
+                HIPCK(hipMemcpyAsync(ha.data(), a_new.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+                HIPCK(hipStreamSynchronize(st));
                 for (int64_t i = 0; i < n; i++) ha[(size_t)i] = remap[(size_t)ha[(size_t)i]];
-                LCK(hipMemcpyAsync(a_new.p, ha.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
-                LCK(hipStreamSynchronize(st));  // (ha is freed at the end of this block)
+                HIPCK(hipMemcpyAsync(a_new.p, ha.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
+                HIPCK(hipStreamSynchronize(st));  // (ha is freed at the end of this block)
                 // offsets of the compacted numbering
                 int t2 = 0;
                 h_off[0] = 0;
@@ -379,14 +362,14 @@ int mmidx_kmeans_device(int device, int64_t n, int d, int k, int max_iter, int64
                         h_off[(size_t)t2 + 1] = h_off[(size_t)t2] + h_counts[(size_t)c];
                         t2++;
                     }
-                LCK(hipMemcpyAsync(off.p, h_off.data(), ((size_t)kept + 1) * 8, hipMemcpyHostToDevice, st));
+                HIPCK(hipMemcpyAsync(off.p, h_off.data(), ((size_t)kept + 1) * 8, hipMemcpyHostToDevice, st));
             }
             k_eff = kept;
             break;
         }
         k_eff = kept;
         std::swap(a_old.p, a_new.p);
-        if (dropped) LCK(hipMemsetAsync(a_old.p, 0xFF, (size_t)n * 4, st));  // numbering changed: everything counts as moved
+        if (dropped) HIPCK(hipMemsetAsync(a_old.p, 0xFF, (size_t)n * 4, st));  // numbering changed: everything counts as moved
     }
     if (h) mmidx_destroy(h);
     if (rc) return rc;
@@ -394,13 +377,13 @@ int mmidx_kmeans_device(int device, int64_t n, int d, int k, int max_iter, int64
     // ---- outputs ------------------------------------------------------------------------------------------
     // squared error in the space the clustering ran in (what SimpleKMeans.getSquaredError reports)
     if (sse_out) {
-        Buf<double> perr;
-        LCK(perr.alloc((size_t)n));
-        LCK(hipMemcpyAsync(dC.p, Ch.data(), (size_t)k_eff * d * 8, hipMemcpyHostToDevice, st));
+        ScopedBuf<double> perr;
+        HIPCK(perr.alloc((size_t)n));
+        HIPCK(hipMemcpyAsync(dC.p, Ch.data(), (size_t)k_eff * d * 8, hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(k_point_sqerr, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, W, dC.p, a_new.p, perr.p, (long long)n, d);
         std::vector<double> he((size_t)n);
-        LCK(hipMemcpyAsync(he.data(), perr.p, (size_t)n * 8, hipMemcpyDeviceToHost, st));
-        LCK(hipStreamSynchronize(st));
+        HIPCK(hipMemcpyAsync(he.data(), perr.p, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+        HIPCK(hipStreamSynchronize(st));
         double s = 0.0;
         for (int64_t i = 0; i < n; i++) s += he[(size_t)i];
         *sse_out = s;
@@ -410,12 +393,12 @@ int mmidx_kmeans_device(int device, int64_t n, int d, int k, int max_iter, int64
         // (SimpleKMeans.moveCentroid averages the un-normalised instances)
         int rc2 = sort_and_mean(dX, dC.p);
         if (rc2) return rc2;
-        LCK(hipMemcpyAsync(Ch.data(), dC.p, (size_t)k_eff * d * 8, hipMemcpyDeviceToHost, st));
-        LCK(hipStreamSynchronize(st));
+        HIPCK(hipMemcpyAsync(Ch.data(), dC.p, (size_t)k_eff * d * 8, hipMemcpyDeviceToHost, st));
+        HIPCK(hipStreamSynchronize(st));
     }
     memcpy(centroids_out, Ch.data(), (size_t)k_eff * d * 8);
-    if (d_assign_out) LCK(hipMemcpyAsync(d_assign_out, a_new.p, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
-    LCK(hipStreamSynchronize(st));
+    if (d_assign_out) HIPCK(hipMemcpyAsync(d_assign_out, a_new.p, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
+    HIPCK(hipStreamSynchronize(st));
     if (iters_out) *iters_out = iters;
     if (k_out) *k_out = k_eff;
     return MMIDX_OK;
@@ -423,18 +406,18 @@ int mmidx_kmeans_device(int device, int64_t n, int d, int k, int max_iter, int64
 
 int mmidx_kmeans(int device, int64_t n, int d, int k, int max_iter, int64_t seed, int flags, const double *X, const double *init_centroids,
                  double *centroids_out, int32_t *assign_out, double *sse_out, int32_t *iters_out, int32_t *k_out) {
-    if (n < 1 || d < 1 || !X || n > (int64_t)INT32_MAX) return MMIDX_ERR_INVALID_ARG;
-    if (mmidx_device_count() < 1) return MMIDX_ERR_NO_DEVICE;
-    LCK(hipSetDevice(device));
-    Buf<double> dX;
-    Buf<int32_t> dA;
-    LCK(dX.alloc((size_t)n * d));
-    LCK(dA.alloc((size_t)n));
-    LCK(hipMemcpy(dX.p, X, (size_t)n * d * 8, hipMemcpyHostToDevice));
+    if (n < 1 || d < 1 || !X || n > (int64_t)INT32_MAX) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "k-means: n and d must be positive (n < 2^31), data non-null");
+    if (mmidx_device_count() < 1) return mmidx_fail(MMIDX_ERR_NO_DEVICE, "no HIP device: libmmidx_hip has no CPU fallback");
+    HIPCK(hipSetDevice(device));
+    ScopedBuf<double> dX;
+    ScopedBuf<int32_t> dA;
+    HIPCK(dX.alloc((size_t)n * d));
+    HIPCK(dA.alloc((size_t)n));
+    HIPCK(hipMemcpy(dX.p, X, (size_t)n * d * 8, hipMemcpyHostToDevice));
     int rc = mmidx_kmeans_device(device, n, d, k, max_iter, seed, flags, dX.p, init_centroids, centroids_out, dA.p, sse_out, iters_out, k_out,
                                  nullptr);
     if (rc) return rc;
-    if (assign_out) LCK(hipMemcpy(assign_out, dA.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+    if (assign_out) HIPCK(hipMemcpy(assign_out, dA.p, (size_t)n * 4, hipMemcpyDeviceToHost));
     return MMIDX_OK;
 }
 

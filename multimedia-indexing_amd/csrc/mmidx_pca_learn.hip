@@ -27,30 +27,12 @@
 #include <mutex>
 #include <vector>
 
-#include "mmidx.h"
+#include "mmidx_host.h"
 #include "mmidx_small_solve.h"
-
-// defined in mmidx_api.hip: the calling thread's last-error text, and the launch of K7 (k_pca_project) as a plain
-// Y[n][nc] = (X[n][ss] - mu[ss]) Vt[nc][ss]^T on device pointers
-extern "C" {
-__attribute__((visibility("hidden"))) int mmidx_internal_fail(int code, const char *msg);
-__attribute__((visibility("hidden"))) int mmidx_internal_gemm_nt(const double *X, const double *mu, const double *Vt, double *Y, long long n,
-                                                                  int nc, int ss, void *stream);
-}
 
 namespace {
 
 typedef __attribute__((ext_vector_type(4))) double f64x4;
-
-#define PLCK(expr)                                                                                          \
-    do {                                                                                                    \
-        hipError_t e__ = (expr);                                                                            \
-        if (e__ != hipSuccess) {                                                                            \
-            char b__[384];                                                                                  \
-            snprintf(b__, sizeof(b__), "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e__), __FILE__, __LINE__); \
-            return mmidx_internal_fail(MMIDX_ERR_HIP, b__);                                                 \
-        }                                                                                                   \
-    } while (0)
 
 // ------------------------------------------------------------------------------------------------
 // column sums: sum[c] += X[r][c], r = 0 .. n-1 in order (PCA.java:144-149).  A thread per column, a wave reads 512 contiguous
@@ -277,15 +259,6 @@ __global__ __launch_bounds__(256) void k_pca_finish(const double *__restrict__ V
     if (threadIdx.x == 0) sv[i] = sqrt(lam[i] > 0.0 ? lam[i] : 0.0);
 }
 
-template <typename T>
-struct Buf {
-    T *p = nullptr;
-    ~Buf() {
-        if (p) (void)hipFree(p);
-    }
-    hipError_t alloc(size_t n) { return hipMalloc((void **)&p, std::max<size_t>(n, 1) * sizeof(T)); }
-};
-
 struct Ev {  // a timing event that is destroyed on every return path
     hipEvent_t e = nullptr;
     ~Ev() {
@@ -304,7 +277,7 @@ int launch_gram(bool sym, const double *A, const double *B, const double *muA, c
         hipLaunchKernelGGL(k_pca_gram<true>, grid, dim3(GR_NT), 0, st, A, B, muA, muB, Cm, n, sa, sb);
     else
         hipLaunchKernelGGL(k_pca_gram<false>, grid, dim3(GR_NT), 0, st, A, B, muA, muB, Cm, n, sa, sb);
-    PLCK(hipGetLastError());
+    HIPCK(hipGetLastError());
     return MMIDX_OK;
 }
 
@@ -324,19 +297,19 @@ namespace {
 // rows [count, count + n) <- src (host or device), then the running sums; `st` = the stream the copy and the sums run on
 int add_rows(mmidx_pca_learner *l, int64_t n, const double *src, hipMemcpyKind kind, hipStream_t st) {
     if (n == 0) return MMIDX_OK;
-    PLCK(hipSetDevice(l->device));
+    HIPCK(hipSetDevice(l->device));
     double *dst = l->dA + (size_t)l->count * l->ss;
-    if (st != l->stream) PLCK(hipStreamWaitEvent(st, l->ev_own, 0));
-    PLCK(hipMemcpyAsync(dst, src, (size_t)n * l->ss * 8, kind, st));
+    if (st != l->stream) HIPCK(hipStreamWaitEvent(st, l->ev_own, 0));
+    HIPCK(hipMemcpyAsync(dst, src, (size_t)n * l->ss * 8, kind, st));
     hipLaunchKernelGGL(k_pca_colsum, dim3((unsigned)((l->ss + 63) / 64)), dim3(64), 0, st, dst, (long long)n, l->ss, l->dsum);
-    PLCK(hipGetLastError());
+    HIPCK(hipGetLastError());
     if (st != l->stream) {
-        PLCK(hipEventRecord(l->ev_ext, st));
-        PLCK(hipStreamWaitEvent(l->stream, l->ev_ext, 0));
+        HIPCK(hipEventRecord(l->ev_ext, st));
+        HIPCK(hipStreamWaitEvent(l->stream, l->ev_ext, 0));
     } else {
-        PLCK(hipStreamSynchronize(st));  // host rows: the caller may reuse its buffer
+        HIPCK(hipStreamSynchronize(st));  // host rows: the caller may reuse its buffer
     }
-    PLCK(hipEventRecord(l->ev_own, l->stream));
+    HIPCK(hipEventRecord(l->ev_own, l->stream));
     l->count += n;
     return MMIDX_OK;
 }
@@ -346,16 +319,16 @@ int add_rows(mmidx_pca_learner *l, int64_t n, const double *src, hipMemcpyKind k
 extern "C" {
 
 int mmidx_pca_learn_create(int nc, int64_t num_samples, int ss, int device, mmidx_pca_learner **out) {
-    if (!out) return mmidx_internal_fail(MMIDX_ERR_INVALID_ARG, "null out pointer");
+    if (!out) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null out pointer");
     *out = nullptr;
-    if (nc < 1 || ss < 1 || num_samples < 0) return mmidx_internal_fail(MMIDX_ERR_INVALID_ARG, "bad PCA shape");
-    if (nc > ss) return mmidx_internal_fail(MMIDX_ERR_INVALID_ARG, "More components requested than the data's length.");  // PCA.java:102-104
+    if (nc < 1 || ss < 1 || num_samples < 0) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "bad PCA shape");
+    if (nc > ss) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "More components requested than the data's length.");  // PCA.java:102-104
     if (ss > 16384 || nc > 1024 || num_samples > (int64_t)INT32_MAX)
-        return mmidx_internal_fail(MMIDX_ERR_UNSUPPORTED, "PCA learning: sampleSize <= 16384, numComponents <= 1024, numSamples < 2^31");
+        return mmidx_fail(MMIDX_ERR_UNSUPPORTED, "PCA learning: sampleSize <= 16384, numComponents <= 1024, numSamples < 2^31");
     const int ndev = mmidx_device_count();
-    if (ndev < 1) return mmidx_internal_fail(MMIDX_ERR_NO_DEVICE, "no HIP device: libmmidx_hip has no CPU fallback");
-    if (device < 0 || device >= ndev) return mmidx_internal_fail(MMIDX_ERR_NO_DEVICE, "device outside the visible range");
-    PLCK(hipSetDevice(device));
+    if (ndev < 1) return mmidx_fail(MMIDX_ERR_NO_DEVICE, "no HIP device: libmmidx_hip has no CPU fallback");
+    if (device < 0 || device >= ndev) return mmidx_fail(MMIDX_ERR_NO_DEVICE, "device outside the visible range");
+    HIPCK(hipSetDevice(device));
     mmidx_pca_learner *l = new mmidx_pca_learner();
     l->nc = nc;
     l->ss = ss;
@@ -370,10 +343,8 @@ int mmidx_pca_learn_create(int nc, int64_t num_samples, int ss, int device, mmid
     if (e == hipSuccess) e = hipEventRecord(l->ev_own, l->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(l->stream);
     if (e != hipSuccess) {
-        char b[256];
-        snprintf(b, sizeof(b), "PCA learner: allocation of %lld x %d samples failed: %s", (long long)num_samples, ss, hipGetErrorString(e));
         mmidx_pca_learn_destroy(l);
-        return mmidx_internal_fail(MMIDX_ERR_HIP, b);
+        return mmidx_fail(MMIDX_ERR_HIP, "PCA learner: allocation of %lld x %d samples failed: %s", (long long)num_samples, ss, hipGetErrorString(e));
     }
     *out = l;
     return MMIDX_OK;
@@ -393,30 +364,30 @@ int mmidx_pca_learn_destroy(mmidx_pca_learner *l) {
 }
 
 int mmidx_pca_learn_add(mmidx_pca_learner *l, int64_t n, const double *X) {
-    if (!l) return mmidx_internal_fail(MMIDX_ERR_INVALID_ARG, "null handle");
-    if (n < 0 || (n > 0 && !X)) return mmidx_internal_fail(MMIDX_ERR_INVALID_ARG, "null argument");
+    if (!l) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null handle");
+    if (n < 0 || (n > 0 && !X)) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null argument");
     std::lock_guard<std::mutex> lk(l->mu);
-    if (l->count + n > l->num) return mmidx_internal_fail(MMIDX_ERR_INVALID_ARG, "Too many samples");  // PCA.java:121-122
+    if (l->count + n > l->num) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "Too many samples");  // PCA.java:121-122
     return add_rows(l, n, X, hipMemcpyHostToDevice, l->stream);
 }
 
 int mmidx_pca_learn_add_device(mmidx_pca_learner *l, int64_t n, const double *dX, void *stream) {
-    if (!l) return mmidx_internal_fail(MMIDX_ERR_INVALID_ARG, "null handle");
-    if (n < 0 || (n > 0 && !dX)) return mmidx_internal_fail(MMIDX_ERR_INVALID_ARG, "null argument");
+    if (!l) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null handle");
+    if (n < 0 || (n > 0 && !dX)) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null argument");
     std::lock_guard<std::mutex> lk(l->mu);
-    if (l->count + n > l->num) return mmidx_internal_fail(MMIDX_ERR_INVALID_ARG, "Too many samples");
+    if (l->count + n > l->num) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "Too many samples");
     return add_rows(l, n, dX, hipMemcpyDeviceToDevice, (hipStream_t)stream);
 }
 
 int mmidx_pca_learn_compute(mmidx_pca_learner *l, double tol, int max_iter, double *means_out, double *sv_out, double *Vt_out,
                             int32_t *iters_out, double *residual_out) {
-    if (!l) return mmidx_internal_fail(MMIDX_ERR_INVALID_ARG, "null handle");
+    if (!l) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null handle");
     std::lock_guard<std::mutex> lk(l->mu);
-    if (l->count != l->num) return mmidx_internal_fail(MMIDX_ERR_INVALID_ARG, "Not all the data has been added");  // PCA.java:136-137
+    if (l->count != l->num) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "Not all the data has been added");  // PCA.java:136-137
     if ((int64_t)l->nc > l->num)
-        return mmidx_internal_fail(MMIDX_ERR_INVALID_ARG, "More data needed to compute the desired number of components");  // :138-140
-    if (!(tol >= 0.0) || max_iter < 1) return mmidx_internal_fail(MMIDX_ERR_INVALID_ARG, "tol must be >= 0 and max_iter >= 1");
-    PLCK(hipSetDevice(l->device));
+        return mmidx_fail(MMIDX_ERR_INVALID_ARG, "More data needed to compute the desired number of components");  // :138-140
+    if (!(tol >= 0.0) || max_iter < 1) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "tol must be >= 0 and max_iter >= 1");
+    HIPCK(hipSetDevice(l->device));
     hipStream_t st = l->stream;
     const int ss = l->ss, nc = l->nc, b = std::min(ss, nc + 32);
     const long long n = (long long)l->num;
@@ -425,41 +396,41 @@ int mmidx_pca_learn_compute(mmidx_pca_learner *l, double tol, int max_iter, doub
 
     // ---- means (PCA.java:150-153) ----
     std::vector<double> h_mu((size_t)ss);
-    PLCK(hipMemcpyAsync(h_mu.data(), l->dsum, (size_t)ss * 8, hipMemcpyDeviceToHost, st));
-    PLCK(hipStreamSynchronize(st));
+    HIPCK(hipMemcpyAsync(h_mu.data(), l->dsum, (size_t)ss * 8, hipMemcpyDeviceToHost, st));
+    HIPCK(hipStreamSynchronize(st));
     for (int j = 0; j < ss; j++) h_mu[(size_t)j] = h_mu[(size_t)j] / (double)n;
     if (means_out) memcpy(means_out, h_mu.data(), (size_t)ss * 8);
 
-    Buf<double> d_mu, d_zero, G, Q, Z, V, ZW, Qt, S, Wd, d_lam, d_res, d_Vt, d_sv;
+    ScopedBuf<double> d_mu, d_zero, G, Q, Z, V, ZW, Qt, S, Wd, d_lam, d_res, d_Vt, d_sv;
     const size_t sb = (size_t)ss * b, bb = (size_t)b * b;
-    PLCK(d_mu.alloc((size_t)ss));
-    PLCK(d_zero.alloc((size_t)ss));
-    PLCK(G.alloc((size_t)ss * ss));
-    PLCK(Q.alloc(sb));
-    PLCK(Z.alloc(sb));
-    PLCK(V.alloc(sb));
-    PLCK(ZW.alloc(sb));
-    PLCK(Qt.alloc(sb));
-    PLCK(S.alloc(bb));
-    PLCK(Wd.alloc(bb));
-    PLCK(d_lam.alloc((size_t)b));
-    PLCK(d_res.alloc((size_t)b));
-    PLCK(d_Vt.alloc((size_t)nc * ss));
-    PLCK(d_sv.alloc((size_t)nc));
-    PLCK(hipMemcpyAsync(d_mu.p, h_mu.data(), (size_t)ss * 8, hipMemcpyHostToDevice, st));
-    PLCK(hipMemsetAsync(d_zero.p, 0, (size_t)ss * 8, st));
+    HIPCK(d_mu.alloc((size_t)ss));
+    HIPCK(d_zero.alloc((size_t)ss));
+    HIPCK(G.alloc((size_t)ss * ss));
+    HIPCK(Q.alloc(sb));
+    HIPCK(Z.alloc(sb));
+    HIPCK(V.alloc(sb));
+    HIPCK(ZW.alloc(sb));
+    HIPCK(Qt.alloc(sb));
+    HIPCK(S.alloc(bb));
+    HIPCK(Wd.alloc(bb));
+    HIPCK(d_lam.alloc((size_t)b));
+    HIPCK(d_res.alloc((size_t)b));
+    HIPCK(d_Vt.alloc((size_t)nc * ss));
+    HIPCK(d_sv.alloc((size_t)nc));
+    HIPCK(hipMemcpyAsync(d_mu.p, h_mu.data(), (size_t)ss * 8, hipMemcpyHostToDevice, st));
+    HIPCK(hipMemsetAsync(d_zero.p, 0, (size_t)ss * 8, st));
 
     // ---- Gram matrix of the centred samples ----
     Ev e0, e1;
-    PLCK(hipEventCreate(&e0.e));
-    PLCK(hipEventCreate(&e1.e));
-    PLCK(hipEventRecord(e0.e, st));
+    HIPCK(hipEventCreate(&e0.e));
+    HIPCK(hipEventCreate(&e1.e));
+    HIPCK(hipEventRecord(e0.e, st));
     int rc = launch_gram(true, l->dA, l->dA, d_mu.p, d_mu.p, G.p, n, ss, ss, st);
     if (rc) return rc;
-    PLCK(hipEventRecord(e1.e, st));
-    PLCK(hipStreamSynchronize(st));
+    HIPCK(hipEventRecord(e1.e, st));
+    HIPCK(hipStreamSynchronize(st));
     float gram_ms = 0.f;
-    PLCK(hipEventElapsedTime(&gram_ms, e0.e, e1.e));
+    HIPCK(hipEventElapsedTime(&gram_ms, e0.e, e1.e));
 
     double t_small = 0.0;  // host time in the b x b solves
     std::vector<double> hS(bb), Linv, lam, Wt;
@@ -470,29 +441,29 @@ int mmidx_pca_learn_compute(mmidx_pca_learner *l, double tol, int max_iter, doub
         for (int pass = 0, clean = 0; pass < 6; pass++) {
             int r = launch_gram(true, src, src, d_zero.p, d_zero.p, S.p, ss, b, b, st);
             if (r) return r;
-            PLCK(hipMemcpyAsync(hS.data(), S.p, bb * 8, hipMemcpyDeviceToHost, st));
-            PLCK(hipStreamSynchronize(st));
+            HIPCK(hipMemcpyAsync(hS.data(), S.p, bb * 8, hipMemcpyDeviceToHost, st));
+            HIPCK(hipStreamSynchronize(st));
             const double t0 = now_s();
             if (!mmidx_small::chol_inverse(hS.data(), b, (double)b * 0x1p-52, Linv, deficient))
-                return mmidx_internal_fail(MMIDX_ERR_INVALID_ARG, NONFINITE);
+                return mmidx_fail(MMIDX_ERR_INVALID_ARG, "%s", NONFINITE);
             t_small += now_s() - t0;
-            PLCK(hipMemcpyAsync(Wd.p, Linv.data(), bb * 8, hipMemcpyHostToDevice, st));
+            HIPCK(hipMemcpyAsync(Wd.p, Linv.data(), bb * 8, hipMemcpyHostToDevice, st));
             r = mmidx_internal_gemm_nt(src, d_zero.p, Wd.p, tmp, ss, b, b, st);  // tmp = src L^-T
             if (r) return r;
             for (int j : deficient)
                 hipLaunchKernelGGL(k_pca_fill, dim3((unsigned)((ss + 255) / 256)), dim3(256), 0, st, tmp, ss, b, j, salt++);
-            PLCK(hipGetLastError());
-            PLCK(hipStreamSynchronize(st));  // (Linv is rewritten by the next pass)
+            HIPCK(hipGetLastError());
+            HIPCK(hipStreamSynchronize(st));  // (Linv is rewritten by the next pass)
             std::swap(src, tmp);
             clean = deficient.empty() ? clean + 1 : 0;
             if (clean >= 2) return MMIDX_OK;
         }
-        return mmidx_internal_fail(MMIDX_ERR_UNSUPPORTED, "PCA learning: the block could not be orthonormalised in 6 CholeskyQR passes");
+        return mmidx_fail(MMIDX_ERR_UNSUPPORTED, "PCA learning: the block could not be orthonormalised in 6 CholeskyQR passes");
     };
 
     double *q = Q.p, *z = Z.p, *zw = ZW.p;
     hipLaunchKernelGGL(k_pca_fill, dim3((unsigned)((sb + 255) / 256)), dim3(256), 0, st, q, ss, b, -1, 0ull);
-    PLCK(hipGetLastError());
+    HIPCK(hipGetLastError());
     rc = orth(q, z);
     if (rc) return rc;
 
@@ -504,13 +475,13 @@ int mmidx_pca_learn_compute(mmidx_pca_learner *l, double tol, int max_iter, doub
     for (;;) {
         iters++;
         hipLaunchKernelGGL(k_pca_transpose, dim3((unsigned)((b + 31) / 32), (unsigned)((ss + 31) / 32)), dim3(256), 0, st, q, Qt.p, ss, b);
-        PLCK(hipGetLastError());
+        HIPCK(hipGetLastError());
         rc = mmidx_internal_gemm_nt(G.p, d_zero.p, Qt.p, z, ss, b, ss, st);  // Z = G Q
         if (rc) return rc;
         rc = launch_gram(false, q, z, d_zero.p, d_zero.p, S.p, ss, b, b, st);  // T = Q^T Z
         if (rc) return rc;
-        PLCK(hipMemcpyAsync(hS.data(), S.p, bb * 8, hipMemcpyDeviceToHost, st));
-        PLCK(hipStreamSynchronize(st));
+        HIPCK(hipMemcpyAsync(hS.data(), S.p, bb * 8, hipMemcpyDeviceToHost, st));
+        HIPCK(hipStreamSynchronize(st));
         {
             const double t0 = now_s();
             for (int i = 0; i < b; i++)
@@ -519,19 +490,19 @@ int mmidx_pca_learn_compute(mmidx_pca_learner *l, double tol, int max_iter, doub
                     hS[(size_t)i * b + j] = m;
                     hS[(size_t)j * b + i] = m;
                 }
-            if (!mmidx_small::sym_eig(hS.data(), b, lam, Wt)) return mmidx_internal_fail(MMIDX_ERR_INVALID_ARG, NONFINITE);
+            if (!mmidx_small::sym_eig(hS.data(), b, lam, Wt)) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "%s", NONFINITE);
             t_small += now_s() - t0;
         }
-        PLCK(hipMemcpyAsync(Wd.p, Wt.data(), bb * 8, hipMemcpyHostToDevice, st));
-        PLCK(hipMemcpyAsync(d_lam.p, lam.data(), (size_t)b * 8, hipMemcpyHostToDevice, st));
+        HIPCK(hipMemcpyAsync(Wd.p, Wt.data(), bb * 8, hipMemcpyHostToDevice, st));
+        HIPCK(hipMemcpyAsync(d_lam.p, lam.data(), (size_t)b * 8, hipMemcpyHostToDevice, st));
         rc = mmidx_internal_gemm_nt(q, d_zero.p, Wd.p, V.p, ss, b, b, st);  // V = Q W (Ritz vectors)
         if (rc) return rc;
         rc = mmidx_internal_gemm_nt(z, d_zero.p, Wd.p, zw, ss, b, b, st);  // Z W = G V
         if (rc) return rc;
         hipLaunchKernelGGL(k_pca_resid, dim3((unsigned)nc), dim3(256), 0, st, zw, V.p, d_lam.p, ss, b, d_res.p);
-        PLCK(hipGetLastError());
-        PLCK(hipMemcpyAsync(h_res.data(), d_res.p, (size_t)nc * 8, hipMemcpyDeviceToHost, st));
-        PLCK(hipStreamSynchronize(st));
+        HIPCK(hipGetLastError());
+        HIPCK(hipMemcpyAsync(h_res.data(), d_res.p, (size_t)nc * 8, hipMemcpyDeviceToHost, st));
+        HIPCK(hipStreamSynchronize(st));
         double mr = 0.0;
         for (int i = 0; i < nc; i++) mr = std::max(mr, h_res[(size_t)i]);
         residual = lam[0] > 0.0 ? mr / lam[0] : (mr == 0.0 ? 0.0 : HUGE_VAL);
@@ -550,10 +521,10 @@ int mmidx_pca_learn_compute(mmidx_pca_learner *l, double tol, int max_iter, doub
 
     // ---- singular values, sign rule, transpose ----
     hipLaunchKernelGGL(k_pca_finish, dim3((unsigned)nc), dim3(256), 0, st, V.p, d_lam.p, ss, b, d_Vt.p, d_sv.p);
-    PLCK(hipGetLastError());
-    if (Vt_out) PLCK(hipMemcpyAsync(Vt_out, d_Vt.p, (size_t)nc * ss * 8, hipMemcpyDeviceToHost, st));
-    if (sv_out) PLCK(hipMemcpyAsync(sv_out, d_sv.p, (size_t)nc * 8, hipMemcpyDeviceToHost, st));
-    PLCK(hipStreamSynchronize(st));
+    HIPCK(hipGetLastError());
+    if (Vt_out) HIPCK(hipMemcpyAsync(Vt_out, d_Vt.p, (size_t)nc * ss * 8, hipMemcpyDeviceToHost, st));
+    if (sv_out) HIPCK(hipMemcpyAsync(sv_out, d_sv.p, (size_t)nc * 8, hipMemcpyDeviceToHost, st));
+    HIPCK(hipStreamSynchronize(st));
     if (iters_out) *iters_out = iters;
     if (residual_out) *residual_out = residual;
     if (trace) {
@@ -563,11 +534,8 @@ int mmidx_pca_learn_compute(mmidx_pca_learner *l, double tol, int max_iter, doub
         fprintf(stderr, "[mmidx] pca_learn: n %lld ss %d nc %d b %d: gram %.3f ms (%.2f TF/s executed), %d iterations %.3f s, host solves %.3f s (start block included), total %.3f s\n",
                 n, ss, nc, b, gram_ms, 2.0 * (double)n * (double)tiles * GR_BM * GR_BN / (gram_ms * 1e-3) * 1e-12, iters, t_iter1 - t_iter0, t_small, now_s() - t_begin);
     }
-    if (!converged) {
-        char msg[256];
-        snprintf(msg, sizeof(msg), "PCA basis not converged: residual %.3e > tol %.3e after %d iterations", residual, tol, iters);
-        return mmidx_internal_fail(MMIDX_ERR_NOT_CONVERGED, msg);
-    }
+    if (!converged)
+        return mmidx_fail(MMIDX_ERR_NOT_CONVERGED, "PCA basis not converged: residual %.3e > tol %.3e after %d iterations", residual, tol, iters);
     return MMIDX_OK;
 }
 

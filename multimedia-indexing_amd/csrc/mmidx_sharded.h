@@ -85,17 +85,17 @@ RcclApi *rccl_api() {
         ok = why.empty();
     });
     if (!ok) {
-        fail(MMIDX_ERR_UNSUPPORTED, "RCCL is not available (%s): a sharded handle over distinct devices needs librccl.so.1", why.c_str());
+        mmidx_fail(MMIDX_ERR_UNSUPPORTED, "RCCL is not available (%s): a sharded handle over distinct devices needs librccl.so.1", why.c_str());
         return nullptr;
     }
     return &api;
 }
 
-#define NCCLCK(expr)                                                                                          \
+#define NCCL_CK(expr)                                                                                          \
     do {                                                                                                      \
         ncclResult_t r__ = (expr);                                                                            \
         if (r__ != ncclSuccess)                                                                               \
-            return fail(MMIDX_ERR_HIP, "%s failed: %s (%s:%d)", #expr, rccl_api()->GetErrorString(r__), __FILE__, __LINE__); \
+            return mmidx_fail(MMIDX_ERR_HIP, "%s failed: %s (%s:%d)", #expr, rccl_api()->GetErrorString(r__), __FILE__, __LINE__); \
     } while (0)
 
 // ---- small kernels of the sharded step -----------------------------------------------------------------------------
@@ -391,12 +391,12 @@ void shard_poison(ShardGroup *g) {
 #define SHARD_ALIVE(g)                                                                                                       \
     do {                                                                                                                     \
         if ((g)->broken)                                                                                                     \
-            return fail(MMIDX_ERR_HIP, "this sharded handle's communicators were aborted after a failed collective round: destroy it"); \
+            return mmidx_fail(MMIDX_ERR_HIP, "this sharded handle's communicators were aborted after a failed collective round: destroy it"); \
     } while (0)
 
 #define BARRIER(g)                                                                          \
     do {                                                                                    \
-        if (!(g)->bar.wait()) return fail(MMIDX_ERR_HIP, "shard barrier aborted: another shard failed"); \
+        if (!(g)->bar.wait()) return mmidx_fail(MMIDX_ERR_HIP, "shard barrier aborted: another shard failed"); \
     } while (0)
 
 // ---- collectives (in place), worker r, on the shard's stream ------------------------------------------------------------
@@ -407,7 +407,7 @@ int coll_allgather(ShardGroup *g, int r, void *buf, size_t bytes, bool second = 
     if (g->rccl) {
         RcclApi *R = rccl_api();
         BARRIER(g);  // (a worker that failed on the way never enqueues: its peers must not either, or their streams hang in the collective)
-        NCCLCK(R->AllGather((const char *)buf + (size_t)r * bytes, buf, bytes, ncclInt8, second ? g->comm2[(size_t)r] : g->comm[(size_t)r], st));
+        NCCL_CK(R->AllGather((const char *)buf + (size_t)r * bytes, buf, bytes, ncclInt8, second ? g->comm2[(size_t)r] : g->comm[(size_t)r], st));
         return MMIDX_OK;
     }
     g->pub[(size_t)r] = buf;
@@ -430,8 +430,8 @@ int coll_allreduce(ShardGroup *g, int r, void *buf, long long n, int op) {
     if (g->rccl) {
         RcclApi *R = rccl_api();
         BARRIER(g);
-        if (op == 0) NCCLCK(R->AllReduce(buf, buf, (size_t)n, ncclFloat64, ncclMin, g->comm[(size_t)r], st));
-        else NCCLCK(R->AllReduce(buf, buf, (size_t)n, ncclInt32, op == 1 ? ncclSum : ncclMax, g->comm[(size_t)r], st));
+        if (op == 0) NCCL_CK(R->AllReduce(buf, buf, (size_t)n, ncclFloat64, ncclMin, g->comm[(size_t)r], st));
+        else NCCL_CK(R->AllReduce(buf, buf, (size_t)n, ncclInt32, op == 1 ? ncclSum : ncclMax, g->comm[(size_t)r], st));
         return MMIDX_OK;
     }
     ShardBufs &B = g->buf[(size_t)r];
@@ -624,16 +624,16 @@ int shard_search_round(ShardGroup *g, int r, int k, int64_t per, const double *Q
             RcclApi *R = rccl_api();
             const size_t ne = (size_t)per * K1;
             BARRIER(g);
-            NCCLCK(R->GroupStart());
+            NCCL_CK(R->GroupStart());
             for (int o = 0; o < W; o++) {
-                NCCLCK(R->Send(B.pd.p + (size_t)o * ne, ne, ncclFloat64, o, g->comm[(size_t)r], st));
-                NCCLCK(R->Recv(B.rpd.p + (size_t)o * ne, ne, ncclFloat64, o, g->comm[(size_t)r], st));
-                NCCLCK(R->Send(B.pk.p + (size_t)o * ne, ne, ncclInt64, o, g->comm[(size_t)r], st));
-                NCCLCK(R->Recv(B.rpk.p + (size_t)o * ne, ne, ncclInt64, o, g->comm[(size_t)r], st));
-                NCCLCK(R->Send(B.pc.p + (size_t)o * per, (size_t)per, ncclInt32, o, g->comm[(size_t)r], st));
-                NCCLCK(R->Recv(B.rpc.p + (size_t)o * per, (size_t)per, ncclInt32, o, g->comm[(size_t)r], st));
+                NCCL_CK(R->Send(B.pd.p + (size_t)o * ne, ne, ncclFloat64, o, g->comm[(size_t)r], st));
+                NCCL_CK(R->Recv(B.rpd.p + (size_t)o * ne, ne, ncclFloat64, o, g->comm[(size_t)r], st));
+                NCCL_CK(R->Send(B.pk.p + (size_t)o * ne, ne, ncclInt64, o, g->comm[(size_t)r], st));
+                NCCL_CK(R->Recv(B.rpk.p + (size_t)o * ne, ne, ncclInt64, o, g->comm[(size_t)r], st));
+                NCCL_CK(R->Send(B.pc.p + (size_t)o * per, (size_t)per, ncclInt32, o, g->comm[(size_t)r], st));
+                NCCL_CK(R->Recv(B.rpc.p + (size_t)o * per, (size_t)per, ncclInt32, o, g->comm[(size_t)r], st));
             }
-            NCCLCK(R->GroupEnd());
+            NCCL_CK(R->GroupEnd());
         } else {  // in-process: fetch my slices from every shard's dense lists
             const size_t ne = (size_t)per * K1;
             HIPCK(hipStreamSynchronize(st));
@@ -717,10 +717,10 @@ int shard_search_round(ShardGroup *g, int r, int k, int64_t per, const double *Q
 
 int sharded_check_search(mmidx_index *h, int k) {
     ShardGroup *g = h->grp;
-    if (k < 1 || k > MMIDX_K_MAX) return fail(MMIDX_ERR_INVALID_ARG, "k must be in 1..%d (got %d)", MMIDX_K_MAX, k);
+    if (k < 1 || k > MMIDX_K_MAX) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "k must be in 1..%d (got %d)", MMIDX_K_MAX, k);
     int rc = check_ready(g->sub[0]);
     if (rc) return rc;
-    if (h->w < 1 || h->w > h->C) return fail(MMIDX_ERR_INVALID_ARG, "w = %d outside 1..%d (setW)", h->w, h->C);
+    if (h->w < 1 || h->w > h->C) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "w = %d outside 1..%d (setW)", h->w, h->C);
     return MMIDX_OK;
 }
 
@@ -1037,7 +1037,7 @@ int sharded_add_vectors(mmidx_index *h, int64_t n, const double *X, const double
     if (rc) return rc;
     if (n == 0) return MMIDX_OK;
     std::lock_guard<std::mutex> lk(g->call_mu);
-    if (sharded_total(h) + n > 2147483647LL) return fail(MMIDX_ERR_CAPACITY, "Maximum index capacity reached, no more vectors can be indexed!");
+    if (sharded_total(h) + n > 2147483647LL) return mmidx_fail(MMIDX_ERR_CAPACITY, "Maximum index capacity reached, no more vectors can be indexed!");
     // (loadCounter: read under the lock that serialises the adds -- two callers that let the library number their vectors must
     //  not see the same total; the plain handle reads its offset under add_mu likewise)
     if (iid0 == MMIDX_IID_AUTO) iid0 = (int32_t)sharded_total(h);
@@ -1107,21 +1107,21 @@ int sharded_add_codes(mmidx_index *h, int64_t n, const int32_t *iids, const int3
     ShardGroup *g = h->grp;
     if (n == 0) return MMIDX_OK;
     for (int64_t i = 0; i < n; i++)
-        if (cells[i] < 0 || cells[i] >= h->C) return fail(MMIDX_ERR_INVALID_ARG, "list id %d outside 0..%d", cells[i], h->C - 1);
+        if (cells[i] < 0 || cells[i] >= h->C) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "list id %d outside 0..%d", cells[i], h->C - 1);
     std::lock_guard<std::mutex> lk(g->call_mu);
-    if (sharded_total(h) + n > 2147483647LL) return fail(MMIDX_ERR_CAPACITY, "Maximum index capacity reached, no more vectors can be indexed!");
+    if (sharded_total(h) + n > 2147483647LL) return mmidx_fail(MMIDX_ERR_CAPACITY, "Maximum index capacity reached, no more vectors can be indexed!");
     // (a record that fails validation fails its shard's batch only: validate the code values here so that the call is all-or-nothing)
     const size_t tot = (size_t)n * h->m;
     if (h->code_bytes == 1) {
         if (h->ks < 256) {
             const signed char *c = (const signed char *)codes;
             for (size_t t = 0; t < tot; t++)
-                if ((int)c[t] + 128 >= h->ks) return fail(MMIDX_ERR_INVALID_ARG, "code value outside 0..%d (numProductCentroids): the batch was not added", h->ks - 1);
+                if ((int)c[t] + 128 >= h->ks) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "code value outside 0..%d (numProductCentroids): the batch was not added", h->ks - 1);
         }
     } else {
         const int16_t *c = (const int16_t *)codes;
         for (size_t t = 0; t < tot; t++)
-            if ((int)(uint16_t)c[t] >= h->ks) return fail(MMIDX_ERR_INVALID_ARG, "code value outside 0..%d (numProductCentroids): the batch was not added", h->ks - 1);
+            if ((int)(uint16_t)c[t] >= h->ks) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "code value outside 0..%d (numProductCentroids): the batch was not added", h->ks - 1);
     }
     return shard_run(g, [=](int r) -> int { return shard_append_owned(g, r, n, iids, 0, cells, (const unsigned char *)codes); });
 }
@@ -1233,7 +1233,7 @@ int sharded_locate(mmidx_index *h, int64_t n, const int32_t *iids, std::vector<i
             if (pos[(size_t)i] >= 0) where[(size_t)i] = r;
     }
     for (int64_t i = 0; i < n; i++)
-        if (where[(size_t)i] < 0) return fail(MMIDX_ERR_INVALID_ARG, "Id does not exist!");  // IVFPQ.java:803-805, :868-870
+        if (where[(size_t)i] < 0) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "Id does not exist!");  // IVFPQ.java:803-805, :868-870
     return MMIDX_OK;
 }
 
@@ -1344,7 +1344,7 @@ int sharded_set_option(mmidx_index *h, const char *name, int value) {
     ShardGroup *g = h->grp;
     const std::string n(name);
     if (n == "shard_exchange") {
-        if (value != 0 && g->n > 1 && !g->rccl) return fail(MMIDX_ERR_UNSUPPORTED, "shard_exchange = 1 needs RCCL (pairwise distinct devices)");
+        if (value != 0 && g->n > 1 && !g->rccl) return mmidx_fail(MMIDX_ERR_UNSUPPORTED, "shard_exchange = 1 needs RCCL (pairwise distinct devices)");
         g->exchange = value != 0;
         return MMIDX_OK;
     }
@@ -1413,16 +1413,16 @@ extern "C" {
 
 int mmidx_create_sharded(int kind, int D, int m, int ks, int C, int transform, const int32_t *perm, const double *rot, int n_dev,
                          const int *devs, mmidx_index **out) {
-    if (!out) return fail(MMIDX_ERR_INVALID_ARG, "null out pointer");
+    if (!out) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null out pointer");
     *out = nullptr;
     if (kind != MMIDX_KIND_IVFPQ)
-        return fail(MMIDX_ERR_UNSUPPORTED, "a sharded handle partitions inverted lists: IVFPQ only (a flat PQ index has one list)");
-    if (n_dev < 1 || n_dev > MMIDX_MAX_SHARDS || !devs) return fail(MMIDX_ERR_INVALID_ARG, "n_dev must be in 1..%d with a device list", MMIDX_MAX_SHARDS);
+        return mmidx_fail(MMIDX_ERR_UNSUPPORTED, "a sharded handle partitions inverted lists: IVFPQ only (a flat PQ index has one list)");
+    if (n_dev < 1 || n_dev > MMIDX_MAX_SHARDS || !devs) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "n_dev must be in 1..%d with a device list", MMIDX_MAX_SHARDS);
     const int ndev = mmidx_device_count();
-    if (ndev < 1) return fail(MMIDX_ERR_NO_DEVICE, "no HIP device: libmmidx_hip has no CPU fallback");
+    if (ndev < 1) return mmidx_fail(MMIDX_ERR_NO_DEVICE, "no HIP device: libmmidx_hip has no CPU fallback");
     bool distinct = true;
     for (int i = 0; i < n_dev; i++) {
-        if (devs[i] < 0 || devs[i] >= ndev) return fail(MMIDX_ERR_NO_DEVICE, "device %d outside 0..%d", devs[i], ndev - 1);
+        if (devs[i] < 0 || devs[i] >= ndev) return mmidx_fail(MMIDX_ERR_NO_DEVICE, "device %d outside 0..%d", devs[i], ndev - 1);
         for (int j = 0; j < i; j++) distinct = distinct && devs[i] != devs[j];
     }
     mmidx_index *h = new mmidx_index();
@@ -1450,15 +1450,15 @@ int mmidx_create_sharded(int kind, int D, int m, int ks, int C, int transform, c
         if (hipSetDevice(devs[r]) != hipSuccess || hipHostMalloc((void **)&g->buf[(size_t)r].pin_nflag, 64) != hipSuccess ||
             hipHostMalloc((void **)&g->buf[(size_t)r].pin_dest, MMIDX_MAX_SHARDS * sizeof(ShardDest)) != hipSuccess ||
             hipEventCreateWithFlags(&g->buf[(size_t)r].ev_b, hipEventDisableTiming) != hipSuccess)
-            return bail(fail(MMIDX_ERR_HIP, "shard %d: pinned word / event allocation failed", r));
+            return bail(mmidx_fail(MMIDX_ERR_HIP, "shard %d: pinned word / event allocation failed", r));
         hipStream_t s2 = nullptr;
-        if (hipStreamCreateWithFlags(&s2, hipStreamNonBlocking) != hipSuccess) return bail(fail(MMIDX_ERR_HIP, "shard %d: second stream", r));
+        if (hipStreamCreateWithFlags(&s2, hipStreamNonBlocking) != hipSuccess) return bail(mmidx_fail(MMIDX_ERR_HIP, "shard %d: second stream", r));
         g->st2.push_back(s2);
         for (int i = 0; i < 2; i++)
             if (hipEventCreateWithFlags(&g->buf[(size_t)r].ev_own[i], hipEventDisableTiming) != hipSuccess ||
                 hipEventCreateWithFlags(&g->buf[(size_t)r].ev_q[i], hipEventDisableTiming) != hipSuccess ||
                 hipEventCreateWithFlags(&g->buf[(size_t)r].ev_free[i], hipEventDisableTiming) != hipSuccess)
-                return bail(fail(MMIDX_ERR_HIP, "shard %d: event allocation failed", r));
+                return bail(mmidx_fail(MMIDX_ERR_HIP, "shard %d: event allocation failed", r));
         memset(g->buf[(size_t)r].pin_nflag, 0, 64);
     }
     // every shard stores pass B's lists into the owners' buffers and (in-process collectives) reads its peers': peer access
@@ -1481,10 +1481,10 @@ int mmidx_create_sharded(int kind, int D, int m, int ks, int C, int transform, c
         if (!R) return bail(MMIDX_ERR_UNSUPPORTED);
         g->comm.assign((size_t)n_dev, nullptr);
         ncclResult_t nr = R->CommInitAll(g->comm.data(), n_dev, devs);
-        if (nr != ncclSuccess) return bail(fail(MMIDX_ERR_HIP, "ncclCommInitAll over %d devices failed: %s", n_dev, R->GetErrorString(nr)));
+        if (nr != ncclSuccess) return bail(mmidx_fail(MMIDX_ERR_HIP, "ncclCommInitAll over %d devices failed: %s", n_dev, R->GetErrorString(nr)));
         g->comm2.assign((size_t)n_dev, nullptr);  // the query exchange's own communicators: it runs next to the main stream's collectives
         nr = R->CommInitAll(g->comm2.data(), n_dev, devs);
-        if (nr != ncclSuccess) return bail(fail(MMIDX_ERR_HIP, "ncclCommInitAll (second set) over %d devices failed: %s", n_dev, R->GetErrorString(nr)));
+        if (nr != ncclSuccess) return bail(mmidx_fail(MMIDX_ERR_HIP, "ncclCommInitAll (second set) over %d devices failed: %s", n_dev, R->GetErrorString(nr)));
         g->rccl = true;
         // Two communicators used concurrently per device can deadlock when the devices schedule the two collective kernels in different
         // orders, and this form has never run on more than one physical GPU: on a real multi-device handle everything goes through the
@@ -1497,7 +1497,7 @@ int mmidx_create_sharded(int kind, int D, int m, int ks, int C, int transform, c
             g->route_host = 1;
         }
     } else if (!g->peer_ok) {
-        return bail(fail(MMIDX_ERR_UNSUPPORTED, "shards on repeated devices use in-process collectives, which need peer access between all of them"));
+        return bail(mmidx_fail(MMIDX_ERR_UNSUPPORTED, "shards on repeated devices use in-process collectives, which need peer access between all of them"));
     }
     for (int r = 0; r < n_dev; r++) g->th.emplace_back(shard_worker, g, r);
     h->kind = kind;
@@ -1516,22 +1516,22 @@ int mmidx_create_sharded(int kind, int D, int m, int ks, int C, int transform, c
 }
 
 int mmidx_shard_count(const mmidx_index *h, int *n_out) {
-    if (!h || !n_out) return fail(MMIDX_ERR_INVALID_ARG, "null argument");
+    if (!h || !n_out) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null argument");
     *n_out = h->grp ? h->grp->n : 1;
     return MMIDX_OK;
 }
 
 int mmidx_shard_info(const mmidx_index *h, int shard, int *device_out, int64_t *size_out, int *uses_rccl_out) {
-    if (!h) return fail(MMIDX_ERR_INVALID_ARG, "null handle");
+    if (!h) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null handle");
     if (!h->grp) {
-        if (shard != 0) return fail(MMIDX_ERR_INVALID_ARG, "a plain handle has one shard");
+        if (shard != 0) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "a plain handle has one shard");
         if (device_out) *device_out = h->device;
         if (size_out) *size_out = total_size(h);
         if (uses_rccl_out) *uses_rccl_out = 0;
         return MMIDX_OK;
     }
     const ShardGroup *g = h->grp;
-    if (shard < 0 || shard >= g->n) return fail(MMIDX_ERR_INVALID_ARG, "shard %d outside 0..%d", shard, g->n - 1);
+    if (shard < 0 || shard >= g->n) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "shard %d outside 0..%d", shard, g->n - 1);
     if (device_out) *device_out = g->dev[(size_t)shard];
     if (size_out) *size_out = total_size(g->sub[(size_t)shard]);
     if (uses_rccl_out) *uses_rccl_out = g->rccl ? 1 : 0;
@@ -1540,15 +1540,15 @@ int mmidx_shard_info(const mmidx_index *h, int shard, int *device_out, int64_t *
 
 int mmidx_search_sliced_device(mmidx_index *h, int k, int64_t nq_per_shard, const double *const *dQ, int32_t *const *d_iid_out,
                                double *const *d_dist_out, int32_t *const *d_count_out) {
-    if (!h || !h->grp) return fail(MMIDX_ERR_INVALID_ARG, "mmidx_search_sliced_device needs a handle made by mmidx_create_sharded");
+    if (!h || !h->grp) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "mmidx_search_sliced_device needs a handle made by mmidx_create_sharded");
     ShardGroup *g = h->grp;
-    if (nq_per_shard < 0) return fail(MMIDX_ERR_INVALID_ARG, "nq < 0");
-    if (nq_per_shard > 0 && (!dQ || !d_iid_out || !d_dist_out || !d_count_out)) return fail(MMIDX_ERR_INVALID_ARG, "null argument");
+    if (nq_per_shard < 0) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "nq < 0");
+    if (nq_per_shard > 0 && (!dQ || !d_iid_out || !d_dist_out || !d_count_out)) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null argument");
     int rc = sharded_check_search(h, k);
     if (rc) return rc;
     if (nq_per_shard == 0) return MMIDX_OK;
     for (int r = 0; r < g->n; r++)
-        if (!dQ[r] || !d_iid_out[r] || !d_dist_out[r] || !d_count_out[r]) return fail(MMIDX_ERR_INVALID_ARG, "null slice pointer (shard %d)", r);
+        if (!dQ[r] || !d_iid_out[r] || !d_dist_out[r] || !d_count_out[r]) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null slice pointer (shard %d)", r);
     std::lock_guard<std::mutex> lk(g->call_mu);
     SHARD_ALIVE(g);
     int64_t cap = 0;
@@ -1587,11 +1587,11 @@ int mmidx_search_sliced_device(mmidx_index *h, int k, int64_t nq_per_shard, cons
 }
 
 int mmidx_add_vectors_sliced_device(mmidx_index *h, const int64_t *n_per_shard, const double *const *dX, int32_t iid0) {
-    if (!h || !h->grp) return fail(MMIDX_ERR_INVALID_ARG, "mmidx_add_vectors_sliced_device needs a handle made by mmidx_create_sharded");
-    if (!n_per_shard || !dX) return fail(MMIDX_ERR_INVALID_ARG, "null argument");
+    if (!h || !h->grp) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "mmidx_add_vectors_sliced_device needs a handle made by mmidx_create_sharded");
+    if (!n_per_shard || !dX) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null argument");
     int64_t n = 0;
     for (int r = 0; r < h->grp->n; r++) {
-        if (n_per_shard[r] < 0 || (n_per_shard[r] > 0 && !dX[r])) return fail(MMIDX_ERR_INVALID_ARG, "bad slice (shard %d)", r);
+        if (n_per_shard[r] < 0 || (n_per_shard[r] > 0 && !dX[r])) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "bad slice (shard %d)", r);
         n += n_per_shard[r];
     }
     return sharded_add_vectors(h, n, nullptr, dX, n_per_shard, nullptr, iid0, nullptr, nullptr);

@@ -109,7 +109,8 @@ def test_option_table_matches_header_and_callers():
     # points of their own (mmidx_vlad_set_option, mmidx_bow_set_option): their names are read from the sources the same way;
     # "no_such_option" is what tests pass to see the refusal.
     api = _read("multimedia-indexing_amd", "csrc", "mmidx_api.hip")
-    vlad = api[api.index("int mmidx_vlad_set_option("):]
+    vlad = _read("multimedia-indexing_amd", "csrc", "mmidx_frontend.hip")
+    vlad = vlad[vlad.index("int mmidx_vlad_set_option("):]
     aggregator = set(re.findall(r'== "(\w+)"', vlad[:vlad.index("\n}\n")] + _read("multimedia-indexing_amd", "csrc", "mmidx_bow.hip")))
     known = set(names) | shard_names | aggregator | {"no_such_option"}
     files = [os.path.join(ROOT, "bench.py"), os.path.join(ROOT, "multimedia-indexing_amd", "csrc", "mmidx_bow.hip")]

@@ -48,6 +48,36 @@ def test_vlad_raw_bit_exact(mi, oracle, nc, dl):
     agg.close()
 
 
+def test_vlad_single_centroid_vocabulary(mi, oracle):
+    """nc = 1: the assignment handle needs two centroids, so the vocabulary's slot stays empty and k_vlad serves it.  An empty
+    slot is no error of mmidx_vlad_create: no text is left behind (the error text is per thread, so the case runs in a thread of
+    its own, where no earlier test's refusal can be what is read)."""
+    import threading
+
+    rng = np.random.default_rng(1)
+    dl = 64
+    cb = rng.standard_normal((1, dl))
+    sets = [rng.standard_normal((n, dl)) for n in (0, 1, 70)]
+    res = {}
+
+    def run():
+        try:
+            agg = mi.VladAggregator(cb)
+            res["out"] = agg.aggregate_batch(sets)
+            res["err"] = mi.lib().mmidx_last_error()
+            agg.close()
+        except Exception as e:  # noqa: BLE001
+            res["exc"] = e
+
+    th = threading.Thread(target=run)
+    th.start()
+    th.join()
+    assert "exc" not in res, res.get("exc")
+    for i, s in enumerate(sets):
+        assert np.array_equal(res["out"][i], oracle.vlad_aggregate(cb, s)), i
+    assert res["err"] == b""
+
+
 def test_vlad_assignment_ties_first_centroid_wins(mi, oracle):
     """computeNearestCentroid (AFA:136-155) updates on `<` only: of several equally near centroids the FIRST wins.  Duplicate
     centroids and descriptors that coincide with centroids: the MFMA assignment cannot certify those and redoes them in fp64."""

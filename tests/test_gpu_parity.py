@@ -1523,6 +1523,101 @@ def test_linear_single_query_callers_are_combined(mi, oracle):
     ix.close()
 
 
+@pytest.mark.parametrize("n,k", [(300, 1), (300, 5), (16385, 1), (16385, 5), (5, 8)])
+def test_linear_distance_handback_matches_coarse_device(mi, oracle, n, k):
+    """Linear and mmidx_coarse_device share one loop (coarse top-w, then the distances of the selected cells).  n = 300: the
+    certified selection hands its distances back from its own list; n = 16385, the first size past the 16384 gate: the exact
+    kernels, distances gathered from the full matrix; k = n + 3: w = min(k, n), the slots past w keep -1 / +inf and count = n.
+    Ids and distance bits equal the oracle's Linear, and an IVFPQ handle with C = n, w = min(k, n) returns the same bytes."""
+    import torch
+
+    nat = importlib.import_module("multimedia-indexing_amd._native")
+    D, nq = 8, 3
+    rng = np.random.default_rng(1000 * n + k)
+    X = rng.standard_normal((n, D))
+    Q = np.concatenate([X[:1] + 0.01 * rng.standard_normal((1, D)), rng.standard_normal((nq - 1, D))])
+    w = min(k, n)
+    lin = mi.Linear(D, n)
+    lin.indexVectors([f"v{i}" for i in range(n)], X)
+    iids, dists, counts = lin.search_batch(k, Q)
+    assert iids.shape == dists.shape == (nq, k)
+    for qi, q in enumerate(Q):
+        rid, rd = oracle.linear_search(X, q, k)
+        assert counts[qi] == len(rid) == w
+        assert np.array_equal(iids[qi, :w], rid) and np.array_equal(dists[qi, :w], rd), qi
+    assert np.all(iids[:, w:] == -1) and np.all(np.isposinf(dists[:, w:]))
+    ix = mi.IVFPQ(D, 10, False, "", 1, 2, 0, n, 512)
+    ix.loadCoarseQuantizer(X)
+    ix.loadProductQuantizer(rng.standard_normal((1, 2, D)))
+    ix.setW(w)
+    dQ = torch.tensor(Q, dtype=torch.float64, device="cuda")
+    cells = torch.empty(nq, w, dtype=torch.int32, device="cuda")
+    cd = torch.empty(nq, w, dtype=torch.float64, device="cuda")
+    nat.check(mi.lib().mmidx_coarse_device(ix._h, nq, dQ.data_ptr(), cells.data_ptr(), cd.data_ptr(), None))
+    torch.cuda.synchronize()
+    assert np.array_equal(cells.cpu().numpy(), iids[:, :w]) and np.array_equal(cd.cpu().numpy(), dists[:, :w])
+    ix.close()
+    lin.close()
+
+
+def test_linear_four_callers_equal_one_call_of_four(mi):
+    """Four threads with one query each and the same k get the bytes that one call of the four queries returns."""
+    import threading
+
+    n, D, k = 300, 8, 5
+    rng = np.random.default_rng(4)
+    X = rng.standard_normal((n, D))
+    Q = rng.standard_normal((4, D))
+    lin = mi.Linear(D, n)
+    lin.indexVectors([f"v{i}" for i in range(n)], X)
+    want = lin.search_batch(k, Q)
+    got = [None] * 4
+    start = threading.Barrier(4)
+
+    def worker(t):
+        start.wait()
+        got[t] = lin.search_batch(k, Q[t:t + 1])
+
+    threads = [threading.Thread(target=worker, args=(t,)) for t in range(4)]
+    for th in threads:
+        th.start()
+    for th in threads:
+        th.join()
+    for part in range(3):
+        assert np.concatenate([g[part] for g in got]).tobytes() == want[part].tobytes()
+    lin.close()
+
+
+def test_argument_refusals_record_their_text(mi):
+    """One refusal per unit of the library (bag of words, VLAD, Linear, PCA, PCA learner, k-means): the status, and a text in
+    mmidx_last_error() that names the problem.  Nothing reaches the device.  Neighbouring cases expect different texts, so a
+    text left over from the call before does not pass."""
+    import ctypes as C
+
+    nat = importlib.import_module("multimedia-indexing_amd._native")
+    L = mi.lib()
+    buf = np.zeros(16)
+    out = C.c_void_p()
+    lin = mi.Linear(4, 8)
+    lin.indexVectors(["a"], np.zeros((1, 4)))
+    i32 = np.zeros(4, np.int32)
+    cases = [
+        ("mmidx_bow_create", lambda: L.mmidx_bow_create(4, 2, 0, buf.ctypes.data, 0, C.byref(out)), "k = 0 must be >= 1"),
+        ("mmidx_vlad_aggregate", lambda: L.mmidx_vlad_aggregate(None, 1, i32.ctypes.data, buf.ctypes.data, buf.ctypes.data), "null handle"),
+        ("mmidx_linear_search", lambda: L.mmidx_linear_search(lin._h, 0, 1, buf.ctypes.data, i32.ctypes.data, buf.ctypes.data, i32.ctypes.data),
+         "k must be positive"),
+        ("mmidx_pca_project", lambda: L.mmidx_pca_project(None, 1, buf.ctypes.data, buf.ctypes.data), "null handle"),
+        ("mmidx_pca_learn_create", lambda: L.mmidx_pca_learn_create(5, 10, 3, 0, C.byref(out)), "More components requested"),
+        # (before the units shared one error function this refusal returned its status and no text)
+        ("mmidx_kmeans", lambda: L.mmidx_kmeans(0, 0, 4, 2, 5, 1, 0, buf.ctypes.data, None, buf.ctypes.data, None, None, None, None), "k-means"),
+    ]
+    for name, call, text in cases:
+        assert call() == nat.ERR_INVALID_ARG, name
+        msg = L.mmidx_last_error().decode()
+        assert msg and text in msg, (name, msg)
+    lin.close()
+
+
 def test_concurrent_reader_threads(mi, oracle):
     """computeNearestNeighbors is not synchronized in the reference (ASS:281-291): several threads may query one index.
     The native host-pointer search queues them on a per-handle lock; every thread must get its own right answer."""

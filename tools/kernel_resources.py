@@ -3,6 +3,9 @@
 
     hipcc --offload-arch=gfx950 ... -c mmidx_api.hip -o /tmp/x.o -Rpass-analysis=kernel-resource-usage 2> res.txt
     python tools/kernel_resources.py res.txt
+
+A kernel lives in the one unit that includes its header: the search path in mmidx_api.hip, K7 / K8 (k_pca_project, k_vlad*) in
+mmidx_frontend.hip, the others in mmidx_bow.hip, mmidx_learn.hip, mmidx_pca_learn.hip and mmidx_probe.hip.
 """
 import re
 import sys
