@@ -22,3 +22,41 @@ __device__ __forceinline__ u32 wave_incl_scan_u32(u32 x) {
     return v;
 }
 __device__ __forceinline__ u32 wave_read_u32(u32 x, int l) { return (u32)__builtin_amdgcn_readlane((int)x, l); }
+
+// ------------------------------------------------------------------------------------------------
+// The certificate of the coarse and assignment filters, written once (derivation: DESIGN.md 5.1).
+//   d~ = |c|^2 + |x|^2 - 2 S,  S = the filter's fp32 dot product of the row x and the centroid c;  claim: |d~ - d| <= eps.
+// Every kernel that decides on d~ (K1d, K1f and its front ends, K6a, K6a', K8'') takes eps from here and certifies a row only
+// where filter_norms_usable() holds, so the copies cannot drift apart.
+//   xnorm, xn2: |x| and |x|^2 (rounded up);  cnorm_max, cn2_max: the largest |c| and |c|^2 (rounded up).
+//
+// filter_underflow_eps: the ABSOLUTE part.  The relative terms below assume that no fp32 (or bf16) result leaves the normal range;
+// one that does carries an error of up to one subnormal step (gradual underflow) or up to the smallest normal number 2^-126 (a unit
+// that flushes).  Which of the two a conversion, a matrix-core product or a VALU operation applies is not something the kernels
+// control or the documentation settles for every step, so the bound takes the larger, U = 2^-126, per operation:
+//   elements: fl32(x_j), its bf16 head and its bf16 tail, three roundings, |x_j - (xh_j + xl_j)| <= 2^-16 |x_j| + 3 U, so the dot
+//             product moves by at most 3.01 U (sum |c_j| + sum |x_j|) <= 3.01 U sqrt(Dk) (|c| + |x|), twice that in d~: 8 U sqrt(Dk) sumn
+//             (the fp32 dot product of K1c / K6a rounds each element once: a third of it);
+//   products and partial sums: at most 3 Dk products and 3 Dk additions, U each, doubled in d~: 12 Dk U;
+//   the epilogue: two norm copies, the operations that combine them with S, the stored value, borrowed mantissa bits: 16 U.
+// At ordinary magnitudes the term is below half a unit in the last place of eps: the certified sets do not change.
+__device__ __forceinline__ double filter_underflow_eps(int Dk, double sumn) {
+    return (12.0 * (double)Dk + 16.0 + 8.0 * sqrt((double)Dk) * sumn) * 0x1p-126;
+}
+// bf16 head / tail split, three matrix-core products accumulated in fp32 over Dp padded dimensions (K1e, K6a', K8'');
+// epi: the epilogue's relative roundings -- 2^-21 (K6a', K8''), 2^-21 + 2^-20 (K1e: three mantissa bits carry a position)
+__device__ __forceinline__ double filter_eps_split16(int Dp, double epi, double xnorm, double xn2, double cnorm_max, double cn2_max) {
+    const double sumn = cnorm_max + xnorm;
+    return (2.0 * 3.1 * 0x1p-16 * xnorm * cnorm_max + 2.0 * (3.0 * (double)Dp + 16.0) * 0x1p-22 * xnorm * cnorm_max +
+            1e-12 * (cn2_max + xn2) + epi * sumn * sumn + filter_underflow_eps(Dp, sumn)) * (1.0 + 1e-9);
+}
+// fp32 fused multiply-add chain over D dimensions, fp64 epilogue, d~ stored as fp32 (K1c / K1d, K6a)
+__device__ __forceinline__ double filter_eps_fp32(int D, double xnorm, double xn2, double cnorm_max, double cn2_max) {
+    const double sumn = cnorm_max + xnorm;
+    return (2.0 * (double)(D + 3) * 0x1p-24 * 1.01 * xnorm * cnorm_max + 1e-12 * (cn2_max + xn2) + 0x1p-23 * sumn * sumn +
+            filter_underflow_eps(D, sumn)) * (1.0 + 1e-9);
+}
+// A row is certified only while the fp32 quantities of the filter mean something: at (|c|max + |x|)^2 >= 1e37 a square or a dot
+// product may have overflowed (an infinite dot product would make a far centroid look nearest), and at <= 1e-37 every one of
+// them is subnormal or zero (the absolute term above already exceeds any gap there; the guard says so outright).  NaN fails both.
+__device__ __forceinline__ bool filter_norms_usable(double sumn) { return sumn * sumn < 1e37 && sumn * sumn > 1e-37; }

@@ -572,9 +572,8 @@ __global__ __launch_bounds__(256, 3) void k_vlad_fused(const double *__restrict_
                 const double xnd = __shfl(xrow[rt], 4 * fg + r);
                 if (fr == 0 && q < nd) {
                     const double xnorm = sqrt(xnd), sumn = cnorm_max + xnorm;
-                    const double eps = (2.0 * 3.1 * 0x1p-16 * xnorm * cnorm_max + 2.0 * (3.0 * (double)Dp + 16.0) * 0x1p-22 * xnorm * cnorm_max +
-                                        1e-12 * (cn_max + xnd) + 0x1p-21 * sumn * sumn) * (1.0 + 1e-9);
-                    const bool sure = ((double)m2 - (double)m1) > 2.0 * eps && sumn * sumn < 1e37;
+                    const double eps = filter_eps_split16(Dp, 0x1p-21, xnorm, xnd, cnorm_max, cn_max);
+                    const bool sure = ((double)m2 - (double)m1) > 2.0 * eps && filter_norms_usable(sumn);
                     nn[q] = ix < nc ? ix : nc - 1;
                     if (!sure) {
                         const int f = atomicAdd(flg, 1);

@@ -918,8 +918,8 @@ __global__ __launch_bounds__(MMIDX_BLOCK) void k_coarse_select_approx(const Appr
     //   fp32 store of d~: 2^-23 |d~| <= 2^-23 (|c| + |q|)^2
     const double qnorm = sqrt(qn);
     const double sumn = A.cnorm_max + qnorm;
-    const double eps = (2.0 * (double)(D + 3) * 0x1p-24 * 1.01 * qnorm * A.cnorm_max + 1e-12 * (A.cn_max + qn) +
-                        0x1p-23 * sumn * sumn) * (1.0 + 1e-9);
+    //   results that leave fp32's normal range: filter_underflow_eps (mmidx_device_util.h)
+    const double eps = filter_eps_fp32(D, qnorm, qn, A.cnorm_max, A.cn_max);
     float dt[PER];  // d~
     float lmin = __int_as_float(0x7f800000);
 #pragma unroll
@@ -967,7 +967,8 @@ __global__ __launch_bounds__(MMIDX_BLOCK) void k_coarse_select_approx(const Appr
         }
     }
     __syncthreads();
-    coarse_select_finish<PER>(A, q, (int)s_n, ckey, cidx, sel_k, sel_i, s_k, s_i);
+    // (outside the guard S may hold inf / NaN, or nothing but zeros: the exact row, as in K1f)
+    coarse_select_finish<PER>(A, q, filter_norms_usable(sumn) ? (int)s_n : MMIDX_CSEL_CAP + 1, ckey, cidx, sel_k, sel_i, s_k, s_i);
 }
 
 
@@ -1713,12 +1714,11 @@ __global__ __launch_bounds__(MMIDX_BLOCK, 2) void k_assign_gmin16_t(const __bf16
             if (fr == 0 && q < n) {
                 const double xnd = FROMX ? xnd_x : xn[q];
                 const double xnorm = sqrt(xnd), sumn = cnorm_max + xnorm;
-                const double eps = (2.0 * 3.1 * 0x1p-16 * xnorm * cnorm_max + 2.0 * (3.0 * (double)Dp + 16.0) * 0x1p-22 * xnorm * cnorm_max +
-                                    1e-12 * (cn_max + xnd) + 0x1p-21 * sumn * sumn) * (1.0 + 1e-9);
+                const double eps = filter_eps_split16(Dp, 0x1p-21, xnorm, xnd, cnorm_max, cn_max);
                 cell_out[q] = ix;
                 // (beyond 1e37 the fp32 quantities above may have overflowed -- an infinite dot product would even make a
-                //  far centroid look nearest: such vectors go to the exact kernel)
-                const bool sure = ((double)m2 - (double)m1) > 2.0 * eps && sumn * sumn < 1e37;  // inf - x = inf > ... when there is one centroid
+                //  far centroid look nearest -- and under 1e-37 they have all underflowed: such vectors go to the exact kernel)
+                const bool sure = ((double)m2 - (double)m1) > 2.0 * eps && filter_norms_usable(sumn);  // inf - x = inf > ... when there is one centroid
                 amb[q] = sure ? 0 : 1;
                 if (!sure && aidx) aidx[atomicAdd(acount, 1)] = (int32_t)q;  // (the list the exact kernel redoes: ~1e-4 of the vectors)
             }
@@ -1748,8 +1748,7 @@ __global__ __launch_bounds__(MMIDX_BLOCK) void k_coarse_select_grp(const ApproxS
     const double sumn = A.cnorm_max + qnorm;
     // (2^-21 (|c| + |q|)^2: fp32 copies of |c|^2, |q|^2 and the three fp32 operations of the epilogue, five roundings of at
     //  most 2^-24 each; + 2^-20: the three mantissa bits borrowed from the runner-up)
-    const double eps16 = (2.0 * 3.1 * 0x1p-16 * qnorm * A.cnorm_max + 2.0 * (3.0 * (double)A.Dp + 16.0) * 0x1p-22 * qnorm * A.cnorm_max +
-                          1e-12 * (A.cn_max + qn) + (0x1p-21 + 0x1p-20) * sumn * sumn) * (1.0 + 1e-9);
+    const double eps16 = filter_eps_split16(A.Dp, 0x1p-21 + 0x1p-20, qnorm, qn, A.cnorm_max, A.cn_max);
     const float inf = __int_as_float(0x7f800000);
     float m1[PERG], m2[PERG];
     int a1[PERG];
@@ -1788,7 +1787,7 @@ __global__ __launch_bounds__(MMIDX_BLOCK) void k_coarse_select_grp(const ApproxS
     __syncthreads();
     // any centroid with exact distance <= tau has d~ <= tau + eps16
     const double cut = ((double)s_tau4[0] + eps16) + eps16;
-    if (!(cut < (double)inf) || !(sumn * sumn < 1e37)) {  // (beyond 1e37 K1e's fp32 values may have overflowed: they are not looked at)
+    if (!(cut < (double)inf) || !filter_norms_usable(sumn)) {  // (beyond 1e37 K1e's fp32 values may have overflowed, under 1e-37 underflowed: they are not looked at)
         // magnitudes beyond fp32 / bf16 (inf or NaN in d~): nothing can be certified -> the exact row (overflow path)
         __syncthreads();
         coarse_select_finish<PER>(A, q, MMIDX_CSEL_CAP + 1, ckey, cidx, sel_k, sel_i, s_k, s_i);
@@ -1844,8 +1843,7 @@ __global__ __launch_bounds__(MMIDX_BLOCK) void k_coarse_front(const ApproxSel A)
     const double qnorm = sqrt(qn);
     const double sumn = A.cnorm_max + qnorm;
     // (the error bound of k_coarse_select_grp)
-    const double eps16 = (2.0 * 3.1 * 0x1p-16 * qnorm * A.cnorm_max + 2.0 * (3.0 * (double)A.Dp + 16.0) * 0x1p-22 * qnorm * A.cnorm_max +
-                          1e-12 * (A.cn_max + qn) + (0x1p-21 + 0x1p-20) * sumn * sumn) * (1.0 + 1e-9);
+    const double eps16 = filter_eps_split16(A.Dp, 0x1p-21 + 0x1p-20, qnorm, qn, A.cnorm_max, A.cn_max);
     const float inf = __int_as_float(0x7f800000);
     float m1[GPL], ry[GPL];
     float km[4] = {inf, inf, inf, inf};
@@ -1878,7 +1876,7 @@ __global__ __launch_bounds__(MMIDX_BLOCK) void k_coarse_front(const ApproxSel A)
     // any centroid with exact distance <= tau has d~ <= tau + eps16
     const double cut = ((double)tau + eps16) + eps16;
     u32 *list = A.clist + (size_t)q * MMIDX_CLIST;
-    if (!(cut < (double)inf) || !(sumn * sumn < 1e37)) {  // nothing can be certified: the exact row
+    if (!(cut < (double)inf) || !filter_norms_usable(sumn)) {  // nothing can be certified: the exact row
         if (lane == 0) list[0] = MMIDX_CSEL_CAP + 1;
         return;
     }
@@ -1933,8 +1931,7 @@ __global__ __launch_bounds__(64, 4) void k_coarse_front_sel(const ApproxSel A) {
     const double qn = A.qn[q];
     const double qnorm = sqrt(qn);
     const double sumn = A.cnorm_max + qnorm;
-    const double eps16 = (2.0 * 3.1 * 0x1p-16 * qnorm * A.cnorm_max + 2.0 * (3.0 * (double)A.Dp + 16.0) * 0x1p-22 * qnorm * A.cnorm_max +
-                          1e-12 * (A.cn_max + qn) + (0x1p-21 + 0x1p-20) * sumn * sumn) * (1.0 + 1e-9);
+    const double eps16 = filter_eps_split16(A.Dp, 0x1p-21 + 0x1p-20, qnorm, qn, A.cnorm_max, A.cn_max);
     const float inf = __int_as_float(0x7f800000);
     u32 *list = A.clist + (size_t)q * MMIDX_CLIST;
     u32 n = 0;  // wave-uniform
@@ -1980,7 +1977,7 @@ __global__ __launch_bounds__(64, 4) void k_coarse_front_sel(const ApproxSel A) {
         }
         CFS_TICK(1);
         const double cut = ((double)tau + eps16) + eps16;
-        if (!(cut < (double)inf) || !(sumn * sumn < 1e37)) {  // nothing can be certified: the exact row
+        if (!(cut < (double)inf) || !filter_norms_usable(sumn)) {  // nothing can be certified: the exact row
             if (lane == 0) {
                 list[0] = MMIDX_CSEL_CAP + 1;
                 A.defer[1 + atomicAdd(A.defer, 1u)] = (u32)q;
@@ -4557,9 +4554,9 @@ __global__ __launch_bounds__(MMIDX_BLOCK) void k_assign_approx(const float *__re
         if ((lane & 15) == 0 && v < n) {
             const double xnorm = sqrt(xnr[r]);
             const double sumn = cnorm_max + xnorm;
-            const double eps = (2.0 * (double)(D + 3) * 0x1p-24 * 1.01 * xnorm * cnorm_max + 1e-12 * (cn_max + xnr[r]) +
-                                0x1p-23 * sumn * sumn) * (1.0 + 1e-9);
-            const bool ok = ((double)m2[r] - (double)m1[r]) > 2.0 * eps;  // inf - x = inf > ... when C == 1
+            const double eps = filter_eps_fp32(D, xnorm, xnr[r], cnorm_max, cn_max);
+            // (outside the guard an fp32 dot product may be infinite -- d~ = -inf would certify a far centroid -- or all of them zero)
+            const bool ok = ((double)m2[r] - (double)m1[r]) > 2.0 * eps && filter_norms_usable(sumn);  // inf - x = inf > ... when C == 1
             cell_out[v] = i1[r];
             amb[v] = ok ? 0 : 1;
         }

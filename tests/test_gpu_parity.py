@@ -1820,7 +1820,7 @@ def test_randomised_differential_fuzz():
 
 
 @pytest.mark.parametrize("D,m", [(64, 8), (256, 16)])
-@pytest.mark.parametrize("scale,qscale", [(1e-25, 1.0), (1e-9, 1.0), (1e9, 1.0), (1e25, 1.0), (1.0, 1e6), (1e-160, 1.0), (1e140, 1.0)])
+@pytest.mark.parametrize("scale,qscale", [(1e-25, 1.0), (1e-9, 1.0), (1e9, 1.0), (1e25, 1.0), (1.0, 1e6), (1e-160, 1.0), (1e140, 1.0), (1e-19, 1.0), (1e-22, 1.0)])
 def test_mfma_pass_b_magnitudes(mi, oracle, scale, qscale, D, m):
     """K3m scales residuals and codebook by powers of two before the fp16 rounding (per item / per index): data 25 orders of
     magnitude away from 1, queries far outside the data (residuals a million times the codebook's scale: the exponent difference

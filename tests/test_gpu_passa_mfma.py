@@ -110,7 +110,7 @@ def test_passa_mfma_short_lists_and_redo(mi, oracle):
     ix.close()
 
 
-@pytest.mark.parametrize("scale", [1e-25, 1e9, 1e140])
+@pytest.mark.parametrize("scale", [1e-25, 1e9, 1e140, 1e-19, 1e-22])
 def test_passa_mfma_magnitudes(mi, oracle, scale):
     """The fp16 scaling of K3m applies to pass A as well: data far from 1 (and, at 1e140, squares beyond fp32: the rows are marked
     and redone exactly) -- never a dropped neighbour."""

@@ -109,7 +109,7 @@ def test_passa_q_more_candidates_than_the_block_takes(mi, oracle):
     ix.close()
 
 
-@pytest.mark.parametrize("scale", [1e-25, 1e-9, 1e9, 1e140])
+@pytest.mark.parametrize("scale", [1e-25, 1e-9, 1e9, 1e140, 1e-19, 1e-22])
 def test_passa_q_magnitudes(mi, oracle, scale):
     """The integer table is scaled per query by its own mean distance, so data far from 1 is served as long as fp32 can hold the
     table's inputs (1e-9, 1e9); beyond that (1e-25: squares under fp32's normal range; 1e140: beyond its largest number) the block's
