@@ -264,17 +264,53 @@ int mmidx_add_vectors_sliced_device(mmidx_index *h, const int64_t *n_per_shard, 
 /* ---- Linear: exhaustive exact search (J/datastructures/Linear.java; BASELINE config 1) ------------------------
  * add = indexVectorInternal (:111-122), search = computeNearestNeighborsInternal(k, double[]) (:138-163): exact
  * sequential fp64 squared distances, bounded-queue order and ties, ids = insertion order; get_vector = getVector
- * (:253-263).  The vectors go through the coarse-stage kernels as if they were centroids (same arithmetic, same
- * queue rule). */
+ * (:253-263).  The vectors live in HBM in arrival order; an append moves and prepares the new rows only.  While
+ * n <= 16384 and k + 1 <= 256 a search is the certified coarse stage of a hidden index handle whose "centroids" the
+ * vectors are; beyond that it is the certified scan of csrc/mmidx_linear_scan.h: a matrix-core filter
+ * with an error bound, exact fp64 for the survivors, and the exact path (fp64 distances to every row + the bounded
+ * queue's selection) for the queries the scan hands back -- a tie between the k-th and (k + 1)-th distance, norms
+ * outside the filter's range, a full survivor list.  Every path returns the reference's bits.
+ *   mmidx_linear_add_device      indexVectorInternal (:111-122) for n rows already in the handle's HBM
+ *   mmidx_linear_search_device   computeNearestNeighborsInternal(k, double[]) (:138-163) on device pointers: ids [nq][k]
+ *                                (-1 beyond the count), distances [nq][k] (+inf beyond it), counts [nq]; asynchronous on
+ *                                `stream` except for one read-back per call (the number of handed-back queries)
+ *   mmidx_linear_search_ids      computeNearestNeighborsInternal(k, int iid) (:181-184): the stored vector is the query;
+ *                                host arrays, the rows are gathered on the device
+ *   mmidx_linear_copy_rows_device  rows iid0 .. iid0+n-1 into a device buffer (the walk of IndexTransformation.java:113-122)
+ *   mmidx_linear_set_option      switches for measurements and tests; none changes a result.  An unknown name is
+ *                                MMIDX_ERR_INVALID_ARG.
+ *        "exact" = 1       every search beyond the small path goes through the exact path
+ *        "mfma_qcap" = n   capacity of the scan's survivor record list (0 = sized from the call)
+ *        "debug_sync" = 1  stage times in the stats (HIP events, one wait per segment)
+ *   mmidx_linear_get_stats       figures of the last search (and of the last add: uploaded_rows) */
 typedef struct mmidx_linear mmidx_linear;
+typedef struct mmidx_linear_stats {
+    int32_t path;          /* what served the last search: 1 coarse stage (small index), 2 exact, 3 scan */
+    int32_t segments;      /* sweep launches of the scan */
+    int64_t rows_scanned;  /* rows the scan went over (seed included), summed over its rounds of queries */
+    int64_t survivors;     /* (query, row) records verified exactly */
+    int64_t redo_queries;  /* queries the scan handed back to the exact path */
+    int64_t uploaded_rows; /* rows the last add moved and produced side data for */
+    double scan_ms, verify_ms; /* sweep / verification + pool reduction, only with "debug_sync" */
+} mmidx_linear_stats;
 int mmidx_linear_create(int D, int64_t capacity, int device, mmidx_linear **out);
 int mmidx_linear_destroy(mmidx_linear *l);
 int mmidx_linear_add(mmidx_linear *l, int64_t n, const double *X);
+int mmidx_linear_add_device(mmidx_linear *l, int64_t n, const double *dX, void *stream);
 int mmidx_linear_size(const mmidx_linear *l, int64_t *n_out);
 int mmidx_linear_get_dim(const mmidx_linear *l, int *D_out); /* vectorLength of the handle (bindings check array lengths against it) */
 int mmidx_linear_get_vector(const mmidx_linear *l, int64_t iid, double *out);
 int mmidx_linear_search(mmidx_linear *l, int k, int64_t nq, const double *Q, int32_t *iid_out, double *dist_out,
                         int32_t *count_out);
+int mmidx_linear_search_device(mmidx_linear *l, int k, int64_t nq, const double *dQ, int32_t *d_iid_out,
+                               double *d_dist_out, int32_t *d_count_out, void *stream);
+/* computeNearestNeighborsInternal(k, int iid), Linear.java:181-184: the stored vector is the query */
+int mmidx_linear_search_ids(mmidx_linear *l, int k, int64_t nq, const int32_t *iids, int32_t *iid_out,
+                            double *dist_out, int32_t *count_out);
+/* rows iid0 .. iid0+n-1 into a device buffer (the walk of IndexTransformation.java:113-122) */
+int mmidx_linear_copy_rows_device(mmidx_linear *l, int64_t iid0, int64_t n, double *d_out, void *stream);
+int mmidx_linear_set_option(mmidx_linear *l, const char *name, int value);
+int mmidx_linear_get_stats(mmidx_linear *l, mmidx_linear_stats *out);
 
 /* ---- codebook learning (J/visual/quantization/AbstractQuantizerLearning.java:39-81) ------
  * k-means on the GPU in place of Weka's SimpleKMeans, which the reference calls with setSeed(seed),

@@ -45,6 +45,11 @@ class Stats(C.Structure):
                 ("passa_mfma_sweep2_ms", C.c_double), ("passa_mfma_verify_ms", C.c_double)]
 
 
+class LinearStats(C.Structure):
+    _fields_ = [("path", C.c_int32), ("segments", C.c_int32), ("rows_scanned", C.c_int64), ("survivors", C.c_int64),
+                ("redo_queries", C.c_int64), ("uploaded_rows", C.c_int64), ("scan_ms", C.c_double), ("verify_ms", C.c_double)]
+
+
 def build(force=False):
     """Compile the HIP library for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
     # make decides what is stale, from the header lists the compiler writes; a fixed job count, never the machine's CPU count
@@ -118,6 +123,12 @@ SIGNATURES = {
     "mmidx_linear_size": (C.c_int, [_vp, C.POINTER(C.c_int64)]),
     "mmidx_linear_get_vector": (C.c_int, [_vp, C.c_int64, _dp]),
     "mmidx_linear_search": (C.c_int, [_vp, C.c_int, C.c_int64, _dp, _i32p, _dp, _i32p]),
+    "mmidx_linear_add_device": (C.c_int, [_vp, C.c_int64, _dp, _vp]),
+    "mmidx_linear_search_device": (C.c_int, [_vp, C.c_int, C.c_int64, _dp, _i32p, _dp, _i32p, _vp]),
+    "mmidx_linear_search_ids": (C.c_int, [_vp, C.c_int, C.c_int64, _i32p, _i32p, _dp, _i32p]),
+    "mmidx_linear_copy_rows_device": (C.c_int, [_vp, C.c_int64, C.c_int64, _dp, _vp]),
+    "mmidx_linear_set_option": (C.c_int, [_vp, C.c_char_p, C.c_int]),
+    "mmidx_linear_get_stats": (C.c_int, [_vp, C.POINTER(LinearStats)]),
     "mmidx_vectorize": (C.c_int, [_vp, _vp, C.c_int64, _vp, _dp, _dp]),
     "mmidx_vectorize_device": (C.c_int, [_vp, _vp, C.c_int64, _vp, _dp, C.c_int, _dp, _vp]),
     "mmidx_kmeans_device": (C.c_int, [C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, _dp, _dp, _dp, _i32p, _dp,

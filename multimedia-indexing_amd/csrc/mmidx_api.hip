@@ -1957,6 +1957,31 @@ int launch_scan_grouped_flat(mmidx_index *h, const ScanParams &P, const SearchPl
     return launch_grouped_common(h, S, P, pl, nch, 1, npairs, st, nq, flat_lut);
 }
 
+// K1b on a distance matrix dist[nq][C]: the w nearest of every row with the bounded queue's semantics (run_coarse's exact
+// path, and Linear's through mmidx_internal_select_topw)
+int launch_coarse_select(const double *dist, int C, int w, int64_t nq, int32_t *d_cells, hipStream_t st) {
+    const size_t lds = (size_t)(w + 1) * 12 + 16;
+    if (lds > 64 * 1024) return mmidx_fail(MMIDX_ERR_UNSUPPORTED, "w = %d too large", w);
+    const bool fast = C >= MMIDX_BLOCK && w + 1 <= MMIDX_BLOCK && C <= 64 * MMIDX_BLOCK;
+    const size_t flds = (size_t)MMIDX_CSEL_CAP * 12 + (size_t)(w + 1) * 12 + 16;
+    if (fast && C <= 8 * MMIDX_BLOCK)
+        hipLaunchKernelGGL(k_coarse_select_fast<8>, dim3((unsigned)nq), dim3(MMIDX_BLOCK), flds, st, dist, C, w, d_cells);
+    else if (fast && C <= 32 * MMIDX_BLOCK)
+        hipLaunchKernelGGL(k_coarse_select_fast<32>, dim3((unsigned)nq), dim3(MMIDX_BLOCK), flds, st, dist, C, w, d_cells);
+    else if (fast)
+        hipLaunchKernelGGL(k_coarse_select_fast<64>, dim3((unsigned)nq), dim3(MMIDX_BLOCK), flds, st, dist, C, w, d_cells);
+    else if (C <= 8 * MMIDX_BLOCK)
+        hipLaunchKernelGGL(k_coarse_select_reg<8>, dim3((unsigned)nq), dim3(MMIDX_BLOCK), lds, st, dist, C, w, d_cells);
+    else if (C <= 32 * MMIDX_BLOCK)
+        hipLaunchKernelGGL(k_coarse_select_reg<32>, dim3((unsigned)nq), dim3(MMIDX_BLOCK), lds, st, dist, C, w, d_cells);
+    else if (C <= 64 * MMIDX_BLOCK)
+        hipLaunchKernelGGL(k_coarse_select_reg<64>, dim3((unsigned)nq), dim3(MMIDX_BLOCK), lds, st, dist, C, w, d_cells);
+    else
+        hipLaunchKernelGGL(k_coarse_select, dim3((unsigned)nq), dim3(MMIDX_BLOCK), lds, st, dist, C, w, d_cells);
+    HIPCK(hipGetLastError());
+    return MMIDX_OK;
+}
+
 int run_coarse(mmidx_index *h, int64_t nq, const double *dQ, int32_t *d_cells, hipStream_t st) {
     constexpr int QT = 8;
     HIPCK(h->ws_cdist.reserve((size_t)nq * h->C));
@@ -2099,26 +2124,7 @@ int run_coarse(mmidx_index *h, int64_t nq, const double *dQ, int32_t *d_cells, h
         hipLaunchKernelGGL(k_coarse_dist<1>, g1, dim3(MMIDX_BLOCK), 0, st, h->d_coarseT, dQ, h->ws_cdist.p, h->C, h->D, (int)nq);
     } else
         hipLaunchKernelGGL(k_coarse_dist<QT>, g1, dim3(MMIDX_BLOCK), 0, st, h->d_coarseT, dQ, h->ws_cdist.p, h->C, h->D, (int)nq);
-    const size_t lds = (size_t)(h->w + 1) * 12 + 16;
-    if (lds > 64 * 1024) return mmidx_fail(MMIDX_ERR_UNSUPPORTED, "w = %d too large", h->w);
-    const bool fast = h->C >= MMIDX_BLOCK && h->w + 1 <= MMIDX_BLOCK && h->C <= 64 * MMIDX_BLOCK;
-    const size_t flds = (size_t)MMIDX_CSEL_CAP * 12 + (size_t)(h->w + 1) * 12 + 16;
-    if (fast && h->C <= 8 * MMIDX_BLOCK)
-        hipLaunchKernelGGL(k_coarse_select_fast<8>, dim3((unsigned)nq), dim3(MMIDX_BLOCK), flds, st, h->ws_cdist.p, h->C, h->w, d_cells);
-    else if (fast && h->C <= 32 * MMIDX_BLOCK)
-        hipLaunchKernelGGL(k_coarse_select_fast<32>, dim3((unsigned)nq), dim3(MMIDX_BLOCK), flds, st, h->ws_cdist.p, h->C, h->w, d_cells);
-    else if (fast)
-        hipLaunchKernelGGL(k_coarse_select_fast<64>, dim3((unsigned)nq), dim3(MMIDX_BLOCK), flds, st, h->ws_cdist.p, h->C, h->w, d_cells);
-    else if (h->C <= 8 * MMIDX_BLOCK)
-        hipLaunchKernelGGL(k_coarse_select_reg<8>, dim3((unsigned)nq), dim3(MMIDX_BLOCK), lds, st, h->ws_cdist.p, h->C, h->w, d_cells);
-    else if (h->C <= 32 * MMIDX_BLOCK)
-        hipLaunchKernelGGL(k_coarse_select_reg<32>, dim3((unsigned)nq), dim3(MMIDX_BLOCK), lds, st, h->ws_cdist.p, h->C, h->w, d_cells);
-    else if (h->C <= 64 * MMIDX_BLOCK)
-        hipLaunchKernelGGL(k_coarse_select_reg<64>, dim3((unsigned)nq), dim3(MMIDX_BLOCK), lds, st, h->ws_cdist.p, h->C, h->w, d_cells);
-    else
-        hipLaunchKernelGGL(k_coarse_select, dim3((unsigned)nq), dim3(MMIDX_BLOCK), lds, st, h->ws_cdist.p, h->C, h->w, d_cells);
-    HIPCK(hipGetLastError());
-    return MMIDX_OK;
+    return launch_coarse_select(h->ws_cdist.p, h->C, h->w, nq, d_cells, st);
 }
 
 
@@ -4159,6 +4165,10 @@ int mmidx_internal_coarse_topw(mmidx_index *h, int w, int64_t nq, const double *
         }
     }
     return MMIDX_OK;
+}
+
+int mmidx_internal_select_topw(const double *d_dist, int C, int w, int64_t nq, int32_t *d_cells, hipStream_t st) {
+    return launch_coarse_select(d_dist, C, w, nq, d_cells, st);
 }
 
 int mmidx_internal_coarse_tables(const mmidx_index *h, MmidxCoarseTables *out) {

@@ -164,6 +164,9 @@ MMIDX_HIDDEN int mmidx_internal_coarse_tables(const mmidx_index *h, MmidxCoarseT
 // [nq][w] and, where asked for, their exact distances.  Sets the handle's w.  mmidx_coarse_device and Linear go through it.
 MMIDX_HIDDEN int mmidx_internal_coarse_topw(mmidx_index *h, int w, int64_t nq, const double *dQ, int32_t *d_cells, double *d_dist_or_null,
                                             hipStream_t st);
+// mmidx_api.hip: K1b alone -- the w nearest columns of every row of a device distance matrix d_dist[nq][C], bounded-queue order
+// and ties, cells [nq][w].  Linear's exact path goes through it.
+MMIDX_HIDDEN int mmidx_internal_select_topw(const double *d_dist, int C, int w, int64_t nq, int32_t *d_cells, hipStream_t st);
 // mmidx_frontend.hip: K7 on plain device pointers, Y[n][nc] = (X[n][ss] - mu[ss]) Vt[nc][ss]^T
 MMIDX_HIDDEN int mmidx_internal_gemm_nt(const double *X, const double *mu, const double *Vt, double *Y, long long n, int nc, int ss,
                                         void *stream);

@@ -543,9 +543,66 @@ class Linear(AbstractSearchStructure):
         n = int(counts[0])
         return iids[0, :n].copy(), dists[0, :n].copy()
 
+    def add_device(self, X):
+        """indexVectorInternal for the rows of a torch tensor [n][vectorLength] (float64, contiguous) already on the handle's
+        device; runs on torch's current stream.  The rows get the next internal ids (no external ids are mapped)."""
+        import torch
+
+        if X.dim() != 2 or X.shape[1] != self.vectorLength or X.dtype != torch.float64 or not X.is_contiguous():
+            raise MmidxError(N.ERR_WRONG_DIM, "The dimensionality of the vector is wrong!")
+        st = torch.cuda.current_stream(X.device).cuda_stream
+        N.check(N.lib().mmidx_linear_add_device(self._h, X.shape[0], X.data_ptr(), st))
+
+    def search_batch_device(self, k, Q):
+        """search_batch on a torch tensor [nq][vectorLength] (float64, contiguous) in HBM: (ids int32 [nq][k], distances
+        float64 [nq][k], counts int32 [nq]) as tensors on the same device, on torch's current stream."""
+        import torch
+
+        if Q.dim() != 2 or Q.shape[1] != self.vectorLength or Q.dtype != torch.float64 or not Q.is_contiguous():
+            raise MmidxError(N.ERR_WRONG_DIM, "The dimensionality of the vector is wrong!")
+        nq = Q.shape[0]
+        iids = torch.empty((nq, max(k, 1)), dtype=torch.int32, device=Q.device)
+        dists = torch.empty((nq, max(k, 1)), dtype=torch.float64, device=Q.device)
+        counts = torch.empty(nq, dtype=torch.int32, device=Q.device)
+        st = torch.cuda.current_stream(Q.device).cuda_stream
+        N.check(N.lib().mmidx_linear_search_device(self._h, k, nq, Q.data_ptr(), iids.data_ptr(), dists.data_ptr(), counts.data_ptr(), st))
+        return iids, dists, counts
+
+    def copy_rows_device(self, iid0, out):
+        """rows iid0 .. iid0 + len(out) - 1 into the torch tensor out [n][vectorLength] (float64, contiguous, in HBM)"""
+        import torch
+
+        if out.dim() != 2 or out.shape[1] != self.vectorLength or out.dtype != torch.float64 or not out.is_contiguous():
+            raise MmidxError(N.ERR_WRONG_DIM, "The dimensionality of the vector is wrong!")
+        st = torch.cuda.current_stream(out.device).cuda_stream
+        N.check(N.lib().mmidx_linear_copy_rows_device(self._h, int(iid0), out.shape[0], out.data_ptr(), st))
+        return out
+
+    def search_ids_batch(self, k, iids):
+        """computeNearestNeighborsInternal(k, int iid) for many ids at once (Linear.java:181-184): the stored vectors are
+        the queries, gathered on the device"""
+        q = np.ascontiguousarray(np.asarray(iids).reshape(-1), np.int32)
+        nq = q.shape[0]
+        out = np.full((nq, max(k, 1)), -1, np.int32)
+        dists = np.full((nq, max(k, 1)), np.inf, np.float64)
+        counts = np.zeros(nq, np.int32)
+        N.check(N.lib().mmidx_linear_search_ids(self._h, k, nq, q.ctypes.data, out.ctypes.data, dists.ctypes.data, counts.ctypes.data))
+        return out, dists, counts
+
     def computeNearestNeighborsInternalById(self, k, iid):
-        # Linear.java:181-186: the stored vector of iid is the query
-        return self.computeNearestNeighborsInternal(k, self.getVector(iid))
+        # Linear.java:181-186: the stored vector of iid is the query (it never leaves the device)
+        iids, dists, counts = self.search_ids_batch(k, [int(iid)])
+        n = int(counts[0])
+        return iids[0, :n].copy(), dists[0, :n].copy()
+
+    def set_option(self, name, value):
+        """"exact", "mfma_qcap", "debug_sync" (include/mmidx.h, Linear section)"""
+        N.check(N.lib().mmidx_linear_set_option(self._h, name.encode(), int(value)))
+
+    def get_stats(self):
+        s = N.LinearStats()
+        N.check(N.lib().mmidx_linear_get_stats(self._h, C.byref(s)))
+        return {f: getattr(s, f) for f, _ in s._fields_}
 
     def getVector(self, iid):
         """Linear.getVector, Linear.java:253-263"""

@@ -72,7 +72,20 @@ public class GpuLinear extends AbstractSearchStructure {
 	}
 
 	protected BoundedPriorityQueue<Result> computeNearestNeighborsInternal(int k, int iid) throws Exception {
-		return computeNearestNeighborsInternal(k, getVector(iid)); // Linear.java:181-186
+		// Linear.java:181-184: the stored vector is the query; it is read in HBM, not fetched from the BDB store
+		int[] iids = new int[k];
+		double[] dists = new double[k];
+		int[] count = new int[1];
+		MmidxNative.linearSearchIds(handle, k, 1, new int[] { iid }, iids, dists, count); // -> mmidx_linear_search_ids
+		BoundedPriorityQueue<Result> nn = new BoundedPriorityQueue<Result>(new Result(), k);
+		for (int i = count[0] - 1; i >= 0; i--)
+			nn.offer(new Result(iids[i], dists[i])); // worst first keeps the tie order
+		return nn;
+	}
+
+	/** measurement and test switches of the native Linear: "exact", "mfma_qcap", "debug_sync" */
+	public void setOption(String name, int value) throws Exception {
+		MmidxNative.linearSetOption(handle, name, value);
 	}
 
 	public double[] getVector(int iid) { // Linear.java:253-280 (disk-based branch)

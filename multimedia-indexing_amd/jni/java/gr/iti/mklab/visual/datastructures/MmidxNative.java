@@ -82,6 +82,13 @@ public final class MmidxNative {
 	public static native void linearSearch(long handle, int k, int nq, int vectorLength, double[] queries, int[] iidOut,
 			double[] distOut, int[] countOut) throws Exception;
 
+	/** computeNearestNeighborsInternal(k, int iid), Linear.java:181-184: the stored vectors are the queries */
+	public static native void linearSearchIds(long handle, int k, int nq, int[] iids, int[] iidOut, double[] distOut,
+			int[] countOut) throws Exception;
+
+	/** "exact", "mfma_qcap", "debug_sync" (include/mmidx.h, Linear section) */
+	public static native void linearSetOption(long handle, String name, int value) throws Exception;
+
 	/* ---- front end (mmidx_pca_*, mmidx_vlad_*, mmidx_vectorize) ---- */
 	public static native long pcaCreate(int numComponents, int sampleSize, boolean whitening, double[] means,
 			double[] eigenvalues, double[] components, int device) throws Exception;

@@ -428,6 +428,41 @@ done:
     (*env)->ReleaseIntArrayElements(env, countOut, cc, 0);
 }
 
+/* computeNearestNeighborsInternal(k, int iid), Linear.java:181-184: the stored vectors are the queries (they stay in HBM) */
+JNIEXPORT void JNICALL JFN(linearSearchIds)(JNIEnv *env, jclass c, jlong h, jint k, jint nq, jintArray iids, jintArray iidOut, jdoubleArray distOut,
+                                            jintArray countOut) {
+    jdouble *dd;
+    jint *qq, *ii, *cc;
+    (void)c;
+    if (nq < 0 || k < 1 || bad_len(env, iids, nq, 0, "iids") || bad_len(env, iidOut, (int64_t)nq * k, 0, "iidOut") ||
+        bad_len(env, distOut, (int64_t)nq * k, 0, "distOut") || bad_len(env, countOut, nq, 0, "countOut"))
+        return;
+    qq = (*env)->GetIntArrayElements(env, iids, NULL);
+    ii = (*env)->GetIntArrayElements(env, iidOut, NULL);
+    dd = (*env)->GetDoubleArrayElements(env, distOut, NULL);
+    cc = (*env)->GetIntArrayElements(env, countOut, NULL);
+    CHECK(mmidx_linear_search_ids(HL(h), k, nq, (const int32_t *)qq, (int32_t *)ii, dd, (int32_t *)cc));
+done:
+    (*env)->ReleaseIntArrayElements(env, iids, qq, JNI_ABORT);
+    (*env)->ReleaseIntArrayElements(env, iidOut, ii, 0);
+    (*env)->ReleaseDoubleArrayElements(env, distOut, dd, 0);
+    (*env)->ReleaseIntArrayElements(env, countOut, cc, 0);
+}
+
+JNIEXPORT void JNICALL JFN(linearSetOption)(JNIEnv *env, jclass c, jlong h, jstring name, jint value) {
+    const char *p;
+    (void)c;
+    if (!name) {
+        throw_msg(env, "java/lang/NullPointerException", "name");
+        return;
+    }
+    p = (*env)->GetStringUTFChars(env, name, NULL);
+    if (!p) return;
+    CHECK(mmidx_linear_set_option(HL(h), p, value));
+done:
+    (*env)->ReleaseStringUTFChars(env, name, p);
+}
+
 /* ---- front end: PCA projection (PCA.java:188-208, :257-318) and VLAD aggregation (VladAggregator.java:56-70,
  *      VladAggregatorMultipleVocabularies.java:84-101) ------------------------------------------------------------- */
 JNIEXPORT jlong JNICALL JFN(pcaCreate)(JNIEnv *env, jclass c, jint nc, jint ss, jboolean whitening, jdoubleArray means, jdoubleArray eig,
