@@ -496,7 +496,17 @@ int mmidx_vlad_create(int nvocab, const int32_t *ncent, int dl, const double *co
  * AFA:136-155; flagged descriptors redone in fp64), then the ordered accumulation.  A/B and test switch (ABI version 6).
  * "two_pass" = 1 (ABI version 7): assignment and accumulation as two kernels (K8') also where the default one-kernel form K8''
  * (k_vlad_fused: 64-dimensional descriptors, vocabularies of <= 128 centroids -- one pass over the descriptors, no host
- * synchronisation inside mmidx_vlad_aggregate_device) applies. */
+ * synchronisation inside mmidx_vlad_aggregate_device) applies.
+ * Envelope of "exact": the block keeps the codebook in LDS beside its lists,
+ *   ncent * dl * 8 + 2 * 4 * max(2, max_desc rounded up to even) + 4 * ((ncent + 2) & ~1) + 32 bytes <= 160 KiB,
+ * else the call returns MMIDX_ERR_UNSUPPORTED ("codebook N x DL plus M descriptors per image exceed the 160 KiB LDS") before any
+ * launch for that vocabulary, and the handle stays usable: 128 x 128 fits, 256 x 128 and 128 x 192 do not.
+ * The _device forms: d_desc_off[nimg + 1] holds ABSOLUTE row offsets into d_descs, so images i0 .. i0 + n of a batch are passed as
+ * (n, d_desc_off + i0) with the same d_descs; the forms that assign as a stage of their own read d_desc_off[nimg] back (one wait on
+ * `stream`) and assign rows 0 .. d_desc_off[nimg].  max_desc may be overstated (it sizes LDS lists only), never understated.
+ * Alignment: d_descs and d_out need the alignment of a double (8 bytes) and no more.  A d_descs that is also 16-byte aligned --
+ * any allocation's base, and every row offset from it when dl is even -- lets the one-kernel form K8'' and the assignment's
+ * single-chunk form load rows as double2; otherwise K8' with single-double loads serves the call, with identical results. */
 int mmidx_vlad_set_option(mmidx_vlad *v, const char *name, int value);
 int mmidx_vlad_destroy(mmidx_vlad *v);
 int mmidx_vlad_vector_length(const mmidx_vlad *v, int *len_out);

@@ -225,9 +225,10 @@ int mmidx_vlad_aggregate_device(mmidx_vlad *v, int64_t nimg, const int64_t *d_de
     long long ndesc = -1;  // descriptors of the launch (read back once when the assignment runs as its own stage)
     for (int i = 0; i < v->nvocab; i++) {
         const int nc = v->nc[(size_t)i];
-        if (!v->exact && !v->two_pass && v->asg[(size_t)i] && d_descs && v->dl == 64 && nc <= 128) {
+        if (!v->exact && !v->two_pass && v->asg[(size_t)i] && d_descs && v->dl == 64 && nc <= 128 && ((uintptr_t)d_descs & 15) == 0) {
             // K8'': one kernel, one pass over the descriptors in HBM, no host synchronisation (the flagged descriptors are redone by the
-            // image's own block): 64-dimensional descriptors, vocabularies of at most 128 centroids
+            // image's own block): 64-dimensional descriptors, vocabularies of at most 128 centroids.  It reads rows as double2, so a
+            // base that is only 8-byte aligned goes to K8', whose kernels read single doubles (as assign_device gates its FROMX form)
             MmidxCoarseTables a;
             int rct = mmidx_internal_coarse_tables(v->asg[(size_t)i], &a);
             if (rct) return rct;
