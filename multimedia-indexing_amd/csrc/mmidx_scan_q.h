@@ -64,7 +64,9 @@
 #define Q_CH 4  // independent lookup chains of the scan (2 / 4 / 8: 0.558 / 0.565 / 0.564 ms per 7525 groups -- no difference)
 #endif
 #ifndef Q_FR
-#define Q_FR 2  // codebook rows in flight per candidate (1 / 2 / 4: 0.567 / 0.550 / 0.556 ms per 7525 groups)
+#define Q_FR 2  // codebook rows in flight per candidate where a thread loads its own rows (DSUB = 16); measured at DSUB = 8 before the
+                // cooperative form took that width: 1 / 2 / 4: 0.567 / 0.550 / 0.556 ms per 7525 groups.  The cooperative form has ONE
+                // sub-quantizer round in flight (one tile per wave fits); two or four rounds through registers: 0.551 / 0.567 ms
 #endif
 
 struct QParams {
@@ -109,6 +111,7 @@ __device__ __forceinline__ u32 q_med3(u32 a, u32 b, u32 c) {
 }
 typedef float q_f2 __attribute__((ext_vector_type(2)));
 typedef float q_f4 __attribute__((ext_vector_type(4)));
+typedef double q_d2 __attribute__((ext_vector_type(2)));
 // packed fp32 (two queries per instruction): r - p.lo / r - p.hi in both halves, fused multiply-add, product
 __device__ __forceinline__ q_f2 q_pk_sub_lo(q_f2 r, q_f2 p) {
     q_f2 d;
@@ -600,18 +603,96 @@ __device__ __forceinline__ void q_scan_group(const QParams &QP, const int4 gd, u
     }
     const u32 ncand = first[G];
     if (ncand == 0) return;  // block-uniform
-    // ---- exact sums, a thread per candidate: d = sum_s [ sum_t (r[s dsub + t] - pq[s][code_s][t])^2 ], t then s ascending from 0.0.
-    //      Two candidates per thread side by side, their codes requested together, Q_FR codebook rows of each in flight ---------------
-    u64 *ckey = (u64 *)smem;  // [ncand] (the table is dead: every wave passed the barrier above after its last lookup)
-    {
-        const u32 ia = (u32)tid, ib = (u32)tid + NT, ic = (u32)tid + 2 * NT;
-        auto which = [&](const u32 idx) -> int {
-            int i = 0;
+    // ---- exact sums: d = sum_s [ sum_t (r[s dsub + t] - pq[s][code_s][t])^2 ], t then s ascending from 0.0, a lane per candidate and
+    //      256 candidates per pass.  The candidates' codebook rows are loaded COOPERATIVELY, sub-quantizer by sub-quantizer: a row of
+    //      DSUB doubles by LPR = DSUB / 2 neighbouring lanes, 16 bytes each, so that a wave's load instruction touches 64 / LPR rows
+    //      (at most as many cache lines) instead of 64 -- a quarter of the L1's look-ups at DSUB = 8 -- and by LDS-DMA
+    //      (global_load_lds_dwordx4) into a per-wave tile [64 rows][row], from which the lane that owns the candidate reads its row
+    //      (staging through registers and ds_write_b128 into a padded tile measured 0.551 ms per 7525 groups against the
+    //      thread-per-candidate form's 0.556 -- the stores' LDS cycles took the gain back --, the DMA 0.532 against 0.562).  The code bytes come from an LDS copy of the
+    //      wave's 64 codes.  A wave works on its own candidates and its own LDS: no block barrier inside.
+    //      LDS (the table is dead: every wave passed the barrier above after its last lookup): ckey [G * HKQ] u64, the codes
+    //      [256][MB], the four tiles [64][RB].  Where that does not fit in the table (DSUB = 16) a thread loads its own rows. ----
+    u64 *ckey = (u64 *)smem;  // [ncand]
+    constexpr int RB = DSUB * 8, LPR = RB / 16, RPL = LPR ? 64 / LPR : 0, MB = CodeVec<M, unsigned char>::WORDS * 4;
+    constexpr size_t XC = (size_t)G * HKQ * 8, XT = XC + (size_t)NT * MB;
+    constexpr bool COOP = RB % 16 == 0 && LPR >= 1 && 16 % LPR == 0 && XT + (size_t)WV * 64 * RB <= (size_t)M * 2048;
+    auto which = [&](const u32 idx) -> int {
+        int i = 0;
 #pragma unroll
-            for (int k = 1; k < G; k++) i += (idx >= first[k]) ? 1 : 0;
-            return i;
+        for (int k = 1; k < G; k++) i += (idx >= first[k]) ? 1 : 0;
+        return i;
+    };
+    auto entry_of = [&](const u32 idx, const int i) -> u32 { return cent[i * HKQ + (idx - (i == 0 ? first[0] : (i == 1 ? first[1] : (i == 2 ? first[2] : first[3]))))]; };
+    if constexpr (COOP) {
+        unsigned char *s_code = smem + XC + (size_t)wv * 64 * MB;  // this wave's [64][MB]
+        unsigned char *s_tile = smem + XT + (size_t)wv * 64 * RB;  // this wave's [64][RB]
+        const u32 row0 = (u32)lane / LPR, chunk = (u32)lane % LPR;
+        auto sums = [&](const u32 idx) {
+            const bool h = idx < ncand;
+            if (!__builtin_amdgcn_ballot_w64(h)) return;
+            const u32 ic = h ? idx : ncand - 1u;  // (a lane past the end: the last candidate's code and query, nothing written)
+            const int q = which(ic);
+            const u32 v = entry_of(ic, q);
+            {
+                CodeVec<M, unsigned char> cv;
+                cv.load(codes0 + (v & 0xFFFFFFu) * (u32)M);
+#pragma unroll
+                for (int i = 0; i < MB / 4; i++) ((u32 *)(s_code + (size_t)lane * MB))[i] = cv.wd[i];
+            }
+            __builtin_amdgcn_wave_barrier();
+            const q_d2 *tq = (const q_d2 *)(s_r + (size_t)q * D);  // (16-byte aligned: D and DSUB are even)
+            double d = 0.0;
+            // Load i of sub-quantizer s brings the rows of the wave's candidates i RPL .. i RPL + RPL - 1; lane l's 16 bytes land at
+            // tile + 1024 i + 16 l (the DMA's own layout: no pad possible).  A row is therefore stored ROTATED by rot(row) chunks and
+            // read back against the rotation: the 16 lanes of a ds_read_b128 group hit 16 different 16-byte slots, no bank conflict.
+            const u32 rot0 = (row0 / (16 / LPR)) % LPR, rotl = ((u32)lane / (16 / LPR)) % LPR;
+            const u32 srcoff = ((chunk + rot0) % LPR) * 16u;
+            // (the code bytes of a round are read together, one round ahead: they are back before the round's waits)
+            auto bytes = [&](u32 (&b)[LPR], const int s) {
+#pragma unroll
+                for (int i = 0; i < LPR; i++) b[i] = s_code[((u32)i * RPL + row0) * MB + (u32)s];
+            };
+            auto dma = [&](const u32 (&b)[LPR], const int s) {
+#pragma unroll
+                for (int i = 0; i < LPR; i++)
+                    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)((const char *)QP.pq + (((u32)s * 256u + b[i]) * (u32)RB + srcoff)),
+                                                     (__attribute__((address_space(3))) void *)(s_tile + i * 1024), 16, 0, 0);
+            };
+            u32 cb[LPR];
+            bytes(cb, 0);
+            dma(cb, 0);
+#pragma unroll 1
+            for (int s = 0; s < M; s++) {
+                q_d2 p2[LPR];
+                bytes(cb, s + 1 < M ? s + 1 : s);
+                __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): the rows of s are in the tile
+#pragma unroll
+                for (int c = 0; c < LPR; c++) p2[c] = *(const q_d2 *)(s_tile + (u32)lane * RB + (((u32)c - rotl) % LPR) * 16u);
+                __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): read, before the next rows may overwrite it
+                if (s + 1 < M) dma(cb, s + 1);
+                double a = 0.0;
+#pragma unroll
+                for (int c = 0; c < LPR; c++) {
+                    const q_d2 r = tq[s * LPR + c];
+                    const double f0 = r.x - p2[c].x, f1 = r.y - p2[c].y;
+                    a += f0 * f0;
+                    a += f1 * f1;
+                }
+                d = s == 0 ? a : d + a;
+            }
+            if (h) {
+                ckey[idx] = dkey(d);
+                if (v & 0x80000000u) atomicMax(s_max + q, dkey(d));  // evidence codes: at least K1 per query
+            }
         };
-        auto entry_of = [&](const u32 idx, const int i) -> u32 { return cent[i * HKQ + (idx - (i == 0 ? first[0] : (i == 1 ? first[1] : (i == 2 ? first[2] : first[3]))))]; };
+        sums((u32)tid);
+        sums((u32)tid + NT);
+        sums((u32)tid + 2 * NT);
+    } else {
+        // a thread per candidate, its own rows: Q_FR codebook rows in flight (the code bytes picked from a register array by the loop
+        // counter: a 16-byte scratch slot per candidate)
+        const u32 ia = (u32)tid, ib = (u32)tid + NT, ic = (u32)tid + 2 * NT;
         auto sum2 = [&](const u32 i0, const u32 i1) {  // candidates i0 and i1 (i1 may be past the end)
             const bool h0 = i0 < ncand, h1 = i1 < ncand;
             if (!__builtin_amdgcn_ballot_w64(h0)) return;
