@@ -30,6 +30,7 @@
 #include <mutex>
 #include <string>
 #include <limits>
+#include <type_traits>
 #include <vector>
 
 namespace {
@@ -606,12 +607,88 @@ int encode_device(mmidx_index *h, int64_t n, const double *dX, int32_t *d_cell, 
     return MMIDX_OK;
 }
 
-template <int M, typename CodeT, int SU, int NT = MMIDX_BLOCK, bool SDC = false, bool GLUT = false>
-int launch_scan_t(const ScanParams &P, dim3 grid, size_t lds, hipStream_t st) {
-    HIPCK(hipFuncSetAttribute((const void *)k_scan<M, CodeT, SU, NT, SDC, GLUT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL((k_scan<M, CodeT, SU, NT, SDC, GLUT>), grid, dim3(NT), lds, st, P);
+// MMIDX_DEBUG_SYNC=1: synchronise after every stage and report the first failing one
+#define DBG_SYNC(name)                                                                        \
+    do {                                                                                      \
+        if (h->sw.debug_sync) {                                                                  \
+            hipError_t e__ = hipStreamSynchronize(st);                                        \
+            fprintf(stderr, "[mmidx] %s: %s\n", name, hipGetErrorString(e__));               \
+            if (e__ != hipSuccess) return mmidx_fail(MMIDX_ERR_HIP, "%s failed: %s", name, hipGetErrorString(e__)); \
+        }                                                                                     \
+    } while (0)
+
+// ---- launching a kernel that sizes its dynamic LDS at run time ------------------------------------------------------------------
+// A kernel that addresses its table from LDS address 0 (byte_x8) must own no static LDS.  What a violation means is the caller's
+// choice: `decline` returns 1 (the chain falls back to another kernel family), `fail` fails the call with the kernel's name.
+enum class StaticLds { unchecked, decline, fail };
+
+// the guard (the attribute is read once per kernel) and the kernel's dynamic-LDS limit
+template <auto K>
+int prepare_launch(size_t lds, StaticLds guard, const char *name) {
+    if (guard != StaticLds::unchecked) {
+        static int static_lds = -1;
+        if (static_lds < 0) {
+            hipFuncAttributes fa{};
+            HIPCK(hipFuncGetAttributes(&fa, (const void *)K));
+            static_lds = (int)fa.sharedSizeBytes;
+        }
+        if (static_lds != 0)
+            return guard == StaticLds::decline ? 1 : mmidx_fail(MMIDX_ERR_UNSUPPORTED, "%s owns %d bytes of static LDS: its table is not at LDS address 0", name, static_lds);
+    }
+    HIPCK(hipFuncSetAttribute((const void *)K, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    return MMIDX_OK;
+}
+
+// a grid the caller chose
+template <auto K, class Params>
+int launch_grid(const Params &P, dim3 grid, int nt, size_t lds, hipStream_t st, StaticLds guard = StaticLds::unchecked, const char *name = "") {
+    if (const int rc = prepare_launch<K>(lds, guard, name)) return rc;
+    hipLaunchKernelGGL(K, grid, dim3((unsigned)nt), lds, st, P);
     HIPCK(hipGetLastError());
     return MMIDX_OK;
+}
+
+// a persistent grid: `blocks` of them (option "mfma_blocks"), or with blocks <= 0 as many as the occupancy allows on every CU; a
+// multiple of eight either way (the kernels map blocks to XCDs)
+template <auto K, class Params>
+int launch_persistent(const mmidx_index *h, const Params &P, int blocks, int nt, size_t lds, hipStream_t st, StaticLds guard = StaticLds::unchecked,
+                      const char *name = "") {
+    if (const int rc = prepare_launch<K>(lds, guard, name)) return rc;
+    if (blocks <= 0) {
+        int occ = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void *)K, nt, lds) != hipSuccess || occ < 1) {
+            (void)hipGetLastError();
+            occ = 1;
+        }
+        blocks = occ * std::max(h->num_cus, 8);
+    }
+    blocks = std::max(8, (blocks + 7) & ~7);
+    hipLaunchKernelGGL(K, dim3((unsigned)blocks), dim3((unsigned)nt), lds, st, P);
+    HIPCK(hipGetLastError());
+    return MMIDX_OK;
+}
+
+// ---- shape dispatch: the generic lambda f gets the compile-time shape as std::integral_constant arguments ------------------------
+// sub-quantizer width 4, 8 or 16 (every caller's gate admits no other)
+template <class F>
+auto for_dsub(int dsub, F &&f) {
+    if (dsub == 4) return f(std::integral_constant<int, 4>{});
+    if (dsub == 8) return f(std::integral_constant<int, 8>{});
+    return f(std::integral_constant<int, 16>{});
+}
+// K3m's and K3ma's shapes: NJ = D / 32 in {1, 2, 4} (build_mfma_tables) x DSUB; their verification kernels' M is NJ * 32 / DSUB
+template <class F>
+int for_nj_dsub(int nj, int dsub, F &&f) {
+    return for_dsub(dsub, [&](auto ds) {
+        if (nj == 4) return f(std::integral_constant<int, 4>{}, ds);
+        if (nj == 2) return f(std::integral_constant<int, 2>{}, ds);
+        return f(std::integral_constant<int, 1>{}, ds);
+    });
+}
+
+template <int M, typename CodeT, int SU, int NT = MMIDX_BLOCK, bool SDC = false, bool GLUT = false>
+int launch_scan_t(const ScanParams &P, dim3 grid, size_t lds, hipStream_t st) {
+    return launch_grid<k_scan<M, CodeT, SU, NT, SDC, GLUT>>(P, grid, NT, lds, st);
 }
 
 // su = codes per thread per segment (1 or 2); P.cap and lds sized for it
@@ -624,11 +701,7 @@ int launch_scan(const mmidx_index *h, const ScanParams &P, dim3 grid, size_t lds
         // 512-code segments, a chunk's partial sums fit the block's table slot
         if (!P.sdc_tt && !h->sw.no_split_table && h->code_bytes == 1 && h->ks == 256 && h->m == 128 && P.chunk <= h->m * h->ks &&
             l + (size_t)64 * 256 * 8 <= 160 * 1024) {
-            const size_t sl = l + (size_t)64 * 256 * 8;
-            HIPCK(hipFuncSetAttribute((const void *)k_scan_split<128, 512>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sl));
-            hipLaunchKernelGGL((k_scan_split<128, 512>), grid, dim3(512), sl, st, P);
-            HIPCK(hipGetLastError());
-            return MMIDX_OK;
+            return launch_grid<k_scan_split<128, 512>>(P, grid, 512, l + (size_t)64 * 256 * 8, st);
         }
         if (P.sdc_tt) return launch_scan_t<0, unsigned char, 2, MMIDX_BLOCK, true, true>(P, grid, l, st);
         if (h->code_bytes == 1) return launch_scan_t<0, unsigned char, 2, MMIDX_BLOCK, false, true>(P, grid, l, st);
@@ -799,23 +872,172 @@ int launch_scan_filtered(const mmidx_index *h, ScanParams P, const SearchPlan &p
     }
 }
 
-template <int M, int KS, int NT>
-int launch_hist_nt(const ScanParams &P, dim3 grid, size_t lds, hipStream_t st) {
-    if (KS == 256) {
-        // the KS = 256 kernel addresses its table from LDS address 0 (byte_x8): it must not own static LDS
-        static int static_lds = -1;
-        if (static_lds < 0) {
-            hipFuncAttributes fa{};
-            HIPCK(hipFuncGetAttributes(&fa, (const void *)k_scan_hist<M, KS, NT>));
-            static_lds = (int)fa.sharedSizeBytes;
-        }
-        if (static_lds != 0)
-            return mmidx_fail(MMIDX_ERR_UNSUPPORTED, "k_scan_hist owns %d bytes of static LDS: its table is not at LDS address 0", static_lds);
+// ---- the steps the launch chains share (K3h, K3q, K3ma, K3g, K3m, K3mk): a new chain is composed from these -----------------------
+// The hand-back list of a chain: the (pair or query, chunk) items its kernels could not finish, served by a tail launch behind them.
+// Carved from ws_fb (count in word 0) or from ws_gfb (word 0 is k_group_build's group count: count in word 1); the items start at
+// word 4, their chunk ids follow the nfb item slots.  The count lives on the device: normally 0, and the tail's blocks leave at once.
+struct HandBack {
+    u32 *count;
+    int32_t *items, *ch;
+    size_t nfb;
+    HandBack(const DevBuf<int32_t> &ws, int count_at, size_t n) : count((u32 *)(ws.p + count_at)), items(ws.p + 4), ch(ws.p + 4 + n), nfb(n) {}
+    template <class Params>
+    void put(Params &P) const {  // (ScanParams, GrpParams, MfmaParams: the producers' view)
+        P.fb_count = count;
+        P.fb_items = items;
+        P.fb_ch = ch;
     }
-    HIPCK(hipFuncSetAttribute((const void *)k_scan_hist<M, KS, NT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL((k_scan_hist<M, KS, NT>), grid, dim3(NT), lds, st, P);
+    void order(ScanParams &F, bool with_ch) const {
+        F.order = items;
+        F.n_order = (const int32_t *)count;
+        F.order_ch = with_ch ? ch : nullptr;
+    }
+    // pass B's tail: K3f's looping kernel alone over the items, with the scan parameters F of the chain's K3f form
+    int tail_filtered(const mmidx_index *h, ScanParams F, const SearchPlan &pl, hipStream_t st) const {
+        order(F, true);
+        F.n_items = (int)std::min<size_t>(nfb, (size_t)0x7fffff00);
+        F.xcd_remap = 0;
+        return launch_scan_filtered(h, F, pl, dim3((unsigned)F.n_items, 1), st, -1);
+    }
+    // pass A's tail: the exact kernel K3 with its own candidate buffer (pl.cap), one block per item slot
+    int tail_exact(const mmidx_index *h, ScanParams F, const SearchPlan &pl, hipStream_t st) const {
+        F.cap = pl.cap;
+        put(F);
+        order(F, F.ivf != 0);
+        F.n_items = (int)nfb;
+        return launch_scan(h, F, dim3((unsigned)nfb, 1), pl.lds, st);
+    }
+};
+
+// ws_fb for nfb items (search_batch_device reserves it and zeroes the header; a direct caller lands in the branch)
+int reserve_fb(mmidx_index *h, size_t nfb, hipStream_t st) {
+    if (h->ws_fb.cap < 2 * nfb + 4) {
+        HIPCK(h->ws_fb.reserve(2 * nfb + 4));
+        HIPCK(hipMemsetAsync(h->ws_fb.p, 0, 4 * sizeof(int32_t), st));
+    }
+    return MMIDX_OK;
+}
+
+// k_group_build: groups of <= G pairs of one list, from the sorted pairs' per-list counts and starts (ws_pcount / ws_pstart), into
+// ws_gdesc; ws_gfb gets the group count in word 0 and a HandBack of nfb items behind it.  nver / hint: where the kernel resets the
+// verified-codes figure and reports it to the host (pass B: d_counters + 7 and pin_hint + 1), or null (pass A).
+int build_groups(mmidx_index *h, int nlists, int G, long long npairs, size_t nfb, unsigned long long *nver, int32_t *hint, bool debug_clear, const char *stage,
+                 hipStream_t st) {
+    HIPCK(h->ws_gdesc.reserve((size_t)npairs / G + (size_t)nlists + 8));
+    HIPCK(h->ws_gfb.reserve(4 + 2 * nfb + 16));
+    if (debug_clear) HIPCK(hipMemsetAsync(h->ws_gfb.p, 0, (4 + 2 * nfb + 16) * sizeof(int32_t), st));
+    hipLaunchKernelGGL(k_group_build, dim3(1), dim3(1024), 0, st, h->ws_pcount.p, h->ws_pstart.p, nlists, G, h->ws_gdesc.p, h->ws_gfb.p, (u32 *)(h->ws_gfb.p + 1), nver,
+                       hint);
+    HIPCK(hipGetLastError());
+    DBG_SYNC(stage);
+    return MMIDX_OK;
+}
+int32_t *passb_hint(const mmidx_index *h) { return h->pin_hint ? h->pin_hint + 1 : nullptr; }
+
+// Pass A's (query, probe 0) pairs sorted by cell: ws_order, per-cell counts / starts / cursors in ws_pcount (zeroed by the caller's
+// k_step_init) / ws_pstart / ws_pcursor, the pair count at ws_pstart[C].  `scan` launches the chain's own prefix kernel between the
+// count and the scatter; the buffers it writes besides are the caller's to reserve first.
+template <class Scan>
+int sort_pairs_by_cell(mmidx_index *h, const ScanParams &P, long long nq, hipStream_t st, Scan &&scan) {
+    const int C = h->C;
+    HIPCK(h->ws_pcount.reserve((size_t)C + 1));
+    HIPCK(h->ws_pstart.reserve((size_t)C + 1));
+    HIPCK(h->ws_pcursor.reserve((size_t)C));
+    HIPCK(h->ws_order.reserve((size_t)nq * (size_t)P.w));  // (pass B's size: its reserve later must not reallocate under these launches)
+    const unsigned gq = (unsigned)((nq + 255) / 256);
+    hipLaunchKernelGGL(k_a1_pair_count, dim3(gq), dim3(256), 0, st, P.cells, P.w, (long long)nq, P.list_off, h->ws_pcount.p, C);
+    scan();
+    hipLaunchKernelGGL(k_a1_pair_scatter, dim3(gq), dim3(256), 0, st, P.cells, P.w, (long long)nq, P.list_off, h->ws_pstart.p, h->ws_pcursor.p, h->ws_order.p);
     HIPCK(hipGetLastError());
     return MMIDX_OK;
+}
+
+// The call's queries in transformed (permuted) order, once per launch chain: contiguous loads instead of 8-byte gathers; the
+// centroids' copy (d_coarseP) is built once per index.  S: any parameter block with Q / coarse / perm.  Needs h->d_perm.
+template <class Params>
+int use_permuted_queries(mmidx_index *h, Params &S, bool ivf, long long nq, hipStream_t st) {
+    HIPCK(h->ws_Qp.reserve((size_t)nq * h->D));
+    const long long tot = (long long)nq * h->D;
+    hipLaunchKernelGGL(k_permute_cols, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, S.Q, h->d_perm, h->ws_Qp.p, h->D, (long long)nq);
+    S.Q = h->ws_Qp.p;
+    if (ivf) S.coarse = h->d_coarseP;
+    S.perm = nullptr;
+    return MMIDX_OK;
+}
+
+// A group of n profiling events from a pool that grows on demand and is handed back by mmidx_get_stats (`used` = 0); null once the
+// pool holds cap_groups groups (the statistics then miss the call).  The group's first event is recorded on st unless the caller
+// says otherwise.
+int take_events(std::vector<hipEvent_t> &pool, size_t &used, size_t n, size_t cap_groups, hipStream_t st, hipEvent_t *&ev, bool record_first = true) {
+    ev = nullptr;
+    if (used + n > n * cap_groups) return MMIDX_OK;
+    while (pool.size() < used + n) {
+        hipEvent_t e;
+        HIPCK(hipEventCreate(&e));
+        pool.push_back(e);
+    }
+    ev = pool.data() + used;
+    used += n;
+    if (record_first) HIPCK(hipEventRecord(ev[0], st));
+    return MMIDX_OK;
+}
+
+// What K3m, K3mk (pass B) and K3ma (pass A) share behind the group build: the per-query workspaces, k_mfma_prep (thresholds and pool
+// counters as the launch finds them, cleared redo flags and control words) and the fields of MfmaParams that do not depend on the
+// chain.  qcap: pass B's survivor list, with the per-query histograms that go with it (k_mfma_prep clears them: 64 threads per
+// query); 0 for K3ma, which has neither.  hb: on ws_gfb, after build_groups.  The chain sets what is its own afterwards.
+int mfma_prepare(mmidx_index *h, MfmaParams &MP, const ScanParams &S, const SearchPlan &pl, const HandBack &hb, size_t qcap, int sub, int nsub, int nchunks_f,
+                 long long npairs, long long nq, hipStream_t st) {
+    const bool passb = qcap > 0;
+    if (passb) HIPCK(h->ws_ghist.reserve((size_t)nq * 256));
+    HIPCK(h->ws_T0.reserve((size_t)nq));
+    HIPCK(h->ws_redo.reserve((size_t)nq));
+    HIPCK(h->ws_psnap.reserve((size_t)nq));
+    HIPCK(h->ws_mfctl.reserve(64));
+    if (passb) HIPCK(h->ws_surv.reserve(qcap));
+    u32 *ghist = passb ? h->ws_ghist.p : nullptr;
+    hipLaunchKernelGGL(k_mfma_prep, dim3((unsigned)std::min<long long>(4096, ((passb ? nq * 64 : nq) + 255) / 256)), dim3(256), 0, st, (const int32_t *)h->ws_gfb.p, ghist,
+                       h->ws_redo.p, h->ws_mfctl.p, S.T, h->ws_T0.p, S.pool_cnt, h->ws_psnap.p, (long long)nq);
+    HIPCK(hipGetLastError());
+    MP.S = S;
+    MP.S.perm = nullptr;  // (rows in transformed order: use_permuted_queries, k_pair_rotate)
+    MP.pq16 = h->d_pq16;
+    MP.xn = h->xn.p;
+    MP.pq = h->d_pq;
+    MP.gdesc = h->ws_gdesc.p;
+    MP.n_groups = h->ws_gfb.p;
+    MP.sub = sub;
+    MP.nsub = nsub;
+    MP.ep = h->pq_ep;
+    MP.xmax = h->rmax;
+    MP.ghist = ghist;
+    MP.T0 = h->ws_T0.p;
+    MP.surv = passb ? h->ws_surv.p : nullptr;
+    MP.surv_cnt = h->ws_mfctl.p;
+    MP.surv_cap = (u32)std::min<size_t>(qcap, 0xFFFFFFF0u);
+    MP.redo = h->ws_redo.p;
+    MP.pool_snap = h->ws_psnap.p;
+    MP.work = h->ws_mfctl.p + 8;
+    hb.put(MP);
+    MP.fb_chunk = pl.chunk;
+    MP.fb_nchunks = std::max(nchunks_f, 1);
+    MP.npairs_flat = npairs;
+    MP.stat = (h->profiling == 1 || h->sw.debug_sync) ? (unsigned long long *)(h->d_counters + 3) : nullptr;
+    MP.nver = (unsigned long long *)(h->d_counters + 7);
+    return MMIDX_OK;
+}
+
+// k_mfma_redo: the queries a chain marked for redo get their pool back as the launch found it and their pairs go to the hand-back list
+int launch_mfma_redo(const MfmaParams &MP, long long npairs, long long nq, hipStream_t st) {
+    const long long span = std::max<long long>(npairs, nq);
+    hipLaunchKernelGGL(k_mfma_redo, dim3((unsigned)((span + 255) / 256)), dim3(256), 0, st, MP, (long long)nq);
+    HIPCK(hipGetLastError());
+    return MMIDX_OK;
+}
+
+template <int M, int KS, int NT>
+int launch_hist_nt(const ScanParams &P, dim3 grid, size_t lds, hipStream_t st) {
+    return launch_grid<k_scan_hist<M, KS, NT>>(P, grid, NT, lds, st, KS == 256 ? StaticLds::fail : StaticLds::unchecked, "k_scan_hist");  // (KS = 256: byte_x8)
 }
 
 template <int M>
@@ -850,10 +1072,8 @@ int launch_scan_hist(mmidx_index *h, ScanParams P, const SearchPlan &pl, dim3 gr
     const size_t lds = fixed + (size_t)cap * 4;
     if (lds > (whole_cu ? 160 * 1024 : 64 * 1024)) return 1;
     const size_t nfb = (size_t)grid.x * grid.y;
-    if (h->ws_fb.cap < 2 * nfb + 4) {  // (search_batch_device reserves and zeroes the header; a direct caller would land here)
-        HIPCK(h->ws_fb.reserve(2 * nfb + 4));
-        HIPCK(hipMemsetAsync(h->ws_fb.p, 0, 4 * sizeof(int32_t), st));
-    }
+    if (const int rc = reserve_fb(h, nfb, st)) return rc;
+    const HandBack hb(h->ws_fb, 0, nfb);
     P.cap = cap;
     // the queries' exact tables ahead of the scan (k_lut_pre: a codebook row read once per 64 queries instead of once per query)
     {
@@ -865,17 +1085,15 @@ int launch_scan_hist(mmidx_index *h, ScanParams P, const SearchPlan &pl, dim3 gr
             HIPCK(h->ws_lutpre.reserve((size_t)nqa * tab));
             const dim3 g((unsigned)h->m, (unsigned)((nqa + LUTPRE_QB - 1) / LUTPRE_QB));
             if (g.y <= 65535) {
-                if (h->dsub == 16) hipLaunchKernelGGL(k_lut_pre<16>, g, dim3(256), 0, st, P.Q, P.coarse, P.cells, P.perm, P.pqT, h->ws_lutpre.p, h->D, h->m, h->ks, P.w, P.ivf, nqa);
-                else if (h->dsub == 8) hipLaunchKernelGGL(k_lut_pre<8>, g, dim3(256), 0, st, P.Q, P.coarse, P.cells, P.perm, P.pqT, h->ws_lutpre.p, h->D, h->m, h->ks, P.w, P.ivf, nqa);
-                else hipLaunchKernelGGL(k_lut_pre<4>, g, dim3(256), 0, st, P.Q, P.coarse, P.cells, P.perm, P.pqT, h->ws_lutpre.p, h->D, h->m, h->ks, P.w, P.ivf, nqa);
+                for_dsub(h->dsub, [&](auto ds) {
+                    hipLaunchKernelGGL(k_lut_pre<decltype(ds)::value>, g, dim3(256), 0, st, P.Q, P.coarse, P.cells, P.perm, P.pqT, h->ws_lutpre.p, h->D, h->m, h->ks, P.w, P.ivf, nqa);
+                });
                 HIPCK(hipGetLastError());
                 P.lut_pre = h->ws_lutpre.p;
             }
         }
     }
-    P.fb_count = (u32 *)h->ws_fb.p;
-    P.fb_items = h->ws_fb.p + 4;
-    P.fb_ch = h->ws_fb.p + 4 + nfb;
+    hb.put(P);
     if (compact_items) {
         const long long nq_items = (long long)grid.x;
         const double share = (double)h->nonempty_lists / (double)h->C;  // expected fraction of queries served here
@@ -907,25 +1125,8 @@ int launch_scan_hist(mmidx_index *h, ScanParams P, const SearchPlan &pl, dim3 gr
                 "debug build only: %d second passes, %.1f appended and %.1f kept per item\n", c4[0], nfb, MMIDX_HKEEP, cap, lds,
                 c4[1], (double)(unsigned)c4[2] / (double)nfb, (double)(unsigned)c4[3] / (double)nfb);
     }
-    // the handed-back items (device-side count; normally none: the blocks exit at once)
-    ScanParams F = P;
-    F.cap = pl.cap;
-    F.order = P.fb_items;
-    F.n_order = (const int32_t *)P.fb_count;
-    F.order_ch = P.ivf ? P.fb_ch : nullptr;
-    F.n_items = (int)nfb;
-    return launch_scan(h, F, dim3((unsigned)nfb, 1), pl.lds, st);
+    return hb.tail_exact(h, P, pl, st);  // the handed-back items
 }
-
-// MMIDX_DEBUG_SYNC=1: synchronise after every stage and report the first failing one
-#define DBG_SYNC(name)                                                                        \
-    do {                                                                                      \
-        if (h->sw.debug_sync) {                                                                  \
-            hipError_t e__ = hipStreamSynchronize(st);                                        \
-            fprintf(stderr, "[mmidx] %s: %s\n", name, hipGetErrorString(e__));               \
-            if (e__ != hipSuccess) return mmidx_fail(MMIDX_ERR_HIP, "%s failed: %s", name, hipGetErrorString(e__)); \
-        }                                                                                     \
-    } while (0)
 
 // ---- K3g (mmidx_scan_grp.h): grouped, list-major pass B -------------------------------------------------------
 // index-side tables: built once per (coarse, product) quantizer pair, on the handle's stream, synchronously
@@ -953,73 +1154,33 @@ int build_grp_tables(mmidx_index *h) {
 
 template <int M, int G, int DSUB, bool FLAT = false, bool UNION = false>
 int launch_grp_t(mmidx_index *h, const GrpParams &GP, size_t lds, hipStream_t st) {
-    {   // the scan addresses the u8 rows from LDS address 0 (GrpLds::lut8 == 0, byte_x8): the kernel must not own static LDS
-        static int static_lds = -1;
-        if (static_lds < 0) {
-            hipFuncAttributes fa{};
-            HIPCK(hipFuncGetAttributes(&fa, (const void *)k_scan_grp<M, G, DSUB, FLAT, UNION>));
-            static_lds = (int)fa.sharedSizeBytes;
-        }
-        if (static_lds != 0) return 1;  // (K3f takes the pairs)
-    }
-    HIPCK(hipFuncSetAttribute((const void *)k_scan_grp<M, G, DSUB, FLAT, UNION>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    int occ = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void *)k_scan_grp<M, G, DSUB, FLAT, UNION>, GRP_NT, lds) != hipSuccess || occ < 1) {
-        (void)hipGetLastError();
-        occ = 1;
-    }
-    const int blocks = std::max(8, (occ * std::max(h->num_cus, 8) + 7) & ~7);
-    hipLaunchKernelGGL((k_scan_grp<M, G, DSUB, FLAT, UNION>), dim3((unsigned)blocks), dim3(GRP_NT), lds, st, GP);
-    HIPCK(hipGetLastError());
-    return MMIDX_OK;
+    // the scan addresses the u8 rows from LDS address 0 (GrpLds::lut8 == 0): with static LDS it declines and K3f takes the pairs.
+    // As many blocks as fit (option "mfma_blocks" is the matrix-core kernels' alone)
+    return launch_persistent<k_scan_grp<M, G, DSUB, FLAT, UNION>>(h, GP, 0, GRP_NT, lds, st, StaticLds::decline);
 }
 
 // ---- K3ma (mmidx_scan_mfma_a.h): pass A through the matrix-core bound ---------------------------------------------------------
-template <int NJ, int DSUB, int MODE, int NWV>
-int launch_mfma_a_scan_w(mmidx_index *h, const MfmaParams &MP, size_t lds, hipStream_t st) {
-    HIPCK(hipFuncSetAttribute((const void *)k_scan_mfma<NJ, DSUB, MODE, NWV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    int blocks = h->sw.mfma_blocks;
-    if (blocks <= 0) {
-        int occ = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void *)k_scan_mfma<NJ, DSUB, MODE, NWV>, NWV * 64, lds) != hipSuccess || occ < 1) {
-            (void)hipGetLastError();
-            occ = 1;
-        }
-        blocks = occ * std::max(h->num_cus, 8);
-    }
-    blocks = std::max(8, (blocks + 7) & ~7);
-    hipLaunchKernelGGL((k_scan_mfma<NJ, DSUB, MODE, NWV>), dim3((unsigned)blocks), dim3(NWV * 64), lds, st, MP);
-    HIPCK(hipGetLastError());
-    return MMIDX_OK;
-}
 // a sweep: the eight-wave instance over the items of <= 32 rows (where it is on), then the four-wave instance over the others.
 // Sweep 2 only: its loop fits 128 registers (1.27 -> 1.13 ms per 131072 queries); sweep 1 keeps 16 / 32 slot values next to the
 // fragments and reloads spilled registers inside the tile loop with eight waves (1.14 -> 2.66 ms), so it stays with four.
-template <int NJ, int DSUB, int MODE>
-int launch_mfma_a_scan_t(mmidx_index *h, const MfmaParams &MP, size_t lds, hipStream_t st) {
-    if constexpr (MODE == 2) {
-        if (MP.a_wide) {
-            const int rc = launch_mfma_a_scan_w<NJ, DSUB, MODE, 8>(h, MP, lds, st);
-            if (rc) return rc;
-        }
-    }
-    return launch_mfma_a_scan_w<NJ, DSUB, MODE, 4>(h, MP, lds, st);
-}
 template <int MODE>
 int launch_mfma_a_scan(mmidx_index *h, const MfmaParams &MP, size_t lds, hipStream_t st) {
-    const int nj = h->D / 32;
-    if (h->dsub == 4) return nj == 4 ? launch_mfma_a_scan_t<4, 4, MODE>(h, MP, lds, st) : nj == 2 ? launch_mfma_a_scan_t<2, 4, MODE>(h, MP, lds, st) : launch_mfma_a_scan_t<1, 4, MODE>(h, MP, lds, st);
-    if (h->dsub == 8) return nj == 4 ? launch_mfma_a_scan_t<4, 8, MODE>(h, MP, lds, st) : nj == 2 ? launch_mfma_a_scan_t<2, 8, MODE>(h, MP, lds, st) : launch_mfma_a_scan_t<1, 8, MODE>(h, MP, lds, st);
-    return nj == 4 ? launch_mfma_a_scan_t<4, 16, MODE>(h, MP, lds, st) : nj == 2 ? launch_mfma_a_scan_t<2, 16, MODE>(h, MP, lds, st) : launch_mfma_a_scan_t<1, 16, MODE>(h, MP, lds, st);
+    return for_nj_dsub(h->D / 32, h->dsub, [&](auto nj, auto ds) {
+        constexpr int NJ = decltype(nj)::value, DSUB = decltype(ds)::value;
+        if constexpr (MODE == 2) {
+            if (MP.a_wide) {
+                const int rc = launch_persistent<k_scan_mfma<NJ, DSUB, MODE, 8>>(h, MP, h->sw.mfma_blocks, 8 * 64, lds, st);
+                if (rc) return rc;
+            }
+        }
+        return launch_persistent<k_scan_mfma<NJ, DSUB, MODE, 4>>(h, MP, h->sw.mfma_blocks, 4 * 64, lds, st);
+    });
 }
 template <int M, int DSUB>
 int launch_a1_verify_t(mmidx_index *h, const MfmaParams &MP, hipStream_t st) {
     const A1VLds L(M, DSUB);
-    HIPCK(hipFuncSetAttribute((const void *)k_a1_verify<M, DSUB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.total));
     const unsigned grid = (unsigned)std::max(h->num_cus, 8);  // (one block of sixteen waves per CU, walking the list)
-    hipLaunchKernelGGL((k_a1_verify<M, DSUB>), dim3(grid), dim3(A1V_NT(DSUB)), L.total, st, MP);
-    HIPCK(hipGetLastError());
-    return MMIDX_OK;
+    return launch_grid<k_a1_verify<M, DSUB>>(MP, dim3(grid), A1V_NT(DSUB), L.total, st);
 }
 
 
@@ -1038,21 +1199,6 @@ bool passa_q_applies(const mmidx_index *h, const ScanParams &P, const SearchPlan
     return 4 * nq >= 5 * std::max<int64_t>(1, h->nonempty_lists) && h->n_csr / std::max<int64_t>(1, h->nonempty_lists) >= 4096;
 }
 
-template <int M, int DSUB>
-int launch_q_t(const QParams &QP, unsigned grid, size_t lds, hipStream_t st) {
-    static int static_lds = -1;  // (the table is addressed from LDS address 0, byte_x8: the kernel must not own static LDS)
-    if (static_lds < 0) {
-        hipFuncAttributes fa{};
-        HIPCK(hipFuncGetAttributes(&fa, (const void *)k_scan_q<M, DSUB>));
-        static_lds = (int)fa.sharedSizeBytes;
-    }
-    if (static_lds != 0) return mmidx_fail(MMIDX_ERR_UNSUPPORTED, "k_scan_q owns %d bytes of static LDS: its table is not at LDS address 0", static_lds);
-    HIPCK(hipFuncSetAttribute((const void *)k_scan_q<M, DSUB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL((k_scan_q<M, DSUB>), dim3(grid), dim3(256), lds, st, QP);
-    HIPCK(hipGetLastError());
-    return MMIDX_OK;
-}
-
 // Pass A of the whole sub-batch through K3q; thresholds in P.T, exact candidates in the pools, as K3h leaves them; the queries it hands
 // back (ties, an unusable scale) go through the exact kernel K3.  Uses ws_pcount (the caller zeroes it again for pass B), ws_pstart /
 // ws_pcursor / ws_order / ws_gdesc / ws_gfb / ws_fb.
@@ -1060,32 +1206,23 @@ int launch_passa_q(mmidx_index *h, const ScanParams &P, const SearchPlan &pl, lo
     constexpr int G = MMIDX_Q_G;
     const int C = h->C;
     const size_t nfb = (size_t)nq * (size_t)std::max(pl.nchunks, 1);
-    HIPCK(h->ws_pcount.reserve((size_t)C + 1));
-    HIPCK(h->ws_pstart.reserve((size_t)C + 1));
-    HIPCK(h->ws_pcursor.reserve((size_t)C));
-    HIPCK(h->ws_order.reserve((size_t)nq * (size_t)P.w));  // (pass B's size: its reserve later must not reallocate under these launches)
     const size_t max_groups = (size_t)nq / G + (size_t)std::min<long long>(nq, C) + 8;
     HIPCK(h->ws_gdesc.reserve(max_groups));
     HIPCK(h->ws_gfb.reserve(8));
-    if (h->ws_fb.cap < 2 * nfb + 4) {
-        HIPCK(h->ws_fb.reserve(2 * nfb + 4));
-        HIPCK(hipMemsetAsync(h->ws_fb.p, 0, 4 * sizeof(int32_t), st));
-    }
+    if (const int rc = reserve_fb(h, nfb, st)) return rc;
     // the (query, probe 0) pairs by cell, groups of <= 4
-    const unsigned gq = (unsigned)((nq + 255) / 256);
-    hipLaunchKernelGGL(k_a1_pair_count, dim3(gq), dim3(256), 0, st, P.cells, P.w, (long long)nq, P.list_off, h->ws_pcount.p, C);
-    hipLaunchKernelGGL(k_q_scan_groups, dim3(1), dim3(1024), 0, st, h->ws_pcount.p, C, G, h->ws_pstart.p, h->ws_pcursor.p, h->ws_gdesc.p, h->ws_gfb.p);
-    hipLaunchKernelGGL(k_a1_pair_scatter, dim3(gq), dim3(256), 0, st, P.cells, P.w, (long long)nq, P.list_off, h->ws_pstart.p, h->ws_pcursor.p, h->ws_order.p);
-    HIPCK(hipGetLastError());
+    if (const int rc = sort_pairs_by_cell(h, P, nq, st, [&] {
+            hipLaunchKernelGGL(k_q_scan_groups, dim3(1), dim3(1024), 0, st, h->ws_pcount.p, C, G, h->ws_pstart.p, h->ws_pcursor.p, h->ws_gdesc.p, h->ws_gfb.p);
+        }))
+        return rc;
+    const HandBack hb(h->ws_fb, 0, nfb);
     QParams QP{};
     QP.S = P;
     QP.S.order = h->ws_order.p;
     QP.S.n_order = h->ws_pstart.p + C;
     QP.S.rot = h->d_rot;
     QP.S.perm = h->d_perm;
-    QP.S.fb_count = (u32 *)h->ws_fb.p;
-    QP.S.fb_items = h->ws_fb.p + 4;
-    QP.S.fb_ch = h->ws_fb.p + 4 + nfb;
+    hb.put(QP.S);
     QP.gdesc = h->ws_gdesc.p;
     QP.n_groups = h->ws_gfb.p;
     QP.pq = h->d_pq;
@@ -1096,12 +1233,9 @@ int launch_passa_q(mmidx_index *h, const ScanParams &P, const SearchPlan &pl, lo
     const QLds L(h->m, h->D);
     // grid: the host's upper bound of the group count (the blocks beyond the device-side count leave at once)
     const unsigned grid = (unsigned)((std::min<size_t>(max_groups, (size_t)nq) + 7 + 7) & ~(size_t)7);  // (eight ranges of ceil(groups / 8): k_scan_q's XCD map)
-    int rc;
-    switch (h->dsub) {
-        case 4: rc = launch_q_t<16, 4>(QP, grid, L.total, st); break;
-        case 8: rc = launch_q_t<16, 8>(QP, grid, L.total, st); break;
-        default: rc = launch_q_t<16, 16>(QP, grid, L.total, st); break;
-    }
+    const int rc = for_dsub(h->dsub, [&](auto ds) {  // (the table is addressed from LDS address 0, byte_x8)
+        return launch_grid<k_scan_q<16, decltype(ds)::value>>(QP, dim3(grid), 256, L.total, st, StaticLds::fail, "k_scan_q");
+    });
     if (rc) return rc;
     if (h->sw.debug_sync) {
         int32_t c4[4], ng = 0;
@@ -1110,17 +1244,7 @@ int launch_passa_q(mmidx_index *h, const ScanParams &P, const SearchPlan &pl, lo
         (void)hipMemcpy(&ng, h->ws_gfb.p, sizeof(ng), hipMemcpyDeviceToHost);
         fprintf(stderr, "[mmidx] K3q: %lld queries in %d groups (grid %u, lds %zu); %d (query, chunk) items handed back to K3\n", nq, ng, grid, L.total, c4[0]);
     }
-    // the handed-back queries (device-side count; normally none: the blocks exit at once)
-    ScanParams F = P;
-    F.cap = pl.cap;
-    F.fb_count = QP.S.fb_count;
-    F.fb_items = QP.S.fb_items;
-    F.fb_ch = QP.S.fb_ch;
-    F.order = QP.S.fb_items;
-    F.n_order = (const int32_t *)QP.S.fb_count;
-    F.order_ch = P.ivf ? QP.S.fb_ch : nullptr;
-    F.n_items = (int)nfb;
-    return launch_scan(h, F, dim3((unsigned)nfb, 1), pl.lds, st);
+    return hb.tail_exact(h, P, pl, st);  // the handed-back queries
 }
 
 // K3ma's items: (group, piece of <= sub codes); at most eight pieces per list (k_a1_select holds a pair's values in registers).  The
@@ -1176,21 +1300,11 @@ int launch_passa_mfma(mmidx_index *h, const ScanParams &P, const SearchPlan &pl,
     const int C = h->C;
     const long long npairs = nq;  // (at most: the queries whose nearest list is non-empty here)
     const size_t nfb = (size_t)npairs * (size_t)std::max(pl.nchunks, 1);
-    HIPCK(h->ws_pcount.reserve((size_t)C + 1));
-    HIPCK(h->ws_pstart.reserve((size_t)C + 1));
-    HIPCK(h->ws_pcursor.reserve((size_t)C));
-    HIPCK(h->ws_order.reserve((size_t)nq * (size_t)P.w));  // (pass B's size: its reserve later must not reallocate under these launches)
-    HIPCK(h->ws_gdesc.reserve((size_t)npairs / G + (size_t)C + 8));
-    HIPCK(h->ws_gfb.reserve(4 + 2 * nfb + 16));
     const PassaMfmaShape SH = passa_mfma_shape(h, npairs);
     if (!SH.fits) return mmidx_fail(MMIDX_ERR_UNSUPPORTED, "K3ma's bitmap does not fit (passa_mfma_applies must have said so)");
     const int sub = SH.sub, nsub = SH.nsub;
     const size_t max_groups = SH.max_groups, bm_stride = SH.bm_stride;
-    HIPCK(h->ws_T0.reserve((size_t)nq));
-    HIPCK(h->ws_redo.reserve((size_t)nq));
-    HIPCK(h->ws_psnap.reserve((size_t)nq));
-    HIPCK(h->ws_mfctl.reserve(64));
-    const int cstride = 256;  // (512: sweep 1 by the eight-wave instance -- not used, see launch_mfma_a_scan_t)
+    const int cstride = 256;  // (512: sweep 1 by the eight-wave instance -- not used, see launch_mfma_a_scan)
     HIPCK(h->ws_acand.reserve((size_t)npairs * nsub * cstride));
     HIPCK(h->ws_arowc.reserve((size_t)npairs));
     HIPCK(h->ws_abm.reserve(max_groups * (size_t)nsub * bm_stride));
@@ -1203,66 +1317,29 @@ int launch_passa_mfma(mmidx_index *h, const ScanParams &P, const SearchPlan &pl,
     if (h->transform != MMIDX_TR_ROTATION) HIPCK(h->ws_arows.reserve((size_t)npairs * h->D));
     HIPCK(h->ws_ameta.reserve((size_t)npairs));
     HIPCK(h->ws_ametaT.reserve((size_t)npairs));
-    if (h->d_perm) HIPCK(h->ws_Qp.reserve((size_t)nq * h->D));
     if (h->transform == MMIDX_TR_ROTATION) HIPCK(h->ws_R.reserve((size_t)npairs * h->D));
     // ---- the (query, probe 0) pairs by cell, groups of <= 64 ----
-    const unsigned gq = (unsigned)((nq + 255) / 256);
-    hipLaunchKernelGGL(k_a1_pair_count, dim3(gq), dim3(256), 0, st, P.cells, P.w, (long long)nq, P.list_off, h->ws_pcount.p, C);
-    hipLaunchKernelGGL(k_pair_scan, dim3(1), dim3(1024), 0, st, h->ws_pcount.p, C, h->ws_pstart.p, h->ws_pcursor.p, (int32_t *)nullptr);
-    hipLaunchKernelGGL(k_a1_pair_scatter, dim3(gq), dim3(256), 0, st, P.cells, P.w, (long long)nq, P.list_off, h->ws_pstart.p, h->ws_pcursor.p, h->ws_order.p);
-    hipLaunchKernelGGL(k_group_build, dim3(1), dim3(1024), 0, st, h->ws_pcount.p, h->ws_pstart.p, C, G, h->ws_gdesc.p, h->ws_gfb.p, (u32 *)(h->ws_gfb.p + 1),
-                       (unsigned long long *)nullptr, (int32_t *)nullptr);
-    hipLaunchKernelGGL(k_mfma_prep, dim3((unsigned)std::min<long long>(4096, (nq + 255) / 256)), dim3(256), 0, st, (const int32_t *)h->ws_gfb.p, (u32 *)nullptr,
-                       h->ws_redo.p, h->ws_mfctl.p, P.T, h->ws_T0.p, P.pool_cnt, h->ws_psnap.p, (long long)nq);
-    HIPCK(hipGetLastError());
-    DBG_SYNC("K3ma pair sort");
+    int rc = sort_pairs_by_cell(h, P, nq, st, [&] {
+        hipLaunchKernelGGL(k_pair_scan, dim3(1), dim3(1024), 0, st, h->ws_pcount.p, C, h->ws_pstart.p, h->ws_pcursor.p, (int32_t *)nullptr);
+    });
+    if (rc) return rc;
+    if ((rc = build_groups(h, C, G, npairs, nfb, nullptr, nullptr, false, "K3ma group build", st))) return rc;
+    const HandBack back(h->ws_gfb, 1, nfb);
     MfmaParams MP{};
-    MP.S = P;
+    if ((rc = mfma_prepare(h, MP, P, pl, back, 0, sub, nsub, pl.nchunks, npairs, nq, st))) return rc;  // (no survivor list, no histogram)
+    DBG_SYNC("K3ma pair sort");
     MP.S.order = h->ws_order.p;
     MP.S.n_order = h->ws_pstart.p + C;
-    if (h->d_perm) {
-        const long long tot = (long long)nq * h->D;
-        hipLaunchKernelGGL(k_permute_cols, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, P.Q, h->d_perm, h->ws_Qp.p, h->D, (long long)nq);
-        MP.S.Q = h->ws_Qp.p;
-        MP.S.coarse = h->d_coarseP;
-    }
-    MP.S.perm = nullptr;
-    MP.R = nullptr;
+    if (h->d_perm && (rc = use_permuted_queries(h, MP.S, true, nq, st))) return rc;
     if (h->transform == MMIDX_TR_ROTATION) {
         hipLaunchKernelGGL(k_pair_rotate, dim3((unsigned)((npairs + 7) / 8)), dim3(128), 8 * (size_t)h->D * sizeof(double), st, P.Q, P.coarse, h->d_rot, P.cells,
                            MP.S.order, MP.S.n_order, (long long)npairs, P.w, h->D, 1, h->ws_R.p);
         HIPCK(hipGetLastError());
         MP.R = h->ws_R.p;
     }
-    MP.pq16 = h->d_pq16;
-    MP.xn = h->xn.p;
-    MP.pq = h->d_pq;
-    MP.flat_lut = nullptr;
-    MP.gdesc = h->ws_gdesc.p;
-    MP.n_groups = h->ws_gfb.p;
-    MP.sub = sub;
-    MP.nsub = nsub;
-    MP.ep = h->pq_ep;
-    MP.xmax = h->rmax;
-    MP.ghist = nullptr;
-    MP.T0 = h->ws_T0.p;
-    MP.surv = nullptr;
-    MP.surv_cnt = h->ws_mfctl.p;
-    MP.surv_cap = 0;
-    MP.redo = h->ws_redo.p;
-    MP.pool_snap = h->ws_psnap.p;
-    MP.work = h->ws_mfctl.p + 8;
-    MP.a_work = h->ws_mfctl.p + 24;  // (sweep 1: words 24 .. 39; sweep 2: 8 .. 23)
+    MP.a_work = h->ws_mfctl.p + 24;  // (sweep 1: words 24 .. 39; sweep 2: MP.work, 8 .. 23)
     MP.a_wide = 0;  // (sweep 1: every item through the four-wave instance; set for sweep 2 below)
     MP.a_cstride = cstride;
-    MP.fb_count = (u32 *)(h->ws_gfb.p + 1);
-    MP.fb_items = h->ws_gfb.p + 4;
-    MP.fb_ch = h->ws_gfb.p + 4 + nfb;
-    MP.fb_chunk = pl.chunk;
-    MP.fb_nchunks = std::max(pl.nchunks, 1);
-    MP.npairs_flat = npairs;
-    MP.stat = (h->profiling == 1 || h->sw.debug_sync) ? (unsigned long long *)(h->d_counters + 3) : nullptr;
-    MP.nver = (unsigned long long *)(h->d_counters + 7);
     MP.a_cand = h->ws_acand.p;
     MP.a_rowc = h->ws_arowc.p;
     MP.a_bm = h->ws_abm.p;
@@ -1278,17 +1355,8 @@ int launch_passa_mfma(mmidx_index *h, const ScanParams &P, const SearchPlan &pl,
     MP.a_rnd_size = rnd_size;
     const MfmaLds L(h->D);
     hipEvent_t *aev = nullptr;
-    if (h->profiling == 1 && h->a_ev_used + 5 <= 5 * 4096) {
-        while (h->a_ev.size() < h->a_ev_used + 5) {
-            hipEvent_t e;
-            HIPCK(hipEventCreate(&e));
-            h->a_ev.push_back(e);
-        }
-        aev = h->a_ev.data() + h->a_ev_used;
-        h->a_ev_used += 5;
-        HIPCK(hipEventRecord(aev[0], st));
-    }
-    int rc = launch_mfma_a_scan<1>(h, MP, L.total, st);  // sweep 1: the slots' best four per pair
+    if (h->profiling == 1 && (rc = take_events(h->a_ev, h->a_ev_used, 5, 4096, st, aev))) return rc;
+    rc = launch_mfma_a_scan<1>(h, MP, L.total, st);  // sweep 1: the slots' best four per pair
     if (rc) return rc;
     if (aev) HIPCK(hipEventRecord(aev[1], st));
     DBG_SYNC("K3ma sweep 1");
@@ -1318,16 +1386,12 @@ int launch_passa_mfma(mmidx_index *h, const ScanParams &P, const SearchPlan &pl,
     hipLaunchKernelGGL(k_a1_records, dim3((unsigned)(8 * std::max(h->num_cus, 8))), dim3(A1R_NT), 0, st, MP);
     HIPCK(hipGetLastError());
     DBG_SYNC("K3ma records");
-    if (h->dsub == 4) rc = h->m == 32 ? launch_a1_verify_t<32, 4>(h, MP, st) : h->m == 16 ? launch_a1_verify_t<16, 4>(h, MP, st) : launch_a1_verify_t<8, 4>(h, MP, st);
-    else if (h->dsub == 8) rc = h->m == 16 ? launch_a1_verify_t<16, 8>(h, MP, st) : h->m == 8 ? launch_a1_verify_t<8, 8>(h, MP, st) : launch_a1_verify_t<4, 8>(h, MP, st);
-    else rc = h->m == 8 ? launch_a1_verify_t<8, 16>(h, MP, st) : h->m == 4 ? launch_a1_verify_t<4, 16>(h, MP, st) : launch_a1_verify_t<2, 16>(h, MP, st);
+    rc = for_nj_dsub(h->D / 32, h->dsub, [&](auto nj, auto ds) { return launch_a1_verify_t<decltype(nj)::value * 32 / decltype(ds)::value, decltype(ds)::value>(h, MP, st); });
     if (rc) return rc;
     if (aev) HIPCK(hipEventRecord(aev[4], st));
     DBG_SYNC("K3ma verify");
     h->a_launches++;
-    const long long span = std::max<long long>(npairs, nq);
-    hipLaunchKernelGGL(k_mfma_redo, dim3((unsigned)((span + 255) / 256)), dim3(256), 0, st, MP, (long long)nq);
-    HIPCK(hipGetLastError());
+    if ((rc = launch_mfma_redo(MP, npairs, nq, st))) return rc;
     DBG_SYNC("K3ma redo");
     if (h->sw.debug_sync) {
         int32_t g2[2], np1 = 0;
@@ -1367,14 +1431,8 @@ int launch_passa_mfma(mmidx_index *h, const ScanParams &P, const SearchPlan &pl,
             }
         }
     }
-    // the queries handed back (device-side count; normally the few whose list is shorter than K1): K3f's looping kernel, from T = +inf
-    ScanParams F = P;
-    F.order = MP.fb_items;
-    F.n_order = (const int32_t *)MP.fb_count;
-    F.order_ch = MP.fb_ch;
-    F.n_items = (int)std::min<size_t>(nfb, (size_t)0x7fffff00);
-    F.xcd_remap = 0;
-    return launch_scan_filtered(h, F, pl, dim3((unsigned)F.n_items, 1), st, -1);
+    // the queries handed back (normally the few whose list is shorter than K1): K3f's looping kernel, from T = +inf
+    return back.tail_filtered(h, P, pl, st);
 }
 
 // pass B over the sorted pairs (P.order / P.n_order as for K3f; per-cell counts and starts in ws_pcount / ws_pstart).
@@ -1388,13 +1446,9 @@ int launch_grouped_common(mmidx_index *h, const ScanParams &S, ScanParams F, con
     const GrpLds L(h->m, G, h->D, cb);
     if (L.total > 160 * 1024 || pl.K1 + GRP_VR > GRP_NT) return 1;
     const size_t nfb = (size_t)npairs * (size_t)nchunks;
-    HIPCK(h->ws_gdesc.reserve((size_t)npairs / G + (size_t)nlists + 8));
-    HIPCK(h->ws_gfb.reserve(4 + 2 * nfb + 16));
-    if (h->sw.debug_sync) HIPCK(hipMemsetAsync(h->ws_gfb.p, 0, (4 + 2 * nfb + 16) * sizeof(int32_t), st));
-    hipLaunchKernelGGL(k_group_build, dim3(1), dim3(1024), 0, st, h->ws_pcount.p, h->ws_pstart.p, nlists, G, h->ws_gdesc.p, h->ws_gfb.p,
-                       (u32 *)(h->ws_gfb.p + 1), (unsigned long long *)(h->d_counters + 7), h->pin_hint ? h->pin_hint + 1 : nullptr);
-    HIPCK(hipGetLastError());
-    DBG_SYNC("K3g group build");
+    int rc = build_groups(h, nlists, G, npairs, nfb, (unsigned long long *)(h->d_counters + 7), passb_hint(h), h->sw.debug_sync != 0, "K3g group build", st);
+    if (rc) return rc;
+    const HandBack hb(h->ws_gfb, 1, nfb);
     GrpParams GP{};
     GP.S = S;
     GP.pq = h->d_pq;
@@ -1404,9 +1458,7 @@ int launch_grouped_common(mmidx_index *h, const ScanParams &S, ScanParams F, con
     GP.gdesc = h->ws_gdesc.p;
     GP.n_groups = h->ws_gfb.p;
     GP.nchunks = nchunks;
-    GP.fb_count = (u32 *)(h->ws_gfb.p + 1);
-    GP.fb_items = h->ws_gfb.p + 4;
-    GP.fb_ch = h->ws_gfb.p + 4 + nfb;
+    hb.put(GP);
     GP.cb = cb;
     GrpExtra GX{};
     GX.flat_lut = flat_lut;
@@ -1424,7 +1476,6 @@ int launch_grouped_common(mmidx_index *h, const ScanParams &S, ScanParams F, con
         GX.T0 = h->ws_T0.p;
     }
     GP.stat = (h->profiling == 1 || h->sw.debug_sync) ? (unsigned long long *)(h->d_counters + 3) : nullptr;  // [0] verified, [1] flag (adds), [2..3] item statistics
-    int rc;
     const int ds = h->dsub;
     // flat PQ with the queries' exact tables: its own instances (m = 8, 16 -- the others verify from the codebook as IVF does)
     const bool flat_inst = GX.flat_lut && (h->m == 8 || h->m == 16);
@@ -1485,13 +1536,7 @@ int launch_grouped_common(mmidx_index *h, const ScanParams &S, ScanParams F, con
         fprintf(stderr, "[mmidx] K3g: %d groups of <= %d pairs, %d (pair, chunk) items handed back to K3f (lds %zu, cb %d)\n", c4[0], G, c4[1],
                 L.total, cb);
     }
-    // the handed-back items (device-side count; normally few): a small main grid, the looping tail covers the rest
-    F.order = GP.fb_items;
-    F.n_order = (const int32_t *)GP.fb_count;
-    F.order_ch = GP.fb_ch;
-    F.n_items = (int)std::min<size_t>(nfb, (size_t)0x7fffff00);
-    F.xcd_remap = 0;
-    return launch_scan_filtered(h, F, pl, dim3((unsigned)F.n_items, 1), st, -1);
+    return hb.tail_filtered(h, F, pl, st);  // the handed-back items (normally few)
 }
 
 // ---- K3m (mmidx_scan_mfma.h): pass B as a certified lower bound on the matrix cores ------------------------------
@@ -1539,23 +1584,6 @@ int build_mfma_tables(mmidx_index *h) {
     return MMIDX_OK;
 }
 
-template <int NJ, int DSUB>
-int launch_mfma_scan_t(mmidx_index *h, const MfmaParams &MP, size_t lds, hipStream_t st) {
-    HIPCK(hipFuncSetAttribute((const void *)k_scan_mfma<NJ, DSUB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    int blocks = h->sw.mfma_blocks;
-    if (blocks <= 0) {
-        int occ = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void *)k_scan_mfma<NJ, DSUB>, MF_NT, lds) != hipSuccess || occ < 1) {
-            (void)hipGetLastError();
-            occ = 1;
-        }
-        blocks = occ * std::max(h->num_cus, 8);
-    }
-    blocks = std::max(8, (blocks + 7) & ~7);
-    hipLaunchKernelGGL((k_scan_mfma<NJ, DSUB>), dim3((unsigned)blocks), dim3(MF_NT), lds, st, MP);
-    HIPCK(hipGetLastError());
-    return MMIDX_OK;
-}
 template <int M, int DSUB>
 int launch_mfma_verify_t(mmidx_index *h, const MfmaParams &MP, hipStream_t st) {
     const unsigned grid = (unsigned)(8 * std::max(h->num_cus, 8));
@@ -1567,20 +1595,7 @@ int launch_mfma_verify_t(mmidx_index *h, const MfmaParams &MP, hipStream_t st) {
 
 template <int DSUB, int TPW>
 int launch_mfma_kc_scan_t(mmidx_index *h, const MfmaKcParams &KP, size_t lds, hipStream_t st) {
-    HIPCK(hipFuncSetAttribute((const void *)k_scan_mfma_kc<DSUB, TPW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    int blocks = h->sw.mfma_blocks;
-    if (blocks <= 0) {
-        int occ = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void *)k_scan_mfma_kc<DSUB, TPW>, MF_NT, lds) != hipSuccess || occ < 1) {
-            (void)hipGetLastError();
-            occ = 1;
-        }
-        blocks = occ * std::max(h->num_cus, 8);
-    }
-    blocks = std::max(8, (blocks + 7) & ~7);
-    hipLaunchKernelGGL((k_scan_mfma_kc<DSUB, TPW>), dim3((unsigned)blocks), dim3(MF_NT), lds, st, KP);
-    HIPCK(hipGetLastError());
-    return MMIDX_OK;
+    return launch_persistent<k_scan_mfma_kc<DSUB, TPW>>(h, KP, h->sw.mfma_blocks, MF_NT, lds, st);
 }
 
 template <int DSUB, int CG>
@@ -1600,8 +1615,6 @@ int launch_mfma_kc(mmidx_index *h, const ScanParams &S, ScanParams F, const Sear
     if (S.ivf && h->d_perm && !h->d_coarseP) return 1;  // (every applicability check ahead of the first launch)
     const int G = MFK_G;
     const size_t nfb = (size_t)npairs * (size_t)std::max(nchunks_f, 1);
-    HIPCK(h->ws_gdesc.reserve((size_t)npairs / G + (size_t)nlists + 8));
-    HIPCK(h->ws_gfb.reserve(4 + 2 * nfb + 16));
     // the DMA form (k_scan_mfma_kc2) where the lanes' code bytes come in aligned words: D a multiple of 256
     const int nb = 32 / h->dsub, quarter = h->m / 4;
     int cg = 0;
@@ -1614,32 +1627,17 @@ int launch_mfma_kc(mmidx_index *h, const ScanParams &S, ScanParams F, const Sear
     else sub = std::min(sub, 64 * tpw);  // (a wave holds at most TPW tiles' accumulators)
     const int nsub = (int)((maxlen + sub - 1) / sub);
     if ((long long)(npairs / G + nlists) * nsub > 0x7fffff00ll) return 1;
-    hipLaunchKernelGGL(k_group_build, dim3(1), dim3(1024), 0, st, h->ws_pcount.p, h->ws_pstart.p, nlists, G, h->ws_gdesc.p, h->ws_gfb.p,
-                       (u32 *)(h->ws_gfb.p + 1), (unsigned long long *)(h->d_counters + 7), h->pin_hint ? h->pin_hint + 1 : nullptr);
-    HIPCK(hipGetLastError());
-    HIPCK(h->ws_ghist.reserve((size_t)nq * 256));
-    HIPCK(h->ws_T0.reserve((size_t)nq));
-    HIPCK(h->ws_redo.reserve((size_t)nq));
-    HIPCK(h->ws_psnap.reserve((size_t)nq));
-    HIPCK(h->ws_mfctl.reserve(64));
-    size_t qcap = h->sw.mfma_qcap > 0 ? (size_t)h->sw.mfma_qcap : std::min<size_t>((size_t)1 << 28, std::max<size_t>((size_t)1 << 20, (size_t)nq * 4096));
-    HIPCK(h->ws_surv.reserve(qcap));
-    HIPCK(h->ws_R16.reserve((size_t)npairs * h->D));
-    HIPCK(h->ws_nrow.reserve((size_t)npairs));
-    hipLaunchKernelGGL(k_mfma_prep, dim3((unsigned)std::min<long long>(4096, (nq * 64 + 255) / 256)), dim3(256), 0, st, (const int32_t *)h->ws_gfb.p, h->ws_ghist.p,
-                       h->ws_redo.p, h->ws_mfctl.p, S.T, h->ws_T0.p, S.pool_cnt, h->ws_psnap.p, (long long)nq);
-    HIPCK(hipGetLastError());
+    int rc = build_groups(h, nlists, G, npairs, nfb, (unsigned long long *)(h->d_counters + 7), passb_hint(h), false, "K3mk group build", st);
+    if (rc) return rc;
+    const HandBack hb(h->ws_gfb, 1, nfb);
+    const size_t qcap = h->sw.mfma_qcap > 0 ? (size_t)h->sw.mfma_qcap : std::min<size_t>((size_t)1 << 28, std::max<size_t>((size_t)1 << 20, (size_t)nq * 4096));
     MfmaKcParams KP{};
     MfmaParams &MP = KP.M;
-    MP.S = S;
-    if (h->d_perm) {
-        HIPCK(h->ws_Qp.reserve((size_t)nq * h->D));
-        const long long tot = (long long)nq * h->D;
-        hipLaunchKernelGGL(k_permute_cols, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, S.Q, h->d_perm, h->ws_Qp.p, h->D, (long long)nq);
-        MP.S.Q = h->ws_Qp.p;
-        if (S.ivf) MP.S.coarse = h->d_coarseP;
-    }
-    MP.S.perm = nullptr;
+    if ((rc = mfma_prepare(h, MP, S, pl, hb, qcap, sub, nsub, nchunks_f, npairs, nq, st))) return rc;
+    if (h->d_perm && (rc = use_permuted_queries(h, MP.S, S.ivf != 0, nq, st))) return rc;
+    MP.flat_lut = flat_lut;
+    HIPCK(h->ws_R16.reserve((size_t)npairs * h->D));
+    HIPCK(h->ws_nrow.reserve((size_t)npairs));
     // the launch's residual scale: |r_i| <= max |centroid element| + max |query element| (ctl words 40: query maximum, 44..45: scale)
     u32 *d_qmax = h->ws_mfctl.p + 40;
     int32_t *d_scale = (int32_t *)(h->ws_mfctl.p + 44);
@@ -1652,50 +1650,13 @@ int launch_mfma_kc(mmidx_index *h, const ScanParams &S, ScanParams F, const Sear
     hipLaunchKernelGGL(k_pair_resid16, dim3((unsigned)((nrows + 3) / 4)), dim3(256), 0, st, MP.S.Q, MP.S.coarse, S.cells, S.order, S.n_order, (long long)nrows, S.w,
                        h->D, S.ivf, (const int32_t *)d_scale, h->ws_R16.p, h->ws_nrow.p);
     HIPCK(hipGetLastError());
-    MP.pq16 = h->d_pq16;
-    MP.xn = h->xn.p;
-    MP.pq = h->d_pq;
-    MP.flat_lut = flat_lut;
-    MP.R = nullptr;
-    MP.gdesc = h->ws_gdesc.p;
-    MP.n_groups = h->ws_gfb.p;
-    MP.sub = sub;
-    MP.nsub = nsub;
-    MP.ep = h->pq_ep;
-    MP.xmax = h->rmax;
-    MP.ghist = h->ws_ghist.p;
-    MP.T0 = h->ws_T0.p;
-    MP.surv = h->ws_surv.p;
-    MP.surv_cnt = h->ws_mfctl.p;
-    MP.surv_cap = (u32)std::min<size_t>(qcap, 0xFFFFFFF0u);
-    MP.redo = h->ws_redo.p;
-    MP.pool_snap = h->ws_psnap.p;
-    MP.work = h->ws_mfctl.p + 8;
-    MP.fb_count = (u32 *)(h->ws_gfb.p + 1);
-    MP.fb_items = h->ws_gfb.p + 4;
-    MP.fb_ch = h->ws_gfb.p + 4 + nfb;
-    MP.fb_chunk = pl.chunk;
-    MP.fb_nchunks = std::max(nchunks_f, 1);
-    MP.npairs_flat = npairs;
-    MP.stat = (h->profiling == 1 || h->sw.debug_sync) ? (unsigned long long *)(h->d_counters + 3) : nullptr;
-    MP.nver = (unsigned long long *)(h->d_counters + 7);
     KP.R16 = h->ws_R16.p;
     KP.nrow = h->ws_nrow.p;
     KP.scale = d_scale;
     KP.D = h->D;
     const MfmaKcLds L;
     hipEvent_t *mev = nullptr;
-    if (h->profiling == 1 && h->mf_ev_used + 3 <= 3 * 4096) {
-        while (h->mf_ev.size() < h->mf_ev_used + 3) {
-            hipEvent_t e;
-            HIPCK(hipEventCreate(&e));
-            h->mf_ev.push_back(e);
-        }
-        mev = h->mf_ev.data() + h->mf_ev_used;
-        h->mf_ev_used += 3;
-        HIPCK(hipEventRecord(mev[0], st));
-    }
-    int rc;
+    if (h->profiling == 1 && (rc = take_events(h->mf_ev, h->mf_ev_used, 3, 4096, st, mev))) return rc;
     if (cg && h->dsub == 16) rc = cg == 8 ? launch_mfma_kc2_scan_t<16, 8>(h, KP, st) : launch_mfma_kc2_scan_t<16, 4>(h, KP, st);
     else if (cg) rc = launch_mfma_kc2_scan_t<8, 8>(h, KP, st);
     else if (h->dsub == 16) rc = tpw == 8 ? launch_mfma_kc_scan_t<16, 8>(h, KP, L.total, st) : launch_mfma_kc_scan_t<16, 16>(h, KP, L.total, st);
@@ -1715,9 +1676,7 @@ int launch_mfma_kc(mmidx_index *h, const ScanParams &S, ScanParams F, const Sear
     if (mev) HIPCK(hipEventRecord(mev[2], st));
     if (MP.stat) hipLaunchKernelGGL(k_mfma_count, dim3(1024), dim3(256), 0, st, MP);
     DBG_SYNC("K3mk verify");
-    const long long span = std::max<long long>(npairs, nq);
-    hipLaunchKernelGGL(k_mfma_redo, dim3((unsigned)((span + 255) / 256)), dim3(256), 0, st, MP, (long long)nq);
-    HIPCK(hipGetLastError());
+    if ((rc = launch_mfma_redo(MP, npairs, nq, st))) return rc;
     if (h->sw.debug_sync) {
         u32 c16[16];
         int32_t g2[2], sc[2];
@@ -1728,12 +1687,7 @@ int launch_mfma_kc(mmidx_index *h, const ScanParams &S, ScanParams F, const Sear
         fprintf(stderr, "[mmidx] K3mk: %d groups of <= %d pairs x %d pieces of %d codes, %u survivor slots (cap %u), %d items handed to the redo, scale 2^%d ok %d\n", g2[0], G, nsub, sub,
                 c16[0], MP.surv_cap, g2[1], sc[0], sc[1]);
     }
-    F.order = MP.fb_items;
-    F.n_order = (const int32_t *)MP.fb_count;
-    F.order_ch = MP.fb_ch;
-    F.n_items = (int)std::min<size_t>(nfb, (size_t)0x7fffff00);
-    F.xcd_remap = 0;
-    return launch_scan_filtered(h, F, pl, dim3((unsigned)F.n_items, 1), st, -1);
+    return hb.tail_filtered(h, F, pl, st);
 }
 
 // pass B over the sorted pairs through K3m.  S: the scan parameters as K3g would get them (list offsets / order / centroids of the
@@ -1750,12 +1704,9 @@ int launch_mfma_common(mmidx_index *h, const ScanParams &S, ScanParams F, const 
     if (h->transform == MMIDX_TR_ROTATION && (!h->d_rot || (size_t)npairs * h->D * 8 > ((size_t)8 << 30))) return 1;
     constexpr int G = MF_QG;
     const size_t nfb = (size_t)npairs * (size_t)std::max(nchunks_f, 1);
-    HIPCK(h->ws_gdesc.reserve((size_t)npairs / G + (size_t)nlists + 8));
-    HIPCK(h->ws_gfb.reserve(4 + 2 * nfb + 16));
-    hipLaunchKernelGGL(k_group_build, dim3(1), dim3(1024), 0, st, h->ws_pcount.p, h->ws_pstart.p, nlists, G, h->ws_gdesc.p, h->ws_gfb.p,
-                       (u32 *)(h->ws_gfb.p + 1), (unsigned long long *)(h->d_counters + 7), h->pin_hint ? h->pin_hint + 1 : nullptr);
-    HIPCK(hipGetLastError());
-    DBG_SYNC("K3m group build");
+    int rc = build_groups(h, nlists, G, npairs, nfb, (unsigned long long *)(h->d_counters + 7), passb_hint(h), false, "K3m group build", st);
+    if (rc) return rc;
+    const HandBack hb(h->ws_gfb, 1, nfb);
     // items: (group, piece of `sub` codes).  One piece per list where the batch fills the chip anyway; shorter pieces when there
     // are few groups (small calls, flat PQ's long chunks), so that the persistent blocks all find work
     int sub = h->sw.mfma_sub;
@@ -1769,27 +1720,11 @@ int launch_mfma_common(mmidx_index *h, const ScanParams &S, ScanParams F, const 
     }
     sub = (std::max(sub, 64) + 15) & ~15;
     const int nsub = (int)((maxlen + sub - 1) / sub);
-    HIPCK(h->ws_ghist.reserve((size_t)nq * 256));
-    HIPCK(h->ws_T0.reserve((size_t)nq));
-    HIPCK(h->ws_redo.reserve((size_t)nq));
-    HIPCK(h->ws_psnap.reserve((size_t)nq));
-    HIPCK(h->ws_mfctl.reserve(64));
-    size_t qcap = h->sw.mfma_qcap > 0 ? (size_t)h->sw.mfma_qcap : std::min<size_t>((size_t)1 << 28, std::max<size_t>((size_t)1 << 20, (size_t)nq * 2048));
-    HIPCK(h->ws_surv.reserve(qcap));
-    hipLaunchKernelGGL(k_mfma_prep, dim3((unsigned)std::min<long long>(4096, (nq * 64 + 255) / 256)), dim3(256), 0, st, (const int32_t *)h->ws_gfb.p, h->ws_ghist.p,
-                       h->ws_redo.p, h->ws_mfctl.p, S.T, h->ws_T0.p, S.pool_cnt, h->ws_psnap.p, (long long)nq);
-    HIPCK(hipGetLastError());
+    const size_t qcap = h->sw.mfma_qcap > 0 ? (size_t)h->sw.mfma_qcap : std::min<size_t>((size_t)1 << 28, std::max<size_t>((size_t)1 << 20, (size_t)nq * 2048));
     MfmaParams MP{};
-    MP.S = S;
-    if (h->d_perm) {  // rows in transformed order: contiguous loads (the centroids once per index, the queries once per call)
-        HIPCK(h->ws_Qp.reserve((size_t)nq * h->D));
-        const long long tot = (long long)nq * h->D;
-        hipLaunchKernelGGL(k_permute_cols, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, S.Q, h->d_perm, h->ws_Qp.p, h->D, (long long)nq);
-        MP.S.Q = h->ws_Qp.p;
-        if (S.ivf) MP.S.coarse = h->d_coarseP;
-    }
-    MP.S.perm = nullptr;
-    MP.R = nullptr;
+    if ((rc = mfma_prepare(h, MP, S, pl, hb, qcap, sub, nsub, nchunks_f, npairs, nq, st))) return rc;
+    if (h->d_perm && (rc = use_permuted_queries(h, MP.S, S.ivf != 0, nq, st))) return rc;
+    MP.flat_lut = flat_lut;
     if (h->transform == MMIDX_TR_ROTATION) {
         // the pairs' exact rotated residuals, once per call (16 k multiply-adds per pair at D = 128 instead of one per survivor)
         HIPCK(h->ws_R.reserve((size_t)npairs * h->D));
@@ -1799,62 +1734,21 @@ int launch_mfma_common(mmidx_index *h, const ScanParams &S, ScanParams F, const 
         MP.R = h->ws_R.p;
         MP.flat_lut = nullptr;  // (k_flat_lut knows permutations only: the survivors' entries come from the rotated rows)
     }
-    MP.pq16 = h->d_pq16;
-    MP.xn = h->xn.p;
-    MP.pq = h->d_pq;
-    if (h->transform != MMIDX_TR_ROTATION) MP.flat_lut = flat_lut;
-    MP.gdesc = h->ws_gdesc.p;
-    MP.n_groups = h->ws_gfb.p;
-    MP.sub = sub;
-    MP.nsub = nsub;
-    MP.ep = h->pq_ep;
-    MP.xmax = h->rmax;
-    MP.ghist = h->ws_ghist.p;
-    MP.T0 = h->ws_T0.p;
-    MP.surv = h->ws_surv.p;
-    MP.surv_cnt = h->ws_mfctl.p;
-    MP.surv_cap = (u32)std::min<size_t>(qcap, 0xFFFFFFF0u);
-    MP.redo = h->ws_redo.p;
-    MP.pool_snap = h->ws_psnap.p;
-    MP.work = h->ws_mfctl.p + 8;
-    MP.fb_count = (u32 *)(h->ws_gfb.p + 1);
-    MP.fb_items = h->ws_gfb.p + 4;
-    MP.fb_ch = h->ws_gfb.p + 4 + nfb;
-    MP.fb_chunk = pl.chunk;
-    MP.fb_nchunks = std::max(nchunks_f, 1);
-    MP.npairs_flat = npairs;
-    MP.stat = (h->profiling == 1 || h->sw.debug_sync) ? (unsigned long long *)(h->d_counters + 3) : nullptr;
-    MP.nver = (unsigned long long *)(h->d_counters + 7);
     const MfmaLds L(h->D);
-    int rc;
     hipEvent_t *mev = nullptr;
-    if (h->profiling == 1 && h->mf_ev_used + 3 <= 3 * 4096) {
-        while (h->mf_ev.size() < h->mf_ev_used + 3) {
-            hipEvent_t e;
-            HIPCK(hipEventCreate(&e));
-            h->mf_ev.push_back(e);
-        }
-        mev = h->mf_ev.data() + h->mf_ev_used;
-        h->mf_ev_used += 3;
-        HIPCK(hipEventRecord(mev[0], st));
-    }
-    const int nj = h->D / 32;
-    if (h->dsub == 4) rc = nj == 4 ? launch_mfma_scan_t<4, 4>(h, MP, L.total, st) : nj == 2 ? launch_mfma_scan_t<2, 4>(h, MP, L.total, st) : launch_mfma_scan_t<1, 4>(h, MP, L.total, st);
-    else if (h->dsub == 8) rc = nj == 4 ? launch_mfma_scan_t<4, 8>(h, MP, L.total, st) : nj == 2 ? launch_mfma_scan_t<2, 8>(h, MP, L.total, st) : launch_mfma_scan_t<1, 8>(h, MP, L.total, st);
-    else rc = nj == 4 ? launch_mfma_scan_t<4, 16>(h, MP, L.total, st) : nj == 2 ? launch_mfma_scan_t<2, 16>(h, MP, L.total, st) : launch_mfma_scan_t<1, 16>(h, MP, L.total, st);
+    if (h->profiling == 1 && (rc = take_events(h->mf_ev, h->mf_ev_used, 3, 4096, st, mev))) return rc;
+    rc = for_nj_dsub(h->D / 32, h->dsub, [&](auto nj, auto ds) {
+        return launch_persistent<k_scan_mfma<decltype(nj)::value, decltype(ds)::value>>(h, MP, h->sw.mfma_blocks, MF_NT, L.total, st);
+    });
     if (rc) return rc;
     if (mev) HIPCK(hipEventRecord(mev[1], st));
     DBG_SYNC("K3m scan");
-    if (h->dsub == 4) rc = h->m == 32 ? launch_mfma_verify_t<32, 4>(h, MP, st) : h->m == 16 ? launch_mfma_verify_t<16, 4>(h, MP, st) : launch_mfma_verify_t<8, 4>(h, MP, st);
-    else if (h->dsub == 8) rc = h->m == 16 ? launch_mfma_verify_t<16, 8>(h, MP, st) : h->m == 8 ? launch_mfma_verify_t<8, 8>(h, MP, st) : launch_mfma_verify_t<4, 8>(h, MP, st);
-    else rc = h->m == 8 ? launch_mfma_verify_t<8, 16>(h, MP, st) : h->m == 4 ? launch_mfma_verify_t<4, 16>(h, MP, st) : launch_mfma_verify_t<2, 16>(h, MP, st);
+    rc = for_nj_dsub(h->D / 32, h->dsub, [&](auto nj, auto ds) { return launch_mfma_verify_t<decltype(nj)::value * 32 / decltype(ds)::value, decltype(ds)::value>(h, MP, st); });
     if (rc) return rc;
     if (mev) HIPCK(hipEventRecord(mev[2], st));
     if (MP.stat) hipLaunchKernelGGL(k_mfma_count, dim3(1024), dim3(256), 0, st, MP);  // (profiling runs only)
     DBG_SYNC("K3m verify");
-    const long long span = std::max<long long>(npairs, nq);
-    hipLaunchKernelGGL(k_mfma_redo, dim3((unsigned)((span + 255) / 256)), dim3(256), 0, st, MP, (long long)nq);
-    HIPCK(hipGetLastError());
+    if ((rc = launch_mfma_redo(MP, npairs, nq, st))) return rc;
     DBG_SYNC("K3m redo");
     if (h->sw.debug_sync) {
         u32 c16[16];
@@ -1865,13 +1759,7 @@ int launch_mfma_common(mmidx_index *h, const ScanParams &S, ScanParams F, const 
         fprintf(stderr, "[mmidx] K3m: %d groups of <= %d pairs x %d pieces of %d codes, %u survivors (cap %u), %d (pair, chunk) items handed to K3f (lds %zu)\n", g2[0], G,
                 nsub, sub, c16[0], MP.surv_cap, g2[1], L.total);
     }
-    // the queries K3m handed back (device-side count; normally none): the looping tail kernel alone
-    F.order = MP.fb_items;
-    F.n_order = (const int32_t *)MP.fb_count;
-    F.order_ch = MP.fb_ch;
-    F.n_items = (int)std::min<size_t>(nfb, (size_t)0x7fffff00);
-    F.xcd_remap = 0;
-    return launch_scan_filtered(h, F, pl, dim3((unsigned)F.n_items, 1), st, -1);
+    return hb.tail_filtered(h, F, pl, st);  // the queries K3m handed back (normally none)
 }
 
 // pass B over the sorted pairs (P.order / P.n_order as for K3f; per-cell counts and starts in ws_pcount / ws_pstart).
@@ -1936,12 +1824,9 @@ int launch_scan_grouped_flat(mmidx_index *h, const ScanParams &P, const SearchPl
             const dim3 g((unsigned)h->m, (unsigned)std::min<long long>(65535, nq - q0));
             const double *Qc = P.Q + (size_t)q0 * h->D;
             double *Lc = h->ws_flatlut.p + (size_t)q0 * h->m * 256;
-            switch (h->dsub) {
-                case 4: hipLaunchKernelGGL(k_flat_lut<4>, g, dim3(256), 0, st, Qc, h->d_perm, h->d_pqT, Lc, h->D, h->m, h->ks, h->dsub); break;
-                case 8: hipLaunchKernelGGL(k_flat_lut<8>, g, dim3(256), 0, st, Qc, h->d_perm, h->d_pqT, Lc, h->D, h->m, h->ks, h->dsub); break;
-                case 16: hipLaunchKernelGGL(k_flat_lut<16>, g, dim3(256), 0, st, Qc, h->d_perm, h->d_pqT, Lc, h->D, h->m, h->ks, h->dsub); break;
-                default: hipLaunchKernelGGL(k_flat_lut<0>, g, dim3(256), 0, st, Qc, h->d_perm, h->d_pqT, Lc, h->D, h->m, h->ks, h->dsub); break;
-            }
+            if (h->dsub == 4 || h->dsub == 8 || h->dsub == 16)
+                for_dsub(h->dsub, [&](auto ds) { hipLaunchKernelGGL(k_flat_lut<decltype(ds)::value>, g, dim3(256), 0, st, Qc, h->d_perm, h->d_pqT, Lc, h->D, h->m, h->ks, h->dsub); });
+            else hipLaunchKernelGGL(k_flat_lut<0>, g, dim3(256), 0, st, Qc, h->d_perm, h->d_pqT, Lc, h->D, h->m, h->ks, h->dsub);  // (the generic width)
         }
         HIPCK(hipGetLastError());
         flat_lut = h->ws_flatlut.p;
@@ -2140,18 +2025,8 @@ int search_batch_device(mmidx_index *h, const SearchPlan &pl, int k, int64_t nq,
     bool prof = h->profiling == 1, plight = h->profiling == 2;
     hipEvent_t *ev = nullptr;
     if (prof || plight) {
-        if (h->ev_used + 6 > 6 * 4096) {
-            prof = plight = false;  // event pool exhausted: call mmidx_get_stats to drain it
-        } else {
-            while (h->evpool.size() < h->ev_used + 6) {
-                hipEvent_t e;
-                HIPCK(hipEventCreate(&e));
-                h->evpool.push_back(e);
-            }
-            ev = h->evpool.data() + h->ev_used;
-            h->ev_used += 6;
-            if (prof) HIPCK(hipEventRecord(ev[0], st));
-        }
+        if (const int rc = take_events(h->evpool, h->ev_used, 6, 4096, st, ev, prof)) return rc;
+        if (!ev) prof = plight = false;  // event pool exhausted: call mmidx_get_stats to drain it
     }
     const int32_t *d_cells = d_cells_in;
     if (ivf && !d_cells) {
@@ -2384,12 +2259,7 @@ int search_batch_device(mmidx_index *h, const SearchPlan &pl, int k, int64_t nq,
                 SP.coarse = h->d_coarse;
                 SP.perm = h->d_perm;
                 if (h->d_perm && h->d_coarseP && !h->sw.smin_valu) {  // transformed copies: contiguous loads instead of 8-byte gathers
-                    HIPCK(h->ws_Qp.reserve((size_t)nq * h->D));
-                    const long long tot = (long long)nq * h->D;
-                    hipLaunchKernelGGL(k_permute_cols, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, dQ, h->d_perm, h->ws_Qp.p, h->D, (long long)nq);
-                    SP.Q = h->ws_Qp.p;
-                    SP.coarse = h->d_coarseP;
-                    SP.perm = nullptr;
+                    if (const int rc = use_permuted_queries(h, SP, true, nq, st)) return rc;
                 }
                 SP.cells = d_cells;
                 SP.cand = h->ws_cand.p;
@@ -2425,15 +2295,10 @@ int search_batch_device(mmidx_index *h, const SearchPlan &pl, int k, int64_t nq,
                     cand_list = h->ws_cand2.p;
                     hint_cand = nullptr;  // (the figure the host steers by is the first stage's input)
                 }
-                if (h->sw.smin_valu) {  // (A/B: the packed-FMA form)
-                    if (h->dsub == 16) hipLaunchKernelGGL(k_pair_smin<16>, sg, dim3(SMIN_NW * 64), 0, st, SP);
-                    else if (h->dsub == 8) hipLaunchKernelGGL(k_pair_smin<8>, sg, dim3(SMIN_NW * 64), 0, st, SP);
-                    else hipLaunchKernelGGL(k_pair_smin<4>, sg, dim3(SMIN_NW * 64), 0, st, SP);
-                } else {
-                    if (h->dsub == 16) hipLaunchKernelGGL(k_pair_smin_mfma<16>, sg, dim3(SMIN_NW * 64), 0, st, SP);
-                    else if (h->dsub == 8) hipLaunchKernelGGL(k_pair_smin_mfma<8>, sg, dim3(SMIN_NW * 64), 0, st, SP);
-                    else hipLaunchKernelGGL(k_pair_smin_mfma<4>, sg, dim3(SMIN_NW * 64), 0, st, SP);
-                }
+                for_dsub(h->dsub, [&](auto ds) {
+                    if (h->sw.smin_valu) hipLaunchKernelGGL(k_pair_smin<decltype(ds)::value>, sg, dim3(SMIN_NW * 64), 0, st, SP);  // (A/B: the packed-FMA form)
+                    else hipLaunchKernelGGL(k_pair_smin_mfma<decltype(ds)::value>, sg, dim3(SMIN_NW * 64), 0, st, SP);
+                });
                 HIPCK(hipGetLastError());
                 DBG_SYNC("K3s pair smin");
                 if (getenv("MMIDX_SMIN_DUMP")) {  // (debugging aid: how far above the thresholds the bounds lie)
