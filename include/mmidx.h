@@ -388,6 +388,7 @@ int mmidx_set_profiling(mmidx_index *h, int enabled);
  *   "coarse_v1": coarse stage by K1c/K1d (fp32 MFMA, full distance matrix) instead of K1e/K1f (env MMIDX_COARSE_V1)
  *   "coarse_fused": K1f as one kernel (front end + selection)
  *   "coarse_dma_kc": K1e with LDS-DMA also for vectors of several k chunks, Dp a multiple of 128 (default 1)
+ *   "coarse_groups": K1e for Dp = 128 as two staggered wave groups, a block of 256 queries per CU (default 1); 0 = the four-wave K1e' with two half-tile buffers
  *   "coarse_wave_sel": the coarse stage's exact selection by one wave per query where its tile applies (default 1); 0 = always a block per query
  *   "passa_q": pass A by K3q: 1 always (where the shape allows), 0 never, -1 = from 1.25 queries per non-empty list of a long-list index (default); K3q is tested before passa_hist, so passa_q = 0 is needed for passa_hist to take effect on long-list m = 16 indexes
  *   "passa_mfma": pass A by K3ma: 1 always (where the shape allows), 0 never, -1 = from 8 queries per list of a long-list index (default)
@@ -422,7 +423,8 @@ int mmidx_set_profiling(mmidx_index *h, int enabled);
 int mmidx_set_option(mmidx_index *h, const char *name, int value);
 int mmidx_get_stats(mmidx_index *h, mmidx_stats *out);
 /* Which kernel family served each stage of the most recent search sub-batch of this handle (ABI version 7), as text:
- * "coarse=<K1..>;pass_a=<K3 | K3h | K3ma | ..>;pre=<K3s | ->;pass_b=<K3m | K3mk | K3g | K3f.. | ->" (DESIGN.md section 5.0 lists the gates;
+ * "coarse=<K1..>;pass_a=<K3 | K3h | K3ma | ..>;pre=<K3s | ->;pass_b=<K3m | K3mk | K3g | K3f.. | ->;coarse_mm=<groups | dma | dma_kc | staged | ->"
+ * (coarse_mm: the form of K1e's matrix kernel, "-" where the coarse stage is not K1e; DESIGN.md section 5.0 lists the gates;
  * tests/test_gpu_dispatch.py asserts the table).  A sharded handle reports its first shard.  Diagnostic: not a stable format. */
 int mmidx_get_dispatch(mmidx_index *h, char *out, int cap);
 

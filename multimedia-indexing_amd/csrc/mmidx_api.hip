@@ -81,7 +81,7 @@ void mmidx_clear_error() { g_err.clear(); }
 // (include/mmidx.h lists the same names).
 struct Switches {
     int no_filter = 0, no_bound = 0, exact_coarse = 0, debug_sync = 0;
-    int coarse_v1 = 0, coarse_fused = 0, coarse_dma_kc = 1, coarse_wave_sel = 1;
+    int coarse_v1 = 0, coarse_fused = 0, coarse_dma_kc = 1, coarse_wave_sel = 1, coarse_groups = 1;
     int passa_q = -1, passa_mfma = -1, passa_mfma_wide = 1, passa_mfma_icnt_sat = 0, passa_hist = -1, passa_wide = 0;
     int passa_item_min = 4096, passa_item_margin = 1024;
     int smin_pre = -1, smin_bf16 = 1, smin_valu = 0;
@@ -117,6 +117,7 @@ const OptionRow kOptions[] = {
     {"coarse_v1", &Switches::coarse_v1, OPT_BOOL, "MMIDX_COARSE_V1", "coarse stage by K1c/K1d (fp32 MFMA, full distance matrix) instead of K1e/K1f"},
     {"coarse_fused", &Switches::coarse_fused, OPT_BOOL, nullptr, "K1f as one kernel (front end + selection)"},
     {"coarse_dma_kc", &Switches::coarse_dma_kc, OPT_BOOL, nullptr, "K1e with LDS-DMA also for vectors of several k chunks, Dp a multiple of 128 (default 1)"},
+    {"coarse_groups", &Switches::coarse_groups, OPT_BOOL, nullptr, "K1e for Dp = 128 as two staggered wave groups, a block of 256 queries per CU (default 1); 0 = the four-wave K1e' with two half-tile buffers"},
     {"coarse_wave_sel", &Switches::coarse_wave_sel, OPT_BOOL, nullptr, "the coarse stage's exact selection by one wave per query where its tile applies (default 1); 0 = always a block per query"},
     {"passa_q", &Switches::passa_q, OPT_RAW, nullptr, "pass A by K3q: 1 always (where the shape allows), 0 never, -1 = from 1.25 queries per non-empty list of a long-list index (default); "
      "K3q is tested before passa_hist, so passa_q = 0 is needed for passa_hist to take effect on long-list m = 16 indexes"},
@@ -278,7 +279,7 @@ struct mmidx_index {
     std::vector<hipEvent_t> mf_ev;   // K3m, full profiling: groups of 3 (scan start, scan end, verification end)
     size_t mf_ev_used = 0;
     // which kernel family served each stage of the most recent search sub-batch (mmidx_get_dispatch; host-side words, a few stores per call)
-    const char *disp_coarse = "-", *disp_passa = "-", *disp_passb = "-", *disp_pre = "-";
+    const char *disp_coarse = "-", *disp_passa = "-", *disp_passb = "-", *disp_pre = "-", *disp_coarse_mm = "-";
     // K3ma (pass A on the matrix cores, mmidx_scan_mfma_a.h)
     hipEvent_t host_ev[4] = {nullptr, nullptr, nullptr, nullptr};  // mmidx_search (host buffers): the answers' slices on their way back
     double *d_pqstat = nullptr;        // K3q: [m * dsub] mean_j p_sj[t], then [m] mean_j ||p_sj||^2
@@ -1893,13 +1894,25 @@ int run_coarse(mmidx_index *h, int64_t nq, const double *dQ, int32_t *d_cells, h
         const int ntiles = h->Cp / G16_BC;
         const int qblocks = (int)((nq + G16_BQ - 1) / G16_BQ);
         const int csplit = std::max(1, std::min(ntiles, (512 + qblocks - 1) / qblocks));
-        if (h->Dp == G16_KC) {
+        // K1e'' (two staggered wave groups, a block of 256 queries per CU): a grid of about one block per CU, and no more tiles
+        // to a block than it has room for norms beside its ring; where that cannot be had, K1e'
+        const int gqblocks = (int)((nq + G16G_BQ - 1) / G16G_BQ);
+        const int gsplit = std::max({1, std::min(ntiles, (std::max(h->num_cus, 1) + gqblocks - 1) / gqblocks), (ntiles + G16G_NORM_TILES - 1) / G16G_NORM_TILES});
+        h->disp_coarse_mm = "staged";
+        if (h->Dp == G16_KC && h->sw.coarse_groups && gsplit <= 65535) {
+            h->disp_coarse_mm = "groups";
+            hipLaunchKernelGGL(k_coarse_gmin16_grp, dim3((unsigned)gqblocks, (unsigned)gsplit), dim3(G16G_BLOCK), 0, st, (const __bf16 *)h->ws_Qh.p,
+                               (const __bf16 *)h->ws_Ql.p, (const __bf16 *)h->d_Ch, (const __bf16 *)h->d_Cl, h->d_cn_pad, h->ws_qn.p,
+                               (float2 *)h->ws_gmin.p, h->Cp, (int)nq, G);
+        } else if (h->Dp == G16_KC) {
             // one k chunk: centroid tiles by LDS-DMA into two half-tile buffers (static LDS)
+            h->disp_coarse_mm = "dma";
             hipLaunchKernelGGL(k_coarse_gmin16_dma, dim3((unsigned)qblocks, (unsigned)csplit), dim3(MMIDX_BLOCK), 0, st, (const __bf16 *)h->ws_Qh.p,
                                (const __bf16 *)h->ws_Ql.p, (const __bf16 *)h->d_Ch, (const __bf16 *)h->d_Cl, h->d_cn_pad, h->ws_qn.p,
                                (float2 *)h->ws_gmin.p, h->Cp, (int)nq, G);
         } else if (h->Dp > G16_KC && h->Dp % G16_KC == 0 && h->sw.coarse_dma_kc) {
             // several k chunks (long vectors): the same double buffering, (chunk, half tile) after (chunk, half tile)
+            h->disp_coarse_mm = "dma_kc";
             hipLaunchKernelGGL(k_coarse_gmin16_dma_kc, dim3((unsigned)qblocks, (unsigned)csplit), dim3(MMIDX_BLOCK), 0, st, (const __bf16 *)h->ws_Qh.p,
                                (const __bf16 *)h->ws_Ql.p, (const __bf16 *)h->d_Ch, (const __bf16 *)h->d_Cl, h->d_cn_pad, h->ws_qn.p,
                                (float2 *)h->ws_gmin.p, h->Cp, (int)nq, G, h->Dp);
@@ -1969,6 +1982,7 @@ int run_coarse(mmidx_index *h, int64_t nq, const double *dQ, int32_t *d_cells, h
     }
     if (approx) {
         h->disp_coarse = "K1c+K1d";
+        h->disp_coarse_mm = "-";
         // K1c + K1d: fp32 dot products for all centroids, fp64 only for the certified candidates
         HIPCK(h->ws_Q32.reserve((size_t)nq * h->D));
         HIPCK(h->ws_qn.reserve((size_t)nq));
@@ -2003,6 +2017,7 @@ int run_coarse(mmidx_index *h, int64_t nq, const double *dQ, int32_t *d_cells, h
         return MMIDX_OK;
     }
     h->disp_coarse = "K1a+K1b(exact)";
+    h->disp_coarse_mm = "-";
     dim3 g1((unsigned)((h->C + MMIDX_BLOCK - 1) / MMIDX_BLOCK), (unsigned)((nq + QT - 1) / QT));
     if ((int64_t)g1.x * g1.y < 2048) {  // few centroids and queries: a query a block, so that the chip has blocks to run
         g1.y = (unsigned)nq;
@@ -2107,7 +2122,7 @@ int search_batch_device(mmidx_index *h, const SearchPlan &pl, int k, int64_t nq,
         if (phase != 2) {
             h->disp_passb = "-";
             h->disp_pre = "-";
-            if (!ivf) h->disp_coarse = "-";
+            if (!ivf) h->disp_coarse = h->disp_coarse_mm = "-";
             if (two_pass && passa_q_applies(h, P, pl, (long long)nq) && !(h->sw.passa_mfma > 0 && passa_mfma_applies(h, P, pl, (long long)nq))) {
                 // K3q: the queries of a nearest list four to a block, decided on integers (mmidx_scan_q.h)
                 h->disp_passa = "K3q";
@@ -3787,7 +3802,7 @@ int mmidx_get_dispatch(mmidx_index *h, char *out, int cap) {
     const bool k3f_ok = s->code_bytes == 1 && s->ks <= 256 && (s->m == 8 || s->m == 16 || s->m == 32) && !s->sw.no_filter;
     const char *pb = s->disp_passb;
     if (!k3f_ok && pb[0] == 'K' && pb[1] == '3' && pb[2] == 'f') pb = "K3(exact scan: no K3f instance for this shape)";
-    snprintf(out, (size_t)cap, "coarse=%s;pass_a=%s;pre=%s;pass_b=%s", s->disp_coarse, s->disp_passa, s->disp_pre, pb);
+    snprintf(out, (size_t)cap, "coarse=%s;pass_a=%s;pre=%s;pass_b=%s;coarse_mm=%s", s->disp_coarse, s->disp_passa, s->disp_pre, pb, s->disp_coarse_mm);
     return MMIDX_OK;
 }
 

@@ -148,6 +148,11 @@ int combiner_submit(Combiner &c, SearchReq &me, int64_t max_q, Serve serve) {
 #define G16_BC 128     // centroids per tile
 #define G16_KC 128     // k per LDS tile
 #define G16_STRIDE 272 // bytes per LDS row: 256 + 16 (conflict-free 16-byte fragment reads)
+// K1e'' (k_coarse_gmin16_grp: two staggered wave groups, Dp == 128)
+#define G16G_BLOCK 512       // threads per block: 8 waves, group = wave >> 2
+#define G16G_BQ 256          // queries per block (32 per wave)
+#define G16G_RING 4          // half-tile buffers of 32 KiB
+#define G16G_NORM_TILES 64   // centroid tiles whose norms a block keeps in LDS beside the ring (4 x 32 KiB + 32 KiB = the CU's 160 KiB)
 
 // ---- calls across units (hidden: none of these is exported) ----------------------------------------------------------------
 extern "C" {

@@ -1342,6 +1342,295 @@ __global__ __launch_bounds__(MMIDX_BLOCK, 2) void k_coarse_gmin16_dma(const __bf
     }
 }
 
+// K1e'', Dp == 128: K1e' as two wave groups that run one phase apart.  One block of 8 waves per CU, 256 queries per block; wave v
+// keeps K1e's per-wave work unchanged (32 query rows, A fragments resident, all 128 columns of a tile in two halves, acc[2][8],
+// the same epilogue) and every accumulator sees the same sequence of matrix instructions, so gpair is K1e's bit for bit.
+// Group g = wave >> 2; waves v and v + 4 share a SIMD.  A tile is two phases -- its products (P: both halves, 192 matrix
+// instructions) and its minima + stores (M: about 600 vector instructions) -- each closed by ONE raw s_barrier of the whole
+// block.  Group 1 runs one phase behind group 0 (one extra barrier before its first phase, group 0 passes one after its last), so
+// a SIMD always pairs one wave's products with the other's minima: the matrix pipe and the vector pipe each have one wave to
+// serve, never two.  (With the tile in three phases -- half, half, minima -- one slot in three paired products with products, and
+// the kernel measured no faster than K1e'.)
+// All LDS is one array: a ring of four half-tile buffers (tile j = buffers 2 (j & 1), 2 (j & 1) + 1; XOR swizzle on the DMA's
+// source address as in K1e') and the block's centroid norms as clamped fp32, loaded once: no ordinary global load is left in
+// the loop (the compiler drains the DMA in front of one).  The DMA of a tile is issued by all 8 waves (8 instructions a wave)
+// and retired by a counted vmcnt.  Slots are the spans between barriers (barrier s closes slot s):
+//
+//   slot      group 0            group 1            DMA issued (slot start)            wait (retires)
+//   0         prologue           prologue           tile 0                             vmcnt(0): tile 0, the ordinary loads
+//   1         P(0) reads tile 0  --                 tile 1 (behind barrier 0)          --
+//   2j+2      M(j)               P(j) reads tile j  --                                 tile j+1   g0: vmcnt(8) behind its 8 stores
+//                                                                                                 g1: vmcnt(0) at the slot's end
+//   2j+3      P(j+1) reads j+1   M(j)               tile j+2 -> the buffers of tile j  --
+//
+//   * read after retire: tile j+1 is waited for by every wave in slot 2j+2 and first read in slot 2j+3, behind the barrier that
+//     follows the wait; group 1 reads it one barrier later still;
+//   * the wait's count: the stores of gpair count on vmcnt too, and a wave with rows past nq may skip some (the compiler
+//     branches around a store no lane executes).  A wave with all 32 rows below nq has issued exactly 8 stores since the DMA:
+//     vmcnt(8); any other wave waits vmcnt(0).  Group 1 waits in its products phase, where it stores nothing; its stores of
+//     M(j-1), a slot old and younger than the DMA, are waited for with it;
+//   * restage after read: the buffers of tile j are last read by group 1 in slot 2j+2 and refilled in slot 2j+3.  One barrier
+//     suffices here: every wave retires its LDS reads with an explicit lgkmcnt(0) in front of each barrier (G16G_SYNC; they
+//     have returned anyway, the matrix instructions that consume them are pinned in front of the barrier), so every read of
+//     the tile has completed when the first wave passes barrier 2j+2.  A second barrier would need a third tile
+//     buffer: 192 KiB;
+//   * the DMA of a tile has two slots to land (issued at the start of slot 2j+3, waited for at the end of slot 2j+4);
+//   * every wave executes 2T + 1 barriers for T tiles.
+// Rows past nq are clamped and their stores masked as in K1e'; a block with no tiles leaves before its first barrier.
+#define G16G_SYNC()                                          \
+    do {                                                     \
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   \
+        __builtin_amdgcn_sched_barrier(0);                   \
+        __builtin_amdgcn_s_barrier();                        \
+        __builtin_amdgcn_sched_barrier(0);                   \
+        asm volatile("" ::: "memory");                       \
+    } while (0)
+#ifdef G16_TIMING
+__device__ unsigned long long g16g_cycles[2][8];  // [group][products, barrier, minima, barrier, -, -, -, tiles] summed over blocks (wave 0 / 4, lane 0)
+#define G16G_STAMP(i)                                                          \
+    do {                                                                       \
+        const unsigned long long now_ = __builtin_amdgcn_s_memtime();          \
+        tacc[i] += now_ - tlast;                                               \
+        tlast = now_;                                                          \
+    } while (0)
+#else
+#define G16G_STAMP(i) \
+    do {              \
+    } while (0)
+#endif
+__global__ __launch_bounds__(G16G_BLOCK, 1) void k_coarse_gmin16_grp(const __bf16 *__restrict__ Qh, const __bf16 *__restrict__ Ql,
+                                                                  const __bf16 *__restrict__ Ch, const __bf16 *__restrict__ Cl,
+                                                                  const double *__restrict__ cn, const double *__restrict__ qn,
+                                                                  float2 *__restrict__ gpair, int Cp, int nq, int G) {
+    constexpr int Dp = G16_KC;               // 128 bf16 = 256 B = 16 units per row
+    constexpr int HROWS = G16_BC / 2;        // centroids per half tile
+    constexpr int HBYTES = HROWS * Dp * 2;   // 16 KiB per part (head / tail)
+    constexpr int BUFB = 2 * HBYTES;         // a ring buffer: head + tail of a half tile
+    constexpr int NORM0 = G16G_RING * BUFB;  // the norms follow the ring
+    __shared__ __attribute__((aligned(1024))) unsigned char lds[NORM0 + G16G_NORM_TILES * G16_BC * 4];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int grp = wave >> 2;
+    const int fr = lane & 15, fg = lane >> 4;
+    const int q0 = blockIdx.x * G16G_BQ + wave * 32;
+    const int ntiles = Cp / G16_BC;
+    const int t_per = (ntiles + gridDim.y - 1) / gridDim.y;  // (the host keeps this <= G16G_NORM_TILES)
+    const int t_lo = blockIdx.y * t_per, t_hi = (t_lo + t_per < ntiles) ? t_lo + t_per : ntiles;
+    if (t_lo >= t_hi) return;  // block-uniform, before the first barrier
+    const int T = t_hi - t_lo;
+    // DMA of half h of this block's range into ring buffer h & 3: 2 + 2 wave-instructions of 1 KiB (4 rows) per wave
+    auto issue = [&](const int h) {
+        unsigned char *buf = lds + (h & (G16G_RING - 1)) * BUFB;
+        const int row0 = t_lo * G16_BC + h * HROWS;
+#pragma unroll
+        for (int i = 0; i < 2; i++) {
+            const int pu = (i * 8 + wave) * 64 + lane;  // 16-byte slot of the part this lane fills
+            const int row = pu >> 4, slot = pu & 15;
+            const size_t src = ((size_t)(row0 + row) * Dp + (size_t)((slot ^ (row & 15)) * 8)) * 2;  // bytes
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)((const unsigned char *)Ch + src),
+                                             (__attribute__((address_space(3))) void *)(buf + (i * 8 + wave) * 1024), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)((const unsigned char *)Cl + src),
+                                             (__attribute__((address_space(3))) void *)(buf + HBYTES + (i * 8 + wave) * 1024), 16, 0, 0);
+        }
+    };
+    issue(0);
+    issue(1);
+    float qn_r[2][4];
+#pragma unroll
+    for (int rt = 0; rt < 2; rt++)
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            // (the load itself is unconditional, from a clamped row: a load under a condition is branched around and waited
+            //  for on its own, eight round trips in a row)
+            const int q = q0 + rt * 16 + 4 * fg + r;
+            const float v = (float)qn[q < nq ? q : nq - 1];
+            qn_r[rt][r] = q < nq ? v : 0.0f;
+        }
+    bf16x8 ah[2][4], al[2][4];  // A fragments: [row tile][k step of 32], resident for the whole block
+#pragma unroll
+    for (int rt = 0; rt < 2; rt++) {
+        int q = q0 + rt * 16 + fr;
+        q = q < nq ? q : nq - 1;
+#pragma unroll
+        for (int ks = 0; ks < 4; ks++) {
+            ah[rt][ks] = *(const bf16x8 *)(Qh + (size_t)q * Dp + ks * 32 + fg * 8);
+            al[rt][ks] = *(const bf16x8 *)(Ql + (size_t)q * Dp + ks * 32 + fg * 8);
+        }
+    }
+    // the block's centroid norms: fp32, the padding centroids' +inf clamped to a finite "far" (the conversion of K1e)
+    // (the loads of a pass are unconditional, from clamped positions, and issued together; the compiler still waits vmcnt(0) in
+    //  front of each of the four conditional LDS writes -- prologue only, one pass at the headline shape)
+    for (int i0 = 0; i0 < T * G16_BC; i0 += 4 * G16G_BLOCK) {
+        float cf[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const int i = i0 + k * G16G_BLOCK + tid;
+            cf[k] = (float)cn[(size_t)t_lo * G16_BC + (i < T * G16_BC ? i : T * G16_BC - 1)];
+        }
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const int i = i0 + k * G16G_BLOCK + tid;
+            if (i < T * G16_BC) ((float *)(lds + NORM0))[i] = cf[k] < 3.0e38f ? cf[k] : 3.0e38f;
+        }
+    }
+    f32x4 acc[2][8];
+    // the products of tile j: its 16 steps (half, k step of 32, pair of column tiles), K1e's order.  The four B fragments of a
+    // step are read during the step before into a second register set: with the SIMD's other wave in its minima nothing else fills
+    // the matrix pipe while a step waits for LDS (read and used in the same step, a tile took 4700 cycles instead of 3100)
+    auto tile_mma = [&](const int j) {
+        const unsigned char *tb = lds + (j & 1) * (2 * BUFB);  // halves 2j, 2j+1 = ring buffers 2 (j & 1), 2 (j & 1) + 1
+        bf16x8 bh[2][2], bl[2][2];                             // [register set][column tile of the pair]
+        auto read_b = [&](const int step, const int set) {
+            const int h = step >> 3, ks = (step >> 1) & 3, cp = (step & 1) * 2;
+#pragma unroll
+            for (int u = 0; u < 2; u++) {
+                const int row = (cp + u) * 16 + fr;
+                const int off = h * BUFB + row * (Dp * 2) + (((ks * 4 + fg) ^ fr) * 16);  // (row & 15 == fr)
+                bh[set][u] = *(const bf16x8 *)(tb + off);
+                bl[set][u] = *(const bf16x8 *)(tb + HBYTES + off);
+            }
+        };
+        read_b(0, 0);
+#pragma unroll
+        for (int step = 0; step < 16; step++) {
+            const int set = step & 1, ks = (step >> 1) & 3, c0 = (step >> 3) * 4 + (step & 1) * 2;
+#pragma unroll
+            for (int u = 0; u < 2; u++)
+#pragma unroll
+                for (int rt = 0; rt < 2; rt++)
+                    acc[rt][c0 + u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[rt][ks], bh[set][u], acc[rt][c0 + u], 0, 0, 0);
+            // (the reads of the next step go behind the first four products: the compiler waits for ALL LDS reads, lgkmcnt(0),
+            //  in front of a step's first product, so reads issued there would be waited for at once; here eight products
+            //  -- 128 cycles of the matrix pipe -- lie between the reads and that wait)
+            __builtin_amdgcn_sched_barrier(0);
+            if (step + 1 < 16) read_b(step + 1, set ^ 1);
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int u = 0; u < 2; u++)
+#pragma unroll
+                for (int rt = 0; rt < 2; rt++)
+                    acc[rt][c0 + u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[rt][ks], bl[set][u], acc[rt][c0 + u], 0, 0, 0);
+#pragma unroll
+            for (int u = 0; u < 2; u++)
+#pragma unroll
+                for (int rt = 0; rt < 2; rt++)
+                    acc[rt][c0 + u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[rt][ks], bh[set][u], acc[rt][c0 + u], 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    };
+    auto zero_acc = [&]() {
+#pragma unroll
+        for (int rt = 0; rt < 2; rt++)
+#pragma unroll
+            for (int ct = 0; ct < 8; ct++) acc[rt][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
+    };
+    // minima + stores of tile j of the block's range: the epilogue of K1e, the norms from LDS
+    auto minima = [&](const int j) {
+        const float *nrm = (const float *)(lds + NORM0) + j * G16_BC;
+        float cn_c[8];
+#pragma unroll
+        for (int ct = 0; ct < 8; ct++) cn_c[ct] = nrm[ct * 16 + fr];
+#pragma unroll
+        for (int rt = 0; rt < 2; rt++) {
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                float m1 = __int_as_float(0x7f7ffff8), m2 = m1;
+#pragma unroll
+                for (int ct = 0; ct < 8; ct++) {
+                    const float tv = __builtin_fmaf(-2.0f, acc[rt][ct][r], cn_c[ct]);
+                    const float tp = __int_as_float((__float_as_int(tv) & ~7) | ct);
+                    m2 = __builtin_amdgcn_fmed3f(m1, m2, tp);
+                    m1 = __builtin_amdgcn_fmed3f(m1, tp, -3.0e38f);
+                }
+                const int a1 = __float_as_int(m1) & 7;
+                const float d1 = m1 + qn_r[rt][r];
+                float d2 = m2 + qn_r[rt][r];
+                d2 = d2 < 0.0f ? 0.0f : d2;
+                const float m2p = __int_as_float((__float_as_int(d2) & ~7) | a1);
+                const int q = q0 + rt * 16 + 4 * fg + r;
+                if (q < nq) gpair[(size_t)q * G + (size_t)(t_lo + j) * 16 + fr] = make_float2(d1, m2p);
+            }
+        }
+    };
+#ifdef G16_TIMING
+    unsigned long long tacc[4] = {0, 0, 0, 0};
+#endif
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");  // halves 0 and 1, the fragments, the norms' LDS writes
+#pragma unroll
+    for (int rt = 0; rt < 2; rt++)
+#pragma unroll
+        for (int r = 0; r < 4; r++) asm volatile("" : "+v"(qn_r[rt][r]));  // (converted here: a later first use would wait for vmcnt(0) with DMA in flight)
+#pragma unroll
+    for (int rt = 0; rt < 2; rt++)
+#pragma unroll
+        for (int ks = 0; ks < 4; ks++) asm volatile("" : "+v"(ah[rt][ks]), "+v"(al[rt][ks]));  // (the same for the fragments)
+    G16G_SYNC();                                                            // barrier 0
+#ifdef G16_TIMING
+    unsigned long long tlast = __builtin_amdgcn_s_memtime();
+#endif
+    if (T > 1) {  // slot 1: tile 1, behind every ordinary load's wait
+        issue(2);
+        issue(3);
+    }
+    if (grp == 1) {  // slot 1: group 1 has no phase yet
+        G16G_SYNC();
+#ifdef G16_TIMING
+        tlast = __builtin_amdgcn_s_memtime();
+#endif
+    }
+    const bool full = q0 + 32 <= nq;  // wave-uniform: all eight stores of a tile are issued
+#pragma unroll 1
+    for (int j = 0; j < T; j++) {
+        const bool more = j + 1 < T;  // block-uniform
+        if (grp == 0) {
+            // slot 2j+1
+            if (j >= 1 && more) {
+                issue(2 * j + 2);
+                issue(2 * j + 3);
+            }
+            zero_acc();
+            tile_mma(j);
+            G16G_STAMP(0);
+            G16G_SYNC();
+            G16G_STAMP(1);
+            // slot 2j+2
+            minima(j);
+            if (more) {  // tile j+1: its 8 DMA instructions are older than the 8 stores of a full wave
+                if (full) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+                else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            }
+            G16G_STAMP(2);
+            G16G_SYNC();
+            G16G_STAMP(3);
+        } else {
+            // slot 2j+2
+            zero_acc();
+            tile_mma(j);
+            if (more) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // tile j+1 (and the stores of MIN(j-1), a slot old)
+            G16G_STAMP(0);
+            G16G_SYNC();
+            G16G_STAMP(1);
+            // slot 2j+3
+            if (j + 2 < T) {
+                issue(2 * j + 4);
+                issue(2 * j + 5);
+            }
+            minima(j);
+            G16G_STAMP(2);
+            if (more) {
+                G16G_SYNC();
+                G16G_STAMP(3);
+            }
+        }
+    }
+#ifdef G16_TIMING
+    if ((wave & 3) == 0 && lane == 0) {
+        for (int i = 0; i < 4; i++) atomicAdd(&g16g_cycles[grp][i], tacc[i]);
+        atomicAdd(&g16g_cycles[grp][7], (unsigned long long)T);
+    }
+#endif
+}
+
 // K1e' for long vectors (Dp a multiple of 128, e.g. the 1024 dimensions of YFCC100MExample.java:85): the same LDS-DMA double
 // buffering with the k chunks of a tile streamed through the two half-tile buffers one after the other -- (chunk, half) is the
 // unit -- the accumulators kept across the chunks of a tile, the query fragments of a chunk reloaded when the previous ones are dead.
