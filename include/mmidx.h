@@ -167,6 +167,31 @@ int mmidx_search_device(mmidx_index *h, int k, int64_t nq, const double *dQ, int
 int mmidx_search_sdc(mmidx_index *h, int k, int64_t nq, const int32_t *iids, int32_t *iid_out,
                      double *dist_out, int32_t *count_out);
 
+/* ---- queries by indexed id on IVFPQ and PQ, and the vectors behind the records ------------------------------
+ * An extension of the reference, which has no id query on IVFPQ (computeKnnIVFSDC returns null) and no getVector on a
+ * quantized index.  The stored record (list, code) of an internal id decodes to the vector the index holds for it:
+ *   z[s * dsub + t] = pq[s][code[s]][t];   y = z, or y[perm[i]] = z[i] (RandomPermutation), or
+ *   y[i] = sum_j z[j] * R[i][j] (RandomRotation, R orthogonal: fp64 from 0.0, j ascending, every product rounded before its add);
+ *   x = coarse[list] - y for IVFPQ (the residual is centroid - vector, IVFPQ.java:645), x = y for PQ.
+ * mmidx_reconstruct: X_out[n][D] for n internal ids, host arrays.  An unknown or negative id fails the call with
+ *   MMIDX_ERR_INVALID_ARG, message "Id does not exist!" (as mmidx_get_codes); X_out is then not written.
+ * mmidx_reconstruct_device: the same on device pointers, asynchronous on `stream`.  d_found_out[n] (may be NULL) is 1 for a
+ *   stored id and 0 for an unknown one, whose row is zeros.
+ * mmidx_search_ids: computeKnnIVFADC(k, x) (IVFPQ) / computeKnnADC(k, x) (PQ) with x the decoded vector of iids[i], on the search
+ *   path the handle would take for any vector; outputs as mmidx_search.  The query's own record is among the answers (as in
+ *   PQ.computeKnnSDC); its distance is rounding residue, not necessarily 0.  Every id is checked before any output is written:
+ *   an unknown id -> MMIDX_ERR_INVALID_ARG, "Id does not exist!".  The decoded vectors never visit the host.
+ * mmidx_search_ids_device: as mmidx_search_device.  The row of an unknown id comes back with count -1, ids -1 and distances
+ *   +inf; the other rows are unaffected.
+ * All four: IVFPQ and PQ handles, byte and short codes, every transformation, k as for mmidx_search; the quantizers must be
+ * loaded (MMIDX_ERR_NOT_READY); a sharded handle answers MMIDX_ERR_UNSUPPORTED. */
+int mmidx_reconstruct(mmidx_index *h, int64_t n, const int32_t *iids, double *X_out);
+int mmidx_reconstruct_device(mmidx_index *h, int64_t n, const int32_t *d_iids, double *dX_out, int32_t *d_found_out, void *stream);
+int mmidx_search_ids(mmidx_index *h, int k, int64_t nq, const int32_t *iids, int32_t *iid_out, double *dist_out,
+                     int32_t *count_out);
+int mmidx_search_ids_device(mmidx_index *h, int k, int64_t nq, const int32_t *d_iids, int32_t *d_iid_out,
+                            double *d_dist_out, int32_t *d_count_out, void *stream);
+
 /* computeNearestCoarseIndex (IVFPQ.java:547-564) for n device-resident vectors: d_cell_out[i] = the exact
  * fp64 argmin cell, first index wins ties.  Needs only the coarse quantizer (used by the codebook learner). */
 int mmidx_assign_device(mmidx_index *h, int64_t n, const double *dX, int32_t *d_cell_out, void *stream);

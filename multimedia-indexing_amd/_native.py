@@ -89,6 +89,10 @@ SIGNATURES = {
     "mmidx_search": (C.c_int, [_vp, C.c_int, C.c_int64, _dp, _i32p, _dp, _i32p]),
     "mmidx_search_sdc": (C.c_int, [_vp, C.c_int, C.c_int64, _i32p, _i32p, _dp, _i32p]),
     "mmidx_search_device": (C.c_int, [_vp, C.c_int, C.c_int64, _dp, _i32p, _dp, _i32p, _vp]),
+    "mmidx_reconstruct": (C.c_int, [_vp, C.c_int64, _i32p, _dp]),
+    "mmidx_reconstruct_device": (C.c_int, [_vp, C.c_int64, _i32p, _dp, _i32p, _vp]),
+    "mmidx_search_ids": (C.c_int, [_vp, C.c_int, C.c_int64, _i32p, _i32p, _dp, _i32p]),
+    "mmidx_search_ids_device": (C.c_int, [_vp, C.c_int, C.c_int64, _i32p, _i32p, _dp, _i32p, _vp]),
     "mmidx_coarse_device": (C.c_int, [_vp, C.c_int64, _dp, _i32p, _dp, _vp]),
     "mmidx_search_partial_device": (C.c_int, [_vp, C.c_int, C.c_int64, _dp, _i32p, _dp, _vp, _i32p, _vp]),
     "mmidx_shard_pass_a_device": (C.c_int, [_vp, C.c_int, C.c_int64, _dp, _i32p, _dp, _vp]),

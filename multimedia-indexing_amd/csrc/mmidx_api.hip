@@ -242,6 +242,10 @@ struct mmidx_index {
     DevBuf<int32_t> ws_inv;   // iid -> position in the list-major arrays (-1: absent), built on demand
     bool inv_valid = false;
     int64_t inv_size = 0;
+    // id queries and reconstruction (K10, mmidx_decode.h): the transposed rotation rotT[j][i] = R[i][j], built on first use; the
+    // call's ids and found flags on the device (host forms, and the fix-up of mmidx_search_ids_device)
+    double *d_rotT = nullptr;
+    DevBuf<int32_t> ws_idq, ws_found;
     DevBuf<int32_t> ws_gfb;
     DevBuf<int64_t> ws_flatoff;  // flat PQ through K3g: chunk offsets standing in for list offsets
     DevBuf<double> ws_flatlut;   // ... and the queries' exact lookup tables [nq][m][256] (k_flat_lut)
@@ -2718,6 +2722,9 @@ int mmidx_destroy(mmidx_index *h) {
     if (h->pin_grpx) (void)hipHostFree(h->pin_grpx);
     h->ws_T0.release();
     h->ws_inv.release();
+    if (h->d_rotT) (void)hipFree(h->d_rotT);
+    h->ws_idq.release();
+    h->ws_found.release();
     for (int e = 0; e < 4; e++)
         if (h->host_ev[e]) (void)hipEventDestroy(h->host_ev[e]);
     if (h->d_pqstat) (void)hipFree(h->d_pqstat);
@@ -3891,6 +3898,190 @@ int mmidx_distance(mmidx_index *h, int64_t n, const double *Q, const int32_t *ii
     if (d_out) (void)hipFree(d_out);
     if (d_cell) (void)hipFree(d_cell);
     if (e != hipSuccess) return mmidx_fail(MMIDX_ERR_HIP, "mmidx_distance failed: %s", hipGetErrorString(e));
+    return MMIDX_OK;
+}
+
+/* ---- queries by indexed id, and the vectors behind the records (K10, mmidx_decode.h) ------------------
+ * The reference stops here: IVFPQ.computeKnnIVFSDC returns null (IVFPQ.java:509-511).  The stored (list, code) of an id decodes to
+ * the vector the index holds for it; that vector is then an ordinary query of computeKnnIVFADC / computeKnnADC. */
+namespace {
+// what every call below needs before it launches: the lists folded, the iid -> position table, the transposed rotation.
+// The caller holds search_mu and has made the handle's device current.
+int idq_prepare(mmidx_index *h) {
+    std::lock_guard<std::mutex> lk(h->mu);
+    int rc = build_csr(h);
+    if (rc) return rc;
+    rc = ensure_inverse(h);
+    if (rc) return rc;
+    if (h->transform == MMIDX_TR_ROTATION && !h->d_rotT) {
+        if (!h->d_rot) return mmidx_fail(MMIDX_ERR_NOT_READY, "the handle has no rotation matrix");
+        double *t = nullptr;
+        HIPCK(hipMalloc((void **)&t, (size_t)h->D * h->D * sizeof(double)));
+        rc = mmidx_internal_transpose_square(h->d_rot, t, h->D, h->stream);
+        if (rc == MMIDX_OK && hipStreamSynchronize(h->stream) != hipSuccess) rc = mmidx_fail(MMIDX_ERR_HIP, "transposing the rotation failed");
+        if (rc) {
+            (void)hipFree(t);
+            return rc;
+        }
+        h->d_rotT = t;
+    }
+    return MMIDX_OK;
+}
+
+int idq_decode(mmidx_index *h, int64_t n, const int32_t *d_iids, double *dX, int32_t *d_found, hipStream_t st) {
+    MmidxDecodeArgs a{};
+    a.n = n;
+    a.d_iids = d_iids;
+    a.d_inv = h->ws_inv.p;
+    a.inv_size = h->inv_size;
+    a.d_off = h->d_off;
+    a.nlists = h->nlists;
+    a.n_csr = h->n_csr;
+    a.d_codes = h->d_codes;
+    a.code_bytes = (int)h->code_bytes;
+    a.d_pq = h->d_pq;
+    a.d_coarse = h->d_coarse;
+    a.d_perm = h->d_perm;
+    a.d_rotT = h->d_rotT;
+    a.D = h->D;
+    a.m = h->m;
+    a.ks = h->ks;
+    a.dsub = h->dsub;
+    a.transform = h->transform;
+    a.ivf = h->kind == MMIDX_KIND_IVFPQ;
+    a.dX = dX;
+    a.d_found = d_found;
+    return mmidx_internal_decode_records(&a, st);
+}
+
+// rows per round of the _device forms: the decoded queries of a round are one workspace of at most 256 MiB
+int64_t idq_round(const mmidx_index *h) { return std::max<int64_t>(MMIDX_COMB_MAX_Q, ((int64_t)256 << 20) / ((int64_t)h->D * 8)); }
+
+// host forms: the call's ids to the device (ws_idq), every one of them checked before anything is written
+int idq_upload_checked(mmidx_index *h, int64_t n, const int32_t *iids) {
+    HIPCK(h->ws_idq.reserve((size_t)n));
+    HIPCK(h->ws_found.reserve((size_t)n));
+    HIPCK(hipMemcpyAsync(h->ws_idq.p, iids, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
+    int rc = mmidx_internal_ids_found(h->ws_idq.p, n, h->ws_inv.p, h->inv_size, h->n_csr, h->ws_found.p, h->stream);
+    if (rc) return rc;
+    std::vector<int32_t> found((size_t)n);
+    HIPCK(hipMemcpyAsync(found.data(), h->ws_found.p, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCK(hipStreamSynchronize(h->stream));
+    for (int64_t i = 0; i < n; i++)
+        if (!found[(size_t)i]) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "Id does not exist!");  // IVFPQ.java:803-805, as mmidx_get_codes
+    return MMIDX_OK;
+}
+}  // namespace
+
+int mmidx_reconstruct_device(mmidx_index *h, int64_t n, const int32_t *d_iids, double *dX_out, int32_t *d_found_out, void *stream) {
+    if (!h) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null handle");
+    if (n < 0) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "n < 0");
+    if (n > 0 && (!d_iids || !dX_out)) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null argument");
+    NOT_ON_SHARDED(h, "mmidx_reconstruct_device");
+    int rc = check_ready(h);
+    if (rc) return rc;
+    if (n == 0) return MMIDX_OK;
+    rc = set_device(h);
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    DeviceCall call(h, st);
+    rc = idq_prepare(h);
+    if (rc) return rc;
+    return idq_decode(h, n, d_iids, dX_out, d_found_out, st);
+}
+
+int mmidx_reconstruct(mmidx_index *h, int64_t n, const int32_t *iids, double *X_out) {
+    if (!h) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null handle");
+    if (n < 0) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "n < 0");
+    if (n > 0 && (!iids || !X_out)) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null argument");
+    NOT_ON_SHARDED(h, "mmidx_reconstruct");
+    int rc = check_ready(h);
+    if (rc) return rc;
+    if (n == 0) return MMIDX_OK;
+    rc = set_device(h);
+    if (rc) return rc;
+    DeviceCall call(h, h->stream);
+    rc = idq_prepare(h);
+    if (rc) return rc;
+    rc = idq_upload_checked(h, n, iids);
+    if (rc) return rc;
+    for (int64_t q0 = 0; q0 < n; q0 += MMIDX_COMB_MAX_Q) {
+        const int64_t nb = std::min<int64_t>(MMIDX_COMB_MAX_Q, n - q0);
+        HIPCK(h->ws_Q.reserve((size_t)nb * h->D));
+        rc = idq_decode(h, nb, h->ws_idq.p + q0, h->ws_Q.p, nullptr, h->stream);
+        if (rc) return rc;
+        HIPCK(hipMemcpyAsync(X_out + (size_t)q0 * h->D, h->ws_Q.p, (size_t)nb * h->D * 8, hipMemcpyDeviceToHost, h->stream));
+        HIPCK(hipStreamSynchronize(h->stream));
+    }
+    return MMIDX_OK;
+}
+
+int mmidx_search_ids_device(mmidx_index *h, int k, int64_t nq, const int32_t *d_iids, int32_t *d_iid_out, double *d_dist_out, int32_t *d_count_out,
+                            void *stream) {
+    if (!h) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null handle");
+    if (nq < 0) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "nq < 0");
+    if (nq > 0 && (!d_iids || !d_iid_out || !d_dist_out || !d_count_out)) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null argument");
+    if (k < 1 || k > MMIDX_K_MAX) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "k must be in 1..%d (got %d)", MMIDX_K_MAX, k);
+    NOT_ON_SHARDED(h, "mmidx_search_ids_device");
+    int rc = check_ready(h);
+    if (rc) return rc;
+    if (nq == 0) return MMIDX_OK;
+    rc = set_device(h);
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    DeviceCall call(h, st);
+    const int64_t QB = idq_round(h);
+    for (int64_t q0 = 0; q0 < nq; q0 += QB) {
+        const int64_t nb = std::min(QB, nq - q0);
+        rc = idq_prepare(h);
+        if (rc) return rc;
+        if ((size_t)nb * h->D > h->ws_Q.cap || (size_t)nb > h->ws_found.cap) HIPCK(hipStreamSynchronize(st));  // (the round before still reads them)
+        HIPCK(h->ws_Q.reserve((size_t)nb * h->D));
+        HIPCK(h->ws_found.reserve((size_t)nb));
+        // the decoded vectors never leave the device: K10 writes the query workspace, the search reads it on the same stream
+        rc = idq_decode(h, nb, d_iids + q0, h->ws_Q.p, h->ws_found.p, st);
+        if (rc) return rc;
+        rc = search_common(h, k, nb, h->ws_Q.p, nullptr, 0, d_iid_out + (size_t)q0 * k, d_dist_out + (size_t)q0 * k, d_count_out + q0, nullptr, nullptr, st);
+        if (rc) return rc;
+        rc = mmidx_internal_mark_unknown_rows(h->ws_found.p, nb, k, d_iid_out + (size_t)q0 * k, d_dist_out + (size_t)q0 * k, d_count_out + q0, st);
+        if (rc) return rc;
+    }
+    return MMIDX_OK;
+}
+
+int mmidx_search_ids(mmidx_index *h, int k, int64_t nq, const int32_t *iids, int32_t *iid_out, double *dist_out, int32_t *count_out) {
+    if (!h) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null handle");
+    if (nq < 0) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "nq < 0");
+    if (nq > 0 && (!iids || !iid_out || !dist_out || !count_out)) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null argument");
+    if (k < 1 || k > MMIDX_K_MAX) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "k must be in 1..%d (got %d)", MMIDX_K_MAX, k);
+    NOT_ON_SHARDED(h, "mmidx_search_ids");
+    int rc = check_ready(h);
+    if (rc) return rc;
+    if (nq == 0) return MMIDX_OK;
+    rc = set_device(h);
+    if (rc) return rc;
+    DeviceCall call(h, h->stream);
+    rc = idq_prepare(h);
+    if (rc) return rc;
+    rc = idq_upload_checked(h, nq, iids);
+    if (rc) return rc;
+    for (int64_t q0 = 0; q0 < nq; q0 += MMIDX_COMB_MAX_Q) {
+        const int64_t nb = std::min<int64_t>(MMIDX_COMB_MAX_Q, nq - q0);
+        rc = idq_prepare(h);  // (records added since the round before move the positions)
+        if (rc) return rc;
+        HIPCK(h->ws_Q.reserve((size_t)nb * h->D));
+        HIPCK(h->ws_oiid.reserve((size_t)nb * k));
+        HIPCK(h->ws_odist.reserve((size_t)nb * k));
+        HIPCK(h->ws_ocnt.reserve((size_t)nb));
+        rc = idq_decode(h, nb, h->ws_idq.p + q0, h->ws_Q.p, nullptr, h->stream);
+        if (rc) return rc;
+        rc = search_common(h, k, nb, h->ws_Q.p, nullptr, 0, h->ws_oiid.p, h->ws_odist.p, h->ws_ocnt.p, nullptr, nullptr, h->stream);
+        if (rc) return rc;
+        HIPCK(hipMemcpyAsync(iid_out + (size_t)q0 * k, h->ws_oiid.p, (size_t)nb * k * 4, hipMemcpyDeviceToHost, h->stream));
+        HIPCK(hipMemcpyAsync(dist_out + (size_t)q0 * k, h->ws_odist.p, (size_t)nb * k * 8, hipMemcpyDeviceToHost, h->stream));
+        HIPCK(hipMemcpyAsync(count_out + q0, h->ws_ocnt.p, (size_t)nb * 4, hipMemcpyDeviceToHost, h->stream));
+        HIPCK(hipStreamSynchronize(h->stream));
+    }
     return MMIDX_OK;
 }
 

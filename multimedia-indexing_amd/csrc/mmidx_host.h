@@ -175,4 +175,30 @@ MMIDX_HIDDEN int mmidx_internal_select_topw(const double *d_dist, int C, int w, 
 // mmidx_frontend.hip: K7 on plain device pointers, Y[n][nc] = (X[n][ss] - mu[ss]) Vt[nc][ss]^T
 MMIDX_HIDDEN int mmidx_internal_gemm_nt(const double *X, const double *mu, const double *Vt, double *Y, long long n, int nc, int ss,
                                         void *stream);
+// mmidx_decode.hip: K10 on plain device pointers -- n records (by internal id) back to the vectors the index holds for them, dX[n][D];
+// d_found[n] (may be null) = 1 for a stored id, 0 for an unknown one, whose row is zeros
+struct MmidxDecodeArgs {
+    int64_t n;
+    const int32_t *d_iids;
+    const int32_t *d_inv;   // iid -> position, -1 = absent
+    int64_t inv_size;
+    const int64_t *d_off;   // [nlists + 1]
+    int nlists;
+    int64_t n_csr;
+    const void *d_codes;
+    int code_bytes;
+    const double *d_pq, *d_coarse;
+    const int32_t *d_perm;
+    const double *d_rotT;   // rotT[j][i] = R[i][j]
+    int D, m, ks, dsub, transform, ivf;
+    double *dX;
+    int32_t *d_found;
+};
+MMIDX_HIDDEN int mmidx_internal_decode_records(const MmidxDecodeArgs *a, hipStream_t st);
+// ... d_found[n] alone; d_dst[j][i] = d_src[i][j] of a D x D matrix; and the rows of an id query whose id is unknown (count -1, ids -1, +inf)
+MMIDX_HIDDEN int mmidx_internal_ids_found(const int32_t *d_iids, int64_t n, const int32_t *d_inv, int64_t inv_size, int64_t n_csr, int32_t *d_found,
+                                          hipStream_t st);
+MMIDX_HIDDEN int mmidx_internal_transpose_square(const double *d_src, double *d_dst, int D, hipStream_t st);
+MMIDX_HIDDEN int mmidx_internal_mark_unknown_rows(const int32_t *d_found, int64_t nq, int k, int32_t *d_iid, double *d_dist, int32_t *d_cnt,
+                                                  hipStream_t st);
 }  // extern "C"

@@ -275,13 +275,40 @@ class _PQBase(AbstractSearchStructure):
         return out_i, out_d, cnt
 
     def computeNearestNeighborsInternalById(self, k, iid):
-        # PQ: computeKnnSDC (PQ.java:334-374).  IVFPQ: computeKnnIVFSDC returns null in the reference
-        # (IVFPQ.java:509-511) -> the native call reports UNSUPPORTED.
+        # PQ: computeKnnSDC (PQ.java:334-374), the reference's behaviour.  (IVFPQ overrides this: the SDC call reports
+        # UNSUPPORTED on its handles, the reference's computeKnnIVFSDC being a stub.)
         if iid < 0:
             raise MmidxError(N.ERR_INVALID_ARG, "Id does not exist!")
         i, d, c = self.search_sdc_batch(k, np.array([iid], np.int32))
         n = int(c[0])
         return i[0, :n].copy(), d[0, :n].copy()
+
+    # -- queries by indexed id and the vectors behind the records (an extension of the reference: DESIGN.md section 5.9) --
+    def reconstruct(self, iids):
+        """[n][vectorLength]: the vector the index holds for each internal id -- the codebook rows its code selects, the
+        transformation undone, for IVFPQ subtracted from the centroid of its list.  An unknown id raises "Id does not exist!"."""
+        q = np.ascontiguousarray(np.asarray(iids).reshape(-1), np.int32)
+        out = np.zeros((q.shape[0], self.vectorLength), np.float64)
+        N.check(N.lib().mmidx_reconstruct(self._h, q.shape[0], q.ctypes.data, out.ctypes.data))
+        return out
+
+    def reconstructVector(self, id_):
+        """reconstruct by external id: the counterpart of Linear.getVector for a quantized index"""
+        iid = self.getInternalId(id_)
+        if iid == -1:
+            raise MmidxError(N.ERR_INVALID_ARG, "Id does not exist!")
+        return self.reconstruct([iid])[0]
+
+    def search_ids_batch(self, k, iids):
+        """search_batch with the reconstructed vectors of the given internal ids as the queries (they never leave the device):
+        computeKnnIVFADC / computeKnnADC on the handle's usual search path.  Every query's own record is among its answers."""
+        q = np.ascontiguousarray(np.asarray(iids).reshape(-1), np.int32)
+        nq = q.shape[0]
+        out = np.full((nq, max(k, 1)), -1, np.int32)
+        dists = np.full((nq, max(k, 1)), np.inf, np.float64)
+        counts = np.zeros(nq, np.int32)
+        N.check(N.lib().mmidx_search_ids(self._h, k, nq, q.ctypes.data, out.ctypes.data, dists.ctypes.data, counts.ctypes.data))
+        return out, dists, counts
 
     def export(self):
         """List-major snapshot (list_off [nlists+1], iids [n], codes [n][m] stored form)."""
@@ -484,6 +511,15 @@ class IVFPQ(_PQBase):
             self._iid_to_id[int(i)] = str(int(i))
             self._id_to_iid[str(int(i))] = int(i)
         self.loadCounter += len(iids)
+
+    def computeNearestNeighborsInternalById(self, k, iid):
+        # The reference's computeKnnIVFSDC returns null (IVFPQ.java:509-511).  Here the id's record is decoded on the device and
+        # searched as any vector (computeKnnIVFADC); the id's own record is among the answers, as in PQ.computeKnnSDC.
+        if iid < 0:
+            raise MmidxError(N.ERR_INVALID_ARG, "Id does not exist!")
+        i, d, c = self.search_ids_batch(k, [int(iid)])
+        n = int(c[0])
+        return i[0, :n].copy(), d[0, :n].copy()
 
     def getInvertedListId(self, id_):
         """IVFPQ.java:865-880: the inverted list (coarse cell) of the vector with the given id"""

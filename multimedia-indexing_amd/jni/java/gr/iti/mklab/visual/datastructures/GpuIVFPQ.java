@@ -213,9 +213,36 @@ public class GpuIVFPQ extends AbstractSearchStructure {
 		return nn;
 	}
 
-	/** hook 3 (ASS:342): IVFPQ.computeKnnIVFSDC returns null in the reference (IVFPQ.java:509-511) */
+	/**
+	 * hook 3 (ASS:342). This extends the reference, whose IVFPQ.computeKnnIVFSDC is a stub (IVFPQ.java:509-511) that makes
+	 * computeNearestNeighbors(k, String id) fail on an IVFPQ index. Here the record of iid (list, code) is decoded on the device to
+	 * the vector the index holds for it -- the codebook rows the code selects, the transformation undone, subtracted from the
+	 * list's centroid -- and that vector is searched as any query (computeKnnIVFADC). The id's own record is among the answers,
+	 * as in PQ.computeKnnSDC; its distance is rounding residue, not necessarily 0.
+	 */
 	protected BoundedPriorityQueue<Result> computeNearestNeighborsInternal(int k, int iid) throws Exception {
-		return null;
+		int[] iids = new int[k];
+		double[] dists = new double[k];
+		int[] count = new int[1];
+		MmidxNative.searchIds(handle, k, 1, new int[] { iid }, iids, dists, count);
+		BoundedPriorityQueue<Result> nn = new BoundedPriorityQueue<Result>(new Result(), k);
+		for (int i = count[0] - 1; i >= 0; i--) // worst first: keeps the queue's tie order
+			nn.offer(new Result(iids[i], dists[i]));
+		return nn;
+	}
+
+	/**
+	 * The vector the index holds for an indexed id (no counterpart in the reference, whose quantized indices keep no vectors):
+	 * what a re-indexing into new codebooks, or a query by id, starts from.
+	 */
+	public double[] reconstructVector(String id) throws Exception {
+		int iid = getInternalId(id);
+		if (iid == -1) {
+			throw new Exception("Id does not exist!");
+		}
+		double[] out = new double[vectorLength];
+		MmidxNative.reconstruct(handle, new int[] { iid }, out);
+		return out;
 	}
 
 	/** loadIndexInMemory IVFPQ.java:680-728: stream the BDB records to the native bulk add */

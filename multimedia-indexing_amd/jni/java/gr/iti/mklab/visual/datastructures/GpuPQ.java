@@ -168,6 +168,20 @@ public class GpuPQ extends AbstractSearchStructure {
 	}
 
 	/** native flat snapshot (mmidx_save / mmidx_load): the arrays loadIndexInMemory builds (PQ.java:436-483), for a fast restart */
+	/**
+	 * The vector the index holds for an indexed id: the codebook rows its code selects, with the transformation undone (no
+	 * counterpart in the reference, whose PQ keeps no vectors).
+	 */
+	public double[] reconstructVector(String id) throws Exception {
+		int iid = getInternalId(id);
+		if (iid == -1) {
+			throw new Exception("Id does not exist!");
+		}
+		double[] out = new double[vectorLength];
+		MmidxNative.reconstruct(handle, new int[] { iid }, out);
+		return out;
+	}
+
 	public synchronized void saveSnapshot(String filename) throws Exception {
 		MmidxNative.saveSnapshot(handle, filename);
 	}

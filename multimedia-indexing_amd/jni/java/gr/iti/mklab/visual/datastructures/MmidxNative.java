@@ -60,6 +60,16 @@ public final class MmidxNative {
 	public static native void searchSdc(long handle, int k, int nq, int[] queryIids, int[] iidOut, double[] distOut,
 			int[] countOut) throws Exception;
 
+	/**
+	 * mmidx_search_ids: queries are internal ids of an IVFPQ or PQ index; each id's stored record is decoded on the device and
+	 * searched as any vector (computeKnnIVFADC / computeKnnADC). An unknown id throws "Id does not exist!".
+	 */
+	public static native void searchIds(long handle, int k, int nq, int[] queryIids, int[] iidOut, double[] distOut,
+			int[] countOut) throws Exception;
+
+	/** mmidx_reconstruct: out[iids.length * vectorLength] = the vectors the index holds for the given internal ids */
+	public static native void reconstruct(long handle, int[] iids, double[] out) throws Exception;
+
 	public static native void listSizes(long handle, int[] out) throws Exception;
 
 	/** mmidx_save / mmidx_load (ABI 8): the native flat snapshot -- list offsets, iids and stored codes as loadIndexInMemory builds them */

@@ -305,6 +305,44 @@ done:
     (*env)->ReleaseIntArrayElements(env, countOut, cc, 0);
 }
 
+/* mmidx_search_ids: the queries are internal ids whose stored records are decoded on the device (IVFPQ and PQ) */
+JNIEXPORT void JNICALL JFN(searchIds)(JNIEnv *env, jclass c, jlong h, jint k, jint nq, jintArray queryIids, jintArray iidOut,
+                                      jdoubleArray distOut, jintArray countOut) {
+    jint *q, *ii, *cc;
+    jdouble *dd;
+    (void)c;
+    if (bad_len(env, queryIids, nq, 0, "queryIids") || bad_len(env, iidOut, (int64_t)nq * k, 0, "iidOut") ||
+        bad_len(env, distOut, (int64_t)nq * k, 0, "distOut") || bad_len(env, countOut, nq, 0, "countOut"))
+        return;
+    q = (*env)->GetIntArrayElements(env, queryIids, NULL);
+    ii = (*env)->GetIntArrayElements(env, iidOut, NULL);
+    dd = (*env)->GetDoubleArrayElements(env, distOut, NULL);
+    cc = (*env)->GetIntArrayElements(env, countOut, NULL);
+    CHECK(mmidx_search_ids(H(h), k, nq, (const int32_t *)q, (int32_t *)ii, dd, (int32_t *)cc));
+done:
+    (*env)->ReleaseIntArrayElements(env, queryIids, q, JNI_ABORT);
+    (*env)->ReleaseIntArrayElements(env, iidOut, ii, 0);
+    (*env)->ReleaseDoubleArrayElements(env, distOut, dd, 0);
+    (*env)->ReleaseIntArrayElements(env, countOut, cc, 0);
+}
+
+/* mmidx_reconstruct: out[iids.length][vectorLength], the vectors the index holds for the given internal ids */
+JNIEXPORT void JNICALL JFN(reconstruct)(JNIEnv *env, jclass c, jlong h, jintArray iids, jdoubleArray out) {
+    dims_t d;
+    jint n, *i;
+    jdouble *o;
+    (void)c;
+    if (bad_len(env, iids, 0, 0, "iids") || get_dims(env, h, &d)) return;
+    n = (*env)->GetArrayLength(env, iids);
+    if (bad_len(env, out, (int64_t)n * d.D, 0, "out")) return;
+    i = (*env)->GetIntArrayElements(env, iids, NULL);
+    o = (*env)->GetDoubleArrayElements(env, out, NULL);
+    CHECK(mmidx_reconstruct(H(h), n, (const int32_t *)i, o));
+done:
+    (*env)->ReleaseIntArrayElements(env, iids, i, JNI_ABORT);
+    (*env)->ReleaseDoubleArrayElements(env, out, o, 0);
+}
+
 JNIEXPORT void JNICALL JFN(listSizes)(JNIEnv *env, jclass c, jlong h, jintArray out) {
     dims_t d;
     jint *o;
