@@ -358,6 +358,29 @@ int mmidx_kmeans(int device, int64_t n, int d, int k, int max_iter, int64_t seed
                  const double *X, const double *init_centroids, double *centroids_out,
                  int32_t *assign_out, double *sse_out, int32_t *iters_out, int32_t *k_out);
 
+/* The whole product quantizer in one device-resident call (ProductQuantizationLearning.java:247-305):
+ * residual w.r.t. the nearest coarse centroid (centroid - x; coarse = NULL, C = 0: flat PQ, no residual), the transformation (perm /
+ * rot as for mmidx_create), then for each of the m sub-spaces k-means++ with the seeds 1..repeats, keeping the repeat of lowest
+ * squared error (a later repeat replaces the kept one only on sse < best).  Each (sub-space, seed) pair runs the algorithm of
+ * mmidx_kmeans with MMIDX_KMEANS_PLUS_PLUS, bit for bit the same centroids; all pairs share every kernel launch, and the host waits
+ * at most once per Lloyd iteration.  flags accepts MMIDX_KMEANS_NORMALIZE only.
+ * pq_out (host, [m][ks][dsub], the order of the product quantizer file): clusters that came out empty are rows of 1000.0
+ * (:285-302).  sse_out / seed_out / k_out / iters_out ([m] each, may be NULL): squared error, seed, number of real centroids and
+ * Lloyd iterations of the kept repeat.
+ * Refusals, all before any device call, pq_out untouched: a null dX or pq_out, a non-positive size, ks > n, n >= 2^31, other flags,
+ * a transformation without its perm / rot -> MMIDX_ERR_INVALID_ARG; D % m != 0 -> MMIDX_ERR_INVALID_SUBVECTORS.
+ * Envelope: dsub = D / m <= 16 and ks * dsub * 8 <= 64 KiB (a job's table lives in LDS), else MMIDX_ERR_UNSUPPORTED: such callers
+ * keep mmidx_kmeans per sub-space.  When all m * repeats pairs do not fit the memory (or 2^31 - 1 sort items) at once they run in
+ * groups, which changes no bit of the result; the environment variable MMIDX_PQ_LEARN_GROUP caps the pairs per group (tests). */
+int mmidx_pq_learn_device(int device, int64_t n, int D, int m, int ks, int max_iter, int repeats, int flags,
+                          const double *dX, int C, const double *coarse, int transform, const int32_t *perm,
+                          const double *rot, double *pq_out, double *sse_out, int32_t *seed_out, int32_t *k_out,
+                          int32_t *iters_out, void *stream);
+int mmidx_pq_learn(int device, int64_t n, int D, int m, int ks, int max_iter, int repeats, int flags,
+                   const double *X, int C, const double *coarse, int transform, const int32_t *perm,
+                   const double *rot, double *pq_out, double *sse_out, int32_t *seed_out, int32_t *k_out,
+                   int32_t *iters_out);
+
 /* ---- instrumentation -------------------------------------------------------------------------
  * Per-handle statistics accumulated over the search calls since the last mmidx_get_stats, measured
  * with HIP events recorded on the stream the kernels are launched on (no host synchronisation

@@ -139,6 +139,10 @@ SIGNATURES = {
                                       _i32p, _i32p, _vp]),
     "mmidx_kmeans": (C.c_int, [C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, _dp, _dp, _dp, _i32p, _dp, _i32p,
                                _i32p]),
+    "mmidx_pq_learn_device": (C.c_int, [C.c_int, C.c_int64] + [C.c_int] * 6 + [_dp, C.c_int, _dp, C.c_int, _i32p, _dp, _dp, _dp, _i32p,
+                                        _i32p, _i32p, _vp]),
+    "mmidx_pq_learn": (C.c_int, [C.c_int, C.c_int64] + [C.c_int] * 6 + [_dp, C.c_int, _dp, C.c_int, _i32p, _dp, _dp, _dp, _i32p, _i32p,
+                                 _i32p]),
     "mmidx_create_sharded": (C.c_int, [C.c_int] * 6 + [_vp, _vp, C.c_int, _vp, C.POINTER(C.c_void_p)]),
     "mmidx_shard_count": (C.c_int, [_vp, C.POINTER(C.c_int)]),
     "mmidx_shard_info": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_int)]),

@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "mmidx_host.h"
+#include "mmidx_learn_kernels.h"
 
 namespace {
 
@@ -419,6 +420,352 @@ int mmidx_kmeans(int device, int64_t n, int d, int k, int max_iter, int64_t seed
     if (rc) return rc;
     if (assign_out) HIPCK(hipMemcpy(assign_out, dA.p, (size_t)n * 4, hipMemcpyDeviceToHost));
     return MMIDX_OK;
+}
+
+}  // extern "C"
+
+// ---- the product quantizer in one device-resident call ------------------------------------------------------
+namespace {
+
+// pinned host memory of one call (uploads and read-backs that overlap the stream)
+template <typename T>
+struct PinnedBuf {
+    T *p = nullptr;
+    ~PinnedBuf() {
+        if (p) (void)hipHostFree(p);
+    }
+    hipError_t alloc(size_t n) { return hipHostMalloc((void **)&p, std::max<size_t>(n, 1) * sizeof(T), hipHostMallocDefault); }
+};
+
+struct PlJobResult {
+    std::vector<double> cent;  // [k_eff][dsub]
+    double sse = 0.0;
+    int k_eff = 0, iters = 0;
+};
+
+// everything the groups of one call share
+struct PlCtx {
+    hipStream_t st = nullptr;
+    long long n = 0, ntl = 0;
+    int m = 0, ks = 0, dsub = 0, DS = 0, max_iter = 0, repeats = 0, G = 0;
+    bool normalize = false;
+    const double *Y = nullptr, *W = nullptr;  // [m][n][dsub]: the data, and the space the clustering runs in (the normalised copy, or Y itself)
+    ScopedBuf<int32_t> assign, iota, sorted, pick, cnt, ctlB;
+    ScopedBuf<uint32_t> keys_in, keys_out;
+    ScopedBuf<double> mind2, tsum, tinc, prob, Ctab, Cfin, sse;
+    ScopedBuf<PlSlot> slots;
+    ScopedBuf<unsigned char> stmp;
+    size_t stmp_bytes = 0;
+    PinnedBuf<PlSlot> h_slots;
+    PinnedBuf<int32_t> h_pick0, h_cnt, h_ctlB;
+    PinnedBuf<double> h_prob, h_sse, h_cent;
+};
+
+template <int DS>
+void pl_launch_assign(const PlCtx &c, int nact, size_t lds) {
+    hipLaunchKernelGGL(k_pl_assign<DS>, dim3((unsigned)((c.n + PL_APTS - 1) / PL_APTS), (unsigned)nact), dim3(PL_BLOCK), lds, c.st, c.W, c.slots.p,
+                       c.Ctab.p, c.assign.p, c.keys_in.p, c.cnt.p, (uint32_t *)(c.cnt.p + (size_t)nact * c.ks), c.n, c.dsub, c.ks);
+}
+
+// jobs g0 .. g0 + Gc of the call, start to finish: seeding, Lloyd iterations, squared error, reported centroids
+int pl_run_group(PlCtx &c, int g0, int Gc, std::vector<PlJobResult> &res) {
+    const long long n = c.n;
+    const int ks = c.ks, dsub = c.dsub, G = c.G;
+    hipStream_t st = c.st;
+    // ---- seeding: every draw comes from the job's own JavaRandom(seed) and none depends on the data, so all are made up front
+    for (int jl = 0; jl < Gc; jl++) {
+        const int g = g0 + jl;
+        JavaRandom rnd((long long)(g % c.repeats) + 1);
+        c.h_pick0.p[(size_t)jl * ks] = rnd.nextInt((int)n);  // (the rest of the row is written by the pick kernel)
+        for (int t = 0; t + 1 < ks; t++) c.h_prob.p[(size_t)jl * (ks - 1) + t] = rnd.nextDouble();
+        c.h_slots.p[jl] = PlSlot{jl, g / c.repeats, ks, 1};
+    }
+    HIPCK(hipMemcpyAsync(c.pick.p, c.h_pick0.p, (size_t)Gc * ks * 4, hipMemcpyHostToDevice, st));
+    HIPCK(hipMemcpyAsync(c.prob.p, c.h_prob.p, (size_t)Gc * (ks - 1) * 8, hipMemcpyHostToDevice, st));
+    HIPCK(hipMemcpyAsync(c.slots.p, c.h_slots.p, (size_t)Gc * sizeof(PlSlot), hipMemcpyHostToDevice, st));
+    for (int t = 1; t < ks; t++) {
+        hipLaunchKernelGGL(k_pl_pp_update, dim3((unsigned)c.ntl, (unsigned)Gc), dim3(PL_BLOCK), 0, st, c.W, c.slots.p, c.pick.p, c.mind2.p,
+                           c.tsum.p, n, dsub, ks, t, c.ntl);
+        hipLaunchKernelGGL(k_pl_pp_pick, dim3((unsigned)Gc), dim3(PL_BLOCK), 0, st, c.mind2.p, c.tsum.p, c.tinc.p, c.prob.p, c.slots.p, c.pick.p,
+                           n, ks, t, c.ntl);
+    }
+    hipLaunchKernelGGL(k_pl_gather_seeds, dim3((unsigned)((ks * dsub + PL_BLOCK - 1) / PL_BLOCK), (unsigned)Gc), dim3(PL_BLOCK), 0, st, c.W,
+                       c.slots.p, c.pick.p, c.Ctab.p, n, dsub, ks);
+    HIPCK(hipGetLastError());
+
+    // ---- Lloyd iterations: one wait per iteration for all jobs together ---------------------------------------------------------
+    std::vector<int> k_eff((size_t)Gc, ks), iters((size_t)Gc, 0), force((size_t)Gc, 1), act((size_t)Gc);
+    for (int jl = 0; jl < Gc; jl++) act[(size_t)jl] = jl;
+    // ctlB: kept [G] | done list [G] | rng_a [G][ks] | rng_b [G][ks] | remap [G][ks]
+    int32_t *hb_kept = c.h_ctlB.p, *hb_done = hb_kept + G, *hb_a = hb_done + G, *hb_b = hb_a + (size_t)G * ks, *hb_remap = hb_b + (size_t)G * ks;
+    const int32_t *db_kept = c.ctlB.p, *db_done = db_kept + G, *db_a = db_done + G, *db_b = db_a + (size_t)G * ks, *db_remap = db_b + (size_t)G * ks;
+    const size_t ctlB_ints = 2 * (size_t)G + 3 * (size_t)G * ks;
+    const unsigned cgrid = (unsigned)((ks * dsub + PL_BLOCK - 1) / PL_BLOCK);
+    std::vector<int> next_act;
+    next_act.reserve((size_t)Gc);
+    while (!act.empty()) {
+        const int nact = (int)act.size();
+        const size_t cnt_ints = (size_t)nact * ks + (size_t)nact;  // the live slots only: counts [slot][ks], then changed [slot]
+        int kmax = 0;
+        for (int s = 0; s < nact; s++) {
+            const int jl = act[(size_t)s];
+            iters[(size_t)jl]++;
+            c.h_slots.p[s] = PlSlot{jl, (g0 + jl) / c.repeats, k_eff[(size_t)jl], force[(size_t)jl]};
+            kmax = std::max(kmax, k_eff[(size_t)jl]);
+        }
+        HIPCK(hipMemcpyAsync(c.slots.p, c.h_slots.p, (size_t)nact * sizeof(PlSlot), hipMemcpyHostToDevice, st));
+        HIPCK(hipMemsetAsync(c.cnt.p, 0, cnt_ints * 4, st));
+        const size_t lds = (size_t)kmax * dsub * 8 + (size_t)kmax * 4;
+        if (c.DS == 4) pl_launch_assign<4>(c, nact, lds);
+        else if (c.DS == 8) pl_launch_assign<8>(c, nact, lds);
+        else pl_launch_assign<16>(c, nact, lds);
+        HIPCK(hipGetLastError());
+        HIPCK(hipMemcpyAsync(c.h_cnt.p, c.cnt.p, cnt_ints * 4, hipMemcpyDeviceToHost, st));
+        // stable grouping of all active jobs' points by (slot, cluster)
+        int bits = 1;
+        while ((1ll << bits) < (long long)nact * ks) bits++;
+        const int items = (int)((long long)nact * n);
+        size_t need = 0;
+        HIPCK(hipcub::DeviceRadixSort::SortPairs(nullptr, need, c.keys_in.p, c.keys_out.p, c.iota.p, c.sorted.p, items, 0, bits, st));
+        if (need > c.stmp_bytes) {  // (sized for the largest sort; fewer items are not expected to ask for more)
+            HIPCK(hipStreamSynchronize(st));
+            HIPCK(hipFree(c.stmp.p));
+            c.stmp.p = nullptr;
+            HIPCK(c.stmp.alloc(need));
+            c.stmp_bytes = need;
+        }
+        HIPCK(hipcub::DeviceRadixSort::SortPairs(c.stmp.p, c.stmp_bytes, c.keys_in.p, c.keys_out.p, c.iota.p, c.sorted.p, items, 0, bits, st));
+        HIPCK(hipStreamSynchronize(st));
+
+        // host: who is done, which clusters emptied (SimpleKMeans: m_NumClusters -= emptyClusterCount; the survivors keep their order)
+        int ndone = 0;
+        next_act.clear();
+        for (int s = 0; s < nact; s++) {
+            const int jl = act[(size_t)s], ke = k_eff[(size_t)jl];
+            const int32_t *cn = c.h_cnt.p + (size_t)s * ks;
+            const uint32_t moved = (uint32_t)c.h_cnt.p[(size_t)nact * ks + s];
+            long long off = (long long)s * n;
+            int kept = 0;
+            for (int k = 0; k < ke; k++) {
+                hb_remap[(size_t)s * ks + k] = cn[k] > 0 ? kept : -1;
+                if (cn[k] > 0) {
+                    hb_a[(size_t)s * ks + kept] = (int32_t)off;
+                    hb_b[(size_t)s * ks + kept] = (int32_t)(off + cn[k]);
+                    kept++;
+                }
+                off += cn[k];
+            }
+            hb_kept[s] = kept;
+            const bool done = moved == 0 || iters[(size_t)jl] >= c.max_iter;
+            force[(size_t)jl] = kept != ke;  // numbering changed: everything counts as moved, for this job only
+            k_eff[(size_t)jl] = kept;
+            if (done) hb_done[ndone++] = s;
+            else next_act.push_back(jl);
+        }
+        HIPCK(hipMemcpyAsync(c.ctlB.p, c.h_ctlB.p, ctlB_ints * 4, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_pl_means, dim3(cgrid, (unsigned)nact), dim3(PL_BLOCK), 0, st, c.W, c.slots.p, (const int32_t *)nullptr, c.sorted.p, db_a,
+                           db_b, db_kept, c.Ctab.p, n, dsub, ks);
+        if (ndone) {
+            // the squared error in the space the clustering ran in, summed in index order; with normalisation the reported
+            // centroids are the means of the original members (SimpleKMeans.moveCentroid)
+            hipLaunchKernelGGL(k_pl_sqerr, dim3((unsigned)((n + PL_BLOCK - 1) / PL_BLOCK), (unsigned)ndone), dim3(PL_BLOCK), 0, st, c.W, c.slots.p,
+                               db_done, c.Ctab.p, c.assign.p, db_remap, c.mind2.p, n, dsub, ks);
+            hipLaunchKernelGGL(k_pl_seqsum, dim3((unsigned)ndone), dim3(PL_BLOCK), 0, st, c.mind2.p, c.slots.p, db_done, c.sse.p, n);
+            if (c.normalize)
+                hipLaunchKernelGGL(k_pl_means, dim3(cgrid, (unsigned)ndone), dim3(PL_BLOCK), 0, st, c.Y, c.slots.p, db_done, c.sorted.p, db_a, db_b,
+                                   db_kept, c.Cfin.p, n, dsub, ks);
+        }
+        HIPCK(hipGetLastError());
+        act.swap(next_act);
+    }
+    HIPCK(hipMemcpyAsync(c.h_sse.p, c.sse.p, (size_t)Gc * 8, hipMemcpyDeviceToHost, st));
+    HIPCK(hipMemcpyAsync(c.h_cent.p, c.normalize ? c.Cfin.p : c.Ctab.p, (size_t)Gc * ks * dsub * 8, hipMemcpyDeviceToHost, st));
+    HIPCK(hipStreamSynchronize(st));
+    for (int jl = 0; jl < Gc; jl++) {
+        PlJobResult &r = res[(size_t)(g0 + jl)];
+        r.k_eff = k_eff[(size_t)jl];
+        r.iters = iters[(size_t)jl];
+        r.sse = c.h_sse.p[jl];
+        r.cent.assign(c.h_cent.p + (size_t)jl * ks * dsub, c.h_cent.p + ((size_t)jl * ks + r.k_eff) * dsub);
+    }
+    return MMIDX_OK;
+}
+
+// the refusals that need no device, shared by the host and the device entry
+int pl_check_args(int64_t n, int D, int m, int ks, int max_iter, int repeats, int flags, const void *X, int C, const double *coarse, int transform,
+                  const int32_t *perm, const double *rot, const double *pq_out) {
+    if (!X || !pq_out) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "pq learn: null argument (the vectors and pq_out are required)");
+    if (n < 1 || D < 1 || m < 1 || ks < 1 || max_iter < 1 || repeats < 1)
+        return mmidx_fail(MMIDX_ERR_INVALID_ARG, "pq learn: n, D, m, ks, max_iter and repeats must be positive");
+    if ((int64_t)ks > n) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "pq learn: ks = %d exceeds the %lld vectors", ks, (long long)n);
+    if (flags & ~MMIDX_KMEANS_NORMALIZE) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "pq learn: flags accepts MMIDX_KMEANS_NORMALIZE only (the seeding is always k-means++)");
+    if (C < 0 || (C > 0 && !coarse) || (C == 0 && coarse))
+        return mmidx_fail(MMIDX_ERR_INVALID_ARG, "pq learn: C coarse centroids need a coarse array, and none (flat PQ) is C = 0 with NULL");
+    if (D % m) return mmidx_fail(MMIDX_ERR_INVALID_SUBVECTORS, "The given number of subvectors is not valid!");
+    if (transform != MMIDX_TR_NONE && transform != MMIDX_TR_ROTATION && transform != MMIDX_TR_PERMUTATION)
+        return mmidx_fail(MMIDX_ERR_INVALID_ARG, "pq learn: unknown transformation %d", transform);
+    if (transform == MMIDX_TR_PERMUTATION && !perm) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "pq learn: a permutation needs perm[D]");
+    if (transform == MMIDX_TR_ROTATION && !rot) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "pq learn: a rotation needs rot[D][D]");
+    if (n > (int64_t)INT32_MAX) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "pq learn: more than 2^31 - 1 vectors");  // point indices, the JDK draws
+    const int dsub = D / m;
+    if (dsub > PL_MAX_DSUB)
+        return mmidx_fail(MMIDX_ERR_UNSUPPORTED, "pq learn: dsub = %d exceeds the limit dsub <= %d of the batched learner (use mmidx_kmeans per sub-space)", dsub,
+                          PL_MAX_DSUB);
+    if ((int64_t)ks * dsub * 8 > 65536)
+        return mmidx_fail(MMIDX_ERR_UNSUPPORTED, "pq learn: a table of ks x dsub = %d x %d doubles exceeds the limit ks * dsub * 8 <= 64 KiB of LDS", ks, dsub);
+    if ((int64_t)m * repeats > (int64_t)INT32_MAX) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "pq learn: m * repeats exceeds 2^31 - 1");
+    return MMIDX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mmidx_pq_learn_device(int device, int64_t n, int D, int m, int ks, int max_iter, int repeats, int flags, const double *dX, int C,
+                          const double *coarse, int transform, const int32_t *perm, const double *rot, double *pq_out, double *sse_out,
+                          int32_t *seed_out, int32_t *k_out, int32_t *iters_out, void *stream) {
+    int rc = pl_check_args(n, D, m, ks, max_iter, repeats, flags, dX, C, coarse, transform, perm, rot, pq_out);
+    if (rc) return rc;
+    if (mmidx_device_count() < 1) return mmidx_fail(MMIDX_ERR_NO_DEVICE, "no HIP device: libmmidx_hip has no CPU fallback");
+    HIPCK(hipSetDevice(device));
+    hipStream_t st = (hipStream_t)stream;
+    const int dsub = D / m, J = m * repeats;
+    const size_t nd = (size_t)n * D;
+    PlCtx c;
+    c.st = st;
+    c.n = n;
+    c.ntl = (n + PL_TILE - 1) / PL_TILE;
+    c.m = m;
+    c.ks = ks;
+    c.dsub = dsub;
+    c.DS = dsub <= 4 ? 4 : dsub <= 8 ? 8 : 16;
+    c.max_iter = max_iter;
+    c.repeats = repeats;
+    c.normalize = (flags & MMIDX_KMEANS_NORMALIZE) != 0;
+
+    // ---- prep: nearest coarse centroid, residual, transform, sub-space-major; the normalised copy -------------------------------
+    ScopedBuf<double> Y, Yn, mn, mx, d_coarse, d_rot;
+    ScopedBuf<int32_t> d_cell, d_perm;
+    HIPCK(Y.alloc(nd));
+    if (C > 0) {
+        HIPCK(d_cell.alloc((size_t)n));
+        HIPCK(d_coarse.alloc((size_t)C * D));
+        HIPCK(hipMemcpyAsync(d_coarse.p, coarse, (size_t)C * D * 8, hipMemcpyHostToDevice, st));
+        mmidx_index *h = nullptr;  // one scratch handle for the whole call
+        rc = mmidx_create(MMIDX_KIND_IVFPQ, D, 1, 2, C, MMIDX_TR_NONE, nullptr, nullptr, device, &h);
+        if (!rc) rc = mmidx_set_coarse(h, coarse);
+        if (!rc) rc = mmidx_assign_device(h, n, dX, d_cell.p, st);
+        if (!rc && hipStreamSynchronize(st) != hipSuccess) rc = mmidx_fail(MMIDX_ERR_HIP, "pq learn: the coarse assignment failed");
+        if (h) mmidx_destroy(h);
+        if (rc) return rc;
+    }
+    if (transform == MMIDX_TR_PERMUTATION) {
+        HIPCK(d_perm.alloc((size_t)D));
+        HIPCK(hipMemcpyAsync(d_perm.p, perm, (size_t)D * 4, hipMemcpyHostToDevice, st));
+    } else if (transform == MMIDX_TR_ROTATION) {
+        HIPCK(d_rot.alloc((size_t)D * D));
+        HIPCK(hipMemcpyAsync(d_rot.p, rot, (size_t)D * D * 8, hipMemcpyHostToDevice, st));
+    }
+    hipLaunchKernelGGL(k_pl_prep, dim3((unsigned)((nd + PL_BLOCK - 1) / PL_BLOCK)), dim3(PL_BLOCK), 0, st, dX, d_cell.p, d_coarse.p, d_perm.p, d_rot.p,
+                       Y.p, (long long)n, D, dsub, transform, C > 0 ? 1 : 0);
+    c.Y = c.W = Y.p;
+    if (c.normalize) {
+        HIPCK(Yn.alloc(nd));
+        HIPCK(mn.alloc((size_t)D));
+        HIPCK(mx.alloc((size_t)D));
+        hipLaunchKernelGGL(k_pl_minmax, dim3((unsigned)D), dim3(PL_BLOCK), 0, st, Y.p, (long long)n, dsub, mn.p, mx.p);
+        hipLaunchKernelGGL(k_pl_normalize, dim3((unsigned)((nd + PL_BLOCK - 1) / PL_BLOCK)), dim3(PL_BLOCK), 0, st, Y.p, Yn.p, mn.p, mx.p, (long long)n,
+                           dsub, (long long)nd);
+        c.W = Yn.p;
+    }
+    HIPCK(hipGetLastError());
+    HIPCK(hipStreamSynchronize(st));  // (perm / rot / coarse are the caller's: their copies are done)
+
+    // ---- jobs per group: the sort's 32-bit item count, the memory that is free, and the test switch ---------------------------------
+    size_t free_b = 0, total_b = 0;
+    HIPCK(hipMemGetInfo(&free_b, &total_b));
+    const size_t per_job = (size_t)n * 48 + (size_t)ks * dsub * 16 + 4096;  // five int32 / uint32 arrays, mind2, the sort's workspace
+    long long G = std::min<long long>(std::min<long long>(J, 65535), (long long)INT32_MAX / n);  // (a grid's y extent walks the jobs)
+    G = std::min<long long>(G, (long long)(free_b / 10 * 8 / per_job));
+    if (const char *e = getenv("MMIDX_PQ_LEARN_GROUP")) {
+        const long long v = atoll(e);
+        if (v >= 1) G = std::min<long long>(G, v);
+    }
+    if (G < 1) G = 1;
+    c.G = (int)G;
+    const size_t Gn = (size_t)G * n;
+    HIPCK(c.assign.alloc(Gn));
+    HIPCK(c.iota.alloc(Gn));
+    HIPCK(c.sorted.alloc(Gn));
+    HIPCK(c.keys_in.alloc(Gn));
+    HIPCK(c.keys_out.alloc(Gn));
+    HIPCK(c.mind2.alloc(Gn));
+    HIPCK(c.tsum.alloc((size_t)G * c.ntl));
+    HIPCK(c.tinc.alloc((size_t)G * c.ntl));
+    HIPCK(c.pick.alloc((size_t)G * ks));
+    HIPCK(c.prob.alloc((size_t)G * ks));
+    HIPCK(c.Ctab.alloc((size_t)G * ks * dsub));
+    if (c.normalize) HIPCK(c.Cfin.alloc((size_t)G * ks * dsub));
+    HIPCK(c.sse.alloc((size_t)G));
+    HIPCK(c.slots.alloc((size_t)G));
+    HIPCK(c.cnt.alloc((size_t)G * ks + (size_t)G));
+    HIPCK(c.ctlB.alloc(2 * (size_t)G + 3 * (size_t)G * ks));
+    HIPCK(c.h_slots.alloc((size_t)G));
+    HIPCK(c.h_pick0.alloc((size_t)G * ks));
+    memset(c.h_pick0.p, 0, (size_t)G * ks * 4);
+    HIPCK(c.h_prob.alloc((size_t)G * ks));
+    HIPCK(c.h_cnt.alloc((size_t)G * ks + (size_t)G));
+    HIPCK(c.h_ctlB.alloc(2 * (size_t)G + 3 * (size_t)G * ks));
+    HIPCK(c.h_sse.alloc((size_t)G));
+    HIPCK(c.h_cent.alloc((size_t)G * ks * dsub));
+    {
+        int bits = 1;
+        while ((1ll << bits) < (long long)G * ks) bits++;
+        HIPCK(hipcub::DeviceRadixSort::SortPairs(nullptr, c.stmp_bytes, c.keys_in.p, c.keys_out.p, c.iota.p, c.sorted.p, (int)Gn, 0, bits, st));
+        HIPCK(c.stmp.alloc(c.stmp_bytes));
+    }
+    hipLaunchKernelGGL(k_pl_iota_mod, dim3((unsigned)((Gn + PL_BLOCK - 1) / PL_BLOCK)), dim3(PL_BLOCK), 0, st, c.iota.p, (long long)n, (long long)Gn);
+    // the assignment's LDS: a table of at most 64 KiB and its histogram of at most 32 KiB
+    HIPCK(hipFuncSetAttribute((const void *)k_pl_assign<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
+    HIPCK(hipFuncSetAttribute((const void *)k_pl_assign<8>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
+    HIPCK(hipFuncSetAttribute((const void *)k_pl_assign<16>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
+    HIPCK(hipGetLastError());
+
+    std::vector<PlJobResult> res((size_t)J);
+    for (int g0 = 0; g0 < J; g0 += (int)G) {
+        rc = pl_run_group(c, g0, std::min<int>((int)G, J - g0), res);
+        if (rc) return rc;
+    }
+
+    // ---- the kept repeat of every sub-space: seeds 1..repeats in order, replaced only on sse < best (ProductQuantizationLearning.java:252-269)
+    for (int s = 0; s < m; s++) {
+        int best = 0;
+        for (int r = 1; r < repeats; r++)
+            if (res[(size_t)s * repeats + r].sse < res[(size_t)s * repeats + best].sse) best = r;
+        const PlJobResult &b = res[(size_t)s * repeats + best];
+        double *out = pq_out + (size_t)s * ks * dsub;
+        std::copy(b.cent.begin(), b.cent.end(), out);
+        std::fill(out + (size_t)b.k_eff * dsub, out + (size_t)ks * dsub, 1000.0);  // missing centres: far-away fakes (:285-302)
+        if (sse_out) sse_out[s] = b.sse;
+        if (seed_out) seed_out[s] = best + 1;
+        if (k_out) k_out[s] = b.k_eff;
+        if (iters_out) iters_out[s] = b.iters;
+    }
+    return MMIDX_OK;
+}
+
+int mmidx_pq_learn(int device, int64_t n, int D, int m, int ks, int max_iter, int repeats, int flags, const double *X, int C, const double *coarse,
+                   int transform, const int32_t *perm, const double *rot, double *pq_out, double *sse_out, int32_t *seed_out, int32_t *k_out,
+                   int32_t *iters_out) {
+    int rc = pl_check_args(n, D, m, ks, max_iter, repeats, flags, X, C, coarse, transform, perm, rot, pq_out);
+    if (rc) return rc;
+    if (mmidx_device_count() < 1) return mmidx_fail(MMIDX_ERR_NO_DEVICE, "no HIP device: libmmidx_hip has no CPU fallback");
+    HIPCK(hipSetDevice(device));
+    ScopedBuf<double> dX;
+    HIPCK(dX.alloc((size_t)n * D));
+    HIPCK(hipMemcpy(dX.p, X, (size_t)n * D * 8, hipMemcpyHostToDevice));
+    return mmidx_pq_learn_device(device, n, D, m, ks, max_iter, repeats, flags, dX.p, C, coarse, transform, perm, rot, pq_out, sse_out, seed_out, k_out,
+                                 iters_out, nullptr);
 }
 
 }  // extern "C"

@@ -120,6 +120,15 @@ public final class MmidxNative {
 	public static native int pcaLearnCompute(long learner, int numComponents, int sampleSize, double tol, int maxIter,
 			double[] means, double[] singularValues, double[] components, double[] residualOut) throws Exception;
 
+	/**
+	 * mmidx_pq_learn: the whole product quantizer in one call. vectors[n * D]; coarse[C * D] or null (flat PQ); perm[D] / rot[D * D]
+	 * or null as the transformation (0 none, 1 rotation, 2 permutation) wants; pq[m * ks * (D / m)]; sse / seed / k / iterations [m]
+	 * each, of the kept repeat, any may be null
+	 */
+	public static native void pqLearn(int device, int n, int vectorLength, int m, int numProductCentroids, int maxIterations,
+			int numKmeansRepeats, boolean normalize, double[] vectors, int numCoarseCentroids, double[] coarse, int transformation,
+			int[] perm, double[] rot, double[] pq, double[] sse, int[] seed, int[] k, int[] iterations) throws Exception;
+
 	public static native long vladCreate(int[] numCentroids, int descriptorLength, double[] codebooks,
 			boolean normalizationsOn, int device) throws Exception;
 

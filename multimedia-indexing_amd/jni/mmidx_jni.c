@@ -591,6 +591,49 @@ done:
     (*env)->ReleaseDoubleArrayElements(env, residualOut, r_, 0);
     return (jint)iters;
 }
+/* ProductQuantizationLearning in one call (mmidx_pq_learn): x[n][D]; coarse[C][D] or null (flat PQ); perm[D] / rot[D][D] or null as the
+ * transformation wants; pq[m][ks][dsub] and the kept repeat's sse / seed / k / iterations per sub-space ([m] each, any may be null) */
+JNIEXPORT void JNICALL JFN(pqLearn)(JNIEnv *env, jclass c, jint device, jint n, jint D, jint m, jint ks, jint maxIter, jint repeats,
+                                    jboolean normalize, jdoubleArray x, jint C, jdoubleArray coarse, jint transform, jintArray perm,
+                                    jdoubleArray rot, jdoubleArray pq, jdoubleArray sse, jintArray seed, jintArray kOut, jintArray iters) {
+    jdouble *x_, *co_ = NULL, *rot_ = NULL, *pq_, *sse_ = NULL;
+    jint *perm_ = NULL, *seed_ = NULL, *k_ = NULL, *it_ = NULL;
+    (void)c;
+    if (n < 1 || D < 1 || m < 1 || ks < 1 || C < 0) {
+        throw_msg(env, "java/lang/IllegalArgumentException", "pqLearn: n, vectorLength, m and numProductCentroids must be positive, numCoarseCentroids not negative");
+        return;
+    }
+    if (bad_len(env, x, (int64_t)n * D, 0, "vectors") || bad_len(env, pq, (int64_t)ks * D, 0, "product quantizer") ||
+        bad_len(env, coarse, (int64_t)C * D, C == 0, "coarse quantizer") || bad_len(env, perm, D, 1, "permutation") ||
+        bad_len(env, rot, (int64_t)D * D, 1, "rotation") || bad_len(env, sse, m, 1, "sse") || bad_len(env, seed, m, 1, "seed") ||
+        bad_len(env, kOut, m, 1, "k") || bad_len(env, iters, m, 1, "iterations"))
+        return;
+    x_ = (*env)->GetDoubleArrayElements(env, x, NULL);
+    pq_ = (*env)->GetDoubleArrayElements(env, pq, NULL);
+    if (coarse) co_ = (*env)->GetDoubleArrayElements(env, coarse, NULL);
+    if (perm) perm_ = (*env)->GetIntArrayElements(env, perm, NULL);
+    if (rot) rot_ = (*env)->GetDoubleArrayElements(env, rot, NULL);
+    if (sse) sse_ = (*env)->GetDoubleArrayElements(env, sse, NULL);
+    if (seed) seed_ = (*env)->GetIntArrayElements(env, seed, NULL);
+    if (kOut) k_ = (*env)->GetIntArrayElements(env, kOut, NULL);
+    if (iters) it_ = (*env)->GetIntArrayElements(env, iters, NULL);
+    if (!x_ || !pq_ || (coarse && !co_) || (perm && !perm_) || (rot && !rot_) || (sse && !sse_) || (seed && !seed_) || (kOut && !k_) ||
+        (iters && !it_)) { /* the JVM could not pin or copy an array: its OutOfMemoryError is already pending */
+        goto done;
+    }
+    CHECK(mmidx_pq_learn(device, n, D, m, ks, maxIter, repeats, normalize ? MMIDX_KMEANS_NORMALIZE : 0, x_, C, co_, transform,
+                         (const int32_t *)perm_, rot_, pq_, sse_, (int32_t *)seed_, (int32_t *)k_, (int32_t *)it_));
+done:
+    if (x_) (*env)->ReleaseDoubleArrayElements(env, x, x_, JNI_ABORT);
+    if (pq_) (*env)->ReleaseDoubleArrayElements(env, pq, pq_, 0);
+    if (co_) (*env)->ReleaseDoubleArrayElements(env, coarse, co_, JNI_ABORT);
+    if (perm_) (*env)->ReleaseIntArrayElements(env, perm, perm_, JNI_ABORT);
+    if (rot_) (*env)->ReleaseDoubleArrayElements(env, rot, rot_, JNI_ABORT);
+    if (sse_) (*env)->ReleaseDoubleArrayElements(env, sse, sse_, 0);
+    if (seed_) (*env)->ReleaseIntArrayElements(env, seed, seed_, 0);
+    if (k_) (*env)->ReleaseIntArrayElements(env, kOut, k_, 0);
+    if (it_) (*env)->ReleaseIntArrayElements(env, iters, it_, 0);
+}
 JNIEXPORT jlong JNICALL JFN(vladCreate)(JNIEnv *env, jclass c, jintArray ncent, jint dl, jdoubleArray codebooks, jboolean normalizationsOn,
                                         jint device) {
     mmidx_vlad *v = NULL;

@@ -16,6 +16,7 @@ are replaced by all-1000 centroids so that nothing quantizes to them, ProductQua
 import numpy as np
 
 from . import _native as N
+from .index import TransformationType
 
 KMEANS_PLUS_PLUS, KMEANS_NORMALIZE = 1, 2
 
@@ -156,6 +157,63 @@ class ProductQuantizationLearning:
                 if best is None or sse < best[1]:
                     best = (cent, sse)
             pq[s, :best[0].shape[0]] = best[0]
+        if outFilePath:
+            with open(outFilePath, "w") as fh:
+                for s in range(m):
+                    _write_centroids(fh, pq[s])
+        return pq
+
+    last_stats = None
+
+    @classmethod
+    def learn_batched(cls, vectors, m, numProductCentroids, maxIterations=100, numKmeansRepeats=1, coarseQuantizer=None,
+                      transformation=TransformationType.None_, perm=None, rot=None, normalize=True, outFilePath=None, device=0):
+        """The same quantizer as learn(), bit for bit, in one device-resident call (mmidx_pq_learn / mmidx_pq_learn_device,
+        DESIGN.md section 5.10): residual, transformation (TransformationType; perm[D] / rot[D][D] as the index takes them), and all
+        m * numKmeansRepeats k-means problems sharing every kernel launch.  vectors: a numpy array [n][D], or an fp64 CUDA tensor
+        (then nothing but the result leaves the device).  Returns pq [m][ks][dsub]; .last_stats holds the kept repeat's
+        squared error, seed, number of real centroids and iterations per sub-space.  dsub <= 16 and ks * dsub * 8 <= 64 KiB,
+        else MmidxError(ERR_UNSUPPORTED): learn() has no such limit."""
+        import ctypes as C
+
+        on_device = hasattr(vectors, "data_ptr")
+        if on_device:
+            import torch
+
+            if not vectors.is_cuda or vectors.dtype != torch.float64 or vectors.dim() != 2:
+                raise N.MmidxError(N.ERR_INVALID_ARG, "a tensor must be [n][D] float64 on the GPU")
+            X = vectors.contiguous()
+            device = X.device.index
+            n, D = X.shape
+        else:
+            X = np.ascontiguousarray(vectors, np.float64)
+            if X.ndim != 2:
+                raise N.MmidxError(N.ERR_INVALID_ARG, "vectors must be [n][D]")
+            n, D = X.shape
+        ks = int(numProductCentroids)
+        coarse = None if coarseQuantizer is None else np.ascontiguousarray(coarseQuantizer, np.float64)
+        if coarse is not None and (coarse.ndim != 2 or coarse.shape[1] != D):
+            raise N.MmidxError(N.ERR_WRONG_DIM, "The dimensionality of the vector is wrong!")
+        p = None if perm is None else np.ascontiguousarray(perm, np.int32)
+        r = None if rot is None else np.ascontiguousarray(rot, np.float64)
+        if (p is not None and p.shape != (D,)) or (r is not None and r.shape != (D, D)):
+            raise N.MmidxError(N.ERR_INVALID_ARG, "perm must be [D] and rot [D][D]")
+        dsub = D // m if m > 0 and D % m == 0 else 1
+        pq = np.zeros((max(m, 1), max(ks, 1), dsub), np.float64)
+        sse = np.zeros(max(m, 1), np.float64)
+        seed, kout, iters = (np.zeros(max(m, 1), np.int32) for _ in range(3))
+        args = [device, n, D, m, ks, maxIterations, numKmeansRepeats, KMEANS_NORMALIZE if normalize else 0,
+                X.data_ptr() if on_device else X.ctypes.data, 0 if coarse is None else coarse.shape[0],
+                None if coarse is None else coarse.ctypes.data, int(transformation), None if p is None else p.ctypes.data,
+                None if r is None else r.ctypes.data, pq.ctypes.data, sse.ctypes.data, seed.ctypes.data, kout.ctypes.data,
+                iters.ctypes.data]
+        if on_device:
+            import torch
+
+            N.check(N.lib().mmidx_pq_learn_device(*args, torch.cuda.current_stream(X.device).cuda_stream))
+        else:
+            N.check(N.lib().mmidx_pq_learn(*args))
+        cls.last_stats = {"sse": sse, "seed": seed, "k_eff": kout, "iterations": iters}
         if outFilePath:
             with open(outFilePath, "w") as fh:
                 for s in range(m):
