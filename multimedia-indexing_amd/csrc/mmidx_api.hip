@@ -681,6 +681,16 @@ auto for_dsub(int dsub, F &&f) {
     if (dsub == 8) return f(std::integral_constant<int, 8>{});
     return f(std::integral_constant<int, 16>{});
 }
+// the coarse selections' centroids per thread: PER = the smallest of 8, 32, 64 with C <= PER * MMIDX_BLOCK (the caller's gate admits
+// no larger C).  MAXPER = 32: the kernels that are instantiated for 8 and 32 only (the list and deferred forms, G <= 1024)
+template <int MAXPER = 64, class F>
+auto for_cwidth(int C, F &&f) {
+    if (C <= 8 * MMIDX_BLOCK) return f(std::integral_constant<int, 8>{});
+    if constexpr (MAXPER == 64) {
+        if (C > 32 * MMIDX_BLOCK) return f(std::integral_constant<int, 64>{});
+    }
+    return f(std::integral_constant<int, 32>{});
+}
 // K3m's and K3ma's shapes: NJ = D / 32 in {1, 2, 4} (build_mfma_tables) x DSUB; their verification kernels' M is NJ * 32 / DSUB
 template <class F>
 int for_nj_dsub(int nj, int dsub, F &&f) {
@@ -1854,22 +1864,33 @@ int launch_coarse_select(const double *dist, int C, int w, int64_t nq, int32_t *
     if (lds > 64 * 1024) return mmidx_fail(MMIDX_ERR_UNSUPPORTED, "w = %d too large", w);
     const bool fast = C >= MMIDX_BLOCK && w + 1 <= MMIDX_BLOCK && C <= 64 * MMIDX_BLOCK;
     const size_t flds = (size_t)MMIDX_CSEL_CAP * 12 + (size_t)(w + 1) * 12 + 16;
-    if (fast && C <= 8 * MMIDX_BLOCK)
-        hipLaunchKernelGGL(k_coarse_select_fast<8>, dim3((unsigned)nq), dim3(MMIDX_BLOCK), flds, st, dist, C, w, d_cells);
-    else if (fast && C <= 32 * MMIDX_BLOCK)
-        hipLaunchKernelGGL(k_coarse_select_fast<32>, dim3((unsigned)nq), dim3(MMIDX_BLOCK), flds, st, dist, C, w, d_cells);
-    else if (fast)
-        hipLaunchKernelGGL(k_coarse_select_fast<64>, dim3((unsigned)nq), dim3(MMIDX_BLOCK), flds, st, dist, C, w, d_cells);
-    else if (C <= 8 * MMIDX_BLOCK)
-        hipLaunchKernelGGL(k_coarse_select_reg<8>, dim3((unsigned)nq), dim3(MMIDX_BLOCK), lds, st, dist, C, w, d_cells);
-    else if (C <= 32 * MMIDX_BLOCK)
-        hipLaunchKernelGGL(k_coarse_select_reg<32>, dim3((unsigned)nq), dim3(MMIDX_BLOCK), lds, st, dist, C, w, d_cells);
+    if (fast)
+        for_cwidth(C, [&](auto per) { hipLaunchKernelGGL(k_coarse_select_fast<decltype(per)::value>, dim3((unsigned)nq), dim3(MMIDX_BLOCK), flds, st, dist, C, w, d_cells); });
     else if (C <= 64 * MMIDX_BLOCK)
-        hipLaunchKernelGGL(k_coarse_select_reg<64>, dim3((unsigned)nq), dim3(MMIDX_BLOCK), lds, st, dist, C, w, d_cells);
+        for_cwidth(C, [&](auto per) { hipLaunchKernelGGL(k_coarse_select_reg<decltype(per)::value>, dim3((unsigned)nq), dim3(MMIDX_BLOCK), lds, st, dist, C, w, d_cells); });
     else
         hipLaunchKernelGGL(k_coarse_select, dim3((unsigned)nq), dim3(MMIDX_BLOCK), lds, st, dist, C, w, d_cells);
     HIPCK(hipGetLastError());
     return MMIDX_OK;
+}
+
+// what both certified selections (K1c + K1d, K1e + K1f) read and write; the caller adds its own front end's fields
+static ApproxSel approx_sel_common(const mmidx_index *h, int cch, const double *dQ, int32_t *d_cells) {
+    ApproxSel A{};
+    A.cand_chunk = cch;
+    A.qn = h->ws_qn.p;
+    A.cnorm_max = h->cnorm_max;
+    A.cn_max = h->cn_max;
+    A.Q = dQ;
+    A.coarse = h->d_coarse;
+    A.coarseT = h->d_coarseT;
+    A.row_scratch = h->ws_cdist.p;
+    A.cells = d_cells;
+    A.cdsel = h->ws_cdsel.p;
+    A.C = h->C;
+    A.D = h->D;
+    A.w = h->w;
+    return A;
 }
 
 int run_coarse(mmidx_index *h, int64_t nq, const double *dQ, int32_t *d_cells, hipStream_t st) {
@@ -1902,46 +1923,31 @@ int run_coarse(mmidx_index *h, int64_t nq, const double *dQ, int32_t *d_cells, h
         // to a block than it has room for norms beside its ring; where that cannot be had, K1e'
         const int gqblocks = (int)((nq + G16G_BQ - 1) / G16G_BQ);
         const int gsplit = std::max({1, std::min(ntiles, (std::max(h->num_cus, 1) + gqblocks - 1) / gqblocks), (ntiles + G16G_NORM_TILES - 1) / G16G_NORM_TILES});
+        // every K1e form takes the same operands, then its own shape arguments
+        auto k1e = [&](auto kern, dim3 grid, int block, size_t lds, auto... shape) {
+            hipLaunchKernelGGL(kern, grid, dim3(block), lds, st, (const __bf16 *)h->ws_Qh.p, (const __bf16 *)h->ws_Ql.p, (const __bf16 *)h->d_Ch,
+                               (const __bf16 *)h->d_Cl, h->d_cn_pad, h->ws_qn.p, (float2 *)h->ws_gmin.p, h->Cp, shape...);
+        };
+        const dim3 qgrid((unsigned)qblocks, (unsigned)csplit);
         h->disp_coarse_mm = "staged";
         if (h->Dp == G16_KC && h->sw.coarse_groups && gsplit <= 65535) {
             h->disp_coarse_mm = "groups";
-            hipLaunchKernelGGL(k_coarse_gmin16_grp, dim3((unsigned)gqblocks, (unsigned)gsplit), dim3(G16G_BLOCK), 0, st, (const __bf16 *)h->ws_Qh.p,
-                               (const __bf16 *)h->ws_Ql.p, (const __bf16 *)h->d_Ch, (const __bf16 *)h->d_Cl, h->d_cn_pad, h->ws_qn.p,
-                               (float2 *)h->ws_gmin.p, h->Cp, (int)nq, G);
+            k1e(k_coarse_gmin16_grp, dim3((unsigned)gqblocks, (unsigned)gsplit), G16G_BLOCK, 0, (int)nq, G);
         } else if (h->Dp == G16_KC) {
             // one k chunk: centroid tiles by LDS-DMA into two half-tile buffers (static LDS)
             h->disp_coarse_mm = "dma";
-            hipLaunchKernelGGL(k_coarse_gmin16_dma, dim3((unsigned)qblocks, (unsigned)csplit), dim3(MMIDX_BLOCK), 0, st, (const __bf16 *)h->ws_Qh.p,
-                               (const __bf16 *)h->ws_Ql.p, (const __bf16 *)h->d_Ch, (const __bf16 *)h->d_Cl, h->d_cn_pad, h->ws_qn.p,
-                               (float2 *)h->ws_gmin.p, h->Cp, (int)nq, G);
+            k1e(k_coarse_gmin16_dma, qgrid, MMIDX_BLOCK, 0, (int)nq, G);
         } else if (h->Dp > G16_KC && h->Dp % G16_KC == 0 && h->sw.coarse_dma_kc) {
             // several k chunks (long vectors): the same double buffering, (chunk, half tile) after (chunk, half tile)
             h->disp_coarse_mm = "dma_kc";
-            hipLaunchKernelGGL(k_coarse_gmin16_dma_kc, dim3((unsigned)qblocks, (unsigned)csplit), dim3(MMIDX_BLOCK), 0, st, (const __bf16 *)h->ws_Qh.p,
-                               (const __bf16 *)h->ws_Ql.p, (const __bf16 *)h->d_Ch, (const __bf16 *)h->d_Cl, h->d_cn_pad, h->ws_qn.p,
-                               (float2 *)h->ws_gmin.p, h->Cp, (int)nq, G, h->Dp);
+            k1e(k_coarse_gmin16_dma_kc, qgrid, MMIDX_BLOCK, 0, (int)nq, G, h->Dp);
         } else {
             const size_t l16 = 2 * (size_t)G16_BC * G16_STRIDE;
             HIPCK(hipFuncSetAttribute((const void *)k_coarse_gmin16, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l16));
-            hipLaunchKernelGGL(k_coarse_gmin16, dim3((unsigned)qblocks, (unsigned)csplit), dim3(MMIDX_BLOCK), l16, st, (const __bf16 *)h->ws_Qh.p,
-                               (const __bf16 *)h->ws_Ql.p, (const __bf16 *)h->d_Ch, (const __bf16 *)h->d_Cl, h->d_cn_pad, h->ws_qn.p,
-                               (float2 *)h->ws_gmin.p, h->Cp, h->Dp, (int)nq, G);
+            k1e(k_coarse_gmin16, qgrid, MMIDX_BLOCK, l16, h->Dp, (int)nq, G);
         }
         HIPCK(hipGetLastError());
-        ApproxSel A{};
-        A.cand_chunk = cch;
-        A.qn = h->ws_qn.p;
-        A.cnorm_max = h->cnorm_max;
-        A.cn_max = h->cn_max;
-        A.Q = dQ;
-        A.coarse = h->d_coarse;
-        A.coarseT = h->d_coarseT;
-        A.row_scratch = h->ws_cdist.p;
-        A.cells = d_cells;
-        A.cdsel = h->ws_cdsel.p;
-        A.C = h->C;
-        A.D = h->D;
-        A.w = h->w;
+        ApproxSel A = approx_sel_common(h, cch, dQ, d_cells);
         A.gpair = (const float2 *)h->ws_gmin.p;
         A.G = G;
         A.Dp = h->Dp;
@@ -1963,22 +1969,12 @@ int run_coarse(mmidx_index *h, int64_t nq, const double *dQ, int32_t *d_cells, h
             else hipLaunchKernelGGL(k_coarse_front, dim3(fgrid), dim3(MMIDX_BLOCK), 0, st, A);
             if (wave_sel) {
                 const unsigned dgrid = (unsigned)std::min<long long>(nq, 2ll * std::max(h->num_cus, 8));
-                if (h->C <= 8 * MMIDX_BLOCK) hipLaunchKernelGGL(k_coarse_select_defer<8>, dim3(dgrid), dim3(MMIDX_BLOCK), glds, st, A);
-                else hipLaunchKernelGGL(k_coarse_select_defer<32>, dim3(dgrid), dim3(MMIDX_BLOCK), glds, st, A);
-            } else if (h->C <= 8 * MMIDX_BLOCK)
-                hipLaunchKernelGGL(k_coarse_select_list<8>, dim3((unsigned)nq), dim3(MMIDX_BLOCK), glds, st, A);
-            else
-                hipLaunchKernelGGL(k_coarse_select_list<32>, dim3((unsigned)nq), dim3(MMIDX_BLOCK), glds, st, A);
-        } else if (h->C <= 8 * MMIDX_BLOCK) {
-            h->disp_coarse = "K1e'+K1f(select_grp)";
-            hipLaunchKernelGGL(k_coarse_select_grp<8>, dim3((unsigned)nq), dim3(MMIDX_BLOCK), glds, st, A);
-        }
-        else if (h->C <= 32 * MMIDX_BLOCK) {
-            h->disp_coarse = "K1e'+K1f(select_grp)";
-            hipLaunchKernelGGL(k_coarse_select_grp<32>, dim3((unsigned)nq), dim3(MMIDX_BLOCK), glds, st, A);
+                for_cwidth<32>(h->C, [&](auto per) { hipLaunchKernelGGL(k_coarse_select_defer<decltype(per)::value>, dim3(dgrid), dim3(MMIDX_BLOCK), glds, st, A); });
+            } else
+                for_cwidth<32>(h->C, [&](auto per) { hipLaunchKernelGGL(k_coarse_select_list<decltype(per)::value>, dim3((unsigned)nq), dim3(MMIDX_BLOCK), glds, st, A); });
         } else {
             h->disp_coarse = "K1e'+K1f(select_grp)";
-            hipLaunchKernelGGL(k_coarse_select_grp<64>, dim3((unsigned)nq), dim3(MMIDX_BLOCK), glds, st, A);
+            for_cwidth(h->C, [&](auto per) { hipLaunchKernelGGL(k_coarse_select_grp<decltype(per)::value>, dim3((unsigned)nq), dim3(MMIDX_BLOCK), glds, st, A); });
         }
         HIPCK(hipGetLastError());
         h->cdsel_valid = true;
@@ -1995,27 +1991,9 @@ int run_coarse(mmidx_index *h, int64_t nq, const double *dQ, int32_t *d_cells, h
         hipLaunchKernelGGL(k_query_prep, dim3((unsigned)((nq + 3) / 4)), dim3(MMIDX_BLOCK), 0, st, dQ, h->ws_Q32.p, h->ws_qn.p, h->D, (long long)nq);
         dim3 g1((unsigned)((h->C + DOT_BN - 1) / DOT_BN), (unsigned)((nq + DOT_BM - 1) / DOT_BM));
         hipLaunchKernelGGL(k_coarse_dot32, g1, dim3(MMIDX_BLOCK), 0, st, h->d_coarseT32, h->ws_Q32.p, h->d_cn, h->ws_qn.p, h->ws_S.p, h->C, h->D, (int)nq);
-        ApproxSel A{};
-        A.cand_chunk = cch;
+        ApproxSel A = approx_sel_common(h, cch, dQ, d_cells);
         A.S = h->ws_S.p;
-        A.qn = h->ws_qn.p;
-        A.cnorm_max = h->cnorm_max;
-        A.cn_max = h->cn_max;
-        A.Q = dQ;
-        A.coarse = h->d_coarse;
-        A.coarseT = h->d_coarseT;
-        A.row_scratch = h->ws_cdist.p;
-        A.cells = d_cells;
-        A.cdsel = h->ws_cdsel.p;
-        A.C = h->C;
-        A.D = h->D;
-        A.w = h->w;
-        if (h->C <= 8 * MMIDX_BLOCK)
-            hipLaunchKernelGGL(k_coarse_select_approx<8>, dim3((unsigned)nq), dim3(MMIDX_BLOCK), alds, st, A);
-        else if (h->C <= 32 * MMIDX_BLOCK)
-            hipLaunchKernelGGL(k_coarse_select_approx<32>, dim3((unsigned)nq), dim3(MMIDX_BLOCK), alds, st, A);
-        else
-            hipLaunchKernelGGL(k_coarse_select_approx<64>, dim3((unsigned)nq), dim3(MMIDX_BLOCK), alds, st, A);
+        for_cwidth(h->C, [&](auto per) { hipLaunchKernelGGL(k_coarse_select_approx<decltype(per)::value>, dim3((unsigned)nq), dim3(MMIDX_BLOCK), alds, st, A); });
         HIPCK(hipGetLastError());
         h->cdsel_valid = true;
         return MMIDX_OK;

@@ -8,6 +8,7 @@
 
 #include "mmidx_device_util.h"
 #include "mmidx_host.h"  // G16_BC, G16_BQ
+#include "mmidx_split16.h"
 
 typedef __attribute__((ext_vector_type(4))) double f64x4;
 
@@ -492,36 +493,9 @@ __global__ __launch_bounds__(256, 3) void k_vlad_fused(const double *__restrict_
         bf16x8 ah[2][2], al[2][2];
         float xn_r[2][4];
         double xrow[2];
-#pragma unroll
-        for (int rt = 0; rt < 2; rt++) {
-            int q = q0 + rt * 16 + fr;
-            q = q < nd ? q : nd - 1;
-            double pn = 0.0;
-#pragma unroll
-            for (int ks = 0; ks < 2; ks++) {
-                const double2 *xp = (const double2 *)(Dg + (size_t)q * DL + ks * 32 + fg * 8);
-                const double2 v0 = xp[0], v1 = xp[1], v2 = xp[2], v3 = xp[3];
-                const double vv[8] = {v0.x, v0.y, v1.x, v1.y, v2.x, v2.y, v3.x, v3.y};
-#pragma unroll
-                for (int e = 0; e < 8; e++) {
-                    const float f = (float)vv[e];
-                    const __bf16 hh = (__bf16)f;
-                    ah[rt][ks][e] = hh;
-                    al[rt][ks][e] = (__bf16)(f - (float)hh);  // f - head is exact in fp32
-                    pn += vv[e] * vv[e];
-                }
-            }
-            pn += __shfl_xor(pn, 16);
-            pn += __shfl_xor(pn, 32);
-            xrow[rt] = pn * (1.0 + 1e-12);  // only ever used inside error bounds: rounded up
-#pragma unroll
-            for (int r = 0; r < 4; r++) xn_r[rt][r] = (float)__shfl(xrow[rt], 4 * fg + r);
-        }
+        split16_load_a_fp64<2>(ah, al, xrow, xn_r, Dg, q0, nd, DL, fr, fg);
         f32x4 acc[2][8];
-#pragma unroll
-        for (int rt = 0; rt < 2; rt++)
-#pragma unroll
-            for (int ct = 0; ct < 8; ct++) acc[rt][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
+        split16_zero_acc(acc);
 #pragma unroll
         for (int ks = 0; ks < 2; ks++) {
 #pragma unroll
@@ -536,11 +510,7 @@ __global__ __launch_bounds__(256, 3) void k_vlad_fused(const double *__restrict_
 #pragma unroll
                 for (int u = 0; u < 2; u++)
 #pragma unroll
-                    for (int rt = 0; rt < 2; rt++) {
-                        acc[rt][ct + u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[rt][ks], bh[u], acc[rt][ct + u], 0, 0, 0);
-                        acc[rt][ct + u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[rt][ks], bl[u], acc[rt][ct + u], 0, 0, 0);
-                        acc[rt][ct + u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[rt][ks], bh[u], acc[rt][ct + u], 0, 0, 0);
-                    }
+                    for (int rt = 0; rt < 2; rt++) split16_mma_one(acc[rt][ct + u], ah[rt][ks], al[rt][ks], bh[u], bl[u]);
             }
         }
 #pragma unroll
@@ -557,8 +527,10 @@ __global__ __launch_bounds__(256, 3) void k_vlad_fused(const double *__restrict_
                     ix = lt1 ? ct * 16 + fr : ix;
                     m1 = lt1 ? dv : m1;
                 }
+                // the 16 lanes of a row: (best, its index, second best).  The steps of row16_best2_merge, written out: as that function
+                // each step's tie test compiled to a branch in this loop (32 more than here) and the kernel measured 1.2 % slower
 #pragma unroll
-                for (int step = 0; step < 4; step++) {  // the 16 lanes of a row: (best, its index, second best)
+                for (int step = 0; step < 4; step++) {
                     const float o1 = dppf(m1, step), o2 = dppf(m2, step);
                     const int oi = dppi(ix, step);
                     const bool take = o1 < m1 || (o1 == m1 && oi < ix);

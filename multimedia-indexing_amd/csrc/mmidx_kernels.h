@@ -12,6 +12,7 @@
 
 #include "mmidx_device_util.h"
 #include "mmidx_host.h"
+#include "mmidx_split16.h"
 
 #define MMIDX_BLOCK 256
 #define MMIDX_KEY_MAX 0xFFFFFFFFFFFFFFFFull
@@ -971,27 +972,10 @@ __global__ __launch_bounds__(MMIDX_BLOCK) void k_coarse_select_approx(const Appr
     coarse_select_finish<PER>(A, q, filter_norms_usable(sumn) ? (int)s_n : MMIDX_CSEL_CAP + 1, ckey, cidx, sel_k, sel_i, s_k, s_i);
 }
 
-
 // ------------------------------------------------------------------------------------------------
-// K1e + K1f: the same certified selection without materialising the [nq][C] matrix of d~.
-//
-// K1c writes 4 bytes per (query, centroid) and K1d reads them back -- 1 GiB of HBM traffic per 16384
-// queries at C = 8192 -- although only ~w+3 entries per row matter.  Here the dot products run on the
-// bf16 matrix cores with a two-term split (x = xh + xl + O(2^-16 x); q.c ~ qh.ch + qh.cl + ql.ch, each
-// product exact in fp32), 16x the fp32 MFMA rate, and the epilogue keeps, per group of 8 centroids (the 8
-// columns one lane holds for a row: no cross-lane work), the smallest d~, its position and the runner-up
-// (K1e: [nq][C/8] float2, a quarter of the traffic).  K1f then
-//   * takes tau = (w+1)-th smallest of its 256 per-thread minima + eps16: w+1 distinct centroids have an
-//     exact distance <= their d~ + eps16, so tau bounds the (w+1)-th smallest exact distance;
-//   * nominates the minimum of every group with d~ <= tau + eps16 (any centroid with exact distance <= tau
-//     satisfies that), and all 8 members of a group whose runner-up passes too (rare: 8 (w+1) / C);
-//   * hands the nominees to the shared exact second half.
-// Error bound of the split dot product (|x - xh - xl| <= 2^-16 |x| elementwise, |xl| <= 2^-8 |x|):
-//   |q.c - (qh.ch + qh.cl + ql.ch)| <= 3.1 * 2^-16 |q||c|   (dropped terms, Cauchy-Schwarz)
-//   accumulation of 3D exact products in fp32, any order, at most 2^-22 relative per step (twice the IEEE
-//   unit roundoff: the MFMA's internal summation order and rounding are not documented)
-//                                   <= (3D + 16) 2^-22 |q||c|
-//   d~ = |c|^2 + |q|^2 - 2 S evaluated in fp32 from fp32 copies of the norms: 2^-21 (|c| + |q|)^2
+// K1e + K1f: the same certified selection without materialising the [nq][C] matrix of d~ -- what the bf16 split is, what K1f
+// does with the group minima and the split's error bound: at the top of mmidx_split16.h, with the pieces the kernels below
+// share.  A kernel body here is its schedule: how a centroid tile reaches LDS, and which barriers and waits surround the products.
 // ------------------------------------------------------------------------------------------------
 // (tile constants G16_BQ / G16_BC / G16_KC / G16_STRIDE: mmidx_host.h -- host code of several units sizes launches by them)
 
@@ -1007,30 +991,13 @@ __global__ __launch_bounds__(MMIDX_BLOCK) void k_split_bf16(const double *__rest
     for (int j = lane; j < Dp; j += 64) {
         const double v = j < D ? X[(size_t)r * D + j] : 0.0;
         const float f = (float)v;
-        const __bf16 h = (__bf16)f;
-        const __bf16 l = (__bf16)(f - (float)h);  // f - h is exact in fp32
-        H[(size_t)r * Dp + j] = h;
-        L[(size_t)r * Dp + j] = l;
+        split16_head_tail(f, H[(size_t)r * Dp + j], L[(size_t)r * Dp + j]);
         if (X32 && j < D) X32[(size_t)r * D + j] = f;
         s += v * v;
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
     if (nrm2 && lane == 0) nrm2[r] = s * (1.0 + 1e-12);  // only ever used inside error bounds: round up
-}
-
-// row-wise minimum over the 16 lanes that share lane >> 4 (all of them receive it); VALU only
-__device__ __forceinline__ float row16_min(float v) {
-    float o;
-    o = __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0xB1, 0xf, 0xf, true));   // quad_perm [1,0,3,2]
-    v = o < v ? o : v;
-    o = __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x4E, 0xf, 0xf, true));   // quad_perm [2,3,0,1]
-    v = o < v ? o : v;
-    o = __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x141, 0xf, 0xf, true));  // row_half_mirror
-    v = o < v ? o : v;
-    o = __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x140, 0xf, 0xf, true));  // row_mirror
-    v = o < v ? o : v;
-    return v;
 }
 
 // K1e.  grid = (ceil(nq / 128), csplit); block = 4 waves, wave w owns query rows [32 w, 32 w + 32).
@@ -1045,77 +1012,23 @@ __global__ __launch_bounds__(MMIDX_BLOCK, 2) void k_coarse_gmin16(const __bf16 *
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int fr = lane & 15, fg = lane >> 4;
     const int q0 = blockIdx.x * G16_BQ + wave * 32;
-    const int ntiles = Cp / G16_BC;
-    const int t_per = (ntiles + gridDim.y - 1) / gridDim.y;
-    const int t_lo = blockIdx.y * t_per, t_hi = (t_lo + t_per < ntiles) ? t_lo + t_per : ntiles;
+    int t_lo, t_hi;
+    split16_tile_range(Cp / G16_BC, gridDim.y, blockIdx.y, t_lo, t_hi);
     const int nkc = (Dp + G16_KC - 1) / G16_KC;
     float qn_r[2][4];
-#pragma unroll
-    for (int rt = 0; rt < 2; rt++)
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-            const int q = q0 + rt * 16 + 4 * fg + r;
-            qn_r[rt][r] = q < nq ? (float)qn[q] : 0.0f;
-        }
+    split16_row_norms(qn_r, qn, q0, nq, fg);
     bf16x8 ah[2][4], al[2][4];  // A fragments of one k chunk: [row tile][k step of 32]
-    auto load_a = [&](int kc) {
-#pragma unroll
-        for (int rt = 0; rt < 2; rt++) {
-            int q = q0 + rt * 16 + fr;
-            q = q < nq ? q : nq - 1;
-#pragma unroll
-            for (int ks = 0; ks < 4; ks++) {
-                const int k = kc * G16_KC + ks * 32 + fg * 8;
-                if (k < Dp) {
-                    ah[rt][ks] = *(const bf16x8 *)(Qh + (size_t)q * Dp + k);
-                    al[rt][ks] = *(const bf16x8 *)(Ql + (size_t)q * Dp + k);
-                } else {
-#pragma unroll
-                    for (int e = 0; e < 8; e++) {
-                        ah[rt][ks][e] = (__bf16)0.0f;
-                        al[rt][ks][e] = (__bf16)0.0f;
-                    }
-                }
-            }
-        }
-    };
-    if (nkc == 1) load_a(0);
+    if (nkc == 1) split16_load_a<true>(ah, al, Qh, Ql, q0, nq, Dp, 0, fr, fg);
     for (int t = t_lo; t < t_hi; t++) {
         const int c0 = t * G16_BC;
         f32x4 acc[2][8];
-#pragma unroll
-        for (int rt = 0; rt < 2; rt++)
-#pragma unroll
-            for (int ct = 0; ct < 8; ct++) acc[rt][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
+        split16_zero_acc(acc);
         for (int kc = 0; kc < nkc; kc++) {
             const int kbase = kc * G16_KC;
             const int kw = (Dp - kbase < G16_KC) ? Dp - kbase : G16_KC;  // multiple of 32
-            const int upr = kw >> 3;                                      // 16-byte units per row
             __syncthreads();  // the previous tile's fragment reads are done
-            if (upr == 16) {  // full-width chunk: all 16 loads of the thread in flight, then the LDS stores
-                uint4 vh[8], vl[8];
-#pragma unroll
-                for (int i = 0; i < 8; i++) {
-                    const int u = tid + i * MMIDX_BLOCK, row = u >> 4, cu = u & 15;
-                    const size_t src = (size_t)(c0 + row) * Dp + kbase + cu * 8;
-                    vh[i] = *(const uint4 *)(Ch + src);
-                    vl[i] = *(const uint4 *)(Cl + src);
-                }
-#pragma unroll
-                for (int i = 0; i < 8; i++) {
-                    const int u = tid + i * MMIDX_BLOCK, row = u >> 4, cu = u & 15;
-                    *(uint4 *)(Bh + row * G16_STRIDE + cu * 16) = vh[i];
-                    *(uint4 *)(Bl + row * G16_STRIDE + cu * 16) = vl[i];
-                }
-            } else {
-                for (int u = tid; u < G16_BC * upr; u += MMIDX_BLOCK) {
-                    const int row = u / upr, cu = u - row * upr;
-                    const size_t src = (size_t)(c0 + row) * Dp + kbase + cu * 8;
-                    *(uint4 *)(Bh + row * G16_STRIDE + cu * 16) = *(const uint4 *)(Ch + src);
-                    *(uint4 *)(Bl + row * G16_STRIDE + cu * 16) = *(const uint4 *)(Cl + src);
-                }
-            }
-            if (nkc > 1) load_a(kc);
+            split16_stage_tile(Bh, Bl, Ch, Cl, c0, Dp, kbase, kw >> 3, tid);
+            if (nkc > 1) split16_load_a<true>(ah, al, Qh, Ql, q0, nq, Dp, kbase, fr, fg);
             __syncthreads();
             // touch the next tile (one word per 128-byte line, this k chunk): after the scan kernels the centroids are
             // not in L2 any more, and the staging loads of the next tile would wait on HBM with nothing else to do
@@ -1125,79 +1038,12 @@ __global__ __launch_bounds__(MMIDX_BLOCK, 2) void k_coarse_gmin16(const __bf16 *
                 touch_h = *(const volatile unsigned *)(Ch + nxt);
                 touch_l = *(const volatile unsigned *)(Cl + nxt);
             }
-#pragma unroll
-            for (int ks = 0; ks < 4; ks++) {
-                if (ks * 32 < kw) {  // block-uniform
-                    // two column tiles at a time: four independent accumulators between dependent MFMAs
-#pragma unroll
-                    for (int ct = 0; ct < 8; ct += 2) {
-                        bf16x8 bh[2], bl[2];
-#pragma unroll
-                        for (int u = 0; u < 2; u++) {
-                            const int off = ((ct + u) * 16 + fr) * G16_STRIDE + (ks * 32 + fg * 8) * 2;
-                            bh[u] = *(const bf16x8 *)(Bh + off);
-                            bl[u] = *(const bf16x8 *)(Bl + off);
-                        }
-#pragma unroll
-                        for (int u = 0; u < 2; u++)
-#pragma unroll
-                            for (int rt = 0; rt < 2; rt++)
-                                acc[rt][ct + u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[rt][ks], bh[u], acc[rt][ct + u], 0, 0, 0);
-#pragma unroll
-                        for (int u = 0; u < 2; u++)
-#pragma unroll
-                            for (int rt = 0; rt < 2; rt++)
-                                acc[rt][ct + u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[rt][ks], bl[u], acc[rt][ct + u], 0, 0, 0);
-#pragma unroll
-                        for (int u = 0; u < 2; u++)
-#pragma unroll
-                            for (int rt = 0; rt < 2; rt++)
-                                acc[rt][ct + u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[rt][ks], bh[u], acc[rt][ct + u], 0, 0, 0);
-                    }
-                }
-            }
+            split16_stage_products(acc, ah, al, Bh, Bl, kw, fr, fg);
             asm volatile("" ::"v"(touch_h), "v"(touch_l));  // (keeps the two loads; their data is not used)
         }
-        // epilogue: d~ = |c|^2 + |q|^2 - 2 S.  A group = the 8 columns one lane holds for a row
-        // (c0 + fr + 16 ct, ct = 0..7): its two smallest d~ and the position of the smallest, no cross-lane work.
-        // The epilogue's VALU work was half of this kernel's time (timing experiment: 155 us with, 48 us without), so
-        // it is four instructions per value: t = fma(-2, S, |c|^2) (|q|^2, constant along the row, is added to the two
-        // survivors only), the column index packed into t's three low mantissa bits (v_and_or_b32: the minimum then
-        // carries its own position), runner-up = med3(best, runner-up, t), best = min(best, t).
-        // Roundings: fp32 copies of the norms, the fma, the final addition (4 x 2^-24) and the three borrowed bits
-        // (2^-20, on either survivor) -- inside eps16's last term (2^-21 + 2^-20)(|c| + |q|)^2.  Nothing here can
-        // overflow or produce a NaN: K1f sends rows with (|c|max + |q|)^2 >= 1e37 to the exact path before it looks at
-        // these values, and the +inf norms of the padding centroids are clamped to a finite "far".
         float cn_c[8];
-#pragma unroll
-        for (int ct = 0; ct < 8; ct++) {
-            const float cf = (float)cn[c0 + ct * 16 + fr];
-            cn_c[ct] = cf < 3.0e38f ? cf : 3.0e38f;
-        }
-#pragma unroll
-        for (int rt = 0; rt < 2; rt++) {
-#pragma unroll
-            for (int r = 0; r < 4; r++) {
-                float m1 = __int_as_float(0x7f7ffff8), m2 = m1;  // (largest finite value with the position bits clear)
-#pragma unroll
-                for (int ct = 0; ct < 8; ct++) {
-                    const float t = __builtin_fmaf(-2.0f, acc[rt][ct][r], cn_c[ct]);
-                    const float tp = __int_as_float((__float_as_int(t) & ~7) | ct);
-                    m2 = __builtin_amdgcn_fmed3f(m1, m2, tp);
-                    // min(m1, tp) as the median with a value below everything (|t| < 1e37 here): a minnum of a value
-                    // assembled from bits would be preceded by a canonicalising v_max, a fifth instruction per value
-                    m1 = __builtin_amdgcn_fmed3f(m1, tp, -3.0e38f);
-                }
-                const int a1 = __float_as_int(m1) & 7;
-                const float d1 = m1 + qn_r[rt][r];
-                float d2 = m2 + qn_r[rt][r];
-                d2 = d2 < 0.0f ? 0.0f : d2;
-                // the position of the minimum rides in the 3 low mantissa bits of the runner-up (masked off by the reader)
-                const float m2p = __int_as_float((__float_as_int(d2) & ~7) | a1);
-                const int q = q0 + rt * 16 + 4 * fg + r;
-                if (q < nq) gpair[(size_t)q * G + (size_t)t * 16 + fr] = make_float2(d1, m2p);
-            }
-        }
+        split16_tile_norms(cn_c, cn, c0, fr);
+        split16_gmin_store(acc, cn_c, qn_r, q0, nq, gpair, G, t, fr, fg);
     }
 }
 
@@ -1205,10 +1051,7 @@ __global__ __launch_bounds__(MMIDX_BLOCK, 2) void k_coarse_gmin16(const __bf16 *
 // (global_load_lds_dwordx4) into TWO buffers of half a tile (64 centroids x 256 B x {head, tail} = 32 KiB each), so that
 // the next half tile lands while the matrix cores work on the current one -- in K1e the staging round trip
 // (global -> registers -> LDS, two barriers) cost a third of the kernel (timing experiment: 155 us with, 103 us without).
-//   * the DMA writes lane-linear (wave-uniform base + lane x 16 B), so the rows cannot be padded; the 16-byte units of a
-//     row are XOR-swizzled instead -- unit u of row r is FETCHED into slot u ^ (r & 15) by choosing the lane's global
-//     address, and read back from that slot: the 16 lanes of a fragment read (rows r .. r + 15, same u) hit 16 different
-//     slots = all 64 banks;
+//   * the DMA writes lane-linear, so the rows are XOR-swizzled instead of padded (split16_dma_half, mmidx_split16.h);
 //   * the two buffers are two distinct __shared__ arrays and the loop is unrolled by two halves, so that the compiler can
 //     tell the buffer being filled from the one being read (it waits for ALL outstanding LDS-DMA before a ds_read it
 //     cannot disambiguate); the barrier that ends a half drains the DMA issued at its start;
@@ -1218,126 +1061,37 @@ __global__ __launch_bounds__(MMIDX_BLOCK, 2) void k_coarse_gmin16_dma(const __bf
                                                                    const __bf16 *__restrict__ Ch, const __bf16 *__restrict__ Cl,
                                                                    const double *__restrict__ cn, const double *__restrict__ qn,
                                                                    float2 *__restrict__ gpair, int Cp, int nq, int G) {
-    constexpr int Dp = G16_KC;               // 128 bf16 = 256 B = 16 units per row
-    constexpr int HROWS = G16_BC / 2;        // centroids per half tile
-    constexpr int HBYTES = HROWS * Dp * 2;   // 16 KiB per part (head / tail)
-    __shared__ __attribute__((aligned(1024))) unsigned char buf0[2 * HBYTES];
-    __shared__ __attribute__((aligned(1024))) unsigned char buf1[2 * HBYTES];
+    constexpr int Dp = G16_KC;  // 128 bf16 = 256 B = 16 units per row
+    __shared__ __attribute__((aligned(1024))) unsigned char buf0[2 * SPLIT16_HBYTES];
+    __shared__ __attribute__((aligned(1024))) unsigned char buf1[2 * SPLIT16_HBYTES];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int fr = lane & 15, fg = lane >> 4;
     const int q0 = blockIdx.x * G16_BQ + wave * 32;
-    const int ntiles = Cp / G16_BC;
-    const int t_per = (ntiles + gridDim.y - 1) / gridDim.y;
-    const int t_lo = blockIdx.y * t_per, t_hi = (t_lo + t_per < ntiles) ? t_lo + t_per : ntiles;
+    int t_lo, t_hi;
+    split16_tile_range(Cp / G16_BC, gridDim.y, blockIdx.y, t_lo, t_hi);
     if (t_lo >= t_hi) return;  // block-uniform
     float qn_r[2][4];
-#pragma unroll
-    for (int rt = 0; rt < 2; rt++)
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-            const int q = q0 + rt * 16 + 4 * fg + r;
-            qn_r[rt][r] = q < nq ? (float)qn[q] : 0.0f;
-        }
+    split16_row_norms(qn_r, qn, q0, nq, fg);
     bf16x8 ah[2][4], al[2][4];  // A fragments: [row tile][k step of 32], resident for the whole block
-#pragma unroll
-    for (int rt = 0; rt < 2; rt++) {
-        int q = q0 + rt * 16 + fr;
-        q = q < nq ? q : nq - 1;
-#pragma unroll
-        for (int ks = 0; ks < 4; ks++) {
-            ah[rt][ks] = *(const bf16x8 *)(Qh + (size_t)q * Dp + ks * 32 + fg * 8);
-            al[rt][ks] = *(const bf16x8 *)(Ql + (size_t)q * Dp + ks * 32 + fg * 8);
-        }
-    }
+    split16_load_a<false>(ah, al, Qh, Ql, q0, nq, Dp, 0, fr, fg);
     // DMA of one half tile (first centroid row0) into a buffer: 4 + 4 wave-instructions of 1 KiB (4 rows) per wave
-    auto issue = [&](unsigned char *buf, int row0) {
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            const int pu = (i * 4 + wave) * 64 + lane;  // 16-byte slot of the part this lane fills
-            const int row = pu >> 4, slot = pu & 15;
-            const size_t src = ((size_t)(row0 + row) * Dp + (size_t)((slot ^ (row & 15)) * 8)) * 2;  // bytes
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)((const unsigned char *)Ch + src),
-                                             (__attribute__((address_space(3))) void *)(buf + (i * 4 + wave) * 1024), 16, 0, 0);
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)((const unsigned char *)Cl + src),
-                                             (__attribute__((address_space(3))) void *)(buf + HBYTES + (i * 4 + wave) * 1024), 16, 0, 0);
-        }
-    };
+    auto issue = [&](unsigned char *buf, int row0) { split16_dma_half<4>(buf, Ch, Cl, row0, Dp, 0, wave, lane); };
     f32x4 acc[2][8];
-    // the four column tiles of one half: acc[rt][ct0 .. ct0 + 3] += A x B
-    auto half_mma = [&](const unsigned char *buf, const int ct0) {
-#pragma unroll
-        for (int ks = 0; ks < 4; ks++) {
-#pragma unroll
-            for (int cp = 0; cp < 4; cp += 2) {
-                bf16x8 bh[2], bl[2];
-#pragma unroll
-                for (int u = 0; u < 2; u++) {
-                    const int row = (cp + u) * 16 + fr;
-                    const int off = row * (Dp * 2) + (((ks * 4 + fg) ^ fr) * 16);  // (row & 15 == fr)
-                    bh[u] = *(const bf16x8 *)(buf + off);
-                    bl[u] = *(const bf16x8 *)(buf + HBYTES + off);
-                }
-#pragma unroll
-                for (int u = 0; u < 2; u++)
-#pragma unroll
-                    for (int rt = 0; rt < 2; rt++)
-                        acc[rt][ct0 + cp + u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[rt][ks], bh[u], acc[rt][ct0 + cp + u], 0, 0, 0);
-#pragma unroll
-                for (int u = 0; u < 2; u++)
-#pragma unroll
-                    for (int rt = 0; rt < 2; rt++)
-                        acc[rt][ct0 + cp + u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[rt][ks], bl[u], acc[rt][ct0 + cp + u], 0, 0, 0);
-#pragma unroll
-                for (int u = 0; u < 2; u++)
-#pragma unroll
-                    for (int rt = 0; rt < 2; rt++)
-                        acc[rt][ct0 + cp + u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[rt][ks], bh[u], acc[rt][ct0 + cp + u], 0, 0, 0);
-            }
-        }
-    };
     issue(buf0, t_lo * G16_BC);
     __syncthreads();
     for (int t = t_lo; t < t_hi; t++) {
         const int c0 = t * G16_BC;
-#pragma unroll
-        for (int rt = 0; rt < 2; rt++)
-#pragma unroll
-            for (int ct = 0; ct < 8; ct++) acc[rt][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
+        split16_zero_acc(acc);
         // (the tile's squared norms are requested before the DMA: a wait for them then does not wait for the DMA)
         float cn_c[8];
-#pragma unroll
-        for (int ct = 0; ct < 8; ct++) {
-            const float cf = (float)cn[c0 + ct * 16 + fr];
-            cn_c[ct] = cf < 3.0e38f ? cf : 3.0e38f;
-        }
+        split16_tile_norms(cn_c, cn, c0, fr);
         // first half (columns c0 + fr + 16 ct, ct = 0..3) from buf0 while the second half lands in buf1
-        issue(buf1, c0 + HROWS);
-        half_mma(buf0, 0);
+        issue(buf1, c0 + SPLIT16_HROWS);
+        split16_dma_products(acc, 0, ah, al, buf0, fr, fg);
         __syncthreads();  // buf1 has landed (every wave waited for its own DMA), buf0 is free
         if (t + 1 < t_hi) issue(buf0, c0 + G16_BC);
-        half_mma(buf1, 4);
-        // epilogue: as in K1e
-#pragma unroll
-        for (int rt = 0; rt < 2; rt++) {
-#pragma unroll
-            for (int r = 0; r < 4; r++) {
-                float m1 = __int_as_float(0x7f7ffff8), m2 = m1;
-#pragma unroll
-                for (int ct = 0; ct < 8; ct++) {
-                    const float tv = __builtin_fmaf(-2.0f, acc[rt][ct][r], cn_c[ct]);
-                    const float tp = __int_as_float((__float_as_int(tv) & ~7) | ct);
-                    m2 = __builtin_amdgcn_fmed3f(m1, m2, tp);
-                    m1 = __builtin_amdgcn_fmed3f(m1, tp, -3.0e38f);
-                }
-                const int a1 = __float_as_int(m1) & 7;
-                const float d1 = m1 + qn_r[rt][r];
-                float d2 = m2 + qn_r[rt][r];
-                d2 = d2 < 0.0f ? 0.0f : d2;
-                const float m2p = __int_as_float((__float_as_int(d2) & ~7) | a1);
-                const int q = q0 + rt * 16 + 4 * fg + r;
-                if (q < nq) gpair[(size_t)q * G + (size_t)t * 16 + fr] = make_float2(d1, m2p);
-            }
-        }
+        split16_dma_products(acc, 4, ah, al, buf1, fr, fg);
+        split16_gmin_store(acc, cn_c, qn_r, q0, nq, gpair, G, t, fr, fg);
         __syncthreads();  // the next tile's first half has landed in buf0, buf1 is free
     }
 }
@@ -1403,8 +1157,7 @@ __global__ __launch_bounds__(G16G_BLOCK, 1) void k_coarse_gmin16_grp(const __bf1
                                                                   const double *__restrict__ cn, const double *__restrict__ qn,
                                                                   float2 *__restrict__ gpair, int Cp, int nq, int G) {
     constexpr int Dp = G16_KC;               // 128 bf16 = 256 B = 16 units per row
-    constexpr int HROWS = G16_BC / 2;        // centroids per half tile
-    constexpr int HBYTES = HROWS * Dp * 2;   // 16 KiB per part (head / tail)
+    constexpr int HROWS = SPLIT16_HROWS, HBYTES = SPLIT16_HBYTES;
     constexpr int BUFB = 2 * HBYTES;         // a ring buffer: head + tail of a half tile
     constexpr int NORM0 = G16G_RING * BUFB;  // the norms follow the ring
     __shared__ __attribute__((aligned(1024))) unsigned char lds[NORM0 + G16G_NORM_TILES * G16_BC * 4];
@@ -1413,50 +1166,20 @@ __global__ __launch_bounds__(G16G_BLOCK, 1) void k_coarse_gmin16_grp(const __bf1
     const int grp = wave >> 2;
     const int fr = lane & 15, fg = lane >> 4;
     const int q0 = blockIdx.x * G16G_BQ + wave * 32;
-    const int ntiles = Cp / G16_BC;
-    const int t_per = (ntiles + gridDim.y - 1) / gridDim.y;  // (the host keeps this <= G16G_NORM_TILES)
-    const int t_lo = blockIdx.y * t_per, t_hi = (t_lo + t_per < ntiles) ? t_lo + t_per : ntiles;
+    int t_lo, t_hi;  // (the host keeps the tiles per block <= G16G_NORM_TILES)
+    split16_tile_range(Cp / G16_BC, gridDim.y, blockIdx.y, t_lo, t_hi);
     if (t_lo >= t_hi) return;  // block-uniform, before the first barrier
     const int T = t_hi - t_lo;
     // DMA of half h of this block's range into ring buffer h & 3: 2 + 2 wave-instructions of 1 KiB (4 rows) per wave
     auto issue = [&](const int h) {
-        unsigned char *buf = lds + (h & (G16G_RING - 1)) * BUFB;
-        const int row0 = t_lo * G16_BC + h * HROWS;
-#pragma unroll
-        for (int i = 0; i < 2; i++) {
-            const int pu = (i * 8 + wave) * 64 + lane;  // 16-byte slot of the part this lane fills
-            const int row = pu >> 4, slot = pu & 15;
-            const size_t src = ((size_t)(row0 + row) * Dp + (size_t)((slot ^ (row & 15)) * 8)) * 2;  // bytes
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)((const unsigned char *)Ch + src),
-                                             (__attribute__((address_space(3))) void *)(buf + (i * 8 + wave) * 1024), 16, 0, 0);
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)((const unsigned char *)Cl + src),
-                                             (__attribute__((address_space(3))) void *)(buf + HBYTES + (i * 8 + wave) * 1024), 16, 0, 0);
-        }
+        split16_dma_half<8>(lds + (h & (G16G_RING - 1)) * BUFB, Ch, Cl, t_lo * G16_BC + h * HROWS, Dp, 0, wave, lane);
     };
     issue(0);
     issue(1);
     float qn_r[2][4];
-#pragma unroll
-    for (int rt = 0; rt < 2; rt++)
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-            // (the load itself is unconditional, from a clamped row: a load under a condition is branched around and waited
-            //  for on its own, eight round trips in a row)
-            const int q = q0 + rt * 16 + 4 * fg + r;
-            const float v = (float)qn[q < nq ? q : nq - 1];
-            qn_r[rt][r] = q < nq ? v : 0.0f;
-        }
+    split16_row_norms<true>(qn_r, qn, q0, nq, fg);
     bf16x8 ah[2][4], al[2][4];  // A fragments: [row tile][k step of 32], resident for the whole block
-#pragma unroll
-    for (int rt = 0; rt < 2; rt++) {
-        int q = q0 + rt * 16 + fr;
-        q = q < nq ? q : nq - 1;
-#pragma unroll
-        for (int ks = 0; ks < 4; ks++) {
-            ah[rt][ks] = *(const bf16x8 *)(Qh + (size_t)q * Dp + ks * 32 + fg * 8);
-            al[rt][ks] = *(const bf16x8 *)(Ql + (size_t)q * Dp + ks * 32 + fg * 8);
-        }
-    }
+    split16_load_a<false>(ah, al, Qh, Ql, q0, nq, Dp, 0, fr, fg);
     // the block's centroid norms: fp32, the padding centroids' +inf clamped to a finite "far" (the conversion of K1e)
     // (the loads of a pass are unconditional, from clamped positions, and issued together; the compiler still waits vmcnt(0) in
     //  front of each of the four conditional LDS writes -- prologue only, one pass at the headline shape)
@@ -1470,7 +1193,7 @@ __global__ __launch_bounds__(G16G_BLOCK, 1) void k_coarse_gmin16_grp(const __bf1
 #pragma unroll
         for (int k = 0; k < 4; k++) {
             const int i = i0 + k * G16G_BLOCK + tid;
-            if (i < T * G16_BC) ((float *)(lds + NORM0))[i] = cf[k] < 3.0e38f ? cf[k] : 3.0e38f;
+            if (i < T * G16_BC) ((float *)(lds + NORM0))[i] = split16_clamp_norm(cf[k]);
         }
     }
     f32x4 acc[2][8];
@@ -1484,8 +1207,7 @@ __global__ __launch_bounds__(G16G_BLOCK, 1) void k_coarse_gmin16_grp(const __bf1
             const int h = step >> 3, ks = (step >> 1) & 3, cp = (step & 1) * 2;
 #pragma unroll
             for (int u = 0; u < 2; u++) {
-                const int row = (cp + u) * 16 + fr;
-                const int off = h * BUFB + row * (Dp * 2) + (((ks * 4 + fg) ^ fr) * 16);  // (row & 15 == fr)
+                const int off = h * BUFB + split16_dma_frag_offset((cp + u) * 16 + fr, ks, fg, fr);
                 bh[set][u] = *(const bf16x8 *)(tb + off);
                 bl[set][u] = *(const bf16x8 *)(tb + HBYTES + off);
             }
@@ -1518,39 +1240,14 @@ __global__ __launch_bounds__(G16G_BLOCK, 1) void k_coarse_gmin16_grp(const __bf1
             __builtin_amdgcn_sched_barrier(0);
         }
     };
-    auto zero_acc = [&]() {
-#pragma unroll
-        for (int rt = 0; rt < 2; rt++)
-#pragma unroll
-            for (int ct = 0; ct < 8; ct++) acc[rt][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
-    };
+    auto zero_acc = [&]() { split16_zero_acc(acc); };
     // minima + stores of tile j of the block's range: the epilogue of K1e, the norms from LDS
     auto minima = [&](const int j) {
         const float *nrm = (const float *)(lds + NORM0) + j * G16_BC;
         float cn_c[8];
 #pragma unroll
         for (int ct = 0; ct < 8; ct++) cn_c[ct] = nrm[ct * 16 + fr];
-#pragma unroll
-        for (int rt = 0; rt < 2; rt++) {
-#pragma unroll
-            for (int r = 0; r < 4; r++) {
-                float m1 = __int_as_float(0x7f7ffff8), m2 = m1;
-#pragma unroll
-                for (int ct = 0; ct < 8; ct++) {
-                    const float tv = __builtin_fmaf(-2.0f, acc[rt][ct][r], cn_c[ct]);
-                    const float tp = __int_as_float((__float_as_int(tv) & ~7) | ct);
-                    m2 = __builtin_amdgcn_fmed3f(m1, m2, tp);
-                    m1 = __builtin_amdgcn_fmed3f(m1, tp, -3.0e38f);
-                }
-                const int a1 = __float_as_int(m1) & 7;
-                const float d1 = m1 + qn_r[rt][r];
-                float d2 = m2 + qn_r[rt][r];
-                d2 = d2 < 0.0f ? 0.0f : d2;
-                const float m2p = __int_as_float((__float_as_int(d2) & ~7) | a1);
-                const int q = q0 + rt * 16 + 4 * fg + r;
-                if (q < nq) gpair[(size_t)q * G + (size_t)(t_lo + j) * 16 + fr] = make_float2(d1, m2p);
-            }
-        }
+        split16_gmin_store(acc, cn_c, qn_r, q0, nq, gpair, G, t_lo + j, fr, fg);
     };
 #ifdef G16_TIMING
     unsigned long long tacc[4] = {0, 0, 0, 0};
@@ -1639,137 +1336,46 @@ __global__ __launch_bounds__(MMIDX_BLOCK, 2) void k_coarse_gmin16_dma_kc(const _
                                                                    const __bf16 *__restrict__ Ch, const __bf16 *__restrict__ Cl,
                                                                    const double *__restrict__ cn, const double *__restrict__ qn,
                                                                    float2 *__restrict__ gpair, int Cp, int nq, int G, int Dp) {
-    constexpr int KC = G16_KC;               // 128 bf16 = 256 B = 16 units per row and k chunk (Dp = nkc x KC)
-    constexpr int HROWS = G16_BC / 2;        // centroids per half tile
-    constexpr int HBYTES = HROWS * KC * 2;   // 16 KiB per part (head / tail)
+    constexpr int KC = G16_KC;  // 128 bf16 = 256 B = 16 units per row and k chunk (Dp = nkc x KC)
     const int nkc = Dp / KC;
-    __shared__ __attribute__((aligned(1024))) unsigned char buf0[2 * HBYTES];
-    __shared__ __attribute__((aligned(1024))) unsigned char buf1[2 * HBYTES];
+    __shared__ __attribute__((aligned(1024))) unsigned char buf0[2 * SPLIT16_HBYTES];
+    __shared__ __attribute__((aligned(1024))) unsigned char buf1[2 * SPLIT16_HBYTES];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int fr = lane & 15, fg = lane >> 4;
     const int q0 = blockIdx.x * G16_BQ + wave * 32;
-    const int ntiles = Cp / G16_BC;
-    const int t_per = (ntiles + gridDim.y - 1) / gridDim.y;
-    const int t_lo = blockIdx.y * t_per, t_hi = (t_lo + t_per < ntiles) ? t_lo + t_per : ntiles;
+    int t_lo, t_hi;
+    split16_tile_range(Cp / G16_BC, gridDim.y, blockIdx.y, t_lo, t_hi);
     if (t_lo >= t_hi) return;  // block-uniform
     float qn_r[2][4];
-#pragma unroll
-    for (int rt = 0; rt < 2; rt++)
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-            const int q = q0 + rt * 16 + 4 * fg + r;
-            qn_r[rt][r] = q < nq ? (float)qn[q] : 0.0f;
-        }
-    bf16x8 ah[2][4], al[2][4];    // A fragments of the current k chunk: [row tile][k step of 32]
-    auto load_a = [&](bf16x8 (&xh)[2][4], bf16x8 (&xl)[2][4], const int kc) {
-#pragma unroll
-        for (int rt = 0; rt < 2; rt++) {
-            int q = q0 + rt * 16 + fr;
-            q = q < nq ? q : nq - 1;
-#pragma unroll
-            for (int ks = 0; ks < 4; ks++) {
-                xh[rt][ks] = *(const bf16x8 *)(Qh + (size_t)q * Dp + kc * KC + ks * 32 + fg * 8);
-                xl[rt][ks] = *(const bf16x8 *)(Ql + (size_t)q * Dp + kc * KC + ks * 32 + fg * 8);
-            }
-        }
-    };
-    load_a(ah, al, 0);
+    split16_row_norms(qn_r, qn, q0, nq, fg);
+    bf16x8 ah[2][4], al[2][4];  // A fragments of the current k chunk: [row tile][k step of 32]
+    auto load_a = [&](const int kc) { split16_load_a<false>(ah, al, Qh, Ql, q0, nq, Dp, kc * KC, fr, fg); };
+    load_a(0);
     // DMA of one half tile (first centroid row0) into a buffer: 4 + 4 wave-instructions of 1 KiB (4 rows) per wave
-    auto issue = [&](unsigned char *buf, int row0, int kbase) {
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            const int pu = (i * 4 + wave) * 64 + lane;  // 16-byte slot of the part this lane fills
-            const int row = pu >> 4, slot = pu & 15;
-            const size_t src = ((size_t)(row0 + row) * Dp + (size_t)kbase + (size_t)((slot ^ (row & 15)) * 8)) * 2;  // bytes
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)((const unsigned char *)Ch + src),
-                                             (__attribute__((address_space(3))) void *)(buf + (i * 4 + wave) * 1024), 16, 0, 0);
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)((const unsigned char *)Cl + src),
-                                             (__attribute__((address_space(3))) void *)(buf + HBYTES + (i * 4 + wave) * 1024), 16, 0, 0);
-        }
-    };
+    auto issue = [&](unsigned char *buf, int row0, int kbase) { split16_dma_half<4>(buf, Ch, Cl, row0, Dp, kbase, wave, lane); };
     f32x4 acc[2][8];
-    // the four column tiles of one half: acc[rt][ct0 .. ct0 + 3] += A x B
-    auto half_mma = [&](const unsigned char *buf, const int ct0) {
-#pragma unroll
-        for (int ks = 0; ks < 4; ks++) {
-#pragma unroll
-            for (int cp = 0; cp < 4; cp += 2) {
-                bf16x8 bh[2], bl[2];
-#pragma unroll
-                for (int u = 0; u < 2; u++) {
-                    const int row = (cp + u) * 16 + fr;
-                    const int off = row * (KC * 2) + (((ks * 4 + fg) ^ fr) * 16);  // (row & 15 == fr)
-                    bh[u] = *(const bf16x8 *)(buf + off);
-                    bl[u] = *(const bf16x8 *)(buf + HBYTES + off);
-                }
-#pragma unroll
-                for (int u = 0; u < 2; u++)
-#pragma unroll
-                    for (int rt = 0; rt < 2; rt++)
-                        acc[rt][ct0 + cp + u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[rt][ks], bh[u], acc[rt][ct0 + cp + u], 0, 0, 0);
-#pragma unroll
-                for (int u = 0; u < 2; u++)
-#pragma unroll
-                    for (int rt = 0; rt < 2; rt++)
-                        acc[rt][ct0 + cp + u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[rt][ks], bl[u], acc[rt][ct0 + cp + u], 0, 0, 0);
-#pragma unroll
-                for (int u = 0; u < 2; u++)
-#pragma unroll
-                    for (int rt = 0; rt < 2; rt++)
-                        acc[rt][ct0 + cp + u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[rt][ks], bh[u], acc[rt][ct0 + cp + u], 0, 0, 0);
-            }
-        }
-    };
     issue(buf0, t_lo * G16_BC, 0);
     __syncthreads();
     for (int t = t_lo; t < t_hi; t++) {
         const int c0 = t * G16_BC;
-#pragma unroll
-        for (int rt = 0; rt < 2; rt++)
-#pragma unroll
-            for (int ct = 0; ct < 8; ct++) acc[rt][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
+        split16_zero_acc(acc);
         // (the tile's squared norms are requested before the DMA: a wait for them then does not wait for the DMA)
         float cn_c[8];
-#pragma unroll
-        for (int ct = 0; ct < 8; ct++) {
-            const float cf = (float)cn[c0 + ct * 16 + fr];
-            cn_c[ct] = cf < 3.0e38f ? cf : 3.0e38f;
-        }
+        split16_tile_norms(cn_c, cn, c0, fr);
 #pragma unroll 1
         for (int kc = 0; kc < nkc; kc++) {
             const bool last = kc + 1 == nkc;
             // first half of this chunk from buf0 while its second half lands in buf1 and the next chunk's queries are requested
-            issue(buf1, c0 + HROWS, kc * KC);
-            half_mma(buf0, 0);
+            issue(buf1, c0 + SPLIT16_HROWS, kc * KC);
+            split16_dma_products(acc, 0, ah, al, buf0, fr, fg);
             __syncthreads();  // buf1 has landed (every wave waited for its own DMA), buf0 is free
             if (!last) issue(buf0, c0, (kc + 1) * KC);
             else if (t + 1 < t_hi) issue(buf0, c0 + G16_BC, 0);
-            half_mma(buf1, 4);
-            load_a(ah, al, last ? 0 : kc + 1);  // (the fragments are dead here: 222 registers leave no room for a second set)
+            split16_dma_products(acc, 4, ah, al, buf1, fr, fg);
+            load_a(last ? 0 : kc + 1);  // (the fragments are dead here: 222 registers leave no room for a second set)
             if (!last) __syncthreads();  // the next chunk's first half has landed in buf0, buf1 is free
         }
-        // epilogue: as in K1e
-#pragma unroll
-        for (int rt = 0; rt < 2; rt++) {
-#pragma unroll
-            for (int r = 0; r < 4; r++) {
-                float m1 = __int_as_float(0x7f7ffff8), m2 = m1;
-#pragma unroll
-                for (int ct = 0; ct < 8; ct++) {
-                    const float tv = __builtin_fmaf(-2.0f, acc[rt][ct][r], cn_c[ct]);
-                    const float tp = __int_as_float((__float_as_int(tv) & ~7) | ct);
-                    m2 = __builtin_amdgcn_fmed3f(m1, m2, tp);
-                    m1 = __builtin_amdgcn_fmed3f(m1, tp, -3.0e38f);
-                }
-                const int a1 = __float_as_int(m1) & 7;
-                const float d1 = m1 + qn_r[rt][r];
-                float d2 = m2 + qn_r[rt][r];
-                d2 = d2 < 0.0f ? 0.0f : d2;
-                const float m2p = __int_as_float((__float_as_int(d2) & ~7) | a1);
-                const int q = q0 + rt * 16 + 4 * fg + r;
-                if (q < nq) gpair[(size_t)q * G + (size_t)t * 16 + fr] = make_float2(d1, m2p);
-            }
-        }
+        split16_gmin_store(acc, cn_c, qn_r, q0, nq, gpair, G, t, fr, fg);
         __syncthreads();  // the next tile's first half has landed in buf0, buf1 is free
     }
 }
@@ -1799,73 +1405,11 @@ __global__ __launch_bounds__(MMIDX_BLOCK, 2) void k_assign_gmin16_t(const __bf16
     const int nkc = (Dp + G16_KC - 1) / G16_KC;
     float xn_r[2][4];
     [[maybe_unused]] double xrow[2] = {0.0, 0.0};  // FROMX: ||x||^2 (rounded up) of row rt * 16 + fr, in all four lanes that share fr
-    if constexpr (!FROMX) {
-#pragma unroll
-        for (int rt = 0; rt < 2; rt++)
-#pragma unroll
-            for (int r = 0; r < 4; r++) {
-                const long long q = q0 + rt * 16 + 4 * fg + r;
-                xn_r[rt][r] = q < n ? (float)xn[q] : 0.0f;
-            }
-    }
+    if constexpr (!FROMX) split16_row_norms(xn_r, xn, q0, n, fg);
     bf16x8 ah[2][4], al[2][4];
     auto load_a = [&](int kc) {
-        if constexpr (FROMX) {
-#pragma unroll
-            for (int rt = 0; rt < 2; rt++) {
-                long long q = q0 + rt * 16 + fr;
-                q = q < n ? q : n - 1;
-                double pn = 0.0;
-#pragma unroll
-                for (int ks = 0; ks < 4; ks++) {
-                    const int k = ks * 32 + fg * 8;
-                    if (k < D) {  // (D a multiple of 8: a lane's eight values are all inside the row or all padding)
-                        const double2 *xp = (const double2 *)(X + (size_t)q * D + k);
-                        const double2 v0 = xp[0], v1 = xp[1], v2 = xp[2], v3 = xp[3];
-                        const double vv[8] = {v0.x, v0.y, v1.x, v1.y, v2.x, v2.y, v3.x, v3.y};
-#pragma unroll
-                        for (int e = 0; e < 8; e++) {
-                            const float f = (float)vv[e];
-                            const __bf16 hh = (__bf16)f;
-                            ah[rt][ks][e] = hh;
-                            al[rt][ks][e] = (__bf16)(f - (float)hh);  // f - head is exact in fp32
-                            pn += vv[e] * vv[e];
-                        }
-                    } else {
-#pragma unroll
-                        for (int e = 0; e < 8; e++) {
-                            ah[rt][ks][e] = (__bf16)0.0f;
-                            al[rt][ks][e] = (__bf16)0.0f;
-                        }
-                    }
-                }
-                pn += __shfl_xor(pn, 16);
-                pn += __shfl_xor(pn, 32);
-                xrow[rt] = pn * (1.0 + 1e-12);  // only ever used inside error bounds: round up (as k_split_bf16)
-#pragma unroll
-                for (int r = 0; r < 4; r++) xn_r[rt][r] = (float)__shfl(xrow[rt], 4 * fg + r);
-            }
-            return;
-        }
-#pragma unroll
-        for (int rt = 0; rt < 2; rt++) {
-            long long q = q0 + rt * 16 + fr;
-            q = q < n ? q : n - 1;
-#pragma unroll
-            for (int ks = 0; ks < 4; ks++) {
-                const int k = kc * G16_KC + ks * 32 + fg * 8;
-                if (k < Dp) {
-                    ah[rt][ks] = *(const bf16x8 *)(Xh + (size_t)q * Dp + k);
-                    al[rt][ks] = *(const bf16x8 *)(Xl + (size_t)q * Dp + k);
-                } else {
-#pragma unroll
-                    for (int e = 0; e < 8; e++) {
-                        ah[rt][ks][e] = (__bf16)0.0f;
-                        al[rt][ks][e] = (__bf16)0.0f;
-                    }
-                }
-            }
-        }
+        if constexpr (FROMX) split16_load_a_fp64<4>(ah, al, xrow, xn_r, X, q0, n, D, fr, fg);
+        else split16_load_a<true>(ah, al, Xh, Xl, q0, n, Dp, kc * G16_KC, fr, fg);
     };
     if (nkc == 1) load_a(0);
     const float inf = __int_as_float(0x7f800000);
@@ -1882,71 +1426,17 @@ __global__ __launch_bounds__(MMIDX_BLOCK, 2) void k_assign_gmin16_t(const __bf16
     for (int t = 0; t < ntiles; t++) {
         const int c0 = t * G16_BC;
         f32x4 acc[2][8];
-#pragma unroll
-        for (int rt = 0; rt < 2; rt++)
-#pragma unroll
-            for (int ct = 0; ct < 8; ct++) acc[rt][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
+        split16_zero_acc(acc);
         for (int kc = 0; kc < nkc; kc++) {
             const int kbase = kc * G16_KC;
             const int kw = (Dp - kbase < G16_KC) ? Dp - kbase : G16_KC;
-            const int upr = kw >> 3;
             __syncthreads();
-            if (upr == 16) {
-                uint4 vh[8], vl[8];
-#pragma unroll
-                for (int i = 0; i < 8; i++) {
-                    const int u = tid + i * MMIDX_BLOCK, row = u >> 4, cu = u & 15;
-                    const size_t src = (size_t)(c0 + row) * Dp + kbase + cu * 8;
-                    vh[i] = *(const uint4 *)(Ch + src);
-                    vl[i] = *(const uint4 *)(Cl + src);
-                }
-#pragma unroll
-                for (int i = 0; i < 8; i++) {
-                    const int u = tid + i * MMIDX_BLOCK, row = u >> 4, cu = u & 15;
-                    *(uint4 *)(Bh + row * G16_STRIDE + cu * 16) = vh[i];
-                    *(uint4 *)(Bl + row * G16_STRIDE + cu * 16) = vl[i];
-                }
-            } else {
-                for (int u = tid; u < G16_BC * upr; u += MMIDX_BLOCK) {
-                    const int row = u / upr, cu = u - row * upr;
-                    const size_t src = (size_t)(c0 + row) * Dp + kbase + cu * 8;
-                    *(uint4 *)(Bh + row * G16_STRIDE + cu * 16) = *(const uint4 *)(Ch + src);
-                    *(uint4 *)(Bl + row * G16_STRIDE + cu * 16) = *(const uint4 *)(Cl + src);
-                }
-            }
+            split16_stage_tile(Bh, Bl, Ch, Cl, c0, Dp, kbase, kw >> 3, tid);
             if (nkc > 1) load_a(kc);
             __syncthreads();
-#pragma unroll
-            for (int ks = 0; ks < 4; ks++) {
-                if (ks * 32 < kw) {
-#pragma unroll
-                    for (int ct = 0; ct < 8; ct += 2) {
-                        bf16x8 bh[2], bl[2];
-#pragma unroll
-                        for (int u = 0; u < 2; u++) {
-                            const int off = ((ct + u) * 16 + fr) * G16_STRIDE + (ks * 32 + fg * 8) * 2;
-                            bh[u] = *(const bf16x8 *)(Bh + off);
-                            bl[u] = *(const bf16x8 *)(Bl + off);
-                        }
-#pragma unroll
-                        for (int u = 0; u < 2; u++)
-#pragma unroll
-                            for (int rt = 0; rt < 2; rt++)
-                                acc[rt][ct + u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[rt][ks], bh[u], acc[rt][ct + u], 0, 0, 0);
-#pragma unroll
-                        for (int u = 0; u < 2; u++)
-#pragma unroll
-                            for (int rt = 0; rt < 2; rt++)
-                                acc[rt][ct + u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[rt][ks], bl[u], acc[rt][ct + u], 0, 0, 0);
-#pragma unroll
-                        for (int u = 0; u < 2; u++)
-#pragma unroll
-                            for (int rt = 0; rt < 2; rt++)
-                                acc[rt][ct + u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[rt][ks], bh[u], acc[rt][ct + u], 0, 0, 0);
-                    }
-                }
-            }
+            split16_stage_products(acc, ah, al, Bh, Bl, kw, fr, fg);
         }
+        // the running best / second best of the columns a lane holds for each of its rows
         float cn_c[8];
 #pragma unroll
         for (int ct = 0; ct < 8; ct++) cn_c[ct] = (float)cn[c0 + ct * 16 + fr];
@@ -1963,40 +1453,13 @@ __global__ __launch_bounds__(MMIDX_BLOCK, 2) void k_assign_gmin16_t(const __bf16
                     b1[rt][r] = lt1 ? dv : b1[rt][r];
                 }
     }
-    // merge the 16 lanes of every row: (best, its index, second best)
-    auto dppf = [](float v, int ctrl) -> float {
-        switch (ctrl) {
-            case 0: return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0xB1, 0xf, 0xf, true));
-            case 1: return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x4E, 0xf, 0xf, true));
-            case 2: return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x141, 0xf, 0xf, true));
-            default: return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x140, 0xf, 0xf, true));
-        }
-    };
-    auto dppi = [](int v, int ctrl) -> int {
-        switch (ctrl) {
-            case 0: return __builtin_amdgcn_mov_dpp(v, 0xB1, 0xf, 0xf, true);
-            case 1: return __builtin_amdgcn_mov_dpp(v, 0x4E, 0xf, 0xf, true);
-            case 2: return __builtin_amdgcn_mov_dpp(v, 0x141, 0xf, 0xf, true);
-            default: return __builtin_amdgcn_mov_dpp(v, 0x140, 0xf, 0xf, true);
-        }
-    };
 #pragma unroll
     for (int rt = 0; rt < 2; rt++)
 #pragma unroll
         for (int r = 0; r < 4; r++) {
             float m1 = b1[rt][r], m2 = b2[rt][r];
             int ix = i1[rt][r];
-#pragma unroll
-            for (int step = 0; step < 4; step++) {
-                const float o1 = dppf(m1, step), o2 = dppf(m2, step);
-                const int oi = dppi(ix, step);
-                const bool take = o1 < m1 || (o1 == m1 && oi < ix);
-                const float hi1 = take ? m1 : o1;  // the larger of the two bests
-                const float lo2 = o2 < m2 ? o2 : m2;
-                m2 = hi1 < lo2 ? hi1 : lo2;
-                ix = take ? oi : ix;
-                m1 = take ? o1 : m1;
-            }
+            row16_best2_merge(m1, ix, m2);  // the 16 lanes of the row
             const long long q = q0 + rt * 16 + 4 * fg + r;
             double xnd_x = 0.0;
             if constexpr (FROMX) xnd_x = __shfl(xrow[rt], 4 * fg + r);

@@ -24,6 +24,7 @@
 // smallest nor tied with the (k + 1)-th.  Queries with (max|x| + |q|)^2 outside filter_norms_usable() are not certified.
 #pragma once
 #include "mmidx_device_util.h"
+#include "mmidx_split16.h"
 
 #define LIN_NT 256
 #define LIN_KEY_MAX 0xFFFFFFFFFFFFFFFFull
@@ -55,11 +56,7 @@ __global__ __launch_bounds__(LIN_NT) void k_lin_split(const double *__restrict__
     double s = 0.0;
     for (int j = lane; j < Dp; j += 64) {
         const double v = j < D ? X[(size_t)r * D + j] : 0.0;
-        const float f = (float)v;
-        const __bf16 h = (__bf16)f;
-        const __bf16 l = (__bf16)(f - (float)h);  // f - h is exact in fp32
-        H[(size_t)r * Dp + j] = h;
-        L[(size_t)r * Dp + j] = l;
+        split16_head_tail((float)v, H[(size_t)r * Dp + j], L[(size_t)r * Dp + j]);
         s += v * v;
     }
 #pragma unroll
@@ -210,27 +207,7 @@ __global__ __launch_bounds__(LIN_NT, 2) void k_lin_sweep(const __bf16 *__restric
         }
     if (!__any(any_q)) return;  // every query of the wave is handed back already
     bf16x8 ah[2][4], al[2][4];
-    auto load_a = [&](int kc) {
-#pragma unroll
-        for (int rt = 0; rt < 2; rt++) {
-            int q = q0 + rt * 16 + fr;
-            q = q < nq ? q : nq - 1;
-#pragma unroll
-            for (int ks = 0; ks < 4; ks++) {
-                const int k = kc * 128 + ks * 32 + fg * 8;
-                if (k < Dp) {
-                    ah[rt][ks] = *(const bf16x8 *)(Qh + (size_t)q * Dp + k);
-                    al[rt][ks] = *(const bf16x8 *)(Ql + (size_t)q * Dp + k);
-                } else {
-#pragma unroll
-                    for (int e = 0; e < 8; e++) {
-                        ah[rt][ks][e] = (__bf16)0.0f;
-                        al[rt][ks][e] = (__bf16)0.0f;
-                    }
-                }
-            }
-        }
-    };
+    auto load_a = [&](int kc) { split16_load_a<true>(ah, al, Qh, Ql, q0, nq, Dp, kc * 128, fr, fg); };
     if (nkc == 1) load_a(0);
     const long long ngroups = (r1 - r0 + 63) / 64;
     const u64 lane_lt = (1ull << lane) - 1ull;
@@ -259,18 +236,7 @@ __global__ __launch_bounds__(LIN_NT, 2) void k_lin_sweep(const __bf16 *__restric
                         bh[ct] = *(const bf16x8 *)(Xh + (size_t)rowc[ct] * Dp + k);
                         bl[ct] = *(const bf16x8 *)(Xl + (size_t)rowc[ct] * Dp + k);
                     }
-#pragma unroll
-                    for (int ct = 0; ct < 4; ct++)
-#pragma unroll
-                        for (int rt = 0; rt < 2; rt++) acc[rt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[rt][ks], bh[ct], acc[rt][ct], 0, 0, 0);
-#pragma unroll
-                    for (int ct = 0; ct < 4; ct++)
-#pragma unroll
-                        for (int rt = 0; rt < 2; rt++) acc[rt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[rt][ks], bl[ct], acc[rt][ct], 0, 0, 0);
-#pragma unroll
-                    for (int ct = 0; ct < 4; ct++)
-#pragma unroll
-                        for (int rt = 0; rt < 2; rt++) acc[rt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[rt][ks], bh[ct], acc[rt][ct], 0, 0, 0);
+                    split16_mma_step<4>(acc, 0, ah, al, ks, bh, bl);
                 }
             }
         }

@@ -1298,6 +1298,13 @@ def test_coarse_stage_group_minima_shapes(mi, oracle, D, C, w):
         nat.check(mi.lib().mmidx_coarse_device(ix._h, len(Q), dQ.data_ptr(), cells.data_ptr(), cd.data_ptr(), None))
         torch.cuda.synchronize()
         res[v1] = (cells.cpu().numpy(), cd.cpu().numpy())
+        if v1 == 0:
+            # which form of K1e ran: "-" where the gates of run_coarse keep K1e out altogether (C < 256 or C > 16384: not certified;
+            # fewer than 4 (w + 1) groups of 8 centroids: K1c + K1d), else by Dp = D rounded up to 32
+            Dp, Cp = (D + 31) // 32 * 32, (C + 127) // 128 * 128
+            k1e = 256 <= C <= 16384 and Cp // 8 >= 4 * (w + 1)
+            mm = "-" if not k1e else "groups" if Dp == 128 else "dma_kc" if Dp % 128 == 0 else "staged"
+            assert ix.get_dispatch()["coarse_mm"] == mm, (D, C, w, ix.get_dispatch())
     exp = np.stack([ref.nearest_coarse(q, w) for q in Q])
     assert np.array_equal(res[0][0], exp) and np.array_equal(res[1][0], exp) and np.array_equal(res[2][0], exp)
     assert np.array_equal(res[0][1], res[1][1]) and np.array_equal(res[0][1], res[2][1])

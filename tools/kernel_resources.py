@@ -5,7 +5,9 @@
     python tools/kernel_resources.py res.txt
 
 A kernel lives in the one unit that includes its header: the search path in mmidx_api.hip, K7 / K8 (k_pca_project, k_vlad*) in
-mmidx_frontend.hip, the others in mmidx_bow.hip, mmidx_learn.hip, mmidx_pca_learn.hip and mmidx_probe.hip.
+mmidx_frontend.hip, the others in mmidx_bow.hip, mmidx_learn.hip, mmidx_pca_learn.hip and mmidx_probe.hip.  The device-only
+header mmidx_split16.h (the shared pieces of the bf16-split kernels) defines no kernel: its functions are inlined into K1e / K1e' /
+K1e'' / K6a' (mmidx_api.hip), K8'' (mmidx_frontend.hip) and the Linear sweep (mmidx_linear.hip), so an edit there shows in all three.
 """
 import re
 import sys
