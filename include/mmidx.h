@@ -473,7 +473,14 @@ int mmidx_get_stats(mmidx_index *h, mmidx_stats *out);
 /* Which kernel family served each stage of the most recent search sub-batch of this handle (ABI version 7), as text:
  * "coarse=<K1..>;pass_a=<K3 | K3h | K3ma | ..>;pre=<K3s | ->;pass_b=<K3m | K3mk | K3g | K3f.. | ->;coarse_mm=<groups | dma | dma_kc | staged | ->"
  * (coarse_mm: the form of K1e's matrix kernel, "-" where the coarse stage is not K1e; DESIGN.md section 5.0 lists the gates;
- * tests/test_gpu_dispatch.py asserts the table).  A sharded handle reports its first shard.  Diagnostic: not a stable format. */
+ * tests/test_gpu_dispatch.py asserts the table).  Three fields follow them for the build path (the "build" table of section 5.0;
+ * tests/test_gpu_build.py asserts it):
+ *   ";assign=<K6a'(rows) | K6a'(copies) | K6a | exact | ->"   the kernel of the most recent assignment: K6a' fed from the fp64 rows,
+ *        K6a' fed from k_split_bf16's copies, the fp32 K6a, the exact kernel alone; "-" for a flat PQ or before any assignment
+ *   ";encode=<K6b' | K6b | ->"   the product quantisation kernel of the most recent encode
+ *   ";flagged=<count | ->"   vectors that the most recent mmidx_encode / _add_vectors / _assign_device / _encode_device /
+ *        _add_vectors_device call sent to the exact redo, summed over its internal chunks; "-" where no certified kernel ran in it
+ * A sharded handle reports its first shard.  Diagnostic: not a stable format. */
 int mmidx_get_dispatch(mmidx_index *h, char *out, int cap);
 
 /* Measured ceilings for the rooflines bench.py reports (csrc/mmidx_probe.hip; SURVEY 8d "secondary: LDS gather rate", A5):

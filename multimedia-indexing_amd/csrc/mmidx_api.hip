@@ -284,6 +284,10 @@ struct mmidx_index {
     size_t mf_ev_used = 0;
     // which kernel family served each stage of the most recent search sub-batch (mmidx_get_dispatch; host-side words, a few stores per call)
     const char *disp_coarse = "-", *disp_passa = "-", *disp_passb = "-", *disp_pre = "-", *disp_coarse_mm = "-";
+    // ... and the build path: the kernels of the most recent assignment / encode, and the vectors the most recent public build call
+    // sent to the exact redo, summed over its chunks (-1: no certified kernel ran in it); see BuildReport
+    const char *disp_assign = "-", *disp_encode = "-";
+    int64_t disp_flagged = -1;
     // K3ma (pass A on the matrix cores, mmidx_scan_mfma_a.h)
     hipEvent_t host_ev[4] = {nullptr, nullptr, nullptr, nullptr};  // mmidx_search (host buffers): the answers' slices on their way back
     double *d_pqstat = nullptr;        // K3q: [m * dsub] mean_j p_sj[t], then [m] mean_j ||p_sj||^2
@@ -492,6 +496,23 @@ size_t scan_lds_bytes(const mmidx_index *h, int cap) {
     return (size_t)h->m * h->ks * 8 + (h->transform ? 2 : 1) * (size_t)h->D * 8 + (size_t)cap * 12 + 16;
 }
 
+// mmidx_get_dispatch's `flagged` counts over one PUBLIC build call.  The host entry points run the device ones chunk by chunk on the
+// same thread, so every entry point holds a BuildReport and only the outermost one on the thread starts a new count.  (Diagnostic:
+// two threads building on one handle at once share the fields.)
+thread_local const mmidx_index *tl_build_call = nullptr;
+struct BuildReport {
+    const mmidx_index *const prev;
+    explicit BuildReport(mmidx_index *h) : prev(tl_build_call) {
+        if (prev != h) {
+            tl_build_call = h;
+            h->disp_flagged = -1;
+        }
+    }
+    ~BuildReport() { tl_build_call = prev; }
+    BuildReport(const BuildReport &) = delete;
+    BuildReport &operator=(const BuildReport &) = delete;
+};
+
 // encode n device-resident vectors into (cell, code); code_out holds centroid indices (CodeT)
 // nearest coarse centroid of n device-resident vectors (computeNearestCoarseIndex, IVFPQ.java:547-564): exact fp64 argmin,
 // first index wins ties; -1 for a PQ index
@@ -512,6 +533,7 @@ int assign_device(mmidx_index *h, int64_t n, const double *dX, int32_t *d_cell, 
             // bf16-split dot products on the matrix cores (K6a'), 5x the rate of the fp32 MFMA
             const size_t l16 = 2 * (size_t)G16_BC * G16_STRIDE;
             const bool fromx = h->Dp <= G16_KC && (h->D % 8) == 0 && ((uintptr_t)dX & 15) == 0;
+            h->disp_assign = fromx ? "K6a'(rows)" : "K6a'(copies)";
             if (fromx) {  // one k chunk: the kernel splits the fp64 rows itself (no k_split_bf16 round trip through HBM)
                 HIPCK(hipFuncSetAttribute((const void *)k_assign_gmin16_t<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l16));
                 hipLaunchKernelGGL(k_assign_gmin16_t<true>, dim3((unsigned)((n + G16_BQ - 1) / G16_BQ)), dim3(MMIDX_BLOCK), l16, st, (const __bf16 *)nullptr,
@@ -529,6 +551,7 @@ int assign_device(mmidx_index *h, int64_t n, const double *dX, int32_t *d_cell, 
                                    h->ws_aidx.p + n);
             }
         } else {
+            h->disp_assign = "K6a";
             hipLaunchKernelGGL(k_query_prep, dim3((unsigned)((n + 3) / 4)), dim3(MMIDX_BLOCK), 0, st, dX, h->ws_Q32.p, h->ws_qn.p, h->D, (long long)n);
             HIPCK(hipFuncSetAttribute((const void *)k_assign_approx, hipFuncAttributeMaxDynamicSharedMemorySize, (int)asg_lds));
             hipLaunchKernelGGL(k_assign_approx, dim3((unsigned)((n + ASG_BM - 1) / ASG_BM)), dim3(MMIDX_BLOCK), asg_lds, st, h->d_coarseT32,
@@ -547,6 +570,7 @@ int assign_device(mmidx_index *h, int64_t n, const double *dX, int32_t *d_cell, 
         HIPCK(hipMemcpyAsync(&na32, d_na, sizeof(int32_t), hipMemcpyDeviceToHost, st));
         HIPCK(hipStreamSynchronize(st));
         h->last_ambiguous = (int64_t)na32;
+        h->disp_flagged = std::max<int64_t>(h->disp_flagged, 0) + na32;
         if (na32 > 0) {
             const int64_t na = (int64_t)na32;
             HIPCK(h->ws_acell.reserve((size_t)na));
@@ -561,8 +585,10 @@ int assign_device(mmidx_index *h, int64_t n, const double *dX, int32_t *d_cell, 
     } else if (ivf) {
         constexpr int QT = 16;
         const unsigned grid = (unsigned)((n + QT - 1) / QT);
+        h->disp_assign = "exact";
         hipLaunchKernelGGL(k_assign_coarse<QT>, dim3(grid), dim3(MMIDX_BLOCK), 0, st, h->d_coarseT, dX, d_cell, h->C, h->D, (long long)n);
     } else {
+        h->disp_assign = "-";
         HIPCK(hipMemsetAsync(d_cell, 0xFF, (size_t)n * sizeof(int32_t), st));  // -1
     }
     return MMIDX_OK;
@@ -578,6 +604,7 @@ int encode_device(mmidx_index *h, int64_t n, const double *dX, int32_t *d_cell, 
         const size_t rl = (size_t)h->ks * h->dsub * 8 + (size_t)MMIDX_BLOCK * h->m * h->code_bytes;
         if (rl <= 64 * 1024) {
             const unsigned g = (unsigned)((n + MMIDX_BLOCK - 1) / MMIDX_BLOCK);
+            h->disp_encode = "K6b'";
 #define LAUNCH_ROWS(DS, CT)                                                                                                     \
     hipLaunchKernelGGL((k_encode_pq_rows<DS, CT>), dim3(g), dim3(MMIDX_BLOCK), rl, st, dX, d_cell, h->d_coarse, h->d_pq, h->d_perm, \
                        (CT *)d_code, h->D, h->m, h->ks, h->transform, ivf, (long long)n)
@@ -599,6 +626,7 @@ int encode_device(mmidx_index *h, int64_t n, const double *dX, int32_t *d_cell, 
     const size_t lds = 2 * (size_t)VT * h->D * 8 + (size_t)h->m * VT * 4 * 12;
     if (lds > 160 * 1024) return mmidx_fail(MMIDX_ERR_UNSUPPORTED, "vector length %d too large for the encode kernel", h->D);
     const unsigned grid = (unsigned)((n + VT - 1) / VT);
+    h->disp_encode = "K6b";
     if (h->code_bytes == 1) {
         HIPCK(hipFuncSetAttribute((const void *)k_encode_pq<VT, unsigned char>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL((k_encode_pq<VT, unsigned char>), dim3(grid), dim3(MMIDX_BLOCK), lds, st, dX, d_cell, h->d_coarse, h->d_pqT,
@@ -2931,6 +2959,7 @@ int mmidx_encode_device(mmidx_index *h, int64_t n, const double *dX, int32_t *d_
     hipStream_t st = (hipStream_t)stream;
     if (n == 0) return MMIDX_OK;
     DeviceCall call(h, st);
+    BuildReport report(h);
     if (h->code_bytes == 1) {
         // kernels produce centroid indices; the boundary carries the stored form idx - 128
         HIPCK(h->ws_tmp.reserve((size_t)n * h->m));
@@ -2956,6 +2985,7 @@ int mmidx_encode(mmidx_index *h, int64_t n, const double *X, int32_t *cell_out, 
     rc = set_device(h);
     if (rc) return rc;
     std::lock_guard<std::mutex> lk(h->mu);
+    BuildReport report(h);
     const size_t cb = (size_t)h->m * h->code_bytes;
     const int64_t B = 1 << 18;
     for (int64_t i0 = 0; i0 < n; i0 += B) {
@@ -3066,6 +3096,7 @@ int mmidx_add_vectors_device(mmidx_index *h, int64_t n, const double *dX, const 
     std::lock_guard<std::recursive_mutex> alk(h->add_mu);
     DeviceCall call(h, h->stream);  // (the encoder uses the search workspaces, on the handle's own stream)
     std::lock_guard<std::mutex> lk(h->mu);
+    BuildReport report(h);
     if (st != h->stream) HIPCK(hipStreamSynchronize(st));
     rc = ensure_pending(h, n);
     if (rc) return rc;
@@ -3095,6 +3126,7 @@ int mmidx_add_vectors(mmidx_index *h, int64_t n, const double *X, const int32_t 
     rc = set_device(h);
     if (rc) return rc;
     std::lock_guard<std::recursive_mutex> alk(h->add_mu);  // (the pending offset read below and the append are one step)
+    BuildReport report(h);
     const size_t cb = (size_t)h->m * h->code_bytes;
     const int64_t B = 1 << 18;
     for (int64_t i0 = 0; i0 < n; i0 += B) {
@@ -3539,7 +3571,9 @@ int mmidx_assign_device(mmidx_index *h, int64_t n, const double *dX, int32_t *d_
     int rc = set_device(h);
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
+    if (n == 0) return MMIDX_OK;
     DeviceCall call(h, st);
+    BuildReport report(h);
     const int64_t step = std::max<int64_t>(1 << 20, ((int64_t)1 << 29) / std::max(h->Dp, 32));  // bounded scratch for the certified approximate path
     for (int64_t i0 = 0; i0 < n; i0 += step) {
         const int64_t nb = std::min(step, n - i0);
@@ -3787,7 +3821,10 @@ int mmidx_get_dispatch(mmidx_index *h, char *out, int cap) {
     const bool k3f_ok = s->code_bytes == 1 && s->ks <= 256 && (s->m == 8 || s->m == 16 || s->m == 32) && !s->sw.no_filter;
     const char *pb = s->disp_passb;
     if (!k3f_ok && pb[0] == 'K' && pb[1] == '3' && pb[2] == 'f') pb = "K3(exact scan: no K3f instance for this shape)";
-    snprintf(out, (size_t)cap, "coarse=%s;pass_a=%s;pre=%s;pass_b=%s;coarse_mm=%s", s->disp_coarse, s->disp_passa, s->disp_pre, pb, s->disp_coarse_mm);
+    char flagged[24] = "-";  // (the build path: assign_device / encode_device / BuildReport)
+    if (s->disp_flagged >= 0) snprintf(flagged, sizeof flagged, "%lld", (long long)s->disp_flagged);
+    snprintf(out, (size_t)cap, "coarse=%s;pass_a=%s;pre=%s;pass_b=%s;coarse_mm=%s;assign=%s;encode=%s;flagged=%s", s->disp_coarse, s->disp_passa,
+             s->disp_pre, pb, s->disp_coarse_mm, s->disp_assign, s->disp_encode, flagged);
     return MMIDX_OK;
 }
 

@@ -398,7 +398,10 @@ class _PQBase(AbstractSearchStructure):
         return {f: getattr(s, f) for f, _ in N.Stats._fields_}
 
     def get_dispatch(self):
-        """which kernel family served each stage of the most recent search sub-batch: {"coarse": .., "pass_a": .., "pre": .., "pass_b": ..}"""
+        """which kernel family served each stage of the most recent search sub-batch: {"coarse": .., "pass_a": .., "pre": .., "pass_b": ..,
+        "coarse_mm": ..}, and of the most recent build call: "assign" (K6a'(rows) | K6a'(copies) | K6a | exact | -), "encode" (K6b' | K6b | -)
+        and "flagged", the number of vectors that call sent to the exact redo as text ("-" where no certified kernel ran).  Diagnostic
+        text of the native library (mmidx_get_dispatch): not a stable format."""
         buf = C.create_string_buffer(512)
         N.check(N.lib().mmidx_get_dispatch(self._h, buf, 512))
         return dict(kv.split("=", 1) for kv in buf.value.decode().split(";"))

@@ -134,6 +134,19 @@ for case in range(cases):
         # test_ivfpq_transforms makes.  What stays an assumption (A2) is that EJML's CommonOps.mult uses that order too;
         # against the Java classes the promise for a rotation is 1e-12, against this oracle it is equality.
         ok = np.array_equal(got[2], want[2]) and np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1])
+        # the stored index itself (a wrong code in a record that none of the queries returns changes no answer): list offsets, the
+        # order inside every list, and (cell, stored code) of 256 ids spread over the id range against the oracle's records
+        off, eids, ecodes = ix.export()
+        ok = ok and np.array_equal(off, np.concatenate([[0], np.cumsum(ref.list_sizes(), dtype=np.int64)]))
+        ok = ok and np.array_equal(np.sort(eids), np.arange(n)) and all(np.all(np.diff(eids[off[c]:off[c + 1]]) > 0) for c in range(len(off) - 1))
+        if ok:
+            pos = np.full(n, -1, np.int64)
+            pos[eids] = np.arange(n)
+            ecell = np.searchsorted(off, np.arange(n), side="right") - 1  # list of a position: the last one that starts at or before it
+            for iid in np.unique(np.linspace(0, n - 1, min(n, 256)).astype(np.int64)):
+                rcell, rcode = ref.get_record(int(iid))
+                gcell = int(ecell[pos[iid]]) if kind == "ivfpq" else -1
+                ok = ok and pos[iid] >= 0 and gcell == rcell and np.array_equal(ecodes[pos[iid]].astype(np.int32), rcode)
         ix.close()
         if not ok:
             bad += 1
