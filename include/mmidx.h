@@ -473,7 +473,10 @@ int mmidx_get_stats(mmidx_index *h, mmidx_stats *out);
 /* Which kernel family served each stage of the most recent search sub-batch of this handle (ABI version 7), as text:
  * "coarse=<K1..>;pass_a=<K3 | K3h | K3ma | ..>;pre=<K3s | ->;pass_b=<K3m | K3mk | K3g | K3f.. | ->;coarse_mm=<groups | dma | dma_kc | staged | ->"
  * (coarse_mm: the form of K1e's matrix kernel, "-" where the coarse stage is not K1e; DESIGN.md section 5.0 lists the gates;
- * tests/test_gpu_dispatch.py asserts the table).  Three fields follow them for the build path (the "build" table of section 5.0;
+ * tests/test_gpu_dispatch.py asserts the table).  pass_a names the kernel launch_scan took: "K3(table in two halves)" only where
+ * k_scan_split ran, "K3(table in global scratch)" for every other table beyond the LDS.  pass_b names the exact scan where the
+ * filtered one fell back to it: "K3(exact scan: no K3f instance for this shape)", or "K3(exact scan: symmetric distances)" after
+ * mmidx_search_sdc on an index of several chunks (tests/test_gpu_sdc.py).  Three fields follow them for the build path (the "build" table of section 5.0;
  * tests/test_gpu_build.py asserts it):
  *   ";assign=<K6a'(rows) | K6a'(copies) | K6a | exact | ->"   the kernel of the most recent assignment: K6a' fed from the fp64 rows,
  *        K6a' fed from k_split_bf16's copies, the fp32 K6a, the exact kernel alone; "-" for a flat PQ or before any assignment

@@ -734,18 +734,22 @@ int launch_scan_t(const ScanParams &P, dim3 grid, size_t lds, hipStream_t st) {
     return launch_grid<k_scan<M, CodeT, SU, NT, SDC, GLUT>>(P, grid, NT, lds, st);
 }
 
+// A table of twice the LDS (m = 128 byte codes) in global scratch: two sweeps with half the table in LDS each (k_scan_split) instead of
+// the generic kernel.  Its cap >= K1 + 512 covers the 512-code segments; a chunk's partial sums must fit the block's table slot, half
+// a table must fit next to the vectors and candidates, and the symmetric distances have no table to halve.  lds: the scan's LDS with
+// the whole table counted (pl.lds).  launch_scan's choice, and the label search_batch_device reports for it.
+bool scan_split_applies(const mmidx_index *h, const ScanParams &P, size_t lds) {
+    return P.glut && !P.sdc_tt && !h->sw.no_split_table && h->code_bytes == 1 && h->ks == 256 && h->m == 128 && P.chunk <= h->m * h->ks &&
+           lds - (size_t)h->m * h->ks * 8 + (size_t)64 * 256 * 8 <= 160 * 1024;
+}
+
 // su = codes per thread per segment (1 or 2); P.cap and lds sized for it
 int launch_scan(const mmidx_index *h, const ScanParams &P, dim3 grid, size_t lds, hipStream_t st, int su = 2) {
     if (P.glut) {  // the table lives in global scratch (make_plan: it does not fit the LDS): generic kernels, LDS = vectors + candidates
         if ((size_t)grid.x * grid.y > h->glut_slots) return mmidx_fail(MMIDX_ERR_UNSUPPORTED, "lookup-table scratch too small for %u x %u blocks", grid.x, grid.y);
         if (P.cap < P.K1 + MMIDX_SEG) return mmidx_fail(MMIDX_ERR_UNSUPPORTED, "candidate buffer of %d entries too small for k + 1 = %d and a %d-code segment", P.cap, P.K1, MMIDX_SEG);
         const size_t l = lds - (size_t)h->m * h->ks * 8;
-        // twice the LDS (m = 128 byte codes): two sweeps with half the table in LDS each (k_scan_split); cap >= K1 + 512 covers its
-        // 512-code segments, a chunk's partial sums fit the block's table slot
-        if (!P.sdc_tt && !h->sw.no_split_table && h->code_bytes == 1 && h->ks == 256 && h->m == 128 && P.chunk <= h->m * h->ks &&
-            l + (size_t)64 * 256 * 8 <= 160 * 1024) {
-            return launch_grid<k_scan_split<128, 512>>(P, grid, 512, l + (size_t)64 * 256 * 8, st);
-        }
+        if (scan_split_applies(h, P, lds)) return launch_grid<k_scan_split<128, 512>>(P, grid, 512, l + (size_t)64 * 256 * 8, st);
         if (P.sdc_tt) return launch_scan_t<0, unsigned char, 2, MMIDX_BLOCK, true, true>(P, grid, l, st);
         if (h->code_bytes == 1) return launch_scan_t<0, unsigned char, 2, MMIDX_BLOCK, false, true>(P, grid, l, st);
         return launch_scan_t<0, unsigned short, 2, MMIDX_BLOCK, false, true>(P, grid, l, st);
@@ -795,7 +799,7 @@ bool coarse_certified(const mmidx_index *h, size_t *alds_out = nullptr, int *cch
 }
 
 struct SearchPlan;
-int launch_scan_filtered(const mmidx_index *h, ScanParams P, const SearchPlan &pl, dim3 grid, hipStream_t st, int main_grid = 0);
+int launch_scan_filtered(const mmidx_index *h, ScanParams P, const SearchPlan &pl, dim3 grid, hipStream_t st, int main_grid = 0, const char **disp = nullptr);
 
 struct SearchPlan {
     int K1, cap, chunk, nchunks, nitems, poolq;
@@ -898,16 +902,23 @@ int launch_filt_t(const mmidx_index *h, ScanParams P, dim3 grid, size_t lds, hip
     return MMIDX_OK;
 }
 
-// pass B: lower-bound filtered scan where it applies (byte codes, templated m), else the exact scan
-int launch_scan_filtered(const mmidx_index *h, ScanParams P, const SearchPlan &pl, dim3 grid, hipStream_t st, int main_grid) {
-    const bool ok = h->code_bytes == 1 && h->ks <= 256 && (h->m == 8 || h->m == 16 || h->m == 32) && !h->sw.no_filter && !P.sdc_tt;
-    if (!ok) return launch_scan(h, P, grid, pl.lds, st);
+// pass B: lower-bound filtered scan where it applies (byte codes, templated m), else the exact scan.  disp: where the caller reports
+// the kernel of this launch (mmidx_get_dispatch) -- rewritten here, where the fall-back to the exact scan is decided.
+int launch_scan_filtered(const mmidx_index *h, ScanParams P, const SearchPlan &pl, dim3 grid, hipStream_t st, int main_grid, const char **disp) {
+    const bool shape_ok = h->code_bytes == 1 && h->ks <= 256 && (h->m == 8 || h->m == 16 || h->m == 32) && !h->sw.no_filter;
+    if (!shape_ok || P.sdc_tt) {  // (the symmetric distances are one chain over all D dimensions: no per-sub-quantizer bound to filter by)
+        if (disp) *disp = P.sdc_tt ? "K3(exact scan: symmetric distances)" : "K3(exact scan: no K3f instance for this shape)";
+        return launch_scan(h, P, grid, pl.lds, st);
+    }
     int cap = 1;
     while (cap < pl.K1 + MMIDX_VROUND) cap <<= 1;
     P.cap = cap;
     const size_t lds = (size_t)h->m * h->ks * 8 + 2 * (size_t)h->D * 8 + (size_t)cap * 12 + 4 * (size_t)h->m * 8 + 16 +
                        (size_t)MMIDX_SURV_CAP * 4 + 16 + (size_t)h->m * 256;
-    if (lds > 160 * 1024) return launch_scan(h, P, grid, pl.lds, st);
+    if (lds > 160 * 1024) {
+        if (disp) *disp = "K3(exact scan: no K3f instance for this shape)";
+        return launch_scan(h, P, grid, pl.lds, st);
+    }
     switch (h->m) {
         case 8: return launch_filt_t<8>(h, P, grid, lds, st, main_grid);
         case 16: return launch_filt_t<16>(h, P, grid, lds, st, main_grid);
@@ -2149,8 +2160,6 @@ int search_batch_device(mmidx_index *h, const SearchPlan &pl, int k, int64_t nq,
                 // (K3h ran -- its empty fallback launch is not counted as a scan launch -- or failed with rc > 1)
                 h->disp_passa = "K3h";
             } else {
-                h->disp_passa = pl.glut ? ((!h->sw.no_split_table && h->code_bytes == 1 && h->ks == 256 && h->m == 128) ? "K3(table in two halves)" : "K3(table in global scratch)")
-                                        : (two_pass ? "K3" : "K3(single pass)");
                 rc = MMIDX_OK;
                 // one code per thread per segment: smaller candidate buffer -> a fourth block per CU
                 ScanParams PA = P;
@@ -2163,6 +2172,9 @@ int search_batch_device(mmidx_index *h, const SearchPlan &pl, int k, int64_t nq,
                     lds_a = scan_lds_bytes(h, cap1);
                     su = 1;
                 }
+                // (the kernel launch_scan takes for these parameters)
+                h->disp_passa = pl.glut ? (scan_split_applies(h, PA, lds_a) ? "K3(table in two halves)" : "K3(table in global scratch)")
+                                        : (two_pass ? "K3" : "K3(single pass)");
                 rc = launch_scan(h, PA, dim3((unsigned)P.n_items, (unsigned)grid_chunks), lds_a, st, su);
             }
             if (rc) return rc;
@@ -2196,7 +2208,7 @@ int search_batch_device(mmidx_index *h, const SearchPlan &pl, int k, int64_t nq,
             P.xcd_remap = 0;
             h->disp_passb = "K3f";
             rc = launch_scan_grouped_flat(h, P, pl, (long long)nq, st);
-            if (rc == 1) rc = launch_scan_filtered(h, P, pl, dim3((unsigned)P.n_items, 1), st);
+            if (rc == 1) rc = launch_scan_filtered(h, P, pl, dim3((unsigned)P.n_items, 1), st, 0, &h->disp_passb);
             if (rc) return rc;
             DBG_SYNC("pass B scan (flat)");
         }
@@ -2382,7 +2394,7 @@ int search_batch_device(mmidx_index *h, const SearchPlan &pl, int k, int64_t nq,
             rc = launch_scan_grouped(h, P, pl, (long long)nq, npairs, st);
             if (rc == 1) {
                 const unsigned gx = (unsigned)(((P.n_items + 7) / 8) * 8);
-                rc = launch_scan_filtered(h, P, pl, dim3(gx, (unsigned)pl.nchunks), st);
+                rc = launch_scan_filtered(h, P, pl, dim3(gx, (unsigned)pl.nchunks), st, 0, &h->disp_passb);
             }
             if (rc) return rc;
             DBG_SYNC("pass B scan");
@@ -3817,7 +3829,8 @@ int lookup_records(mmidx_index *h, int64_t n, const int32_t *iids, int32_t **d_p
 int mmidx_get_dispatch(mmidx_index *h, char *out, int cap) {
     if (!h || !out || cap < 1) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null argument");
     const mmidx_index *s = h->grp ? sharded_first(h) : h;
-    // (launch_scan_filtered / launch_scan: K3f falls back to the exact scan K3 for shapes it has no instance of)
+    // (launch_scan_filtered / launch_scan: K3f falls back to the exact scan K3 for shapes it has no instance of.  The two pass B sites
+    //  of search_batch_device have launch_scan_filtered record that where it decides it; this covers the K3f labels of the other paths.)
     const bool k3f_ok = s->code_bytes == 1 && s->ks <= 256 && (s->m == 8 || s->m == 16 || s->m == 32) && !s->sw.no_filter;
     const char *pb = s->disp_passb;
     if (!k3f_ok && pb[0] == 'K' && pb[1] == '3' && pb[2] == 'f') pb = "K3(exact scan: no K3f instance for this shape)";

@@ -400,8 +400,12 @@ class _PQBase(AbstractSearchStructure):
     def get_dispatch(self):
         """which kernel family served each stage of the most recent search sub-batch: {"coarse": .., "pass_a": .., "pre": .., "pass_b": ..,
         "coarse_mm": ..}, and of the most recent build call: "assign" (K6a'(rows) | K6a'(copies) | K6a | exact | -), "encode" (K6b' | K6b | -)
-        and "flagged", the number of vectors that call sent to the exact redo as text ("-" where no certified kernel ran).  Diagnostic
-        text of the native library (mmidx_get_dispatch): not a stable format."""
+        and "flagged", the number of vectors that call sent to the exact redo as text ("-" where no certified kernel ran).
+        "pass_a" names the kernel that was launched: "K3(table in two halves)" only where k_scan_split ran (ADC, m = 128 byte codes, a
+        chunk of at most 32768 codes), "K3(table in global scratch)" for every other table beyond the LDS, "K3" / "K3(single pass)"
+        otherwise.  After search_sdc_batch "pass_a" is one of these three K3 forms, "pre" is "-" and "pass_b" is
+        "K3(exact scan: symmetric distances)" on an index of several chunks, "-" on one chunk.  Diagnostic text of the native library
+        (mmidx_get_dispatch): not a stable format."""
         buf = C.create_string_buffer(512)
         N.check(N.lib().mmidx_get_dispatch(self._h, buf, 512))
         return dict(kv.split("=", 1) for kv in buf.value.decode().split(";"))

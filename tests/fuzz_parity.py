@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Randomised differential test: random small IVFPQ / PQ configurations through the HIP path and through the CPU oracle
-(checker), ids and distance bits compared, ties included (the oracle replays the bounded queue).
+(checker), ids and distance bits compared, ties included (the oracle replays the bounded queue).  Flat PQ draws with byte codes
+also make one call by internal id (symmetric distances, mmidx_search_sdc) under the same options.
 
     python tests/fuzz_parity.py [cases] [seed]
 """
@@ -134,6 +135,18 @@ for case in range(cases):
         # test_ivfpq_transforms makes.  What stays an assumption (A2) is that EJML's CommonOps.mult uses that order too;
         # against the Java classes the promise for a rotation is 1e-12, against this oracle it is equality.
         ok = np.array_equal(got[2], want[2]) and np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1])
+        if kind == "pq" and ks <= 256:
+            # flat PQ with byte codes: one call by internal id (PQ.computeKnnSDC, mmidx_search_sdc) under the options of the draw --
+            # the first and the last record, random ones, one of them twice.  (Drawn from a generator of its own: the cases after this
+            # one stay what they were.)
+            srng = np.random.default_rng([int(sys.argv[2]) if len(sys.argv) > 2 else 0, case])
+            rid = [int(x) for x in srng.integers(0, n, 5)]
+            qi = np.array([0, n - 1, rid[0], rid[1], rid[0], rid[2], rid[3], rid[4]], np.int32)
+            si, sd, scnt = ix.search_sdc_batch(k, qi)
+            for j, iid in enumerate(qi):
+                wi, wd = ref.search_sdc(int(iid), k)
+                ok = ok and scnt[j] == len(wi) and np.array_equal(si[j, :len(wi)], wi) and np.array_equal(sd[j, :len(wd)], wd)
+                ok = ok and np.all(si[j, len(wi):] == -1) and np.all(np.isinf(sd[j, len(wi):]))
         # the stored index itself (a wrong code in a record that none of the queries returns changes no answer): list offsets, the
         # order inside every list, and (cell, stored code) of 256 ids spread over the id range against the oracle's records
         off, eids, ecodes = ix.export()

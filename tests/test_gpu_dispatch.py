@@ -40,6 +40,10 @@ ROWS = [
     ("ivfpq", 128, 16, 256, 8, 4, 40000, 30, 100, 0, {"no_mfma": 1}, ("K1a+K1b(exact)", "K3q", "-", "K3g")),
     # flat PQ (cfg2's shape at small scale): chunk 0 through K3h, the others through K3m
     ("pq", 128, 8, 256, 0, 0, 80000, 40, 100, 0, {}, ("-", "K3h", "-", "K3m")),
+    # flat PQ, m = 128: the table in two halves while a chunk's partial sums fit the block's table slot (chunk <= m * ks = 32768 codes) ...
+    ("pq", 128, 128, 256, 0, 0, 6000, 12, 10, 0, {}, ("-", "K3(table in two halves)", "-", "-")),
+    # ... with a longer chunk launch_scan takes the generic kernel, and the label says so (scan_split_applies)
+    ("pq", 128, 128, 256, 0, 0, 6000, 12, 10, 0, {"flat_chunk": 36864}, ("-", "K3(table in global scratch)", "-", "-")),
     # w = 1: a single pass
     ("ivfpq", 64, 8, 256, 6, 1, 12000, 20, 10, 0, {}, ("K1a+K1b(exact)", "K3(single pass)", "-", "-")),
 ]
