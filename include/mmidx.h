@@ -337,6 +337,40 @@ int mmidx_linear_copy_rows_device(mmidx_linear *l, int64_t iid0, int64_t n, doub
 int mmidx_linear_set_option(mmidx_linear *l, const char *name, int value);
 int mmidx_linear_get_stats(mmidx_linear *l, mmidx_linear_stats *out);
 
+/* ---- exact re-ranking of a PQ / IVFPQ answer against a Linear handle ---------------------------------
+ * An extension of the reference, whose deployment keeps both structures: IndexTransformation.java:61-125 walks a full-vector
+ * Linear index into a PQ / IVFPQ one, and Example.java:155-182 compares their answers.  Identity contract: the record with
+ * internal id i of the compressed handle h is row i of the Linear handle l, which is what that walk produces (:113-122).
+ * refine(k, R, q), for nq queries:
+ *   1. the candidates are exactly the answer of mmidx_search(h, R, q): at most R records, ascending code distance, the bounded
+ *      queue's order among equal ones;
+ *   2. a candidate whose internal id is outside [0, size(l)) is dropped and counted in `missing`; its row is never read;
+ *   3. every other candidate gets d = sum_j (q[j] - x[j])^2 from row iid of l: fp64, j ascending, uncontracted (Linear.java:147-149);
+ *   4. the pairs (iid, d) are offered in the candidates' order to a bounded queue of size k under ASS.lookUp's rule (ASS:345-358):
+ *      a candidate equal to the worst kept is rejected, a better one evicts the earliest-inserted of the equal-worst.
+ * Row i of iid_out / dist_out holds count_out[i] = min(k, candidates kept) results, nearest first by exact squared distance, the
+ * later-offered first among equal distances; unused tail entries are iid -1 / +inf, as mmidx_search pads.  *missing_out (may be
+ * NULL) is the number of dropped candidates summed over the call.  With R = size and w = C on tie-free data the answer is
+ * mmidx_linear_search's, bit for bit.
+ *   mmidx_search_refine          host arrays, synchronous, in rounds on the index handle's stream
+ *   mmidx_search_refine_device   device pointers, asynchronous on `stream`; nothing is read back.  d_missing_out (may be NULL) is
+ *                                one int64 in HBM, zeroed and then added to by the call.  The Linear handle orders the call
+ *                                against its adds on other streams, as its own _device calls do.
+ *   mmidx_search_refine_ids      computeNearestNeighbors(k, String id) in exact form (Linear.java:181-184): the query is row
+ *                                iids[q] of l, gathered on the device, then refined like any other.  An id outside [0, size(l))
+ *                                gives count 0 and a padded row, and adds nothing to `missing`.
+ * Refused before any launch, the message naming the offending value: a null handle, k < 1, R < k, R > 4095 (the k of
+ * mmidx_search), vector lengths of h and l that differ, handles on different devices -- MMIDX_ERR_INVALID_ARG; a sharded h --
+ * MMIDX_ERR_UNSUPPORTED.  nq == 0 is MMIDX_OK and writes nothing but *missing_out = 0 (host forms).  An empty l is legal: every
+ * candidate is missing and the counts are 0.  Locks: the index handle first, then the Linear handle. */
+int mmidx_search_refine(mmidx_index *h, mmidx_linear *l, int k, int R, int64_t nq, const double *Q, int32_t *iid_out,
+                        double *dist_out, int32_t *count_out, int64_t *missing_out);
+int mmidx_search_refine_device(mmidx_index *h, mmidx_linear *l, int k, int R, int64_t nq, const double *dQ,
+                               int32_t *d_iid_out, double *d_dist_out, int32_t *d_count_out, int64_t *d_missing_out,
+                               void *stream);
+int mmidx_search_refine_ids(mmidx_index *h, mmidx_linear *l, int k, int R, int64_t nq, const int32_t *iids, int32_t *iid_out,
+                            double *dist_out, int32_t *count_out, int64_t *missing_out);
+
 /* ---- codebook learning (J/visual/quantization/AbstractQuantizerLearning.java:39-81) ------
  * k-means on the GPU in place of Weka's SimpleKMeans, which the reference calls with setSeed(seed),
  * setNumClusters(k), setMaxIterations(max_iter) and, optionally, k-means++ seeding.  flags:

@@ -246,6 +246,11 @@ struct mmidx_index {
     // call's ids and found flags on the device (host forms, and the fix-up of mmidx_search_ids_device)
     double *d_rotT = nullptr;
     DevBuf<int32_t> ws_idq, ws_found;
+    // exact re-ranking (K11, mmidx_refine.h): a round's compressed answer for k = R -- ids, distances (the exact ones take their place),
+    // counts -- and the call's `missing` counter of the host forms
+    DevBuf<int32_t> ws_rfi, ws_rfc;
+    DevBuf<double> ws_rfd;
+    DevBuf<int64_t> ws_rfm;
     DevBuf<int32_t> ws_gfb;
     DevBuf<int64_t> ws_flatoff;  // flat PQ through K3g: chunk offsets standing in for list offsets
     DevBuf<double> ws_flatlut;   // ... and the queries' exact lookup tables [nq][m][256] (k_flat_lut)
@@ -2743,6 +2748,10 @@ int mmidx_destroy(mmidx_index *h) {
     if (h->d_rotT) (void)hipFree(h->d_rotT);
     h->ws_idq.release();
     h->ws_found.release();
+    h->ws_rfi.release();
+    h->ws_rfc.release();
+    h->ws_rfd.release();
+    h->ws_rfm.release();
     for (int e = 0; e < 4; e++)
         if (h->host_ev[e]) (void)hipEventDestroy(h->host_ev[e]);
     if (h->d_pqstat) (void)hipFree(h->d_pqstat);
@@ -4111,6 +4120,180 @@ int mmidx_search_ids(mmidx_index *h, int k, int64_t nq, const int32_t *iids, int
         HIPCK(hipStreamSynchronize(h->stream));
     }
     return MMIDX_OK;
+}
+
+// ---- exact re-ranking of a PQ / IVFPQ answer against a Linear handle (K11, mmidx_refine.h) ----------------------
+// The deployment of IndexTransformation.java:61-125 keeps both structures; record iid of the compressed index is row iid of the
+// Linear one (:113-122).  A call is mmidx_search for k = R into workspace, then K11a (exact distances of the R records from their
+// rows, Linear.java:147-149) and K11b (the bounded queue of size k over them in the answer's order) on the same stream.
+namespace {
+
+// the Linear rows of one call: locked after the index handle (DeviceCall), released on every return path
+struct RefineRows {
+    mmidx_linear *l;
+    MmidxLinearRows rows{};
+    bool held = false;
+    explicit RefineRows(mmidx_linear *l_) : l(l_) {}
+    int acquire(hipStream_t st) {
+        const int rc = mmidx_internal_linear_rows_acquire(l, st, &rows);
+        held = rc == MMIDX_OK;
+        return rc;
+    }
+    ~RefineRows() {
+        if (held) mmidx_internal_linear_rows_release(l);
+    }
+};
+
+// everything a refine call is refused for, before any launch
+int refine_check(const char *name, const mmidx_index *h, const mmidx_linear *l, int k, int R, int64_t nq, bool have_ptrs) {
+    if (!h) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "%s: null index handle", name);
+    if (!l) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "%s: null Linear handle", name);
+    if (k < 1) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "%s: k must be positive (got %d)", name, k);
+    if (R < k) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "%s: R = %d is below k = %d", name, R, k);
+    if (R > MMIDX_K_MAX) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "%s: R must be in k..%d (got %d)", name, MMIDX_K_MAX, R);
+    if (nq < 0) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "%s: nq < 0", name);
+    if (nq > 0 && !have_ptrs) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "%s: null argument", name);
+    if (h->grp)
+        return mmidx_fail(MMIDX_ERR_UNSUPPORTED, "%s takes a plain handle: a sharded handle has one device per shard (use the "
+                                                 "host-pointer entry points or the _sliced_device forms)", name);
+    int lD = 0, ldev = 0;
+    mmidx_internal_linear_dims(l, &lD, &ldev);
+    if (h->D != lD) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "%s: the index holds vectors of length %d, the Linear handle of length %d", name, h->D, lD);
+    if (h->device != ldev) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "%s: the index is on device %d, the Linear handle on device %d", name, h->device, ldev);
+    return check_ready(h);
+}
+
+// queries per round of the _device form: the round's R-record answers are one workspace of at most 16 Mi records (192 MiB)
+int64_t refine_round_size(int R) { return std::max<int64_t>(MMIDX_COMB_MAX_Q, ((int64_t)16 << 20) / R); }
+
+int refine_reserve(mmidx_index *h, int64_t nb, int R, hipStream_t st) {
+    const size_t rec = (size_t)nb * R;
+    if (rec > h->ws_rfi.cap || rec > h->ws_rfd.cap || (size_t)nb > h->ws_rfc.cap) HIPCK(hipStreamSynchronize(st));  // (the call before may still read them)
+    HIPCK(h->ws_rfi.reserve(rec));
+    HIPCK(h->ws_rfd.reserve(rec));
+    HIPCK(h->ws_rfc.reserve((size_t)nb));
+    return MMIDX_OK;
+}
+
+// one round of nb queries on the device: answers [nb][k], counts [nb]; d_missing (may be null) is added to
+int refine_round(mmidx_index *h, const MmidxLinearRows &rows, int k, int R, int64_t nb, const double *dQ, const int32_t *d_qvalid, int32_t *d_iid,
+                 double *d_dist, int32_t *d_cnt, int64_t *d_missing, hipStream_t st) {
+    int rc = search_common(h, R, nb, dQ, nullptr, 0, h->ws_rfi.p, h->ws_rfd.p, h->ws_rfc.p, nullptr, nullptr, st);
+    if (rc) return rc;
+    MmidxRefineArgs a{};
+    a.dX = rows.dX;
+    a.n = rows.n;
+    a.D = rows.D;
+    a.k = k;
+    a.R = R;
+    a.nq = nb;
+    a.dQ = dQ;
+    a.d_qvalid = d_qvalid;
+    a.d_cand_iid = h->ws_rfi.p;
+    a.d_cand_dist = h->ws_rfd.p;
+    a.d_cand_cnt = h->ws_rfc.p;
+    a.d_iid_out = d_iid;
+    a.d_dist_out = d_dist;
+    a.d_cnt_out = d_cnt;
+    a.d_missing = d_missing;
+    return mmidx_internal_refine_round(&a, st);
+}
+
+// the host forms, in rounds of MMIDX_COMB_MAX_Q on the handle's own stream: the queries are Q, or the Linear rows iids[q] (gathered on
+// the device, K11g).  The caller holds the DeviceCall and the rows.
+int refine_host(mmidx_index *h, const MmidxLinearRows &rows, int k, int R, int64_t nq, const double *Q, const int32_t *iids, int32_t *iid_out,
+                double *dist_out, int32_t *count_out, int64_t *missing_out) {
+    hipStream_t st = h->stream;
+    const int64_t qb = std::min<int64_t>(nq, MMIDX_COMB_MAX_Q);
+    HIPCK(h->ws_Q.reserve((size_t)qb * h->D));
+    HIPCK(h->ws_oiid.reserve((size_t)qb * k));
+    HIPCK(h->ws_odist.reserve((size_t)qb * k));
+    HIPCK(h->ws_ocnt.reserve((size_t)qb));
+    HIPCK(h->ws_rfm.reserve(1));
+    if (iids) {
+        HIPCK(h->ws_idq.reserve((size_t)qb));
+        HIPCK(h->ws_found.reserve((size_t)qb));
+    }
+    int rc = refine_reserve(h, qb, R, st);
+    if (rc) return rc;
+    HIPCK(hipMemsetAsync(h->ws_rfm.p, 0, 8, st));
+    for (int64_t q0 = 0; q0 < nq; q0 += qb) {
+        const int64_t nb = std::min(qb, nq - q0);
+        if (iids) {
+            HIPCK(hipMemcpyAsync(h->ws_idq.p, iids + q0, (size_t)nb * 4, hipMemcpyHostToDevice, st));
+            rc = mmidx_internal_refine_gather_queries(rows.dX, rows.n, rows.D, nb, h->ws_idq.p, h->ws_Q.p, h->ws_found.p, st);
+            if (rc) return rc;
+        } else
+            HIPCK(hipMemcpyAsync(h->ws_Q.p, Q + (size_t)q0 * h->D, (size_t)nb * h->D * 8, hipMemcpyHostToDevice, st));
+        rc = refine_round(h, rows, k, R, nb, h->ws_Q.p, iids ? h->ws_found.p : nullptr, h->ws_oiid.p, h->ws_odist.p, h->ws_ocnt.p, h->ws_rfm.p, st);
+        if (rc) return rc;
+        HIPCK(hipMemcpyAsync(iid_out + (size_t)q0 * k, h->ws_oiid.p, (size_t)nb * k * 4, hipMemcpyDeviceToHost, st));
+        HIPCK(hipMemcpyAsync(dist_out + (size_t)q0 * k, h->ws_odist.p, (size_t)nb * k * 8, hipMemcpyDeviceToHost, st));
+        HIPCK(hipMemcpyAsync(count_out + q0, h->ws_ocnt.p, (size_t)nb * 4, hipMemcpyDeviceToHost, st));
+        HIPCK(hipStreamSynchronize(st));
+    }
+    int64_t missing = 0;
+    HIPCK(hipMemcpyAsync(&missing, h->ws_rfm.p, 8, hipMemcpyDeviceToHost, st));
+    HIPCK(hipStreamSynchronize(st));
+    if (missing_out) *missing_out = missing;
+    return MMIDX_OK;
+}
+
+}  // namespace
+
+int mmidx_search_refine_device(mmidx_index *h, mmidx_linear *l, int k, int R, int64_t nq, const double *dQ, int32_t *d_iid_out, double *d_dist_out,
+                               int32_t *d_count_out, int64_t *d_missing_out, void *stream) {
+    int rc = refine_check("mmidx_search_refine_device", h, l, k, R, nq, dQ && d_iid_out && d_dist_out && d_count_out);
+    if (rc) return rc;
+    if (nq == 0) return MMIDX_OK;
+    rc = set_device(h);
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    DeviceCall call(h, st);
+    RefineRows lr(l);
+    rc = lr.acquire(st);
+    if (rc) return rc;
+    const int64_t QB = refine_round_size(R);
+    rc = refine_reserve(h, std::min(QB, nq), R, st);
+    if (rc) return rc;
+    if (d_missing_out) HIPCK(hipMemsetAsync(d_missing_out, 0, 8, st));
+    for (int64_t q0 = 0; q0 < nq; q0 += QB) {  // (nothing is read back: a round's kernels follow the search in stream order)
+        const int64_t nb = std::min(QB, nq - q0);
+        rc = refine_round(h, lr.rows, k, R, nb, dQ + (size_t)q0 * h->D, nullptr, d_iid_out + (size_t)q0 * k, d_dist_out + (size_t)q0 * k, d_count_out + q0,
+                          d_missing_out, st);
+        if (rc) return rc;
+    }
+    return MMIDX_OK;
+}
+
+int mmidx_search_refine(mmidx_index *h, mmidx_linear *l, int k, int R, int64_t nq, const double *Q, int32_t *iid_out, double *dist_out,
+                        int32_t *count_out, int64_t *missing_out) {
+    int rc = refine_check("mmidx_search_refine", h, l, k, R, nq, Q && iid_out && dist_out && count_out);
+    if (rc) return rc;
+    if (missing_out) *missing_out = 0;
+    if (nq == 0) return MMIDX_OK;
+    rc = set_device(h);
+    if (rc) return rc;
+    DeviceCall call(h, h->stream);
+    RefineRows lr(l);
+    rc = lr.acquire(h->stream);
+    if (rc) return rc;
+    return refine_host(h, lr.rows, k, R, nq, Q, nullptr, iid_out, dist_out, count_out, missing_out);
+}
+
+int mmidx_search_refine_ids(mmidx_index *h, mmidx_linear *l, int k, int R, int64_t nq, const int32_t *iids, int32_t *iid_out, double *dist_out,
+                            int32_t *count_out, int64_t *missing_out) {
+    int rc = refine_check("mmidx_search_refine_ids", h, l, k, R, nq, iids && iid_out && dist_out && count_out);
+    if (rc) return rc;
+    if (missing_out) *missing_out = 0;
+    if (nq == 0) return MMIDX_OK;
+    rc = set_device(h);
+    if (rc) return rc;
+    DeviceCall call(h, h->stream);
+    RefineRows lr(l);
+    rc = lr.acquire(h->stream);
+    if (rc) return rc;
+    return refine_host(h, lr.rows, k, R, nq, nullptr, iids, iid_out, dist_out, count_out, missing_out);
 }
 
 /* snapshot of the in-memory index, list-major (the layout loadIndexInMemory builds) */

@@ -201,4 +201,39 @@ MMIDX_HIDDEN int mmidx_internal_ids_found(const int32_t *d_iids, int64_t n, cons
 MMIDX_HIDDEN int mmidx_internal_transpose_square(const double *d_src, double *d_dst, int D, hipStream_t st);
 MMIDX_HIDDEN int mmidx_internal_mark_unknown_rows(const int32_t *d_found, int64_t nq, int k, int32_t *d_iid, double *d_dist, int32_t *d_cnt,
                                                   hipStream_t st);
+// mmidx_linear.hip: what the exact re-ranking (mmidx_search_refine*) reads of a Linear handle -- the fp64 rows in arrival order
+// (row iid = the vector of internal id iid, IndexTransformation.java:113-122), their number, the vector length and the device.
+// _acquire locks l->mu and, where it returns MMIDX_OK, leaves it locked until _release: an add cannot move the rows under a
+// launch that is being enqueued.  It honours lin_wait_other_stream: work another stream still has in flight on the handle (an
+// mmidx_linear_add_device, say) is waited for, and `st` becomes the handle's last stream, so a later add on another stream waits
+// for the kernels enqueued here.  LOCK ORDER: always the index handle first (DeviceCall, mmidx_index::search_mu), then the Linear
+// handle; nothing in the library takes them the other way round.  _dims reads what never changes after mmidx_linear_create.
+struct MmidxLinearRows {
+    const double *dX;  // [n][D]; null while n == 0
+    int64_t n;
+    int D, device;
+};
+MMIDX_HIDDEN void mmidx_internal_linear_dims(const mmidx_linear *l, int *D_out, int *device_out);
+MMIDX_HIDDEN int mmidx_internal_linear_rows_acquire(mmidx_linear *l, hipStream_t st, MmidxLinearRows *out);
+MMIDX_HIDDEN void mmidx_internal_linear_rows_release(mmidx_linear *l);
+// mmidx_refine.hip: K11g -- rows d_iids[q] of dX as queries dQ[nq][D]; d_valid[q] = 0 and a row of zeros for an id outside [0, n)
+MMIDX_HIDDEN int mmidx_internal_refine_gather_queries(const double *dX, int64_t n, int D, int64_t nq, const int32_t *d_iids, double *dQ,
+                                                      int32_t *d_valid, hipStream_t st);
+// mmidx_refine.hip: K11a + K11b for one round of queries on plain device pointers (mmidx_refine.h)
+struct MmidxRefineArgs {
+    const double *dX;  // the Linear rows [n][D]
+    int64_t n;
+    int D, k, R;
+    int64_t nq;
+    const double *dQ;          // [nq][D]
+    const int32_t *d_qvalid;   // [nq] or null: 0 = the query does not exist (count 0, padding, nothing counted as missing)
+    int32_t *d_cand_iid;       // [nq][R] the compressed answer for k = R; dropped records are overwritten with -1
+    double *d_cand_dist;       // [nq][R] its distances on entry, the exact ones of the records kept on return
+    const int32_t *d_cand_cnt; // [nq]
+    int32_t *d_iid_out;        // [nq][k]
+    double *d_dist_out;        // [nq][k]
+    int32_t *d_cnt_out;        // [nq]
+    int64_t *d_missing;        // one counter the round adds to, or null
+};
+MMIDX_HIDDEN int mmidx_internal_refine_round(const MmidxRefineArgs *a, hipStream_t st);
 }  // extern "C"

@@ -599,4 +599,23 @@ int mmidx_linear_search(mmidx_linear *l, int k, int64_t nq, const double *Q, int
     });
 }
 
+// ---- the rows, for the exact re-ranking of a PQ / IVFPQ answer (mmidx_search_refine* in mmidx_api.hip; mmidx_host.h has the contract) ----
+void mmidx_internal_linear_dims(const mmidx_linear *l, int *D_out, int *device_out) {
+    *D_out = l->D;
+    *device_out = l->device;
+}
+
+// Lock order: the caller already holds its index handle's search_mu; l->mu is taken second, never the other way round.
+int mmidx_internal_linear_rows_acquire(mmidx_linear *l, hipStream_t st, MmidxLinearRows *out) {
+    l->mu.lock();
+    lin_wait_other_stream(l, st);
+    out->dX = l->n > 0 ? l->dX : nullptr;
+    out->n = l->n;
+    out->D = l->D;
+    out->device = l->device;
+    return MMIDX_OK;
+}
+
+void mmidx_internal_linear_rows_release(mmidx_linear *l) { l->mu.unlock(); }
+
 }  // extern "C"

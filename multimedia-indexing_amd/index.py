@@ -310,6 +310,68 @@ class _PQBase(AbstractSearchStructure):
         N.check(N.lib().mmidx_search_ids(self._h, k, nq, q.ctypes.data, out.ctypes.data, dists.ctypes.data, counts.ctypes.data))
         return out, dists, counts
 
+    # -- exact re-ranking against a Linear index over the same vectors (an extension of the reference: DESIGN.md section 5.11) --
+    def search_refine_batch(self, k, R, Q, linear):
+        """The R best records of search_batch(R, Q), re-ranked by their exact distances from the rows of `linear` (record iid = row
+        iid, as IndexTransformation.java:113-122 builds the pair), the k best kept under the bounded queue's rule:
+        (iids [nq][k], exact squared distances [nq][k], counts [nq], missing).  `missing` counts candidates without a row."""
+        Q = _f64(Q)
+        if Q.ndim != 2 or Q.shape[1] != self.vectorLength:
+            raise MmidxError(N.ERR_WRONG_DIM, "The dimensionality of the vector is wrong!")
+        nq = Q.shape[0]
+        iids = np.full((nq, max(k, 1)), -1, np.int32)
+        dists = np.full((nq, max(k, 1)), np.inf, np.float64)
+        counts = np.zeros(nq, np.int32)
+        missing = C.c_int64(0)
+        N.check(N.lib().mmidx_search_refine(self._h, linear._h, k, R, nq, Q.ctypes.data, iids.ctypes.data, dists.ctypes.data, counts.ctypes.data,
+                                            C.byref(missing)))
+        return iids, dists, counts, missing.value
+
+    def search_refine_ids_batch(self, k, R, iids, linear):
+        """search_refine_batch with the rows iids[q] of `linear` as the queries (gathered on the device, Linear.java:181-184).  An id
+        outside the Linear index gives count 0 and a padded row."""
+        q = np.ascontiguousarray(np.asarray(iids).reshape(-1), np.int32)
+        nq = q.shape[0]
+        out = np.full((nq, max(k, 1)), -1, np.int32)
+        dists = np.full((nq, max(k, 1)), np.inf, np.float64)
+        counts = np.zeros(nq, np.int32)
+        missing = C.c_int64(0)
+        N.check(N.lib().mmidx_search_refine_ids(self._h, linear._h, k, R, nq, q.ctypes.data, out.ctypes.data, dists.ctypes.data, counts.ctypes.data,
+                                                C.byref(missing)))
+        return out, dists, counts, missing.value
+
+    def search_refine_batch_device(self, k, R, Q, linear):
+        """search_refine_batch on a torch tensor [nq][vectorLength] (float64, contiguous) in HBM: (ids int32 [nq][k], distances
+        float64 [nq][k], counts int32 [nq], missing int64 [1]) as tensors on the same device, on torch's current stream; nothing
+        is read back."""
+        import torch
+
+        if Q.dim() != 2 or Q.shape[1] != self.vectorLength or Q.dtype != torch.float64 or not Q.is_contiguous():
+            raise MmidxError(N.ERR_WRONG_DIM, "The dimensionality of the vector is wrong!")
+        nq = Q.shape[0]
+        iids = torch.empty((nq, max(k, 1)), dtype=torch.int32, device=Q.device)
+        dists = torch.empty((nq, max(k, 1)), dtype=torch.float64, device=Q.device)
+        counts = torch.empty(nq, dtype=torch.int32, device=Q.device)
+        missing = torch.zeros(1, dtype=torch.int64, device=Q.device)
+        st = torch.cuda.current_stream(Q.device).cuda_stream
+        N.check(N.lib().mmidx_search_refine_device(self._h, linear._h, k, R, nq, Q.data_ptr(), iids.data_ptr(), dists.data_ptr(), counts.data_ptr(),
+                                                   missing.data_ptr(), st))
+        return iids, dists, counts, missing
+
+    def computeNearestNeighborsRefined(self, k, R, query, linear):
+        """computeNearestNeighbors with the exact re-ranking: `query` is a vector or an indexed id (its row of `linear` is then the
+        query).  The Answer carries this index's external ids and exact squared distances.  R is always explicit."""
+        start = time.perf_counter_ns()
+        if isinstance(query, str):
+            iid = self.getInternalId(query)
+            if iid < 0:
+                raise MmidxError(N.ERR_INVALID_ARG, "Id does not exist!")
+            i, d, c, _ = self.search_refine_ids_batch(k, R, [iid], linear)
+        else:
+            i, d, c, _ = self.search_refine_batch(k, R, _f64(query).reshape(1, -1), linear)
+        n = int(c[0])
+        return self._look_up((i[0, :n].copy(), d[0, :n].copy()), time.perf_counter_ns() - start)
+
     def export(self):
         """List-major snapshot (list_off [nlists+1], iids [n], codes [n][m] stored form)."""
         nl = self.numCoarseCentroids if self._kind == N.KIND_IVFPQ else 1

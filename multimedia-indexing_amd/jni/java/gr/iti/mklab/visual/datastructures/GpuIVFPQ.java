@@ -2,6 +2,7 @@ package gr.iti.mklab.visual.datastructures;
 
 import gr.iti.mklab.visual.aggregation.AbstractFeatureAggregator;
 import gr.iti.mklab.visual.datastructures.PQ.TransformationType;
+import gr.iti.mklab.visual.utilities.Answer;
 import gr.iti.mklab.visual.utilities.Result;
 
 import java.io.BufferedReader;
@@ -229,6 +230,50 @@ public class GpuIVFPQ extends AbstractSearchStructure {
 		for (int i = count[0] - 1; i >= 0; i--) // worst first: keeps the queue's tie order
 			nn.offer(new Result(iids[i], dists[i]));
 		return nn;
+	}
+
+	/**
+	 * computeNearestNeighbors with an exact re-ranking (no counterpart in the reference, whose deployment keeps a Linear index
+	 * beside the compressed one, IndexTransformation.java:61-125, and compares them by hand, Example.java:155-182): the R best
+	 * records by code distance meet their full vectors in <code>exact</code> on the GPU, and the k best by exact squared distance
+	 * come back, under the bounded queue's rule. Record iid of this index must be row iid of <code>exact</code>, which is what
+	 * IndexTransformation produces. R is explicit: k &lt;= R &lt;= 4095.
+	 */
+	public Answer computeNearestNeighborsRefined(int k, int R, double[] query, GpuLinear exact) throws Exception {
+		if (!loadIndexInMemory) {
+			throw new Exception("Cannot execute query because the index is not loaded in memory!");
+		}
+		long start = System.nanoTime();
+		int[] iids = new int[k];
+		double[] dists = new double[k];
+		int[] count = new int[1];
+		MmidxNative.searchRefine(handle, exact.nativeHandle(), k, R, 1, query, iids, dists, count);
+		return refinedAnswer(iids, dists, count[0], System.nanoTime() - start);
+	}
+
+	/** the same with an indexed vector as the query: its full vector in <code>exact</code>, not its code (Linear.java:181-184) */
+	public Answer computeNearestNeighborsRefined(int k, int R, String queryId, GpuLinear exact) throws Exception {
+		int iid = getInternalId(queryId);
+		if (iid == -1) {
+			throw new Exception("Id does not exist!");
+		}
+		long start = System.nanoTime();
+		int[] iids = new int[k];
+		double[] dists = new double[k];
+		int[] count = new int[1];
+		MmidxNative.searchRefineIds(handle, exact.nativeHandle(), k, R, 1, new int[] { iid }, iids, dists, count);
+		return refinedAnswer(iids, dists, count[0], System.nanoTime() - start);
+	}
+
+	private Answer refinedAnswer(int[] iids, double[] dists, int n, long indexSearchTime) {
+		long start = System.nanoTime();
+		String[] ids = new String[n];
+		double[] distances = new double[n];
+		for (int i = 0; i < n; i++) { // nearest first, as ASS.lookUp returns them (ASS:345-358)
+			ids[i] = getId(iids[i]);
+			distances[i] = dists[i];
+		}
+		return new Answer(ids, distances, System.nanoTime() - start, indexSearchTime);
 	}
 
 	/**

@@ -42,6 +42,11 @@ public class GpuLinear extends AbstractSearchStructure {
 		this(vectorLength, maxNumVectors, readOnly, BDBEnvHome, true, true, 0);
 	}
 
+	/** the native handle, for the calls that pair this index with a compressed one (GpuIVFPQ / GpuPQ.computeNearestNeighborsRefined) */
+	long nativeHandle() {
+		return handle;
+	}
+
 	protected void indexVectorInternal(double[] vector) throws Exception { // Linear.java:111-122
 		if (vector.length != vectorLength) {
 			throw new Exception("The dimensionality of the vector is wrong!");

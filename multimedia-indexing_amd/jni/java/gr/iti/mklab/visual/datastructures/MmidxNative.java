@@ -67,6 +67,18 @@ public final class MmidxNative {
 	public static native void searchIds(long handle, int k, int nq, int[] queryIids, int[] iidOut, double[] distOut,
 			int[] countOut) throws Exception;
 
+	/**
+	 * mmidx_search_refine: the R best records of the compressed answer (exactly search(handle, R, ...)) re-ranked by their exact
+	 * squared distances from the rows of the Linear handle, the k best kept under the bounded queue's rule. Record iid of the
+	 * index must be row iid of the Linear index (IndexTransformation.java:113-122). Returns the number of candidates without a row.
+	 */
+	public static native long searchRefine(long handle, long linearHandle, int k, int R, int nq, double[] queries, int[] iidOut,
+			double[] distOut, int[] countOut) throws Exception;
+
+	/** mmidx_search_refine_ids: the same with the rows queryIids[q] of the Linear handle as the queries (Linear.java:181-184) */
+	public static native long searchRefineIds(long handle, long linearHandle, int k, int R, int nq, int[] queryIids, int[] iidOut,
+			double[] distOut, int[] countOut) throws Exception;
+
 	/** mmidx_reconstruct: out[iids.length * vectorLength] = the vectors the index holds for the given internal ids */
 	public static native void reconstruct(long handle, int[] iids, double[] out) throws Exception;
 

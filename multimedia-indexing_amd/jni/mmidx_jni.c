@@ -326,6 +326,54 @@ done:
     (*env)->ReleaseIntArrayElements(env, countOut, cc, 0);
 }
 
+/* mmidx_search_refine: the R best records of the compressed answer re-ranked by their exact distances from the rows of the Linear
+ * handle `linear` (record iid = row iid, IndexTransformation.java:113-122); returns the number of candidates without a row */
+JNIEXPORT jlong JNICALL JFN(searchRefine)(JNIEnv *env, jclass c, jlong h, jlong linear, jint k, jint R, jint nq, jdoubleArray queries,
+                                          jintArray iidOut, jdoubleArray distOut, jintArray countOut) {
+    dims_t d;
+    jdouble *q, *dd;
+    jint *ii, *cc;
+    int64_t missing = 0;
+    (void)c;
+    if (get_dims(env, h, &d) || bad_len(env, queries, (int64_t)nq * d.D, 0, "queries") || bad_len(env, iidOut, (int64_t)nq * k, 0, "iidOut") ||
+        bad_len(env, distOut, (int64_t)nq * k, 0, "distOut") || bad_len(env, countOut, nq, 0, "countOut"))
+        return 0;
+    q = (*env)->GetDoubleArrayElements(env, queries, NULL);
+    ii = (*env)->GetIntArrayElements(env, iidOut, NULL);
+    dd = (*env)->GetDoubleArrayElements(env, distOut, NULL);
+    cc = (*env)->GetIntArrayElements(env, countOut, NULL);
+    CHECK(mmidx_search_refine(H(h), (mmidx_linear *)(intptr_t)linear, k, R, nq, q, (int32_t *)ii, dd, (int32_t *)cc, &missing));
+done:
+    (*env)->ReleaseDoubleArrayElements(env, queries, q, JNI_ABORT);
+    (*env)->ReleaseIntArrayElements(env, iidOut, ii, 0);
+    (*env)->ReleaseDoubleArrayElements(env, distOut, dd, 0);
+    (*env)->ReleaseIntArrayElements(env, countOut, cc, 0);
+    return (jlong)missing;
+}
+
+/* mmidx_search_refine_ids: the queries are rows of the Linear handle (Linear.java:181-184), gathered on the device */
+JNIEXPORT jlong JNICALL JFN(searchRefineIds)(JNIEnv *env, jclass c, jlong h, jlong linear, jint k, jint R, jint nq, jintArray queryIids,
+                                             jintArray iidOut, jdoubleArray distOut, jintArray countOut) {
+    jint *q, *ii, *cc;
+    jdouble *dd;
+    int64_t missing = 0;
+    (void)c;
+    if (bad_len(env, queryIids, nq, 0, "queryIids") || bad_len(env, iidOut, (int64_t)nq * k, 0, "iidOut") ||
+        bad_len(env, distOut, (int64_t)nq * k, 0, "distOut") || bad_len(env, countOut, nq, 0, "countOut"))
+        return 0;
+    q = (*env)->GetIntArrayElements(env, queryIids, NULL);
+    ii = (*env)->GetIntArrayElements(env, iidOut, NULL);
+    dd = (*env)->GetDoubleArrayElements(env, distOut, NULL);
+    cc = (*env)->GetIntArrayElements(env, countOut, NULL);
+    CHECK(mmidx_search_refine_ids(H(h), (mmidx_linear *)(intptr_t)linear, k, R, nq, (const int32_t *)q, (int32_t *)ii, dd, (int32_t *)cc, &missing));
+done:
+    (*env)->ReleaseIntArrayElements(env, queryIids, q, JNI_ABORT);
+    (*env)->ReleaseIntArrayElements(env, iidOut, ii, 0);
+    (*env)->ReleaseDoubleArrayElements(env, distOut, dd, 0);
+    (*env)->ReleaseIntArrayElements(env, countOut, cc, 0);
+    return (jlong)missing;
+}
+
 /* mmidx_reconstruct: out[iids.length][vectorLength], the vectors the index holds for the given internal ids */
 JNIEXPORT void JNICALL JFN(reconstruct)(JNIEnv *env, jclass c, jlong h, jintArray iids, jdoubleArray out) {
     dims_t d;
