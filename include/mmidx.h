@@ -371,6 +371,53 @@ int mmidx_search_refine_device(mmidx_index *h, mmidx_linear *l, int k, int R, in
 int mmidx_search_refine_ids(mmidx_index *h, mmidx_linear *l, int k, int R, int64_t nq, const int32_t *iids, int32_t *iid_out,
                             double *dist_out, int32_t *count_out, int64_t *missing_out);
 
+/* ---- re-indexing a Linear index: project, truncate, renormalise -------------------------------------------
+ * The two drivers of the reference that turn one index into another, as one native walk: IndexTransformation.java:61-125 (a full
+ * Linear index into a shorter Linear, a PQ or an IVFPQ one) and PCAProjectionExample.java:74-88 (project every row once, index
+ * several truncations).  It produces what mmidx_search_refine's identity contract (above) asks for.
+ *
+ * mmidx_truncate_l2_device reads rows x_r = dX[r * ld .. r * ld + ncols), ld >= ncols.  lens, normalize and dY are HOST arrays of
+ * nt entries (1 <= nt <= 8); dY[t] is a device pointer to [n][lens[t]], dense.  For every target t with T = lens[t], 1 <= T <= ncols:
+ *   y = x_r[0..T);  normalize[t] = 0: never normalise; 1: always (PCAProjectionExample.java:83-85); 2: if and only if T < ncols
+ *   (IndexTransformation.java:118-120).  Normalising is Normalization.normalizeL2 (Normalization.java:21-37) literally:
+ *     s = 0; for i in 0..T-1: s += y[i] * y[i]   (fp64, the product rounded before the add, index order)
+ *     norm = sqrt(s), correctly rounded;  norm == 0: every entry becomes 1.0;  otherwise y[i] = y[i] / norm (IEEE division).
+ *   A target that is not normalised is a bit copy.  Columns from max(lens) on are never read.  No NaN inputs.
+ * Asynchronous on `stream`; nothing is read back.  Refusals (MMIDX_ERR_INVALID_ARG, before any launch): nt outside 1..8, n < 0,
+ * ncols < 1, ld < ncols, a null array, a length outside 1..ncols, a normalize value outside 0..2, a null dX / dY[t] with n > 0.
+ *
+ * mmidx_linear_reindex handles rows iid0 .. iid0 + n - 1 of src in chunks of chunk_rows rows (0 = 2^25 / W rows, W the widest row
+ * the walk buffers: nc with a pca, else the longest target, the stored rows being read in place; i.e. 256 MiB of such rows, kept
+ * within 4096 .. 2^20 and rounded down to a multiple of 64).  Without pca the chunk is the
+ * stored rows (ncols = D_src), read in place; with pca it is mmidx_pca_project_device of them (ncols = nc, whitening included as
+ * that call does it, PCA.java:199-204).  The chunk goes through mmidx_truncate_l2_device's kernel once for all targets, lens[t]
+ * being the target handle's own vector length, and each output is appended to its target in row order:
+ *   kinds[t] = 0   targets[t] is a mmidx_linear, appended as mmidx_linear_add_device does;
+ *   kinds[t] = 1   targets[t] is a mmidx_index (PQ or IVFPQ, any transformation), appended as mmidx_add_vectors_device does with
+ *                  the internal ids iid0 + i.
+ * Synchronous: on return every target is complete.  Nothing leaves HBM.
+ * Identity is checked, not assumed: every target must hold exactly iid0 records / rows when the call starts, so that record i of
+ * every target is row i of src.  An index that has grown is brought up to date by a second call with iid0 = the old size.
+ * Refusals, all before any launch, the message naming the offending value, no target changed:
+ *   MMIDX_ERR_INVALID_ARG   a null src, targets or targets[t]; nt outside 1..8; a kinds[t] outside 0..1 or normalize[t] outside
+ *                           0..2; n < 0; chunk_rows < 0; iid0 < 0 (all of these before any handle is looked into); the same handle
+ *                           twice, or src among the targets; iid0 + n > size(src); a target longer than ncols; a pca whose sample
+ *                           size is not D_src; a target whose size is not iid0; a target whose remaining capacity is below n;
+ *                           handles on different devices
+ *   MMIDX_ERR_NOT_READY     an index target without its codebooks
+ *   MMIDX_ERR_UNSUPPORTED   a sharded target
+ * n == 0 is MMIDX_OK after the checks.  A HIP failure in the middle of the walk can leave targets of different sizes; their sizes
+ * say which chunks arrived.  Locks, held for the whole call: every index target first (its add lock, then its search lock, as
+ * mmidx_add_vectors_device takes them), then the Linear handles, src and the Linear targets alike; within each class in ascending
+ * address order, so that the argument order of two concurrent walks does not matter.  This is mmidx_search_refine's order (index
+ * handle first, then the Linear handle): a refine over a pair that a walk is filling runs before or after the walk, never across
+ * it.  Searches and adds on any handle of the walk wait until it returns. */
+int mmidx_truncate_l2_device(int device, int64_t n, int ncols, int64_t ld, const double *dX, int nt, const int32_t *lens,
+                             const int32_t *normalize, double *const *dY, void *stream);
+struct mmidx_pca; /* the PCA handle of the front end, below */
+int mmidx_linear_reindex(mmidx_linear *src, int64_t iid0, int64_t n, struct mmidx_pca *pca, int nt, const int32_t *kinds,
+                         void *const *targets, const int32_t *normalize, int64_t chunk_rows);
+
 /* ---- codebook learning (J/visual/quantization/AbstractQuantizerLearning.java:39-81) ------
  * k-means on the GPU in place of Weka's SimpleKMeans, which the reference calls with setSeed(seed),
  * setNumClusters(k), setMaxIterations(max_iter) and, optionally, k-means++ seeding.  flags:

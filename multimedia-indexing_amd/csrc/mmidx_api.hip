@@ -4459,4 +4459,22 @@ int mmidx_internal_coarse_tables(const mmidx_index *h, MmidxCoarseTables *out) {
     return MMIDX_OK;
 }
 
+// mmidx_linear_reindex (mmidx_reindex.hip): no add can slip in between its checks and its appends.  add_mu, then search_mu: the
+// order mmidx_add_vectors_device takes them in (both recursive: it takes them again inside the walk).  The walk holds search_mu
+// BEFORE it locks any Linear handle, as mmidx_search_refine* does.
+void mmidx_internal_index_add_lock(mmidx_index *h, MmidxIndexInfo *out) {
+    h->add_mu.lock();
+    h->search_mu.lock();
+    out->sharded = h->grp != nullptr;
+    out->n = h->grp ? sharded_total(h) : total_size(h);
+    out->D = h->D;
+    out->device = h->device;
+    out->ready = h->pq_set && (h->kind != MMIDX_KIND_IVFPQ || h->coarse_set);
+}
+
+void mmidx_internal_index_add_unlock(mmidx_index *h) {
+    h->search_mu.unlock();
+    h->add_mu.unlock();
+}
+
 #include "mmidx_sharded.h"

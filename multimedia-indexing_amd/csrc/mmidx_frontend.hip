@@ -72,6 +72,8 @@ int mmidx_pca_get_dims(const mmidx_pca *p, int *nc_out, int *ss_out) {
     return MMIDX_OK;
 }
 
+int mmidx_internal_pca_device(const mmidx_pca *p) { return p->device; }  // (mmidx_linear_reindex checks it against its handles')
+
 int mmidx_pca_destroy(mmidx_pca *p) {
     if (!p) return MMIDX_OK;
     (void)hipSetDevice(p->device);

@@ -236,4 +236,33 @@ struct MmidxRefineArgs {
     int64_t *d_missing;        // one counter the round adds to, or null
 };
 MMIDX_HIDDEN int mmidx_internal_refine_round(const MmidxRefineArgs *a, hipStream_t st);
+// ---- the walk of one Linear index into others (mmidx_linear_reindex, mmidx_reindex.hip) --------------------------------------
+// LOCK ORDER of that call, the library's one order: index handles before Linear handles.  First every index target (add_mu, then
+// search_mu, as mmidx_add_vectors_device takes them; both recursive, so the appends inside the walk take them again), in ascending
+// address order; then the Linear handles -- the source and the Linear targets -- by l->mu, in ascending address order.  The refine rule
+// above is the same order (an index handle's search_mu, then the Linear handle), so a refine over a pair that a walk is filling
+// waits for the walk or the walk for it; and two walks over the same handles in different argument orders cannot cross.
+// mmidx_linear.hip: _lock takes l->mu and reports the handle without any device call; it stays locked until _unlock.  settle = true:
+// the caller has waited for everything it enqueued on the handle, so that no later call waits on the caller's stream.
+struct MmidxLinearInfo {
+    const double *dX;     // [n][D]; null while n == 0
+    int64_t n, capacity;  // capacity 0 = unbounded
+    int D, device;
+    hipStream_t stream;   // the handle's private stream
+};
+MMIDX_HIDDEN void mmidx_internal_linear_lock(mmidx_linear *l, MmidxLinearInfo *out);
+MMIDX_HIDDEN void mmidx_internal_linear_unlock(mmidx_linear *l, bool settle);
+// ... orders `st` behind whatever another stream still has in flight on the locked handle (lin_wait_other_stream)
+MMIDX_HIDDEN void mmidx_internal_linear_order(mmidx_linear *l, hipStream_t st);
+// ... mmidx_linear_add_device on the locked handle
+MMIDX_HIDDEN int mmidx_internal_linear_append_locked(mmidx_linear *l, int64_t n, const double *dX, hipStream_t st);
+// mmidx_api.hip: the same for an index handle: add_mu and search_mu, and what the walk checks before it launches anything
+struct MmidxIndexInfo {
+    int64_t n;  // loadCounter
+    int D, device, sharded, ready;  // ready: the quantizers the kind needs are loaded
+};
+MMIDX_HIDDEN void mmidx_internal_index_add_lock(mmidx_index *h, MmidxIndexInfo *out);
+MMIDX_HIDDEN void mmidx_internal_index_add_unlock(mmidx_index *h);
+// mmidx_frontend.hip: the device of a PCA handle (its sizes: mmidx_pca_get_dims)
+MMIDX_HIDDEN int mmidx_internal_pca_device(const mmidx_pca *p);
 }  // extern "C"

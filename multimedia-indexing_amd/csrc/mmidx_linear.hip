@@ -618,4 +618,24 @@ int mmidx_internal_linear_rows_acquire(mmidx_linear *l, hipStream_t st, MmidxLin
 
 void mmidx_internal_linear_rows_release(mmidx_linear *l) { l->mu.unlock(); }
 
+// ---- the walk into other indexes (mmidx_linear_reindex in mmidx_reindex.hip; mmidx_host.h has the lock order) ----
+void mmidx_internal_linear_lock(mmidx_linear *l, MmidxLinearInfo *out) {
+    l->mu.lock();
+    out->dX = l->n > 0 ? l->dX : nullptr;
+    out->n = l->n;
+    out->capacity = l->capacity;
+    out->D = l->D;
+    out->device = l->device;
+    out->stream = l->stream;
+}
+
+void mmidx_internal_linear_unlock(mmidx_linear *l, bool settle) {
+    if (settle) l->last_stream_valid = false;
+    l->mu.unlock();
+}
+
+void mmidx_internal_linear_order(mmidx_linear *l, hipStream_t st) { lin_wait_other_stream(l, st); }
+
+int mmidx_internal_linear_append_locked(mmidx_linear *l, int64_t n, const double *dX, hipStream_t st) { return lin_append(l, n, dX, true, st); }
+
 }  // extern "C"

@@ -720,7 +720,68 @@ class Linear(AbstractSearchStructure):
         N.check(N.lib().mmidx_linear_size(self._h, C.byref(n)))
         return n.value
 
+    def reindex(self, targets, iid0=None, n=None, pca=None, normalize=2, chunk_rows=0):
+        """The walk of IndexTransformation.java:111-123 / PCAProjectionExample.java:74-88 as one native call
+        (mmidx_linear_reindex): rows iid0 .. iid0 + n - 1 of this index, projected through `pca` (a frontend.PCA) where given,
+        truncated to every target's vectorLength, L2-normalised by `normalize` (0 never, 1 always, 2 where the target is
+        shorter; one value or one per target) and appended to the targets (Linear / PQ / IVFPQ mirrors) -- nothing leaves HBM.
+        iid0 defaults to the targets' common loadCounter, n to the rest of this index.  The ids go with the rows
+        (fromIndex.getId(i) -> the target's maps, :114, :121): a row of this index without an id gets none.  Refused before the
+        native call, with the reference's messages: an id already indexed in a target, a target whose maxNumVectors would be
+        passed.  The targets' loadCounter and maps change only after the native call has succeeded.  Returns n."""
+        targets = list(targets)
+        if iid0 is None:
+            counters = {t.loadCounter for t in targets}
+            if len(counters) != 1:
+                raise MmidxError(N.ERR_INVALID_ARG, f"the targets hold different numbers of vectors ({sorted(counters)}): give iid0")
+            iid0 = counters.pop()
+        iid0 = int(iid0)
+        n = self.loadCounter - iid0 if n is None else int(n)
+        modes = [int(normalize)] * len(targets) if np.isscalar(normalize) else [int(v) for v in normalize]
+        if len(modes) != len(targets):
+            raise MmidxError(N.ERR_INVALID_ARG, "one normalize value, or one per target")
+        ids = [self.getId(i) for i in range(iid0, iid0 + max(n, 0))]
+        for t in targets:
+            if t.loadCounter + max(n, 0) > t.maxNumVectors:
+                raise MmidxError(N.ERR_CAPACITY, "Maximum index capacity reached, no more vectors can be indexed!")
+            for id_ in ids:
+                if id_ is not None and t.isIndexed(id_):
+                    raise MmidxError(N.ERR_INVALID_ARG, f"Vector '{id_}' already indexed!")
+        kinds = np.array([0 if isinstance(t, Linear) else 1 for t in targets], np.int32)
+        handles = (C.c_void_p * len(targets))(*[t._h for t in targets])
+        mode_arr = np.array(modes, np.int32)
+        N.check(N.lib().mmidx_linear_reindex(self._h, iid0, n, pca._h if pca is not None else None, len(targets), kinds.ctypes.data,
+                                             C.addressof(handles), mode_arr.ctypes.data, int(chunk_rows)))
+        for t in targets:
+            for i, id_ in enumerate(ids):
+                if id_ is not None:
+                    t._iid_to_id[iid0 + i] = id_
+                    t._id_to_iid[id_] = iid0 + i
+            t.loadCounter = iid0 + n
+        return n
+
     def close(self):
         if self._h:
             N.lib().mmidx_linear_destroy(self._h)
             self._h = None
+
+
+class IndexTransformation:
+    """IndexTransformation.java:61-125: a full-length Linear index into a shorter Linear, a PQ or an IVFPQ one."""
+
+    @staticmethod
+    def transform(fromIndex, toIndex, chunk_rows=0):
+        """The loop of :111-123: every vector of fromIndex, its first toIndex.vectorLength entries (:117), L2-normalised when
+        that was a truncation (:118-120), indexed in toIndex under the same id (:121).  A toIndex that already holds the first
+        rows is brought up to date.  Returns the number of vectors moved."""
+        return fromIndex.reindex([toIndex], normalize=2, chunk_rows=chunk_rows)
+
+
+class PCAProjection:
+    """PCAProjectionExample.java:74-88: project every vector once, index its truncations."""
+
+    @staticmethod
+    def project(fullVectors, pca, projectedVectors, L2Normalization=True, chunk_rows=0):
+        """Every vector of the Linear index fullVectors through pca.sampleToEigenSpace (:79), truncated to the length of each
+        Linear index of projectedVectors (:82), L2-normalised on request (:83-85) and indexed there under its id (:86)."""
+        return fullVectors.reindex(list(projectedVectors), pca=pca, normalize=1 if L2Normalization else 0, chunk_rows=chunk_rows)

@@ -96,6 +96,11 @@ public class GpuIVFPQ extends AbstractSearchStructure {
 		MmidxNative.setCoarse(handle, flat);
 	}
 
+	/** the native handle, for GpuLinear.reindexInto (the walk of IndexTransformation.java:111-123 on the GPU) */
+	long nativeHandle() {
+		return handle;
+	}
+
 	public void loadProductQuantizer(String filename) throws Exception { // IVFPQ.java:275-288
 		int dsub = vectorLength / numSubVectors;
 		double[] flat = new double[numSubVectors * numProductCentroids * dsub];

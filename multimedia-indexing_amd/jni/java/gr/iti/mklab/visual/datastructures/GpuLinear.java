@@ -47,6 +47,69 @@ public class GpuLinear extends AbstractSearchStructure {
 		return handle;
 	}
 
+	/**
+	 * The walks of IndexTransformation.java:111-123 and PCAProjectionExample.java:74-88 as one native call (mmidx_linear_reindex):
+	 * the rows of this index from the targets' common size up to its own, through the PCA handle pcaHandle (0 = none;
+	 * GpuPCA.nativeHandle()), truncated to every target's vectorLength, L2-normalised by normalize[t] (0 never, 1 always, 2 where
+	 * truncated) and appended to the in-memory part of the targets (GpuLinear, GpuPQ or GpuIVFPQ), without leaving the GPU. The ids
+	 * are carried over here, on the Java side (getId(i) -> createMapping, as :114 and :121 do). Checked before the native call, with
+	 * the reference's messages: a target whose maxNumVectors would be passed, an id a target already holds. The targets'
+	 * persistent record stores are not written: a target filled this way is kept with saveSnapshot, or re-walked after a restart.
+	 * Returns the number of vectors moved.
+	 */
+	public synchronized int reindexInto(AbstractSearchStructure[] targets, long pcaHandle, int[] normalize, long chunkRows)
+			throws Exception {
+		if (targets.length == 0 || normalize.length != targets.length) {
+			throw new Exception("One normalization mode per target is needed!");
+		}
+		int iid0 = targets[0].loadCounter;
+		int[] kinds = new int[targets.length];
+		long[] handles = new long[targets.length];
+		for (int t = 0; t < targets.length; t++) {
+			if (targets[t].loadCounter != iid0) {
+				throw new Exception("The target indices hold different numbers of vectors!");
+			}
+			if (targets[t] instanceof GpuLinear) {
+				handles[t] = ((GpuLinear) targets[t]).handle;
+			} else if (targets[t] instanceof GpuIVFPQ) {
+				kinds[t] = 1;
+				handles[t] = ((GpuIVFPQ) targets[t]).nativeHandle();
+			} else if (targets[t] instanceof GpuPQ) {
+				kinds[t] = 1;
+				handles[t] = ((GpuPQ) targets[t]).nativeHandle();
+			} else {
+				throw new Exception("Unsupported index transformation type!");
+			}
+		}
+		int n = loadCounter - iid0;
+		String[] ids = new String[Math.max(n, 0)];
+		for (int i = 0; i < n; i++) {
+			ids[i] = getId(iid0 + i);
+		}
+		for (AbstractSearchStructure target : targets) {
+			if (iid0 + n > target.maxNumVectors) {
+				throw new Exception("Maximum index capacity reached, no more vectors can be indexed!");
+			}
+			for (int i = 0; i < n; i++) {
+				if (ids[i] != null && target.isIndexed(ids[i])) {
+					throw new Exception("Vector '" + ids[i] + "' already indexed!");
+				}
+			}
+		}
+		MmidxNative.linearReindex(handle, iid0, n, pcaHandle, kinds, handles, normalize, chunkRows); // -> mmidx_linear_reindex
+		for (AbstractSearchStructure target : targets) {
+			synchronized (target) {
+				for (int i = 0; i < n; i++) {
+					if (ids[i] != null) { // (a source row without an id gets none, as in Linear.reindex of the Python mirror)
+						target.createMapping(ids[i]); // maps ids[i] <-> target.loadCounter
+					}
+					target.loadCounter++;
+				}
+			}
+		}
+		return n;
+	}
+
 	protected void indexVectorInternal(double[] vector) throws Exception { // Linear.java:111-122
 		if (vector.length != vectorLength) {
 			throw new Exception("The dimensionality of the vector is wrong!");

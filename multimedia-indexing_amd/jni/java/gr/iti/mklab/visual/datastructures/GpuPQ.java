@@ -60,6 +60,11 @@ public class GpuPQ extends AbstractSearchStructure {
 				true, 0, true, cacheSize);
 	}
 
+	/** the native handle, for GpuLinear.reindexInto (the walk of IndexTransformation.java:111-123 on the GPU) */
+	long nativeHandle() {
+		return handle;
+	}
+
 	public void loadProductQuantizer(String filename) throws Exception { // PQ.java:210-223
 		int dsub = vectorLength / numSubVectors;
 		double[] flat = new double[numSubVectors * numProductCentroids * dsub];

@@ -111,6 +111,15 @@ public final class MmidxNative {
 	/** "exact", "mfma_qcap", "debug_sync" (include/mmidx.h, Linear section) */
 	public static native void linearSetOption(long handle, String name, int value) throws Exception;
 
+	/**
+	 * mmidx_linear_reindex: rows iid0 .. iid0 + n - 1 of the Linear handle src, projected through the PCA handle pca (0 = none),
+	 * truncated to every target's vector length, L2-normalised (normalize[t]: 0 never, 1 always, 2 where truncated) and appended
+	 * to the targets in one pass on the GPU (IndexTransformation.java:111-123, PCAProjectionExample.java:74-88). kinds[t] = 0:
+	 * targets[t] is a Linear handle, 1: a PQ / IVFPQ handle. Every target must hold exactly iid0 vectors. chunkRows 0 = default.
+	 */
+	public static native void linearReindex(long src, long iid0, long n, long pca, int[] kinds, long[] targets, int[] normalize,
+			long chunkRows) throws Exception;
+
 	/* ---- front end (mmidx_pca_*, mmidx_vlad_*, mmidx_vectorize) ---- */
 	public static native long pcaCreate(int numComponents, int sampleSize, boolean whitening, double[] means,
 			double[] eigenvalues, double[] components, int device) throws Exception;

@@ -549,6 +549,34 @@ done:
     (*env)->ReleaseStringUTFChars(env, name, p);
 }
 
+/* mmidx_linear_reindex: rows iid0 .. iid0 + n - 1 of the Linear handle `src`, through the PCA handle `pca` (0 = none), truncated and
+ * L2-normalised once for all targets and appended to them (IndexTransformation.java:111-123, PCAProjectionExample.java:74-88).
+ * kinds[t] = 0: targets[t] is a Linear handle, 1: a PQ / IVFPQ handle; the three arrays have one entry per target */
+JNIEXPORT void JNICALL JFN(linearReindex)(JNIEnv *env, jclass c, jlong src, jlong iid0, jlong n, jlong pca, jintArray kinds, jlongArray targets,
+                                          jintArray normalize, jlong chunkRows) {
+    jint nt, *kk = NULL, *nn = NULL;
+    jlong *tt = NULL;
+    void *handles[8];
+    int t;
+    (void)c;
+    if (bad_len(env, kinds, 1, 0, "kinds")) return;
+    nt = (*env)->GetArrayLength(env, kinds);
+    if (nt > 8) {
+        throw_msg(env, "java/lang/IllegalArgumentException", "at most 8 targets in one walk");
+        return;
+    }
+    if (bad_len(env, targets, nt, 0, "targets") || bad_len(env, normalize, nt, 0, "normalize")) return;
+    kk = (*env)->GetIntArrayElements(env, kinds, NULL);
+    tt = (*env)->GetLongArrayElements(env, targets, NULL);
+    nn = (*env)->GetIntArrayElements(env, normalize, NULL);
+    for (t = 0; t < nt; t++) handles[t] = (void *)(intptr_t)tt[t];
+    CHECK(mmidx_linear_reindex(HL(src), iid0, n, (mmidx_pca *)(intptr_t)pca, nt, (const int32_t *)kk, handles, (const int32_t *)nn, chunkRows));
+done:
+    (*env)->ReleaseIntArrayElements(env, kinds, kk, JNI_ABORT);
+    (*env)->ReleaseLongArrayElements(env, targets, tt, JNI_ABORT);
+    (*env)->ReleaseIntArrayElements(env, normalize, nn, JNI_ABORT);
+}
+
 /* ---- front end: PCA projection (PCA.java:188-208, :257-318) and VLAD aggregation (VladAggregator.java:56-70,
  *      VladAggregatorMultipleVocabularies.java:84-101) ------------------------------------------------------------- */
 JNIEXPORT jlong JNICALL JFN(pcaCreate)(JNIEnv *env, jclass c, jint nc, jint ss, jboolean whitening, jdoubleArray means, jdoubleArray eig,
