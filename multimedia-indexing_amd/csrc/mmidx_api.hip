@@ -147,7 +147,9 @@ const OptionRow kOptions[] = {
 
 struct ShardGroup;  // mmidx_sharded.h
 
-struct mmidx_index {
+struct MMIDX_HIDDEN mmidx_index {
+    // Members are destroyed in reverse order: the streams stand first, so that they outlive everything that was enqueued on them.
+    Stream stream;
     // a handle made by mmidx_create_sharded is a parent: it owns no device memory itself, `grp` holds one sub-index per shard
     ShardGroup *grp = nullptr;
     // a sub-index of such a group: where pass B's partial lists go (MergeParams::dest), set per search round by the group
@@ -158,15 +160,14 @@ struct mmidx_index {
     size_t code_bytes = 1;  // per sub-quantizer
     bool coarse_set = false, pq_set = false;
     Switches sw;  // every runtime switch (kOptions above)
-    int32_t *pin_hint = nullptr;  // pinned host word: pass B's item count of the previous call (launch sizing hint)
+    PinBuf<int32_t> pin_hint;  // pinned host word: pass B's item count of the previous call (launch sizing hint)
     double rmax = 0.0;       // sqrt(sum_s max_j ||pq[s][j]||^2) * (1 + 1e-12)
     double rot_shrink = 0.0; // RandomRotation: |v R| >= rot_shrink |v| for every v (0: the matrix is too far from orthogonal to say)
     // K3g (grouped pass B, mmidx_scan_grp.h): fp32 copy of the codebook (entry index innermost), ||p||^2 and their maxima
-    float *d_pq32T = nullptr, *d_pn32 = nullptr;
-    double *d_pnmax = nullptr;
+    DevPtr<float> d_pq32T, d_pn32;
+    DevPtr<double> d_pnmax;
     bool grp_valid = false;  // tables match the current quantizers
     int num_cus = 0;
-    hipStream_t stream = nullptr;
     std::mutex mu;
     // every search / encode entry point (host or device pointers) shares the handle's workspaces: calls are serialised on the
     // host by this mutex, and on the device by stream order -- a call arriving on another stream than the previous one first
@@ -176,12 +177,12 @@ struct mmidx_index {
     bool last_stream_valid = false;
     std::recursive_mutex add_mu;  // adds are `synchronized` in the reference (ASS:229, IVFPQ.java:357): one at a time
     Combiner comb;  // concurrent mmidx_search callers are served together (see mmidx_search)
-    unsigned char *pin_stage = nullptr;  // pinned staging: queries in, (distances | ids | counts) out
+    PinBuf<unsigned char> pin_stage;  // pinned staging: queries in, (distances | ids | counts) out
     // large host-pointer requests (> MMIDX_COMB_MAX_Q queries): a few callers in flight at once, each with its own copy stream and
     // device buffers -- one caller's queries and answers are on the bus while another's kernels run (see search_host_big)
     struct HostSlot {
-        hipStream_t st = nullptr;
-        hipEvent_t e_in = nullptr, e_done = nullptr;
+        Stream st;
+        Event e_in, e_done;
         DevBuf<double> dQ;
         DevBuf<unsigned char> out;
         bool busy = false;
@@ -192,29 +193,28 @@ struct mmidx_index {
     std::condition_variable slot_cv;
     size_t pin_stage_cap = 0;
 
-    double *d_coarse = nullptr, *d_coarseT = nullptr, *d_pq = nullptr, *d_pqT = nullptr,
-           *d_rot = nullptr, *d_cn = nullptr, *d_cnorm = nullptr;
-    float *d_coarseT32 = nullptr;
+    DevPtr<double> d_coarse, d_coarseT, d_pq, d_pqT, d_rot, d_cn, d_cnorm;
+    DevPtr<float> d_coarseT32;
     // K1e/K1f (bf16-split coarse dot products + group minima): padded bf16 head/tail copies of the centroids
-    unsigned short *d_Ch = nullptr, *d_Cl = nullptr;
-    double *d_cn_pad = nullptr;  // [Cp] |c|^2, +inf on the padding rows
+    DevPtr<unsigned short> d_Ch, d_Cl;
+    DevPtr<double> d_cn_pad;  // [Cp] |c|^2, +inf on the padding rows
     int Cp = 0, Dp = 0;          // C rounded up to 128, D rounded up to 32
     double cn_max = 0.0, cnorm_max = 0.0;
     bool cdsel_valid = false;   // ws_cdsel holds the selected cells' exact distances for the current batch
-    int32_t *d_perm = nullptr;
+    DevPtr<int32_t> d_perm;
 
     // CSR
     int64_t n_csr = 0;
     std::vector<int64_t> h_off;  // [nlists+1]
     int64_t max_list_len = 0;
     int64_t nonempty_lists = 0;  // (a shard holds only its share of the lists: averages are taken over these)
-    int64_t *d_off = nullptr;
-    void *d_codes = nullptr;
-    int32_t *d_ids = nullptr;
+    DevPtr<int64_t> d_off;
+    DevPtr<void> d_codes;
+    DevPtr<int32_t> d_ids;
     // pending (device, arrival order)
     int64_t n_pend = 0, cap_pend = 0;
-    int32_t *d_pcell = nullptr, *d_pid = nullptr;
-    void *d_pcodes = nullptr;
+    DevPtr<int32_t> d_pcell, d_pid;
+    DevPtr<void> d_pcodes;
 
     // workspaces
     DevBuf<int32_t> ws_fb;
@@ -238,13 +238,13 @@ struct mmidx_index {
     DevBuf<double> ws_Qp;     // K3s: the call's queries in transformed (permuted) order
     DevBuf<int32_t> ws_cand2; // K3s: what the bf16 stage could not drop (+ count in the last word)
     DevBuf<double> ws_smin1;  // K3s: the bf16 stage's bounds
-    double *d_coarseP = nullptr;  // K3s: the centroids in transformed order (RandomPermutation only; built with the K3g tables)
+    DevPtr<double> d_coarseP;  // K3s: the centroids in transformed order (RandomPermutation only; built with the K3g tables)
     DevBuf<int32_t> ws_inv;   // iid -> position in the list-major arrays (-1: absent), built on demand
     bool inv_valid = false;
     int64_t inv_size = 0;
     // id queries and reconstruction (K10, mmidx_decode.h): the transposed rotation rotT[j][i] = R[i][j], built on first use; the
     // call's ids and found flags on the device (host forms, and the fix-up of mmidx_search_ids_device)
-    double *d_rotT = nullptr;
+    DevPtr<double> d_rotT;
     DevBuf<int32_t> ws_idq, ws_found;
     // exact re-ranking (K11, mmidx_refine.h): a round's compressed answer for k = R -- ids, distances (the exact ones take their place),
     // counts -- and the call's `missing` counter of the host forms
@@ -259,8 +259,8 @@ struct mmidx_index {
     bool pre_on = false;         // the call before ran K3s (which pair of hint words describes it)
     int pre_skip = 0;            // calls K3s still sits out in front of K3mk (it removed next to nothing the last time)
     // K3m (mmidx_scan_mfma.h): pass B as a certified lower bound on the matrix cores
-    unsigned short *d_pq16 = nullptr;  // fp16 codebook [D / 8][256][8], scaled by 2^pq_ep
-    double *d_pn64 = nullptr;          // [m][256] ||p_sj||^2
+    DevPtr<unsigned short> d_pq16;  // fp16 codebook [D / 8][256][8], scaled by 2^pq_ep
+    DevPtr<double> d_pn64;          // [m][256] ||p_sj||^2
     DevBuf<float> xn;                  // ||x||^2 of every stored code (list-major)
     bool xn_valid = false, mfma_valid = false, mfma_ok = false;
     int pq_ep = 0;
@@ -277,15 +277,16 @@ struct mmidx_index {
     double coarse_maxabs = 0.0;        // largest |centroid element| (set_coarse)
     DevBuf<u32> ws_mfctl, ws_psnap;
     DevBuf<unsigned char> ws_redo;
-    void *d_grpx = nullptr, *pin_grpx = nullptr;  // K3g's GrpExtra on the device and its pinned mirror
-    double *d_zero = nullptr;    // ... and the zero "centroid"
+    DevPtr<void> d_grpx;    // K3g's GrpExtra on the device
+    PinBuf<void> pin_grpx;  // ... its pinned mirror
+    DevPtr<double> d_zero;  // ... and the zero "centroid"
 
     // profiling: HIP events recorded on the launch stream, resolved lazily by mmidx_get_stats
     int profiling = 0;  // 0 off, 1 full (six events per call + code counters), 2 light (the pass-A pair only)
     mmidx_stats stats{};
-    std::vector<hipEvent_t> evpool;  // groups of 6: start, coarse end, scan start, scan end, end, pass A end
+    std::vector<Event> evpool;  // groups of 6: start, coarse end, scan start, scan end, end, pass A end
     size_t ev_used = 0;
-    std::vector<hipEvent_t> mf_ev;   // K3m, full profiling: groups of 3 (scan start, scan end, verification end)
+    std::vector<Event> mf_ev;   // K3m, full profiling: groups of 3 (scan start, scan end, verification end)
     size_t mf_ev_used = 0;
     // which kernel family served each stage of the most recent search sub-batch (mmidx_get_dispatch; host-side words, a few stores per call)
     const char *disp_coarse = "-", *disp_passa = "-", *disp_passb = "-", *disp_pre = "-", *disp_coarse_mm = "-";
@@ -294,9 +295,9 @@ struct mmidx_index {
     const char *disp_assign = "-", *disp_encode = "-";
     int64_t disp_flagged = -1;
     // K3ma (pass A on the matrix cores, mmidx_scan_mfma_a.h)
-    hipEvent_t host_ev[4] = {nullptr, nullptr, nullptr, nullptr};  // mmidx_search (host buffers): the answers' slices on their way back
-    double *d_pqstat = nullptr;        // K3q: [m * dsub] mean_j p_sj[t], then [m] mean_j ||p_sj||^2
-    float *d_pqT32 = nullptr;          // K3q: the transposed codebook in fp32, dimension pairs side by side [m][dsub / 2][256][2] (ks = 256, even dsub)
+    Event host_ev[4];  // mmidx_search (host buffers): the answers' slices on their way back
+    DevPtr<double> d_pqstat;        // K3q: [m * dsub] mean_j p_sj[t], then [m] mean_j ||p_sj||^2
+    DevPtr<float> d_pqT32;          // K3q: the transposed codebook in fp32, dimension pairs side by side [m][dsub / 2][256][2] (ks = 256, even dsub)
     DevBuf<float> ws_acand;            // [pairs][pieces][256] sweep 1's kept accumulator values
     DevBuf<double2> ws_arowc;          // [pairs] upper-bound maps
     DevBuf<unsigned char> ws_abm;      // [items][stride] sweep 2's compare masks
@@ -306,10 +307,10 @@ struct mmidx_index {
     DevBuf<int4> ws_ameta;             // [pairs] {query, rank, list start}
     DevBuf<u64> ws_ametaT;             // [pairs] thresholds
     DevBuf<uint2> ws_arnd;             // [rounds] slot ranges
-    std::vector<hipEvent_t> a_ev;      // full profiling: groups of 5 (sweep 1 start / end, selection end, sweep 2 end, verification end)
+    std::vector<Event> a_ev;      // full profiling: groups of 5 (sweep 1 start / end, selection end, sweep 2 end, verification end)
     size_t a_ev_used = 0;
     long long a_launches = 0;
-    u64 *d_counters = nullptr;       // [0] scan codes, [1] tie fallbacks, [2] codes of the probe-rank-0 lists (pass A), [3] verified codes (K3g); [4] add-validation flag
+    DevPtr<u64> d_counters;       // [0] scan codes, [1] tie fallbacks, [2] codes of the probe-rank-0 lists (pass A), [3] verified codes (K3g); [4] add-validation flag
     int64_t host_codes = 0;          // PQ: nq * n, known on the host
     int32_t launches = 0;
     int32_t passa_launches = 0;
@@ -378,11 +379,11 @@ int ensure_pending(mmidx_index *h, int64_t extra) {
     if (need <= h->cap_pend) return MMIDX_OK;
     int64_t cap = std::max<int64_t>(need, h->cap_pend * 2);
     cap = std::max<int64_t>(cap, 1024);
-    int32_t *ncell = nullptr, *nid = nullptr;
-    void *ncodes = nullptr;
-    HIPCK(hipMalloc((void **)&ncell, cap * sizeof(int32_t)));
-    HIPCK(hipMalloc((void **)&nid, cap * sizeof(int32_t)));
-    HIPCK(hipMalloc(&ncodes, (size_t)cap * h->m * h->code_bytes));
+    DevPtr<int32_t> ncell, nid;
+    DevPtr<void> ncodes;
+    HIPCK(ncell.alloc((size_t)cap));
+    HIPCK(nid.alloc((size_t)cap));
+    HIPCK(ncodes.alloc((size_t)cap * h->m * h->code_bytes));
     if (h->n_pend) {
         HIPCK(hipMemcpyAsync(ncell, h->d_pcell, h->n_pend * sizeof(int32_t), hipMemcpyDeviceToDevice, h->stream));
         HIPCK(hipMemcpyAsync(nid, h->d_pid, h->n_pend * sizeof(int32_t), hipMemcpyDeviceToDevice, h->stream));
@@ -390,12 +391,9 @@ int ensure_pending(mmidx_index *h, int64_t extra) {
                              hipMemcpyDeviceToDevice, h->stream));
         HIPCK(hipStreamSynchronize(h->stream));
     }
-    if (h->d_pcell) (void)hipFree(h->d_pcell);
-    if (h->d_pid) (void)hipFree(h->d_pid);
-    if (h->d_pcodes) (void)hipFree(h->d_pcodes);
-    h->d_pcell = ncell;
-    h->d_pid = nid;
-    h->d_pcodes = ncodes;
+    h->d_pcell = std::move(ncell);
+    h->d_pid = std::move(nid);
+    h->d_pcodes = std::move(ncodes);
     h->cap_pend = cap;
     return MMIDX_OK;
 }
@@ -429,12 +427,12 @@ int build_csr(mmidx_index *h) {
     std::vector<long long> dest((size_t)np);
     for (int64_t i = 0; i < np; i++) dest[(size_t)i] = cursor[(size_t)pcell[(size_t)i]]++;
 
-    int64_t *d_off_new = nullptr;
-    void *d_codes_new = nullptr;
-    int32_t *d_ids_new = nullptr;
-    HIPCK(hipMalloc((void **)&d_off_new, ((size_t)nl + 1) * sizeof(int64_t)));
-    HIPCK(hipMalloc(&d_codes_new, std::max<size_t>((size_t)ntot * h->m * h->code_bytes, 16)));
-    HIPCK(hipMalloc((void **)&d_ids_new, std::max<size_t>((size_t)ntot * sizeof(int32_t), 16)));
+    DevPtr<int64_t> d_off_new;
+    DevPtr<void> d_codes_new;
+    DevPtr<int32_t> d_ids_new;
+    HIPCK(d_off_new.alloc((size_t)nl + 1));
+    HIPCK(d_codes_new.alloc(std::max<size_t>((size_t)ntot * h->m * h->code_bytes, 16)));
+    HIPCK(d_ids_new.alloc(std::max<size_t>((size_t)ntot, 4)));
     HIPCK(hipMemcpyAsync(d_off_new, off_new.data(), ((size_t)nl + 1) * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
     if (nold) {
         const unsigned grid = (unsigned)((nold + 255) / 256);
@@ -458,22 +456,17 @@ int build_csr(mmidx_index *h) {
     }
     HIPCK(hipGetLastError());
     HIPCK(hipStreamSynchronize(h->stream));
-    if (h->d_off) (void)hipFree(h->d_off);
-    if (h->d_codes) (void)hipFree(h->d_codes);
-    if (h->d_ids) (void)hipFree(h->d_ids);
-    h->d_off = d_off_new;
-    h->d_codes = d_codes_new;
-    h->d_ids = d_ids_new;
+    h->d_off = std::move(d_off_new);
+    h->d_codes = std::move(d_codes_new);
+    h->d_ids = std::move(d_ids_new);
     h->h_off = off_new;
     h->n_csr = ntot;
     h->n_pend = 0;
     // release the pending buffers of a bulk load (they can be as large as the index)
     if (h->cap_pend > (1 << 20)) {
-        (void)hipFree(h->d_pcell);
-        (void)hipFree(h->d_pid);
-        (void)hipFree(h->d_pcodes);
-        h->d_pcell = h->d_pid = nullptr;
-        h->d_pcodes = nullptr;
+        h->d_pcell.release();
+        h->d_pid.release();
+        h->d_pcodes.release();
         h->cap_pend = 0;
         h->ws_dest.release();
     }
@@ -1027,15 +1020,15 @@ int use_permuted_queries(mmidx_index *h, Params &S, bool ivf, long long nq, hipS
 // A group of n profiling events from a pool that grows on demand and is handed back by mmidx_get_stats (`used` = 0); null once the
 // pool holds cap_groups groups (the statistics then miss the call).  The group's first event is recorded on st unless the caller
 // says otherwise.
-int take_events(std::vector<hipEvent_t> &pool, size_t &used, size_t n, size_t cap_groups, hipStream_t st, hipEvent_t *&ev, bool record_first = true) {
+int take_events(std::vector<Event> &pool, size_t &used, size_t n, size_t cap_groups, hipStream_t st, hipEvent_t *&ev, bool record_first = true) {
     ev = nullptr;
     if (used + n > n * cap_groups) return MMIDX_OK;
     while (pool.size() < used + n) {
-        hipEvent_t e;
-        HIPCK(hipEventCreate(&e));
-        pool.push_back(e);
+        Event e;
+        HIPCK(e.create());
+        pool.push_back(std::move(e));
     }
-    ev = pool.data() + used;
+    ev = &pool[used].p;  // (an Event is its hipEvent_t and nothing more: the group is an array of them)
     used += n;
     if (record_first) HIPCK(hipEventRecord(ev[0], st));
     return MMIDX_OK;
@@ -1194,13 +1187,13 @@ int build_grp_tables(mmidx_index *h) {
     const bool shape_ok = (h->kind == MMIDX_KIND_IVFPQ || h->kind == MMIDX_KIND_PQ) && h->code_bytes == 1 && h->ks <= 256 &&
                           (h->m == 8 || h->m == 16 || h->m == 32 || h->m == 64) && h->transform != MMIDX_TR_ROTATION;
     if (!shape_ok || !h->pq_set) return MMIDX_OK;
-    if (!h->d_pq32T) HIPCK(hipMalloc((void **)&h->d_pq32T, (size_t)h->m * h->dsub * 256 * sizeof(float)));
-    if (!h->d_pn32) HIPCK(hipMalloc((void **)&h->d_pn32, (size_t)h->m * 256 * sizeof(float)));
-    if (!h->d_pnmax) HIPCK(hipMalloc((void **)&h->d_pnmax, 2 * (size_t)h->m * sizeof(double)));
+    HIPCK(h->d_pq32T.ensure((size_t)h->m * h->dsub * 256));
+    HIPCK(h->d_pn32.ensure((size_t)h->m * 256));
+    HIPCK(h->d_pnmax.ensure(2 * (size_t)h->m));
     hipLaunchKernelGGL(k_pq32_table, dim3((unsigned)h->m), dim3(256), 0, h->stream, h->d_pqT, h->d_pq32T, h->d_pn32, h->m, h->ks, h->dsub);
     hipLaunchKernelGGL(k_pn_max, dim3((unsigned)h->m), dim3(256), 0, h->stream, h->d_pqT, h->d_pnmax, h->m, h->ks, h->dsub);
     if (h->kind == MMIDX_KIND_IVFPQ && h->d_perm && h->coarse_set) {  // K3s reads contiguous dimensions
-        if (!h->d_coarseP) HIPCK(hipMalloc((void **)&h->d_coarseP, (size_t)h->C * h->D * sizeof(double)));
+        HIPCK(h->d_coarseP.ensure((size_t)h->C * h->D));
         const long long tot = (long long)h->C * h->D;
         hipLaunchKernelGGL(k_permute_cols, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, h->stream, h->d_coarse, h->d_perm, h->d_coarseP, h->D,
                            (long long)h->C);
@@ -1541,8 +1534,8 @@ int launch_grouped_common(mmidx_index *h, const ScanParams &S, ScanParams F, con
     if (!flat_inst) GX.flat_lut = nullptr;
     // the extra pointers live in a small device struct, re-sent only when they change (pinned mirror; one search at a time per handle)
     if (!h->d_grpx) {
-        HIPCK(hipMalloc((void **)&h->d_grpx, sizeof(GrpExtra)));
-        HIPCK(hipHostMalloc((void **)&h->pin_grpx, sizeof(GrpExtra)));
+        HIPCK(h->d_grpx.alloc(sizeof(GrpExtra)));
+        HIPCK(h->pin_grpx.alloc(sizeof(GrpExtra)));
         memset(h->pin_grpx, 0xFF, sizeof(GrpExtra));
     }
     if (memcmp(h->pin_grpx, &GX, sizeof(GrpExtra)) != 0) {
@@ -1621,8 +1614,8 @@ int build_mfma_tables(mmidx_index *h) {
         }
         if (ep < -110 || ep > 110) return MMIDX_OK;
         h->pq_ep = ep;
-        if (!h->d_pq16) HIPCK(hipMalloc((void **)&h->d_pq16, (size_t)h->D * 512));
-        if (!h->d_pn64) HIPCK(hipMalloc((void **)&h->d_pn64, (size_t)h->m * 256 * sizeof(double)));
+        HIPCK(h->d_pq16.ensure((size_t)h->D * 256));
+        HIPCK(h->d_pn64.ensure((size_t)h->m * 256));
         const int rows = h->D / 8 * 256;
         hipLaunchKernelGGL(k_pq16_table, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, h->stream, h->d_pqT, h->d_pq16, h->m, h->ks, h->dsub,
                            std::ldexp(1.0, ep));
@@ -1862,7 +1855,7 @@ int launch_scan_grouped_flat(mmidx_index *h, const ScanParams &P, const SearchPl
     HIPCK(h->ws_order.reserve((size_t)npairs));
     HIPCK(h->ws_flatoff.reserve((size_t)nch + 1));
     if (!h->d_zero) {
-        HIPCK(hipMalloc((void **)&h->d_zero, (size_t)h->D * sizeof(double)));
+        HIPCK(h->d_zero.alloc((size_t)h->D));
         HIPCK(hipMemsetAsync(h->d_zero, 0, (size_t)h->D * sizeof(double), st));
     }
     const long long work = std::max<long long>(npairs, nch + 1);
@@ -2592,7 +2585,7 @@ int mmidx_create(int kind, int D, int m, int ks, int C, int transform, const int
     if (ndev < 1) return mmidx_fail(MMIDX_ERR_NO_DEVICE, "no HIP device: libmmidx_hip has no CPU fallback");
     if (device < 0 || device >= ndev) return mmidx_fail(MMIDX_ERR_NO_DEVICE, "device %d outside 0..%d", device, ndev - 1);
     HIPCK(hipSetDevice(device));
-    mmidx_index *h = new mmidx_index();
+    std::unique_ptr<mmidx_index> h(new mmidx_index());  // (nothing enqueued yet: a failing step below frees what was made)
     h->kind = kind;
     h->D = D;
     h->m = m;
@@ -2609,27 +2602,21 @@ int mmidx_create(int kind, int D, int m, int ks, int C, int transform, const int
         if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) (void)hipGetLastError();
         h->num_cus = ncu > 0 ? ncu : 256;
     }
-    if (hipHostMalloc((void **)&h->pin_hint, 64) == hipSuccess) {
+    if (h->pin_hint.alloc(16) == hipSuccess) {
         memset(h->pin_hint, 0, 64);  // [0] pass B's pair count of the previous call, [1] codes its K3g verified
     } else {
-        h->pin_hint = nullptr;  // (launches are then sized for the worst case)
+        h->pin_hint.p = nullptr;  // (launches are then sized for the worst case)
         (void)hipGetLastError();
     }
-    hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-    if (e != hipSuccess) {
-        delete h;
-        return mmidx_fail(MMIDX_ERR_HIP, "hipStreamCreate failed: %s", hipGetErrorString(e));
-    }
-    if (hipMalloc((void **)&h->d_counters, 16 * sizeof(u64)) != hipSuccess || hipMemset(h->d_counters, 0, 16 * sizeof(u64)) != hipSuccess) {
-        delete h;
+    hipError_t e = h->stream.create();
+    if (e != hipSuccess) return mmidx_fail(MMIDX_ERR_HIP, "hipStreamCreate failed: %s", hipGetErrorString(e));
+    if (h->d_counters.alloc(16) != hipSuccess || hipMemset(h->d_counters, 0, 16 * sizeof(u64)) != hipSuccess)
         return mmidx_fail(MMIDX_ERR_HIP, "hipMalloc failed");
-    }
     if (transform == MMIDX_TR_PERMUTATION) {
         std::vector<int32_t> p((size_t)D);
         if (perm) {
             for (int i = 0; i < D; i++) {
                 if (perm[i] < 0 || perm[i] >= D) {
-                    mmidx_destroy(h);
                     return mmidx_fail(MMIDX_ERR_INVALID_ARG, "permutation index out of range");
                 }
                 p[(size_t)i] = perm[i];
@@ -2637,10 +2624,10 @@ int mmidx_create(int kind, int D, int m, int ks, int C, int transform, const int
         } else {
             jdk_random_permutation(1, D, p.data());  // seed = 1: IVFPQ.java:136, PQ.java:108
         }
-        HIPCK(hipMalloc((void **)&h->d_perm, (size_t)D * sizeof(int32_t)));
+        HIPCK(h->d_perm.alloc((size_t)D));
         HIPCK(hipMemcpy(h->d_perm, p.data(), (size_t)D * sizeof(int32_t), hipMemcpyHostToDevice));
     } else if (transform == MMIDX_TR_ROTATION) {
-        HIPCK(hipMalloc((void **)&h->d_rot, (size_t)D * D * sizeof(double)));
+        HIPCK(h->d_rot.alloc((size_t)D * D));
         HIPCK(hipMemcpy(h->d_rot, rot, (size_t)D * D * sizeof(double), hipMemcpyHostToDevice));
         // The matrix is an input (EJML's createOrthogonal stream cannot be reproduced: SURVEY 8c): how far is it from orthogonal?
         // v -> v R keeps lengths up to |v| sqrt(||R R^T - I||_2) <= |v| sqrt(D max|R R^T - I|): with that measured, the coarse bound
@@ -2666,7 +2653,7 @@ int mmidx_create(int kind, int D, int m, int ks, int C, int transform, const int
         }
         if (h->sw.no_filter) h->sw.no_bound = 1;
     }
-    *out = h;
+    *out = h.release();
     return MMIDX_OK;
 }
 
@@ -2679,118 +2666,7 @@ int mmidx_destroy(mmidx_index *h) {
     }
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    if (h->pin_hint) {
-        (void)hipDeviceSynchronize();  // a read-back of the hint may still be queued on the caller's stream
-        (void)hipHostFree(h->pin_hint);
-        h->pin_hint = nullptr;
-    }
-    if (h->pin_stage) (void)hipHostFree(h->pin_stage);
-    h->pin_stage = nullptr;
-    for (auto &sl : h->host_slot) {
-        if (sl.e_in) (void)hipEventDestroy(sl.e_in);
-        if (sl.e_done) (void)hipEventDestroy(sl.e_done);
-        if (sl.st) (void)hipStreamDestroy(sl.st);
-        sl.e_in = sl.e_done = nullptr;
-        sl.st = nullptr;
-        sl.dQ.release();
-        sl.out.release();
-    }
-    h->ws_out.release();
-    void *ptrs[] = {h->d_Ch, h->d_Cl, h->d_cn_pad, h->d_cn, h->d_cnorm, h->d_coarseT32, h->d_coarse, h->d_coarseT, h->d_pq, h->d_pqT, h->d_rot, h->d_perm, h->d_off, h->d_codes,
-                    h->d_ids,    h->d_pcell,   h->d_pid, h->d_pcodes};
-    for (void *p : ptrs)
-        if (p) (void)hipFree(p);
-    h->ws_Q.release();
-    h->ws_cdist.release();
-    h->ws_odist.release();
-    h->ws_X.release();
-    h->ws_qn.release();
-    h->ws_Xa.release();
-    h->ws_sdc.release();
-    h->ws_fb.release();
-    h->ws_Qh.release();
-    h->ws_Ql.release();
-    h->ws_gmin.release();
-    h->ws_clist.release();
-    h->ws_glut.release();
-    h->ws_cdsel.release();
-    h->ws_Q32.release();
-    h->ws_S.release();
-    h->ws_cells.release();
-    h->ws_oiid.release();
-    h->ws_ocnt.release();
-    h->ws_flag.release();
-    h->ws_ecell.release();
-    h->ws_pcount.release();
-    h->ws_pstart.release();
-    h->ws_pcursor.release();
-    h->ws_order.release();
-    h->ws_T.release();
-    h->ws_pkey.release();
-    h->ws_pval.release();
-    h->ws_pcnt.release();
-    h->ws_ecode.release();
-    h->ws_tmp.release();
-    h->ws_keep.release();
-    h->ws_amb.release();
-    h->ws_aidx.release();
-    h->ws_acell.release();
-    h->ws_dest.release();
-    h->ws_gdesc.release();
-    h->ws_gfb.release();
-    h->ws_flatoff.release();
-    h->ws_flatlut.release();
-    h->ws_ghist.release();
-    if (h->d_grpx) (void)hipFree(h->d_grpx);
-    if (h->pin_grpx) (void)hipHostFree(h->pin_grpx);
-    h->ws_T0.release();
-    h->ws_inv.release();
-    if (h->d_rotT) (void)hipFree(h->d_rotT);
-    h->ws_idq.release();
-    h->ws_found.release();
-    h->ws_rfi.release();
-    h->ws_rfc.release();
-    h->ws_rfd.release();
-    h->ws_rfm.release();
-    for (int e = 0; e < 4; e++)
-        if (h->host_ev[e]) (void)hipEventDestroy(h->host_ev[e]);
-    if (h->d_pqstat) (void)hipFree(h->d_pqstat);
-    if (h->d_pqT32) (void)hipFree(h->d_pqT32);
-    if (h->d_pq32T) (void)hipFree(h->d_pq32T);
-    if (h->d_pn32) (void)hipFree(h->d_pn32);
-    if (h->d_pnmax) (void)hipFree(h->d_pnmax);
-    if (h->d_coarseP) (void)hipFree(h->d_coarseP);
-    if (h->d_zero) (void)hipFree(h->d_zero);
-    if (h->d_pq16) (void)hipFree(h->d_pq16);
-    if (h->d_pn64) (void)hipFree(h->d_pn64);
-    h->xn.release();
-    h->ws_surv.release();
-    h->ws_R.release();
-    h->ws_R16.release();
-    h->ws_defer.release();
-    h->ws_nrow.release();
-    h->ws_lutpre.release();
-    h->ws_acand.release();
-    h->ws_arowc.release();
-    h->ws_abm.release();
-    h->ws_aicnt.release();
-    h->ws_arec.release();
-    h->ws_arows.release();
-    h->ws_ameta.release();
-    h->ws_ametaT.release();
-    h->ws_arnd.release();
-    for (hipEvent_t e : h->a_ev) (void)hipEventDestroy(e);
-    h->a_ev.clear();
-    h->ws_mfctl.release();
-    h->ws_psnap.release();
-    h->ws_redo.release();
-    h->ws_Qp.release();
-    for (auto &ev : h->evpool)
-        if (ev) (void)hipEventDestroy(ev);
-    for (auto &ev : h->mf_ev)
-        if (ev) (void)hipEventDestroy(ev);
-    if (h->d_counters) (void)hipFree(h->d_counters);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
+    if (h->pin_hint) (void)hipDeviceSynchronize();  // a read-back of the hint may still be queued on the caller's stream
     delete h;
     return MMIDX_OK;
 }
@@ -2809,8 +2685,8 @@ int mmidx_set_coarse(mmidx_index *h, const double *coarse) {
     std::vector<double> T(n);
     for (int c = 0; c < h->C; c++)
         for (int j = 0; j < h->D; j++) T[(size_t)j * h->C + c] = coarse[(size_t)c * h->D + j];
-    if (!h->d_coarse) HIPCK(hipMalloc((void **)&h->d_coarse, n * sizeof(double)));
-    if (!h->d_coarseT) HIPCK(hipMalloc((void **)&h->d_coarseT, n * sizeof(double)));
+    HIPCK(h->d_coarse.ensure(n));
+    HIPCK(h->d_coarseT.ensure(n));
     HIPCK(hipMemcpy(h->d_coarse, coarse, n * sizeof(double), hipMemcpyHostToDevice));
     HIPCK(hipMemcpy(h->d_coarseT, T.data(), n * sizeof(double), hipMemcpyHostToDevice));
     // certified approximate coarse stage: |c|^2, |c| (fp64) and an fp32 transposed copy
@@ -2832,24 +2708,22 @@ int mmidx_set_coarse(mmidx_index *h, const double *coarse) {
         h->cn_max = std::max(h->cn_max, s2 * (1.0 + 1e-12));
         h->cnorm_max = std::max(h->cnorm_max, cnorm[(size_t)c]);
     }
-    if (!h->d_cn) HIPCK(hipMalloc((void **)&h->d_cn, (size_t)h->C * 8));
-    if (!h->d_cnorm) HIPCK(hipMalloc((void **)&h->d_cnorm, (size_t)h->C * 8));
-    if (!h->d_coarseT32) HIPCK(hipMalloc((void **)&h->d_coarseT32, n * sizeof(float)));
+    HIPCK(h->d_cn.ensure((size_t)h->C));
+    HIPCK(h->d_cnorm.ensure((size_t)h->C));
+    HIPCK(h->d_coarseT32.ensure(n));
     HIPCK(hipMemcpy(h->d_cn, cn.data(), (size_t)h->C * 8, hipMemcpyHostToDevice));
     HIPCK(hipMemcpy(h->d_cnorm, cnorm.data(), (size_t)h->C * 8, hipMemcpyHostToDevice));
     HIPCK(hipMemcpy(h->d_coarseT32, T32.data(), n * sizeof(float), hipMemcpyHostToDevice));
     // bf16 head / tail copies, rows padded to a multiple of 128 (zero rows, |c|^2 = +inf), k to a multiple of 32
     h->Cp = (h->C + 127) / 128 * 128;
     h->Dp = (h->D + 31) / 32 * 32;
-    if (h->d_Ch) (void)hipFree(h->d_Ch);
-    if (h->d_Cl) (void)hipFree(h->d_Cl);
-    if (h->d_cn_pad) (void)hipFree(h->d_cn_pad);
-    h->d_Ch = h->d_Cl = nullptr;
-    h->d_cn_pad = nullptr;
+    h->d_Ch.release();
+    h->d_Cl.release();
+    h->d_cn_pad.release();
     const size_t nb = (size_t)h->Cp * h->Dp;
-    HIPCK(hipMalloc((void **)&h->d_Ch, nb * 2));
-    HIPCK(hipMalloc((void **)&h->d_Cl, nb * 2));
-    HIPCK(hipMalloc((void **)&h->d_cn_pad, (size_t)h->Cp * 8));
+    HIPCK(h->d_Ch.alloc(nb));
+    HIPCK(h->d_Cl.alloc(nb));
+    HIPCK(h->d_cn_pad.alloc((size_t)h->Cp));
     HIPCK(hipMemset(h->d_Ch, 0, nb * 2));
     HIPCK(hipMemset(h->d_Cl, 0, nb * 2));
     {
@@ -2881,8 +2755,8 @@ int mmidx_set_pq(mmidx_index *h, const double *pq) {
         for (int j = 0; j < h->ks; j++)
             for (int t = 0; t < h->dsub; t++)
                 T[((size_t)s * h->dsub + t) * h->ks + j] = pq[((size_t)s * h->ks + j) * h->dsub + t];
-    if (!h->d_pq) HIPCK(hipMalloc((void **)&h->d_pq, n * sizeof(double)));
-    if (!h->d_pqT) HIPCK(hipMalloc((void **)&h->d_pqT, n * sizeof(double)));
+    HIPCK(h->d_pq.ensure(n));
+    HIPCK(h->d_pqT.ensure(n));
     HIPCK(hipMemcpy(h->d_pq, pq, n * sizeof(double), hipMemcpyHostToDevice));
     HIPCK(hipMemcpy(h->d_pqT, T.data(), n * sizeof(double), hipMemcpyHostToDevice));
     double amax = 0.0;
@@ -2916,17 +2790,16 @@ int mmidx_set_pq(mmidx_index *h, const double *pq) {
                 }
                 stt[(size_t)h->m * h->dsub + s] += nn / h->ks;
             }
-        if (!h->d_pqstat) HIPCK(hipMalloc((void **)&h->d_pqstat, stt.size() * sizeof(double)));
+        HIPCK(h->d_pqstat.ensure(stt.size()));
         HIPCK(hipMemcpy(h->d_pqstat, stt.data(), stt.size() * sizeof(double), hipMemcpyHostToDevice));
-        if (h->d_pqT32) (void)hipFree(h->d_pqT32);
-        h->d_pqT32 = nullptr;
+        h->d_pqT32.release();
         if (h->ks == 256 && h->dsub % 2 == 0) {
             std::vector<float> t32(n);
             for (int s = 0; s < h->m; s++)
                 for (int j = 0; j < 256; j++)
                     for (int t = 0; t < h->dsub; t++)
                         t32[(((size_t)s * (h->dsub / 2) + t / 2) * 256 + j) * 2 + (t & 1)] = (float)pq[((size_t)s * h->ks + j) * h->dsub + t];
-            HIPCK(hipMalloc((void **)&h->d_pqT32, n * sizeof(float)));
+            HIPCK(h->d_pqT32.alloc(n));
             HIPCK(hipMemcpy(h->d_pqT32, t32.data(), n * sizeof(float), hipMemcpyHostToDevice));
         }
     }
@@ -3089,19 +2962,15 @@ int mmidx_add_codes(mmidx_index *h, int64_t n, const int32_t *iids, const int32_
     int rc = set_device(h);
     if (rc) return rc;
     const size_t cb = (size_t)h->m * h->code_bytes;
-    int32_t *d_i = nullptr, *d_c = nullptr;
-    void *d_k = nullptr;
-    HIPCK(hipMalloc((void **)&d_i, (size_t)n * 4));
-    HIPCK(hipMalloc((void **)&d_c, (size_t)n * 4));
-    HIPCK(hipMalloc(&d_k, (size_t)n * cb));
+    DevPtr<int32_t> d_i, d_c;
+    DevPtr<void> d_k;
+    HIPCK(d_i.alloc((size_t)n));
+    HIPCK(d_c.alloc((size_t)n));
+    HIPCK(d_k.alloc((size_t)n * cb));
     HIPCK(hipMemcpy(d_i, iids, (size_t)n * 4, hipMemcpyHostToDevice));
     if (cells) HIPCK(hipMemcpy(d_c, cells, (size_t)n * 4, hipMemcpyHostToDevice));
     HIPCK(hipMemcpy(d_k, codes, (size_t)n * cb, hipMemcpyHostToDevice));
-    rc = mmidx_add_codes_device(h, n, d_i, cells ? d_c : nullptr, d_k, nullptr);
-    (void)hipFree(d_i);
-    (void)hipFree(d_c);
-    (void)hipFree(d_k);
-    return rc;
+    return mmidx_add_codes_device(h, n, d_i, cells ? d_c.p : nullptr, d_k, nullptr);
 }
 
 int mmidx_add_vectors_device(mmidx_index *h, int64_t n, const double *dX, const int32_t *d_iids, int32_t iid0, void *stream) {
@@ -3152,12 +3021,12 @@ int mmidx_add_vectors(mmidx_index *h, int64_t n, const double *X, const int32_t 
     const int64_t B = 1 << 18;
     for (int64_t i0 = 0; i0 < n; i0 += B) {
         const int64_t nb = std::min(B, n - i0);
-        double *dX = nullptr;
-        int32_t *d_i = nullptr;
-        HIPCK(hipMalloc((void **)&dX, (size_t)nb * h->D * 8));
+        DevPtr<double> dX;
+        DevPtr<int32_t> d_i;
+        HIPCK(dX.alloc((size_t)nb * h->D));
         HIPCK(hipMemcpy(dX, X + (size_t)i0 * h->D, (size_t)nb * h->D * 8, hipMemcpyHostToDevice));
         if (iids) {
-            HIPCK(hipMalloc((void **)&d_i, (size_t)nb * 4));
+            HIPCK(d_i.alloc((size_t)nb));
             HIPCK(hipMemcpy(d_i, iids + i0, (size_t)nb * 4, hipMemcpyHostToDevice));
         }
         const int64_t o = h->n_pend;
@@ -3173,8 +3042,6 @@ int mmidx_add_vectors(mmidx_index *h, int64_t n, const double *X, const int32_t 
                 for (size_t t = 0; t < (size_t)nb * cb; t++) c[t] = (signed char)((int)(unsigned char)c[t] - 128);
             }
         }
-        (void)hipFree(dX);
-        if (d_i) (void)hipFree(d_i);
         if (rc) return rc;
     }
     return MMIDX_OK;
@@ -3248,10 +3115,10 @@ static int search_host_big(mmidx_index *h, const SearchReq &r) {
             h->slot_cv.notify_one();
         }
     } release{h, sl};
-    if (!sl->st) {
-        HIPCK(hipStreamCreateWithFlags(&sl->st, hipStreamNonBlocking));
-        HIPCK(hipEventCreateWithFlags(&sl->e_in, hipEventDisableTiming));
-        HIPCK(hipEventCreateWithFlags(&sl->e_done, hipEventDisableTiming));
+    if (!sl->e_done) {  // (the last of the three: a slot whose set-up failed half way starts again)
+        HIPCK(sl->st.create());
+        HIPCK(sl->e_in.create(hipEventDisableTiming));
+        HIPCK(sl->e_done.create(hipEventDisableTiming));
     }
     const size_t od = (size_t)nq * k * 8, oi = (size_t)nq * k * 4, oc = (size_t)nq * 4;
     if ((size_t)nq * h->D > sl->dQ.cap || od + oi + oc > sl->out.cap) HIPCK(hipStreamSynchronize(sl->st));
@@ -3291,15 +3158,13 @@ static int search_host_batch(mmidx_index *h, SearchReq *const *batch, size_t nb)
     const size_t od = (size_t)tot * k * 8, oi = (size_t)tot * k * 4, oc = (size_t)tot * 4;
     const size_t need = in_bytes + od + oi + oc;
     if (need > h->pin_stage_cap) {
-        if (h->pin_stage) (void)hipHostFree(h->pin_stage);
-        h->pin_stage = nullptr;
         h->pin_stage_cap = 0;
         const size_t want = need + need / 4 + 4096;
-        if (hipHostMalloc((void **)&h->pin_stage, want) == hipSuccess) {
+        if (h->pin_stage.alloc(want) == hipSuccess) {
             h->pin_stage_cap = want;
         } else {
             (void)hipGetLastError();
-            h->pin_stage = nullptr;
+            h->pin_stage.p = nullptr;
         }
     }
     if (!h->pin_stage) {  // no pinned memory: every request on its own, pageable copies
@@ -3339,7 +3204,7 @@ static int search_host_batch(mmidx_index *h, SearchReq *const *batch, size_t nb)
     // next one is still on the bus (events between the slices; the handle keeps them)
     constexpr int NSL = 4;
     if (!h->host_ev[0]) {
-        for (int e = 0; e < NSL; e++) HIPCK(hipEventCreateWithFlags(&h->host_ev[e], hipEventDisableTiming));
+        for (int e = NSL - 1; e >= 0; e--) HIPCK(h->host_ev[e].create(hipEventDisableTiming));  // ([0] last: it marks the set complete)
     }
     std::vector<int64_t> req_q0(nb + 1, 0);  // first query of every request in the combined batch
     for (size_t i = 0; i < nb; i++) req_q0[i + 1] = req_q0[i] + batch[i]->nq;
@@ -3673,7 +3538,7 @@ int mmidx_get_stats(mmidx_index *h, mmidx_stats *out) {
     if (h->ev_used) HIPCK(hipEventSynchronize(h->evpool[h->ev_used - 1]));
     HIPCK(hipDeviceSynchronize());
     for (size_t g = 0; g + 6 <= h->ev_used; g += 6) {
-        hipEvent_t *ev = h->evpool.data() + g;
+        const Event *ev = h->evpool.data() + g;
         float a = 0, b = 0, c = 0, t = 0, pa = 0;
         if (h->profiling == 2) {  // light: only the pass-A pair was recorded
             HIPCK(hipEventElapsedTime(&pa, ev[2], ev[5]));
@@ -3756,8 +3621,8 @@ namespace {
 // iid -> position map over the list-major arrays; h->mu held by the caller
 int ensure_inverse(mmidx_index *h) {
     if (h->inv_valid) return MMIDX_OK;
-    int32_t *d_max = nullptr;
-    HIPCK(hipMalloc((void **)&d_max, sizeof(int32_t)));
+    DevPtr<int32_t> d_max;
+    HIPCK(d_max.alloc(1));
     int32_t mx = -1;
     HIPCK(hipMemcpy(d_max, &mx, sizeof(mx), hipMemcpyHostToDevice));
     const long long n = h->n_csr;
@@ -3766,7 +3631,6 @@ int ensure_inverse(mmidx_index *h) {
         HIPCK(hipStreamSynchronize(h->stream));
     }
     hipError_t e = hipMemcpy(&mx, d_max, sizeof(mx), hipMemcpyDeviceToHost);
-    (void)hipFree(d_max);
     if (e != hipSuccess) return mmidx_fail(MMIDX_ERR_HIP, "hipMemcpy failed: %s", hipGetErrorString(e));
     h->inv_size = (int64_t)mx + 1;
     HIPCK(h->ws_inv.reserve((size_t)std::max<int64_t>(h->inv_size, 1)));
@@ -3779,26 +3643,17 @@ int ensure_inverse(mmidx_index *h) {
 }
 
 // device lookup of n records: d_pos[n], d_code[n][m] (stored form); host cells from the list offsets
-int lookup_records(mmidx_index *h, int64_t n, const int32_t *iids, int32_t **d_pos_out, void **d_code_out, std::vector<int32_t> &pos,
+int lookup_records(mmidx_index *h, int64_t n, const int32_t *iids, DevPtr<int32_t> &d_pos, DevPtr<void> &d_code, std::vector<int32_t> &pos,
                    std::vector<int32_t> &cells, bool allow_missing = false) {
     int rc = build_csr(h);
     if (rc) return rc;
     rc = ensure_inverse(h);
     if (rc) return rc;
-    int32_t *d_iids = nullptr, *d_pos = nullptr;
-    void *d_code = nullptr;
+    DevPtr<int32_t> d_iids;
     const size_t cbytes = (size_t)n * h->m * h->code_bytes;
-    HIPCK(hipMalloc((void **)&d_iids, std::max<size_t>((size_t)n * 4, 16)));
-    if (hipMalloc((void **)&d_pos, std::max<size_t>((size_t)n * 4, 16)) != hipSuccess || hipMalloc(&d_code, std::max<size_t>(cbytes, 16)) != hipSuccess) {
-        (void)hipFree(d_iids);
-        if (d_pos) (void)hipFree(d_pos);
+    HIPCK(d_iids.alloc(std::max<size_t>((size_t)n, 4)));
+    if (d_pos.alloc(std::max<size_t>((size_t)n, 4)) != hipSuccess || d_code.alloc(std::max<size_t>(cbytes, 16)) != hipSuccess)
         return mmidx_fail(MMIDX_ERR_HIP, "hipMalloc failed");
-    }
-    auto cleanup = [&]() {
-        (void)hipFree(d_iids);
-        (void)hipFree(d_pos);
-        (void)hipFree(d_code);
-    };
     pos.assign((size_t)n, -1);
     cells.assign((size_t)n, -1);
     hipError_t e = hipMemcpyAsync(d_iids, iids, (size_t)n * 4, hipMemcpyHostToDevice, h->stream);
@@ -3814,23 +3669,16 @@ int lookup_records(mmidx_index *h, int64_t n, const int32_t *iids, int32_t **d_p
     }
     if (e == hipSuccess) e = hipMemcpyAsync(pos.data(), d_pos, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (e != hipSuccess) {
-        cleanup();
-        return mmidx_fail(MMIDX_ERR_HIP, "record lookup failed: %s", hipGetErrorString(e));
-    }
+    if (e != hipSuccess) return mmidx_fail(MMIDX_ERR_HIP, "record lookup failed: %s", hipGetErrorString(e));
     for (int64_t i = 0; i < n; i++) {
         if (pos[(size_t)i] < 0) {
             if (allow_missing) continue;  // (a shard of a sharded handle: the id lives on another shard)
-            cleanup();
             return mmidx_fail(MMIDX_ERR_INVALID_ARG, "Id does not exist!");  // IVFPQ.java:803-805, :868-870
         }
         // list of a position: the last list whose start is <= pos
         const auto it = std::upper_bound(h->h_off.begin(), h->h_off.end(), (int64_t)pos[(size_t)i]);
         cells[(size_t)i] = (int32_t)(it - h->h_off.begin()) - 1;
     }
-    (void)hipFree(d_iids);
-    *d_pos_out = d_pos;
-    *d_code_out = d_code;
     return MMIDX_OK;
 }
 }  // namespace
@@ -3869,15 +3717,13 @@ int mmidx_get_codes(mmidx_index *h, int64_t n, const int32_t *iids, int32_t *cel
     if (rc) return rc;
     DeviceCall call(h, h->stream);  // (the CSR rebuild below must not move the arrays under a search another stream is still running)
     std::lock_guard<std::mutex> lk(h->mu);
-    int32_t *d_pos = nullptr;
-    void *d_code = nullptr;
+    DevPtr<int32_t> d_pos;
+    DevPtr<void> d_code;
     std::vector<int32_t> pos, cells;
-    rc = lookup_records(h, n, iids, &d_pos, &d_code, pos, cells);
+    rc = lookup_records(h, n, iids, d_pos, d_code, pos, cells);
     if (rc) return rc;
     hipError_t e = hipSuccess;
     if (code_out) e = hipMemcpy(code_out, d_code, (size_t)n * h->m * h->code_bytes, hipMemcpyDeviceToHost);
-    (void)hipFree(d_pos);
-    (void)hipFree(d_code);
     if (e != hipSuccess) return mmidx_fail(MMIDX_ERR_HIP, "hipMemcpy failed: %s", hipGetErrorString(e));
     if (cell_out)
         for (int64_t i = 0; i < n; i++) cell_out[i] = h->kind == MMIDX_KIND_IVFPQ ? cells[(size_t)i] : -1;
@@ -3895,17 +3741,17 @@ int mmidx_distance(mmidx_index *h, int64_t n, const double *Q, const int32_t *ii
     if (rc) return rc;
     DeviceCall call(h, h->stream);
     std::lock_guard<std::mutex> lk(h->mu);
-    int32_t *d_pos = nullptr;
-    void *d_code = nullptr;
+    DevPtr<int32_t> d_pos;
+    DevPtr<void> d_code;
     std::vector<int32_t> pos, cells;
-    rc = lookup_records(h, n, iids, &d_pos, &d_code, pos, cells);
+    rc = lookup_records(h, n, iids, d_pos, d_code, pos, cells);
     if (rc) return rc;
-    (void)hipFree(d_code);
-    double *dQ = nullptr, *d_out = nullptr;
-    int32_t *d_cell = nullptr;
-    hipError_t e = hipMalloc((void **)&dQ, (size_t)n * h->D * 8);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_out, (size_t)n * 8);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_cell, (size_t)n * 4);
+    d_code.release();
+    DevPtr<double> dQ, d_out;
+    DevPtr<int32_t> d_cell;
+    hipError_t e = dQ.alloc((size_t)n * h->D);
+    if (e == hipSuccess) e = d_out.alloc((size_t)n);
+    if (e == hipSuccess) e = d_cell.alloc((size_t)n);
     if (e == hipSuccess) e = hipMemcpyAsync(dQ, Q, (size_t)n * h->D * 8, hipMemcpyHostToDevice, h->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(d_cell, cells.data(), (size_t)n * 4, hipMemcpyHostToDevice, h->stream);
     if (e == hipSuccess) {
@@ -3930,10 +3776,6 @@ int mmidx_distance(mmidx_index *h, int64_t n, const double *Q, const int32_t *ii
     }
     if (e == hipSuccess) e = hipMemcpyAsync(dist_out, d_out, (size_t)n * 8, hipMemcpyDeviceToHost, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    (void)hipFree(d_pos);
-    if (dQ) (void)hipFree(dQ);
-    if (d_out) (void)hipFree(d_out);
-    if (d_cell) (void)hipFree(d_cell);
     if (e != hipSuccess) return mmidx_fail(MMIDX_ERR_HIP, "mmidx_distance failed: %s", hipGetErrorString(e));
     return MMIDX_OK;
 }
@@ -3952,15 +3794,12 @@ int idq_prepare(mmidx_index *h) {
     if (rc) return rc;
     if (h->transform == MMIDX_TR_ROTATION && !h->d_rotT) {
         if (!h->d_rot) return mmidx_fail(MMIDX_ERR_NOT_READY, "the handle has no rotation matrix");
-        double *t = nullptr;
-        HIPCK(hipMalloc((void **)&t, (size_t)h->D * h->D * sizeof(double)));
+        DevPtr<double> t;
+        HIPCK(t.alloc((size_t)h->D * h->D));
         rc = mmidx_internal_transpose_square(h->d_rot, t, h->D, h->stream);
         if (rc == MMIDX_OK && hipStreamSynchronize(h->stream) != hipSuccess) rc = mmidx_fail(MMIDX_ERR_HIP, "transposing the rotation failed");
-        if (rc) {
-            (void)hipFree(t);
-            return rc;
-        }
-        h->d_rotT = t;
+        if (rc) return rc;
+        h->d_rotT = std::move(t);
     }
     return MMIDX_OK;
 }

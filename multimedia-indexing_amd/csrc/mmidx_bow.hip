@@ -104,14 +104,14 @@ __global__ __launch_bounds__(256) void k_bow_single(const long long *__restrict_
 
 }  // namespace
 
-struct mmidx_bow {
+struct MMIDX_HIDDEN mmidx_bow {
+    Stream stream;  // (before what is used on it: members are destroyed in reverse order)
     std::mutex mu;  // one call at a time per handle enqueues: the workspaces, the options and last_stream are shared
     hipStream_t last_stream = nullptr;  // the stream the workspaces were last used on: another stream waits for it first
     bool last_stream_valid = false;
-    long long *pin_ends = nullptr;  // 16 pinned bytes for the read-back of the call's descriptor range
+    PinBuf<long long> pin_ends;  // 16 pinned bytes for the read-back of the call's descriptor range
     int nc = 0, dl = 0, k = 1, device = 0;
     mmidx_index *asg = nullptr;  // the vocabulary as the coarse quantizer of a hidden index (nc >= 2)
-    hipStream_t stream = nullptr;
     DevBuf<int32_t> ws_cells;
     DevBuf<double> ws_desc, ws_out;
     DevBuf<long long> ws_off;
@@ -193,20 +193,17 @@ int mmidx_bow_create(int nc, int dl, int k, const double *codebook, int device, 
     if (ndev < 1) return mmidx_fail(MMIDX_ERR_NO_DEVICE, "no HIP device: libmmidx_hip has no CPU fallback");
     if (device < 0 || device >= ndev) return mmidx_fail(MMIDX_ERR_NO_DEVICE, "device %d outside 0..%d", device, ndev - 1);
     HIPCK(hipSetDevice(device));
-    mmidx_bow *b = new mmidx_bow();
-    if (hipHostMalloc((void **)&b->pin_ends, 16) != hipSuccess) {  // (the read-back then lands in pageable memory)
-        b->pin_ends = nullptr;
+    std::unique_ptr<mmidx_bow, int (*)(mmidx_bow *)> b(new mmidx_bow(), mmidx_bow_destroy);  // (destroy: the hidden index goes with it)
+    if (b->pin_ends.alloc(2) != hipSuccess) {  // (the read-back then lands in pageable memory)
+        b->pin_ends.p = nullptr;
         (void)hipGetLastError();
     }
     b->nc = nc;
     b->dl = dl;
     b->k = k;
     b->device = device;
-    hipError_t e = hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking);
-    if (e != hipSuccess) {
-        delete b;
-        return mmidx_fail(MMIDX_ERR_HIP, "hipStreamCreate failed: %s", hipGetErrorString(e));
-    }
+    hipError_t e = b->stream.create();
+    if (e != hipSuccess) return mmidx_fail(MMIDX_ERR_HIP, "hipStreamCreate failed: %s", hipGetErrorString(e));
     if (nc >= 2) {
         // m = 1, ks = 2 with an all-zero product quantizer: never used, but mmidx_coarse_device wants a complete index
         int rc = mmidx_create(MMIDX_KIND_IVFPQ, dl, 1, 2, nc, MMIDX_TR_NONE, nullptr, nullptr, device, &b->asg);
@@ -216,12 +213,9 @@ int mmidx_bow_create(int nc, int dl, int k, const double *codebook, int device, 
             rc = mmidx_set_pq(b->asg, zero.data());
             if (rc == MMIDX_OK) rc = mmidx_set_w(b->asg, k);
         }
-        if (rc != MMIDX_OK) {  // (the message of the failing call stands)
-            mmidx_bow_destroy(b);
-            return rc;
-        }
+        if (rc != MMIDX_OK) return rc;  // (the message of the failing call stands)
     }
-    *out = b;
+    *out = b.release();
     return MMIDX_OK;
 }
 
@@ -229,12 +223,6 @@ int mmidx_bow_destroy(mmidx_bow *b) {
     if (!b) return MMIDX_OK;
     (void)hipSetDevice(b->device);
     if (b->asg) mmidx_destroy(b->asg);
-    if (b->pin_ends) (void)hipHostFree(b->pin_ends);
-    b->ws_cells.release();
-    b->ws_desc.release();
-    b->ws_out.release();
-    b->ws_off.release();
-    if (b->stream) (void)hipStreamDestroy(b->stream);
     delete b;
     return MMIDX_OK;
 }
@@ -273,7 +261,7 @@ int mmidx_bow_aggregate_device(mmidx_bow *b, int64_t nimg, const int64_t *d_desc
     HIPCK(hipSetDevice(b->device));
     hipStream_t st = (hipStream_t)stream;
     long long stack_ends[2] = {0, 0};
-    long long *ends = b->pin_ends ? b->pin_ends : stack_ends;  // the descriptor range of the call: the assignment is sized by it
+    long long *ends = b->pin_ends ? b->pin_ends.p : stack_ends;  // the descriptor range of the call: the assignment is sized by it
     ends[0] = ends[1] = 0;
     if (b->nc > 1) {
         if (nimg == 1) {

@@ -9,20 +9,20 @@
 #include <string>
 #include <vector>
 
-struct mmidx_pca {
+struct MMIDX_HIDDEN mmidx_pca {
     std::mutex mu;  // host-pointer calls share the workspaces
     int nc = 0, ss = 0, whitening = 0, device = 0;
-    double *d_mu = nullptr, *d_Vt = nullptr;
-    hipStream_t stream = nullptr;
+    Stream stream;  // (before what is used on it: members are destroyed in reverse order)
+    DevPtr<double> d_mu, d_Vt;
     DevBuf<double> ws_X, ws_Y;
 };
-struct mmidx_vlad {
+struct MMIDX_HIDDEN mmidx_vlad {
     std::mutex mu;  // host-pointer calls share the workspaces
     int nvocab = 0, dl = 0, norms = 0, device = 0, veclen = 0;
     std::vector<int> nc;
     std::vector<size_t> cb_off;  // element offset of each codebook
-    double *d_cb = nullptr;
-    hipStream_t stream = nullptr;
+    Stream stream;  // (before what is used on it: members are destroyed in reverse order)
+    DevPtr<double> d_cb;
     DevBuf<double> ws_desc, ws_out;
     DevBuf<long long> ws_off;
     // K8': the assignment of every descriptor of a launch through the encoder's certified MFMA argmin -- one hidden index handle
@@ -45,7 +45,7 @@ int mmidx_pca_create(int nc, int ss, int whitening, const double *means, const d
     if (ndev < 1) return mmidx_fail(MMIDX_ERR_NO_DEVICE, "no HIP device: libmmidx_hip has no CPU fallback");
     if (device < 0 || device >= ndev) return mmidx_fail(MMIDX_ERR_NO_DEVICE, "device %d outside 0..%d", device, ndev - 1);
     HIPCK(hipSetDevice(device));
-    mmidx_pca *p = new mmidx_pca();
+    std::unique_ptr<mmidx_pca> p(new mmidx_pca());
     p->nc = nc;
     p->ss = ss;
     p->whitening = whitening ? 1 : 0;
@@ -56,12 +56,12 @@ int mmidx_pca_create(int nc, int ss, int whitening, const double *means, const d
         const double wv = whitening ? std::pow(eig[i], -0.5) : 1.0;
         for (int j = 0; j < ss; j++) V[(size_t)i * ss + j] = whitening ? wv * Vt[(size_t)i * ss + j] : Vt[(size_t)i * ss + j];
     }
-    HIPCK(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
-    HIPCK(hipMalloc((void **)&p->d_mu, (size_t)ss * 8));
-    HIPCK(hipMalloc((void **)&p->d_Vt, (size_t)nc * ss * 8));
+    HIPCK(p->stream.create());
+    HIPCK(p->d_mu.alloc((size_t)ss));
+    HIPCK(p->d_Vt.alloc((size_t)nc * ss));
     HIPCK(hipMemcpy(p->d_mu, means, (size_t)ss * 8, hipMemcpyHostToDevice));
     HIPCK(hipMemcpy(p->d_Vt, V.data(), (size_t)nc * ss * 8, hipMemcpyHostToDevice));
-    *out = p;
+    *out = p.release();
     return MMIDX_OK;
 }
 
@@ -77,11 +77,6 @@ int mmidx_internal_pca_device(const mmidx_pca *p) { return p->device; }  // (mmi
 int mmidx_pca_destroy(mmidx_pca *p) {
     if (!p) return MMIDX_OK;
     (void)hipSetDevice(p->device);
-    if (p->d_mu) (void)hipFree(p->d_mu);
-    if (p->d_Vt) (void)hipFree(p->d_Vt);
-    p->ws_X.release();
-    p->ws_Y.release();
-    if (p->stream) (void)hipStreamDestroy(p->stream);
     delete p;
     return MMIDX_OK;
 }
@@ -139,24 +134,21 @@ int mmidx_vlad_create(int nvocab, const int32_t *ncent, int dl, const double *co
     if (ndev < 1) return mmidx_fail(MMIDX_ERR_NO_DEVICE, "no HIP device: libmmidx_hip has no CPU fallback");
     if (device < 0 || device >= ndev) return mmidx_fail(MMIDX_ERR_NO_DEVICE, "device %d outside 0..%d", device, ndev - 1);
     HIPCK(hipSetDevice(device));
-    mmidx_vlad *v = new mmidx_vlad();
+    std::unique_ptr<mmidx_vlad> v(new mmidx_vlad());
     v->nvocab = nvocab;
     v->dl = dl;
     v->norms = normalizations_on ? 1 : 0;
     v->device = device;
     size_t tot = 0;
     for (int i = 0; i < nvocab; i++) {
-        if (ncent[i] < 1) {
-            delete v;
-            return mmidx_fail(MMIDX_ERR_INVALID_ARG, "empty codebook");
-        }
+        if (ncent[i] < 1) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "empty codebook");
         v->nc.push_back(ncent[i]);
         v->cb_off.push_back(tot);
         tot += (size_t)ncent[i] * dl;
     }
     v->veclen = (int)tot;
-    HIPCK(hipStreamCreateWithFlags(&v->stream, hipStreamNonBlocking));
-    HIPCK(hipMalloc((void **)&v->d_cb, tot * 8));
+    HIPCK(v->stream.create());
+    HIPCK(v->d_cb.alloc(tot));
     HIPCK(hipMemcpy(v->d_cb, codebooks, tot * 8, hipMemcpyHostToDevice));
     for (int i = 0; i < nvocab; i++) {  // (a vocabulary the assignment kernels cannot take leaves its slot empty: k_vlad serves it)
         mmidx_index *a = nullptr;
@@ -171,7 +163,7 @@ int mmidx_vlad_create(int nvocab, const int32_t *ncent, int dl, const double *co
         }
         v->asg.push_back(a);
     }
-    *out = v;
+    *out = v.release();
     return MMIDX_OK;
 }
 
@@ -191,14 +183,8 @@ int mmidx_vlad_set_option(mmidx_vlad *v, const char *name, int value) {
 int mmidx_vlad_destroy(mmidx_vlad *v) {
     if (!v) return MMIDX_OK;
     (void)hipSetDevice(v->device);
-    if (v->d_cb) (void)hipFree(v->d_cb);
     for (mmidx_index *a : v->asg)
         if (a) mmidx_destroy(a);
-    v->ws_nn.release();
-    v->ws_desc.release();
-    v->ws_out.release();
-    v->ws_off.release();
-    if (v->stream) (void)hipStreamDestroy(v->stream);
     delete v;
     return MMIDX_OK;
 }

@@ -11,8 +11,11 @@
 #include <cstddef>
 #include <cstdint>
 #include <deque>
+#include <memory>
 #include <mutex>
 #include <string>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "../../include/mmidx.h"
@@ -35,36 +38,100 @@ MMIDX_HIDDEN void mmidx_clear_error();
 // (the types below stay inside the library: hidden, so that their instantiations add nothing to the exported symbols)
 #pragma GCC visibility push(hidden)
 
+// ---- owners: every device block, pinned block, event and stream of the library is a field or a local of one of these types.  Each
+// is movable and not copyable, reads as the plain handle it holds, and its destructor frees that handle and nothing else: a handle
+// struct needs no release list (members go in reverse order of declaration), and a return between an allocation and its use leaks nothing.
+template <typename H, typename A, hipError_t (*Free)(A)>
+struct Owned {
+    H p{};
+    Owned() = default;
+    Owned(const Owned &) = delete;
+    Owned &operator=(const Owned &) = delete;
+    Owned(Owned &&o) noexcept : p(o.p) { o.p = H{}; }
+    Owned &operator=(Owned &&o) noexcept {
+        if (this != &o) {
+            release();
+            p = o.p;
+            o.p = H{};
+        }
+        return *this;
+    }
+    ~Owned() { release(); }
+    void release() {
+        if (p) (void)Free(p);
+        p = H{};
+    }
+    operator H() const { return p; }
+};
+
+template <typename T>
+constexpr size_t elem_bytes = sizeof(T);
+template <>
+inline constexpr size_t elem_bytes<void> = 1;  // an untyped block is sized in bytes
+
+// a device array of exact size: a handle's persistent table, or the array of one call
+template <typename T>
+struct DevPtr : Owned<T *, void *, hipFree> {
+    hipError_t alloc(size_t n) {  // frees the block held before
+        this->release();
+        return hipMalloc((void **)&this->p, std::max<size_t>(n, 1) * elem_bytes<T>);
+    }
+    hipError_t ensure(size_t n) { return this->p ? hipSuccess : alloc(n); }  // allocate if empty
+    template <typename U>
+    explicit operator U *() const {  // (const unsigned char *)h->d_codes, (__bf16 *)h->d_Ch: the casts a raw pointer allowed
+        return (U *)this->p;
+    }
+};
+
 // a workspace that grows and is released by its owner
 template <typename T>
-struct DevBuf {
-    T *p = nullptr;
+struct DevBuf : Owned<T *, void *, hipFree> {
     size_t cap = 0;  // elements
+    DevBuf() = default;
+    DevBuf(DevBuf &&o) noexcept : Owned<T *, void *, hipFree>(std::move(o)), cap(o.cap) { o.cap = 0; }
+    DevBuf &operator=(DevBuf &&o) noexcept {
+        Owned<T *, void *, hipFree>::operator=(std::move(o));
+        cap = o.cap;
+        o.cap = 0;
+        return *this;
+    }
     hipError_t reserve(size_t n) {
         if (n <= cap) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
+        release();
         size_t want = n + n / 8 + 64;
-        hipError_t e = hipMalloc((void **)&p, want * sizeof(T));
+        hipError_t e = hipMalloc((void **)&this->p, want * sizeof(T));
         if (e == hipSuccess) cap = want;
         return e;
     }
     void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
+        Owned<T *, void *, hipFree>::release();
         cap = 0;
     }
 };
+static_assert(!std::is_copy_constructible<DevBuf<int>>::value && !std::is_copy_constructible<DevPtr<int>>::value, "owners are not copied");
 
-// a device array of one call: exact size, freed on every return path
+// pinned host memory
 template <typename T>
-struct ScopedBuf {
-    T *p = nullptr;
-    ~ScopedBuf() {
-        if (p) (void)hipFree(p);
+struct PinBuf : Owned<T *, void *, hipHostFree> {
+    hipError_t alloc(size_t n, unsigned flags = hipHostMallocDefault) {
+        this->release();
+        return hipHostMalloc((void **)&this->p, std::max<size_t>(n, 1) * elem_bytes<T>, flags);
     }
-    hipError_t alloc(size_t n) { return hipMalloc((void **)&p, std::max<size_t>(n, 1) * sizeof(T)); }
+};
+
+struct Event : Owned<hipEvent_t, hipEvent_t, hipEventDestroy> {
+    hipError_t create(unsigned flags = hipEventDefault) {
+        release();
+        return hipEventCreateWithFlags(&p, flags);
+    }
+};
+static_assert(sizeof(Event) == sizeof(hipEvent_t), "a pool of Event is read as an array of hipEvent_t (take_events)");
+
+struct Stream : Owned<hipStream_t, hipStream_t, hipStreamDestroy> {
+    hipError_t create(unsigned flags = hipStreamNonBlocking) {
+        release();
+        return hipStreamCreateWithFlags(&p, flags);
+    }
 };
 
 #define MMIDX_COMB_MAX_Q 4096   // queries per combined batch; larger requests run alone with direct copies

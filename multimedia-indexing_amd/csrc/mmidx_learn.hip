@@ -179,7 +179,7 @@ int mmidx_kmeans_device(int device, int64_t n, int d, int k, int max_iter, int64
     const size_t nd = (size_t)n * d;
 
     // ---- working copy of the data (normalised attributes: Weka's default distance) --------------------
-    ScopedBuf<double> Xn, mn, mx;
+    DevPtr<double> Xn, mn, mx;
     const double *W = dX;
     std::vector<double> h_mn((size_t)d, 0.0), h_mx((size_t)d, 1.0);
     if (normalize) {
@@ -198,7 +198,7 @@ int mmidx_kmeans_device(int device, int64_t n, int d, int k, int max_iter, int64
     // ---- seeding ----------------------------------------------------------------------------------------
     std::vector<double> Ch((size_t)k * d);
     int k_seed = k;  // centres seeded: fewer than k when default seeding runs out of distinct rows
-    ScopedBuf<double> dC;
+    DevPtr<double> dC;
     HIPCK(dC.alloc((size_t)k * d));
     if (init_centroids) {
         for (int c = 0; c < k; c++)
@@ -218,8 +218,8 @@ int mmidx_kmeans_device(int device, int64_t n, int d, int k, int max_iter, int64
             std::vector<int32_t> perm((size_t)n);
             for (int64_t i = 0; i < n; i++) perm[(size_t)i] = (int32_t)i;
             const int64_t B = std::min<int64_t>(n, std::max<int64_t>(2 * (int64_t)k, 64));
-            ScopedBuf<long long> didx;
-            ScopedBuf<double> drows;
+            DevPtr<long long> didx;
+            DevPtr<double> drows;
             HIPCK(didx.alloc((size_t)B));
             HIPCK(drows.alloc((size_t)B * d));
             std::vector<long long> cand;
@@ -244,9 +244,9 @@ int mmidx_kmeans_device(int device, int64_t n, int d, int k, int max_iter, int64
             }
         } else {
             // k-means++ (Arthur & Vassilvitskii): first centre uniform, the others with probability ~ D^2
-            ScopedBuf<double> mind2, cum;
-            ScopedBuf<long long> dpick;
-            ScopedBuf<unsigned char> tmp;
+            DevPtr<double> mind2, cum;
+            DevPtr<long long> dpick;
+            DevPtr<unsigned char> tmp;
             HIPCK(mind2.alloc((size_t)n));
             HIPCK(cum.alloc((size_t)n));
             HIPCK(dpick.alloc(1));
@@ -277,10 +277,10 @@ int mmidx_kmeans_device(int device, int64_t n, int d, int k, int max_iter, int64
     }
 
     // ---- Lloyd iterations -------------------------------------------------------------------------------
-    ScopedBuf<int32_t> a_old, a_new, iota, sorted_idx, keys_out, counts;
-    ScopedBuf<long long> off;
-    ScopedBuf<u64> changed;
-    ScopedBuf<unsigned char> stmp;
+    DevPtr<int32_t> a_old, a_new, iota, sorted_idx, keys_out, counts;
+    DevPtr<long long> off;
+    DevPtr<u64> changed;
+    DevPtr<unsigned char> stmp;
     HIPCK(a_old.alloc((size_t)n));
     HIPCK(a_new.alloc((size_t)n));
     HIPCK(iota.alloc((size_t)n));
@@ -378,7 +378,7 @@ int mmidx_kmeans_device(int device, int64_t n, int d, int k, int max_iter, int64
     // ---- outputs ------------------------------------------------------------------------------------------
     // squared error in the space the clustering ran in (what SimpleKMeans.getSquaredError reports)
     if (sse_out) {
-        ScopedBuf<double> perr;
+        DevPtr<double> perr;
         HIPCK(perr.alloc((size_t)n));
         HIPCK(hipMemcpyAsync(dC.p, Ch.data(), (size_t)k_eff * d * 8, hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(k_point_sqerr, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, W, dC.p, a_new.p, perr.p, (long long)n, d);
@@ -410,8 +410,8 @@ int mmidx_kmeans(int device, int64_t n, int d, int k, int max_iter, int64_t seed
     if (n < 1 || d < 1 || !X || n > (int64_t)INT32_MAX) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "k-means: n and d must be positive (n < 2^31), data non-null");
     if (mmidx_device_count() < 1) return mmidx_fail(MMIDX_ERR_NO_DEVICE, "no HIP device: libmmidx_hip has no CPU fallback");
     HIPCK(hipSetDevice(device));
-    ScopedBuf<double> dX;
-    ScopedBuf<int32_t> dA;
+    DevPtr<double> dX;
+    DevPtr<int32_t> dA;
     HIPCK(dX.alloc((size_t)n * d));
     HIPCK(dA.alloc((size_t)n));
     HIPCK(hipMemcpy(dX.p, X, (size_t)n * d * 8, hipMemcpyHostToDevice));
@@ -427,16 +427,6 @@ int mmidx_kmeans(int device, int64_t n, int d, int k, int max_iter, int64_t seed
 // ---- the product quantizer in one device-resident call ------------------------------------------------------
 namespace {
 
-// pinned host memory of one call (uploads and read-backs that overlap the stream)
-template <typename T>
-struct PinnedBuf {
-    T *p = nullptr;
-    ~PinnedBuf() {
-        if (p) (void)hipHostFree(p);
-    }
-    hipError_t alloc(size_t n) { return hipHostMalloc((void **)&p, std::max<size_t>(n, 1) * sizeof(T), hipHostMallocDefault); }
-};
-
 struct PlJobResult {
     std::vector<double> cent;  // [k_eff][dsub]
     double sse = 0.0;
@@ -450,15 +440,15 @@ struct PlCtx {
     int m = 0, ks = 0, dsub = 0, DS = 0, max_iter = 0, repeats = 0, G = 0;
     bool normalize = false;
     const double *Y = nullptr, *W = nullptr;  // [m][n][dsub]: the data, and the space the clustering runs in (the normalised copy, or Y itself)
-    ScopedBuf<int32_t> assign, iota, sorted, pick, cnt, ctlB;
-    ScopedBuf<uint32_t> keys_in, keys_out;
-    ScopedBuf<double> mind2, tsum, tinc, prob, Ctab, Cfin, sse;
-    ScopedBuf<PlSlot> slots;
-    ScopedBuf<unsigned char> stmp;
+    DevPtr<int32_t> assign, iota, sorted, pick, cnt, ctlB;
+    DevPtr<uint32_t> keys_in, keys_out;
+    DevPtr<double> mind2, tsum, tinc, prob, Ctab, Cfin, sse;
+    DevPtr<PlSlot> slots;
+    DevPtr<unsigned char> stmp;
     size_t stmp_bytes = 0;
-    PinnedBuf<PlSlot> h_slots;
-    PinnedBuf<int32_t> h_pick0, h_cnt, h_ctlB;
-    PinnedBuf<double> h_prob, h_sse, h_cent;
+    PinBuf<PlSlot> h_slots;
+    PinBuf<int32_t> h_pick0, h_cnt, h_ctlB;
+    PinBuf<double> h_prob, h_sse, h_cent;
 };
 
 template <int DS>
@@ -529,8 +519,6 @@ int pl_run_group(PlCtx &c, int g0, int Gc, std::vector<PlJobResult> &res) {
         HIPCK(hipcub::DeviceRadixSort::SortPairs(nullptr, need, c.keys_in.p, c.keys_out.p, c.iota.p, c.sorted.p, items, 0, bits, st));
         if (need > c.stmp_bytes) {  // (sized for the largest sort; fewer items are not expected to ask for more)
             HIPCK(hipStreamSynchronize(st));
-            HIPCK(hipFree(c.stmp.p));
-            c.stmp.p = nullptr;
             HIPCK(c.stmp.alloc(need));
             c.stmp_bytes = need;
         }
@@ -644,8 +632,8 @@ int mmidx_pq_learn_device(int device, int64_t n, int D, int m, int ks, int max_i
     c.normalize = (flags & MMIDX_KMEANS_NORMALIZE) != 0;
 
     // ---- prep: nearest coarse centroid, residual, transform, sub-space-major; the normalised copy -------------------------------
-    ScopedBuf<double> Y, Yn, mn, mx, d_coarse, d_rot;
-    ScopedBuf<int32_t> d_cell, d_perm;
+    DevPtr<double> Y, Yn, mn, mx, d_coarse, d_rot;
+    DevPtr<int32_t> d_cell, d_perm;
     HIPCK(Y.alloc(nd));
     if (C > 0) {
         HIPCK(d_cell.alloc((size_t)n));
@@ -761,7 +749,7 @@ int mmidx_pq_learn(int device, int64_t n, int D, int m, int ks, int max_iter, in
     if (rc) return rc;
     if (mmidx_device_count() < 1) return mmidx_fail(MMIDX_ERR_NO_DEVICE, "no HIP device: libmmidx_hip has no CPU fallback");
     HIPCK(hipSetDevice(device));
-    ScopedBuf<double> dX;
+    DevPtr<double> dX;
     HIPCK(dX.alloc((size_t)n * D));
     HIPCK(hipMemcpy(dX.p, X, (size_t)n * D * 8, hipMemcpyHostToDevice));
     return mmidx_pq_learn_device(device, n, D, m, ks, max_iter, repeats, flags, dX.p, C, coarse, transform, perm, rot, pq_out, sse_out, seed_out, k_out,

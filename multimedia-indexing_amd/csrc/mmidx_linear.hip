@@ -40,20 +40,20 @@ struct LinStatsAcc {
 
 extern "C" {
 
-struct mmidx_linear {
+struct MMIDX_HIDDEN mmidx_linear {
+    Stream stream;  // first: members are destroyed in reverse order, and everything below was used on it
     mutable std::mutex mu;
     int D = 0, Dp = 0, device = 0;
     int64_t capacity = 0;
     int64_t n = 0, cap = 0;           // rows stored / rows the device arrays have room for
-    double *dX = nullptr;             // [cap][D], arrival order (TDoubleArrayList, Linear.java:45)
-    __bf16 *dXh = nullptr, *dXl = nullptr;  // [cap][Dp]
-    double *dxn = nullptr;            // [cap] |x|^2, rounded up
-    u64 *d_nmax = nullptr;            // bits of the largest |x|^2 so far
+    DevPtr<double> dX;                // [cap][D], arrival order (TDoubleArrayList, Linear.java:45)
+    DevPtr<__bf16> dXh, dXl;          // [cap][Dp]
+    DevPtr<double> dxn;               // [cap] |x|^2, rounded up
+    DevPtr<u64> d_nmax;               // bits of the largest |x|^2 so far
     std::vector<double> X;            // host mirror for the hidden handle, kept only while n <= LIN_SMALL_N
     bool mirror = true;
     mmidx_index *inner = nullptr;
     int64_t inner_n = -1;   // number of vectors the inner handle was built for
-    hipStream_t stream = nullptr;
     hipStream_t last_stream = nullptr;  // a _device call is asynchronous on its caller's stream: the next call on another waits
     bool last_stream_valid = false;
     int opt_exact = 0, opt_qcap = 0, opt_prof = 0;
@@ -82,29 +82,22 @@ void lin_wait_other_stream(mmidx_linear *l, hipStream_t st) {
     l->last_stream_valid = true;
 }
 
-void lin_free_rows(double *X, __bf16 *H, __bf16 *L, double *N) {
-    if (X) (void)hipFree(X);
-    if (H) (void)hipFree(H);
-    if (L) (void)hipFree(L);
-    if (N) (void)hipFree(N);
-}
-
 // room for `need` rows; on failure nothing has changed.  Growth by half: an append copies earlier rows only when the arrays
 // are full, O(1) amortised per row.
 int lin_grow(mmidx_linear *l, int64_t need) {
     if (!l->d_nmax) {
-        HIPCK(hipMalloc((void **)&l->d_nmax, 8));
+        HIPCK(l->d_nmax.alloc(1));
         HIPCK(hipMemset(l->d_nmax, 0, 8));
     }
     if (need <= l->cap) return MMIDX_OK;
     int64_t cap = std::max<int64_t>(std::max<int64_t>(need, l->cap + l->cap / 2), 4096);
     if (l->capacity > 0) cap = std::max<int64_t>(need, std::min<int64_t>(cap, l->capacity));
-    double *nX = nullptr, *nN = nullptr;
-    __bf16 *nH = nullptr, *nL = nullptr;
-    hipError_t e = hipMalloc((void **)&nX, (size_t)cap * l->D * 8);
-    if (e == hipSuccess) e = hipMalloc((void **)&nH, (size_t)cap * l->Dp * 2);
-    if (e == hipSuccess) e = hipMalloc((void **)&nL, (size_t)cap * l->Dp * 2);
-    if (e == hipSuccess) e = hipMalloc((void **)&nN, (size_t)cap * 8);
+    DevPtr<double> nX, nN;
+    DevPtr<__bf16> nH, nL;
+    hipError_t e = nX.alloc((size_t)cap * l->D);
+    if (e == hipSuccess) e = nH.alloc((size_t)cap * l->Dp);
+    if (e == hipSuccess) e = nL.alloc((size_t)cap * l->Dp);
+    if (e == hipSuccess) e = nN.alloc((size_t)cap);
     if (e == hipSuccess && l->n > 0) {
         hipStream_t st = l->stream;
         lin_wait_other_stream(l, st);
@@ -115,15 +108,13 @@ int lin_grow(mmidx_linear *l, int64_t need) {
         if (e == hipSuccess) e = hipStreamSynchronize(st);
     }
     if (e != hipSuccess) {
-        lin_free_rows(nX, nH, nL, nN);
         (void)hipGetLastError();
         return mmidx_fail(MMIDX_ERR_HIP, "Linear: no room for %lld vectors on device %d: %s", (long long)need, l->device, hipGetErrorString(e));
     }
-    lin_free_rows(l->dX, l->dXh, l->dXl, l->dxn);
-    l->dX = nX;
-    l->dXh = nH;
-    l->dXl = nL;
-    l->dxn = nN;
+    l->dX = std::move(nX);
+    l->dXh = std::move(nH);
+    l->dXl = std::move(nL);
+    l->dxn = std::move(nN);
     l->cap = cap;
     return MMIDX_OK;
 }
@@ -239,9 +230,9 @@ int lin_scan_round(mmidx_linear *l, int k, int nq, const double *dQ, int32_t *d_
     hipLaunchKernelGGL(k_lin_reduce, dim3((unsigned)nq), dim3(LIN_NT), rlds, st, l->ws_pk.p, l->ws_pr.p, pcnt, pkept, l->ws_T.p, redo, PC, k1);
     HIPCK(hipGetLastError());
     l->st.rows_scanned += S;
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    Event ev[3];
     if (l->opt_prof)
-        for (int i = 0; i < 3; i++) HIPCK(hipEventCreate(&ev[i]));
+        for (int i = 0; i < 3; i++) HIPCK(ev[i].create());
     // Segments grow geometrically: after `done` rows T[q] is the (k + 1)-th of them, so the next g * done rows leave about
     // g (k + 1) survivors per query; g keeps that a quarter of the pool's spare room.  A segment holds fewer than 2^31 / nq
     // rows, so that the record counter cannot wrap even where every pair survives.
@@ -277,8 +268,6 @@ int lin_scan_round(mmidx_linear *l, int k, int nq, const double *dQ, int32_t *d_
         l->st.rows_scanned += r1 - done;
         done = r1;
     }
-    for (int i = 0; i < 3; i++)
-        if (ev[i]) (void)hipEventDestroy(ev[i]);
     if (rc) return rc;
     hipLaunchKernelGGL(k_lin_answer, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, st, l->ws_pk.p, l->ws_pr.p, pcnt, redo, PC, k, d_iid, d_dist, d_cnt,
                        l->ws_redo.p, redo_cnt, nq);
@@ -389,17 +378,14 @@ int mmidx_linear_create(int D, int64_t capacity, int device, mmidx_linear **out)
     if (ndev < 1) return mmidx_fail(MMIDX_ERR_NO_DEVICE, "no HIP device: libmmidx_hip has no CPU fallback");
     if (device < 0 || device >= ndev) return mmidx_fail(MMIDX_ERR_NO_DEVICE, "device %d outside 0..%d", device, ndev - 1);
     HIPCK(hipSetDevice(device));
-    mmidx_linear *l = new mmidx_linear();
+    std::unique_ptr<mmidx_linear> l(new mmidx_linear());
     l->D = D;
     l->Dp = (D + 31) / 32 * 32;  // the matrix instruction's depth
     l->device = device;
     l->capacity = capacity;
-    const hipError_t e = hipStreamCreateWithFlags(&l->stream, hipStreamNonBlocking);
-    if (e != hipSuccess) {
-        delete l;
-        return mmidx_fail(MMIDX_ERR_HIP, "Linear: no stream on device %d: %s", device, hipGetErrorString(e));
-    }
-    *out = l;
+    const hipError_t e = l->stream.create();
+    if (e != hipSuccess) return mmidx_fail(MMIDX_ERR_HIP, "Linear: no stream on device %d: %s", device, hipGetErrorString(e));
+    *out = l.release();
     return MMIDX_OK;
 }
 
@@ -411,28 +397,6 @@ int mmidx_linear_destroy(mmidx_linear *l) {
         (void)hipDeviceSynchronize();
     }
     if (l->inner) mmidx_destroy(l->inner);
-    lin_free_rows(l->dX, l->dXh, l->dXl, l->dxn);
-    if (l->d_nmax) (void)hipFree(l->d_nmax);
-    l->ws_Q.release();
-    l->ws_d.release();
-    l->ws_cd.release();
-    l->ws_qn.release();
-    l->ws_a.release();
-    l->ws_dmat.release();
-    l->ws_i.release();
-    l->ws_c.release();
-    l->ws_cells.release();
-    l->ws_redo.release();
-    l->ws_ids.release();
-    l->ws_Qh.release();
-    l->ws_Ql.release();
-    l->ws_T.release();
-    l->ws_pk.release();
-    l->ws_rec.release();
-    l->ws_ctr.release();
-    l->ws_u32.release();
-    l->ws_pr.release();
-    if (l->stream) (void)hipStreamDestroy(l->stream);
     delete l;
     return MMIDX_OK;
 }

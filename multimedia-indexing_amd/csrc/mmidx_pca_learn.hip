@@ -259,13 +259,6 @@ __global__ __launch_bounds__(256) void k_pca_finish(const double *__restrict__ V
     if (threadIdx.x == 0) sv[i] = sqrt(lam[i] > 0.0 ? lam[i] : 0.0);
 }
 
-struct Ev {  // a timing event that is destroyed on every return path
-    hipEvent_t e = nullptr;
-    ~Ev() {
-        if (e) (void)hipEventDestroy(e);
-    }
-};
-
 const char *const NONFINITE = "PCA learning: the samples hold non-finite values, or their Gram matrix overflows";
 
 double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
@@ -283,13 +276,13 @@ int launch_gram(bool sym, const double *A, const double *B, const double *muA, c
 
 }  // namespace
 
-struct mmidx_pca_learner {
+struct MMIDX_HIDDEN mmidx_pca_learner {
     std::mutex mu;
     int nc = 0, ss = 0, device = 0;
     int64_t num = 0, count = 0;
-    double *dA = nullptr, *dsum = nullptr;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev_own = nullptr, ev_ext = nullptr;  // order the library's stream and a caller's stream (add_device) on the running sums
+    Stream stream;  // (before what is used on it: members are destroyed in reverse order)
+    DevPtr<double> dA, dsum;
+    Event ev_own, ev_ext;  // order the library's stream and a caller's stream (add_device) on the running sums
 };
 
 namespace {
@@ -329,24 +322,22 @@ int mmidx_pca_learn_create(int nc, int64_t num_samples, int ss, int device, mmid
     if (ndev < 1) return mmidx_fail(MMIDX_ERR_NO_DEVICE, "no HIP device: libmmidx_hip has no CPU fallback");
     if (device < 0 || device >= ndev) return mmidx_fail(MMIDX_ERR_NO_DEVICE, "device outside the visible range");
     HIPCK(hipSetDevice(device));
-    mmidx_pca_learner *l = new mmidx_pca_learner();
+    std::unique_ptr<mmidx_pca_learner, int (*)(mmidx_pca_learner *)> l(new mmidx_pca_learner(), mmidx_pca_learn_destroy);  // (destroy: it waits for the stream)
     l->nc = nc;
     l->ss = ss;
     l->num = num_samples;
     l->device = device;
-    hipError_t e = hipStreamCreateWithFlags(&l->stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&l->ev_own, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&l->ev_ext, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipMalloc((void **)&l->dA, std::max<size_t>((size_t)num_samples * ss, 1) * 8);  // the samples stay resident (A, :109)
-    if (e == hipSuccess) e = hipMalloc((void **)&l->dsum, (size_t)ss * 8);
+    hipError_t e = l->stream.create();
+    if (e == hipSuccess) e = l->ev_own.create(hipEventDisableTiming);
+    if (e == hipSuccess) e = l->ev_ext.create(hipEventDisableTiming);
+    if (e == hipSuccess) e = l->dA.alloc((size_t)num_samples * ss);  // the samples stay resident (A, :109)
+    if (e == hipSuccess) e = l->dsum.alloc((size_t)ss);
     if (e == hipSuccess) e = hipMemsetAsync(l->dsum, 0, (size_t)ss * 8, l->stream);
     if (e == hipSuccess) e = hipEventRecord(l->ev_own, l->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(l->stream);
-    if (e != hipSuccess) {
-        mmidx_pca_learn_destroy(l);
+    if (e != hipSuccess)
         return mmidx_fail(MMIDX_ERR_HIP, "PCA learner: allocation of %lld x %d samples failed: %s", (long long)num_samples, ss, hipGetErrorString(e));
-    }
-    *out = l;
+    *out = l.release();
     return MMIDX_OK;
 }
 
@@ -354,11 +345,6 @@ int mmidx_pca_learn_destroy(mmidx_pca_learner *l) {
     if (!l) return MMIDX_OK;
     (void)hipSetDevice(l->device);
     if (l->stream) (void)hipStreamSynchronize(l->stream);
-    if (l->dA) (void)hipFree(l->dA);
-    if (l->dsum) (void)hipFree(l->dsum);
-    if (l->ev_own) (void)hipEventDestroy(l->ev_own);
-    if (l->ev_ext) (void)hipEventDestroy(l->ev_ext);
-    if (l->stream) (void)hipStreamDestroy(l->stream);
     delete l;
     return MMIDX_OK;
 }
@@ -401,7 +387,7 @@ int mmidx_pca_learn_compute(mmidx_pca_learner *l, double tol, int max_iter, doub
     for (int j = 0; j < ss; j++) h_mu[(size_t)j] = h_mu[(size_t)j] / (double)n;
     if (means_out) memcpy(means_out, h_mu.data(), (size_t)ss * 8);
 
-    ScopedBuf<double> d_mu, d_zero, G, Q, Z, V, ZW, Qt, S, Wd, d_lam, d_res, d_Vt, d_sv;
+    DevPtr<double> d_mu, d_zero, G, Q, Z, V, ZW, Qt, S, Wd, d_lam, d_res, d_Vt, d_sv;
     const size_t sb = (size_t)ss * b, bb = (size_t)b * b;
     HIPCK(d_mu.alloc((size_t)ss));
     HIPCK(d_zero.alloc((size_t)ss));
@@ -421,16 +407,16 @@ int mmidx_pca_learn_compute(mmidx_pca_learner *l, double tol, int max_iter, doub
     HIPCK(hipMemsetAsync(d_zero.p, 0, (size_t)ss * 8, st));
 
     // ---- Gram matrix of the centred samples ----
-    Ev e0, e1;
-    HIPCK(hipEventCreate(&e0.e));
-    HIPCK(hipEventCreate(&e1.e));
-    HIPCK(hipEventRecord(e0.e, st));
+    Event e0, e1;
+    HIPCK(e0.create());
+    HIPCK(e1.create());
+    HIPCK(hipEventRecord(e0, st));
     int rc = launch_gram(true, l->dA, l->dA, d_mu.p, d_mu.p, G.p, n, ss, ss, st);
     if (rc) return rc;
-    HIPCK(hipEventRecord(e1.e, st));
+    HIPCK(hipEventRecord(e1, st));
     HIPCK(hipStreamSynchronize(st));
     float gram_ms = 0.f;
-    HIPCK(hipEventElapsedTime(&gram_ms, e0.e, e1.e));
+    HIPCK(hipEventElapsedTime(&gram_ms, e0, e1));
 
     double t_small = 0.0;  // host time in the b x b solves
     std::vector<double> hS(bb), Linv, lam, Wt;

@@ -212,7 +212,7 @@ int mmidx_linear_reindex(mmidx_linear *src, int64_t iid0, int64_t n, mmidx_pca *
     const int wide = pca ? ncols : *std::max_element(lens, lens + nt);
     int64_t chunk = chunk_rows > 0 ? chunk_rows : std::min<int64_t>(1 << 20, std::max<int64_t>(4096, ((int64_t)1 << 25) / wide)) / TRL_ROWS * TRL_ROWS;
     chunk = std::min(chunk, n);
-    ScopedBuf<double> proj, out[TRL_MAX_T];
+    DevPtr<double> proj, out[TRL_MAX_T];
     double *dY[TRL_MAX_T] = {};
     if (pca) HIPCK(proj.alloc((size_t)chunk * ncols));
     for (int t = 0; t < nt; t++) {

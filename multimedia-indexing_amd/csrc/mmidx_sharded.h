@@ -234,46 +234,27 @@ struct ShardBufs {  // everything on the shard's device
     DevBuf<unsigned char> ecode;
     DevBuf<int32_t> rblk, rcell, riid;  // device-side routing of a round's records (sharded_add_vectors): block counts / offsets, the shard's own records
     DevBuf<unsigned char> rcode;
-    int32_t *pin_nflag = nullptr;  // pinned host words: [0] flagged queries of the round, [1] the round's sequence number
+    PinBuf<int32_t> pin_nflag;  // pinned host words: [0] flagged queries of the round, [1] the round's sequence number
     int32_t seq = 0;
-    ShardDest *pin_dest = nullptr; // pinned host copy of `dest` (what was last uploaded: re-sent only when a pointer changed)
+    PinBuf<ShardDest> pin_dest; // pinned host copy of `dest` (what was last uploaded: re-sent only when a pointer changed)
     int dest_n = 0;
-    hipEvent_t ev_b = nullptr;     // pass B of this shard has been enqueued up to here
+    Event ev_b;     // pass B of this shard has been enqueued up to here
     // the query exchange runs on the shard's SECOND stream (its own communicator), next to the coarse stage of the own slice and,
     // in a call of several rounds, under the previous round's scans.  Per buffer: own slice landed / everybody's landed / the
     // main stream has finished reading it
-    hipEvent_t ev_own[2] = {nullptr, nullptr}, ev_q[2] = {nullptr, nullptr}, ev_free[2] = {nullptr, nullptr};
+    Event ev_own[2], ev_q[2], ev_free[2];
     bool free_valid[2] = {false, false};
-    void release() {
-        for (int i = 0; i < 2; i++) {
-            if (ev_own[i]) (void)hipEventDestroy(ev_own[i]);
-            if (ev_q[i]) (void)hipEventDestroy(ev_q[i]);
-            if (ev_free[i]) (void)hipEventDestroy(ev_free[i]);
-            ev_own[i] = ev_q[i] = ev_free[i] = nullptr;
-        }
-        Q2.release();
-        Q.release(); cdist.release(); T.release(); pd.release(); rpd.release(); odist.release(); tau_own.release(); tau.release();
-        pk.release(); rpk.release(); cells.release(); pc.release(); rpc.release(); oiid.release(); ocnt.release(); flag.release();
-        nflag.release(); rows_own.release(); fq_own.release(); fq.release(); counts.release(); pB.release(); ties.release();
-        tmp.release(); dest.release(); X.release(); ecell.release(); ecode.release();
-        rblk.release(); rcell.release(); riid.release(); rcode.release();
-        if (pin_nflag) (void)hipHostFree(pin_nflag);
-        pin_nflag = nullptr;
-        if (pin_dest) (void)hipHostFree(pin_dest);
-        pin_dest = nullptr;
-        if (ev_b) (void)hipEventDestroy(ev_b);
-        ev_b = nullptr;
-    }
 };
 
 }  // namespace
 
-struct ShardGroup {
+struct MMIDX_HIDDEN ShardGroup {
+    // (members are destroyed in reverse order: the streams stand before the buffers and events used on them)
     int n = 0;
     std::vector<int> dev;
     std::vector<mmidx_index *> sub;
-    std::vector<hipStream_t> st;
-    std::vector<hipStream_t> st2;   // the query exchange's streams
+    std::vector<hipStream_t> st;    // the sub-indexes' own streams
+    std::vector<Stream> st2;        // the query exchange's streams
     std::vector<ncclComm_t> comm2;  // ... and communicators (null: in-process collectives)
     int pipeline = 1;               // option "shard_pipeline": 1 = query exchange on the second stream (overlapped), 0 = everything on one stream
                                     // (default 1 for in-process shards, 0 for two or more physical devices: mmidx_create_sharded)
@@ -1222,13 +1203,11 @@ int sharded_locate(mmidx_index *h, int64_t n, const int32_t *iids, std::vector<i
         int rc = set_device(s);
         if (rc) return rc;
         std::lock_guard<std::mutex> lk(s->mu);
-        int32_t *d_pos = nullptr;
-        void *d_code = nullptr;
+        DevPtr<int32_t> d_pos;
+        DevPtr<void> d_code;
         std::vector<int32_t> pos, cells;
-        rc = lookup_records(s, n, iids, &d_pos, &d_code, pos, cells, true);
+        rc = lookup_records(s, n, iids, d_pos, d_code, pos, cells, true);
         if (rc) return rc;
-        (void)hipFree(d_pos);
-        (void)hipFree(d_code);
         for (int64_t i = 0; i < n; i++)
             if (pos[(size_t)i] >= 0) where[(size_t)i] = r;
     }
@@ -1388,11 +1367,8 @@ void sharded_destroy(mmidx_index *h) {
     for (int r = 0; r < (int)g->buf.size(); r++) {
         (void)hipSetDevice(g->dev[(size_t)r]);
         if (r < (int)g->st.size() && g->st[(size_t)r]) (void)hipStreamSynchronize(g->st[(size_t)r]);
-        if (r < (int)g->st2.size() && g->st2[(size_t)r]) {
-            (void)hipStreamSynchronize(g->st2[(size_t)r]);
-            (void)hipStreamDestroy(g->st2[(size_t)r]);
-        }
-        g->buf[(size_t)r].release();
+        if (r < (int)g->st2.size() && g->st2[(size_t)r]) (void)hipStreamSynchronize(g->st2[(size_t)r]);
+        g->buf[(size_t)r] = ShardBufs();  // (freed with the shard's device current)
     }
     {
         RcclApi *R = (g->rccl || !g->comm.empty() || !g->comm2.empty()) ? rccl_api() : nullptr;
@@ -1447,19 +1423,18 @@ int mmidx_create_sharded(int kind, int D, int m, int ks, int C, int transform, c
         int rc = mmidx_create(kind, D, m, ks, C, transform, perm, rot, devs[r], &g->sub[(size_t)r]);
         if (rc) return bail(rc);
         g->st.push_back(g->sub[(size_t)r]->stream);
-        if (hipSetDevice(devs[r]) != hipSuccess || hipHostMalloc((void **)&g->buf[(size_t)r].pin_nflag, 64) != hipSuccess ||
-            hipHostMalloc((void **)&g->buf[(size_t)r].pin_dest, MMIDX_MAX_SHARDS * sizeof(ShardDest)) != hipSuccess ||
-            hipEventCreateWithFlags(&g->buf[(size_t)r].ev_b, hipEventDisableTiming) != hipSuccess)
+        ShardBufs &b = g->buf[(size_t)r];
+        if (hipSetDevice(devs[r]) != hipSuccess || b.pin_nflag.alloc(16) != hipSuccess || b.pin_dest.alloc(MMIDX_MAX_SHARDS) != hipSuccess ||
+            b.ev_b.create(hipEventDisableTiming) != hipSuccess)
             return bail(mmidx_fail(MMIDX_ERR_HIP, "shard %d: pinned word / event allocation failed", r));
-        hipStream_t s2 = nullptr;
-        if (hipStreamCreateWithFlags(&s2, hipStreamNonBlocking) != hipSuccess) return bail(mmidx_fail(MMIDX_ERR_HIP, "shard %d: second stream", r));
-        g->st2.push_back(s2);
+        Stream s2;
+        if (s2.create() != hipSuccess) return bail(mmidx_fail(MMIDX_ERR_HIP, "shard %d: second stream", r));
+        g->st2.push_back(std::move(s2));
         for (int i = 0; i < 2; i++)
-            if (hipEventCreateWithFlags(&g->buf[(size_t)r].ev_own[i], hipEventDisableTiming) != hipSuccess ||
-                hipEventCreateWithFlags(&g->buf[(size_t)r].ev_q[i], hipEventDisableTiming) != hipSuccess ||
-                hipEventCreateWithFlags(&g->buf[(size_t)r].ev_free[i], hipEventDisableTiming) != hipSuccess)
+            if (b.ev_own[i].create(hipEventDisableTiming) != hipSuccess || b.ev_q[i].create(hipEventDisableTiming) != hipSuccess ||
+                b.ev_free[i].create(hipEventDisableTiming) != hipSuccess)
                 return bail(mmidx_fail(MMIDX_ERR_HIP, "shard %d: event allocation failed", r));
-        memset(g->buf[(size_t)r].pin_nflag, 0, 64);
+        memset(b.pin_nflag, 0, 64);
     }
     // every shard stores pass B's lists into the owners' buffers and (in-process collectives) reads its peers': peer access
     for (int i = 0; i < n_dev; i++)
