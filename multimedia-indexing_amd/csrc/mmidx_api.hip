@@ -1264,7 +1264,7 @@ int launch_passa_q(mmidx_index *h, const ScanParams &P, const SearchPlan &pl, lo
     if (const int rc = reserve_fb(h, nfb, st)) return rc;
     // the (query, probe 0) pairs by cell, groups of <= 4
     if (const int rc = sort_pairs_by_cell(h, P, nq, st, [&] {
-            hipLaunchKernelGGL(k_q_scan_groups, dim3(1), dim3(1024), 0, st, h->ws_pcount.p, C, G, h->ws_pstart.p, h->ws_pcursor.p, h->ws_gdesc.p, h->ws_gfb.p);
+            hipLaunchKernelGGL(k_q_scan_groups, dim3(1), dim3(1024), 0, st, h->ws_pcount.p, C, h->ws_pstart.p, h->ws_pcursor.p, h->ws_gdesc.p, h->ws_gfb.p);
         }))
         return rc;
     const HandBack hb(h->ws_fb, 0, nfb);
@@ -1283,8 +1283,9 @@ int launch_passa_q(mmidx_index *h, const ScanParams &P, const SearchPlan &pl, lo
     QP.pmax = h->rmax;
     QP.timing = nullptr;
     const QLds L(h->m, h->D);
-    // grid: the host's upper bound of the group count (the blocks beyond the device-side count leave at once)
-    const unsigned grid = (unsigned)((std::min<size_t>(max_groups, (size_t)nq) + 7 + 7) & ~(size_t)7);  // (eight ranges of ceil(groups / 8): k_scan_q's XCD map)
+    // grid: the host's upper bound of the group count (the blocks beyond the device-side count leave at once); block b takes
+    // gdesc[b], which k_q_scan_groups wrote largest groups first
+    const unsigned grid = (unsigned)((std::min<size_t>(max_groups, (size_t)nq) + 7 + 7) & ~(size_t)7);
     const int rc = for_dsub(h->dsub, [&](auto ds) {  // (the table is addressed from LDS address 0, byte_x8)
         return launch_grid<k_scan_q<16, decltype(ds)::value>>(QP, dim3(grid), 256, L.total, st, StaticLds::fail, "k_scan_q");
     });

@@ -83,6 +83,7 @@ struct QParams {
 typedef unsigned int q_u32x2 __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) const q_u32x2 lds_cuint2;
 typedef __attribute__((address_space(3))) const unsigned int lds_cu32;
+typedef __attribute__((address_space(3))) const unsigned short lds_cu16;
 
 // LDS layout, shared by host (size) and device (offsets)
 struct QLds {
@@ -153,11 +154,17 @@ __device__ __forceinline__ double wave_sum_f64(double x) {
 }
 
 // K3q's pair sort, middle step: the exclusive prefix of the per-cell pair counts (start[], cursor[] = 0: k_pair_scan's work) AND the
-// groups of <= G pairs per cell (gdesc[], their number: k_group_build's work) in ONE single-block launch -- each of the two walks the
-// same C counters and costs ~12 us of latency on its own.  It leaves the counters ZEROED.
-__global__ __launch_bounds__(1024) void k_q_scan_groups(int32_t *__restrict__ cnt, int C, int G, int32_t *__restrict__ start, int32_t *__restrict__ cursor,
+// groups of <= G = MMIDX_Q_G pairs per cell (gdesc[], their number: k_group_build's work) in ONE single-block launch -- each of the
+// two walks the same C counters and costs ~12 us of latency on its own.  It leaves the counters ZEROED.
+// The descriptors are emitted BY SIZE: the groups of three or four pairs first, then those of two, then those of one, each class in
+// cell order (a list's full groups stay neighbours) -- three group counts per thread and three prefix sums instead of one.  k_scan_q
+// takes block b's group from gdesc[b]: the costliest bodies start first and the kernel drains on the cheapest (Q_NO_SIZE_ORDER: one
+// class, the cell order).
+__global__ __launch_bounds__(1024) void k_q_scan_groups(int32_t *__restrict__ cnt, int C, int32_t *__restrict__ start, int32_t *__restrict__ cursor,
                                                         int4 *__restrict__ gdesc, int32_t *__restrict__ n_groups) {
-    __shared__ u32 s_wa[16], s_wb[16];
+    constexpr int G = MMIDX_Q_G;  // (a constant: n / G and n % G are a shift and a mask, in code that runs once from a cold cache)
+    static_assert(G >= 3, "a full group belongs to the first class");
+    __shared__ uint4 s_w[16];  // per wave: {pairs, groups of class 0, 1, 2}
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int per = (C + 1023) / 1024;
     const int lo = tid * per, hi = (lo + per < C) ? lo + per : C;
@@ -165,40 +172,67 @@ __global__ __launch_bounds__(1024) void k_q_scan_groups(int32_t *__restrict__ cn
     // the counters in registers measured 20 us against 16 for the plain loops.  Where every thread has a whole multiple of four
     // counters (C = 4096 k: the headline's 8192 cells) they are read as 16-byte vectors, two in flight.
     const bool vec = C == per * 1024 && (per & 3) == 0;
-    auto groups_of = [&](const int n) -> u32 { return ((u32)n + (u32)G - 1u) / (u32)G; };
-    u32 sa = 0, sb = 0;
+    // a cell's n pairs: n / G full groups and one of the remainder r; class 0 = three or more pairs, 1 = two, 2 = one
+    u32 sa = 0, s0 = 0, s1 = 0, s2 = 0;
+    auto count = [&](const int n) {
+        const u32 full = (u32)n / (u32)G, r = (u32)n % (u32)G;
+        sa += (u32)n;
+#ifdef Q_NO_SIZE_ORDER
+        s0 += full + (r ? 1u : 0u);
+#else
+        s0 += full + (r >= 3u ? 1u : 0u);
+        s1 += r == 2u ? 1u : 0u;
+        s2 += r == 1u ? 1u : 0u;
+#endif
+    };
     if (vec) {
         const int4 *p4 = (const int4 *)(cnt + lo);
 #pragma unroll 2
         for (int i4 = 0; i4 < per / 4; i4++) {
             const int4 a4 = p4[i4];
-            sa += (u32)a4.x + (u32)a4.y + (u32)a4.z + (u32)a4.w;
-            sb += groups_of(a4.x) + groups_of(a4.y) + groups_of(a4.z) + groups_of(a4.w);
+            count(a4.x);
+            count(a4.y);
+            count(a4.z);
+            count(a4.w);
         }
     } else {
-        for (int c = lo; c < hi; c++) {
-            const int n = cnt[c];
-            sa += (u32)n;
-            sb += groups_of(n);
-        }
+        for (int c = lo; c < hi; c++) count(cnt[c]);
     }
-    const u32 ia = wave_incl_scan_u32(sa), ib = wave_incl_scan_u32(sb);
-    if (lane == 63) {
-        s_wa[wv] = ia;
-        s_wb[wv] = ib;
-    }
+    const u32 ia = wave_incl_scan_u32(sa), i0 = wave_incl_scan_u32(s0), i1 = wave_incl_scan_u32(s1), i2 = wave_incl_scan_u32(s2);
+    if (lane == 63) s_w[wv] = make_uint4(ia, i0, i1, i2);
     __syncthreads();
-    u32 ba = 0, bb = 0;
+    u32 ba = 0, b0 = 0, b1 = 0, b2 = 0, t0 = 0, t1 = 0, t2 = 0;  // b: the waves before this one; t: every wave
 #pragma unroll
     for (int i = 0; i < 16; i++) {
-        ba += (i < wv) ? s_wa[i] : 0u;
-        bb += (i < wv) ? s_wb[i] : 0u;
+        const uint4 w = s_w[i];
+        ba += (i < wv) ? w.x : 0u;
+        b0 += (i < wv) ? w.y : 0u;
+        b1 += (i < wv) ? w.z : 0u;
+        b2 += (i < wv) ? w.w : 0u;
+        t0 += w.y;
+        t1 += w.z;
+        t2 += w.w;
     }
-    u32 ra = ba + ia - sa, rb = bb + ib - sb;  // exclusive prefixes of this thread's range
+    // exclusive prefixes of this thread's range: pairs; groups of each class, behind the classes before it
+    u32 ra = ba + ia - sa, r0 = b0 + i0 - s0, r1 = t0 + b1 + i1 - s1, r2 = t0 + t1 + b2 + i2 - s2;
     auto emit = [&](const int c, const int n) {
         start[c] = (int32_t)ra;
         cursor[c] = 0;
-        for (int o = 0; o < n; o += G) gdesc[rb++] = make_int4(c, (int)ra + o, (n - o < G) ? n - o : G, 0);
+        int o = 0;
+        for (; o + G <= n; o += G) gdesc[r0++] = make_int4(c, (int)ra + o, G, 0);
+        const int r = n - o;
+        if (r) {
+#ifdef Q_NO_SIZE_ORDER
+            const u32 at = r0++;
+#else
+            // (every select against a constant: a select BETWEEN the three counters sent all of them to scratch memory, 38 us)
+            const u32 at = (r >= 3 ? r0 : 0u) + (r == 2 ? r1 : 0u) + (r == 1 ? r2 : 0u);
+            r0 += r >= 3 ? 1u : 0u;
+            r1 += r == 2 ? 1u : 0u;
+            r2 += r == 1 ? 1u : 0u;
+#endif
+            gdesc[at] = make_int4(c, (int)ra + o, r, 0);
+        }
         ra += (u32)n;
     };
     // (the counters are left zeroed: pass B's pair sort counts in the same array and finds it clean, no memset in between)
@@ -224,7 +258,7 @@ __global__ __launch_bounds__(1024) void k_q_scan_groups(int32_t *__restrict__ cn
     if (tid == 1023) {
         cnt[C] = 0;  // (the pairs' total, k_a1_pair_count's: k_pair_scan leaves at once when pass B's sort finds it zero)
         start[C] = (int32_t)(ba + ia);
-        *n_groups = (int32_t)(bb + ib);
+        *n_groups = (int32_t)(t0 + t1 + t2);
     }
 }
 
@@ -233,10 +267,15 @@ __global__ __launch_bounds__(1024) void k_q_scan_groups(int32_t *__restrict__ cn
 #else
 #define Q_T(n) do {} while (0)
 #endif
-// One group.  GA = the queries the block is compiled for: 4, or 2 for a group of one or two pairs (six in ten at the headline batch:
-// two queries per list on average) -- half the table (4-byte entries, ds_read_b32), half the insertions, half the table's arithmetic.
-template <int M, int DSUB, int GA>
+// One group.  GT = the table's width in queries: entries of 8 bytes (ds_read_b64), of 4 (ds_read_b32: half the table, half its
+// arithmetic) or of 2 (ds_read_u16, 512-byte rows, built with scalar fp32).  GA <= GT = the queries the body is compiled for: their
+// insertions, selections and slots.  <4, 4> and <2, 2> take any group of up to GA pairs; <1, 1> and <4, 3> (the fourth column is
+// computed for nothing: the packed arithmetic has it for free) are entered with EXACTLY GA pairs, the count is a constant there.
+// At the headline batch (two queries per list on average) three groups in ten hold one pair, three two, two three.
+template <int M, int DSUB, int GT, int GA>
 __device__ __forceinline__ void q_scan_group(const QParams &QP, const int4 gd, unsigned char *smem) {
+    static_assert((GT == 1 || GT == 2 || GT == 4) && GA >= 1 && GA <= GT, "table widths: one, two or four queries");
+    constexpr bool EXACT = GA != GT || GT == 1;  // entered with exactly GA pairs
     constexpr int G = MMIDX_Q_G, NT = 256, WV = 4, U = MMIDX_Q_U, HKQ = MMIDX_Q_HKQ, NS = MMIDX_Q_SLOTS;
     static_assert(G == WV, "wave i takes query i in the selection");
     static_assert(M * 2048 >= G * MMIDX_Q_HKQ * 8, "the candidates' exact sums re-use the table");
@@ -259,7 +298,7 @@ __device__ __forceinline__ void q_scan_group(const QParams &QP, const int4 gd, u
     u32 *s_cut = (u32 *)(smem + L.misc) + 24;      // [24..27]: a* + M + 1 per query (17 at M = 16)
     u32 *cent = (u32 *)(smem + L.cent);            // [G][HKQ]
 
-    const int cell = gd.x, ng = gd.z;
+    const int cell = gd.x, ng = EXACT ? GA : gd.z;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
 #ifdef Q_TIMING
     unsigned long long qt_last = __builtin_readcyclecounter();
@@ -349,45 +388,66 @@ __device__ __forceinline__ void q_scan_group(const QParams &QP, const int4 gd, u
     // else converted from the fp64 residuals on the way (the rescue's rebuild, the copies' place taken: the same values, the same table)
     auto calc_rows = [&](const q_f2 (&p)[Q_TU][DSUB / 2], const int s0, auto from_lds) {
         constexpr bool FROM_LDS = decltype(from_lds)::value;
-        q_f2 inv2[GA / 2];
+        if constexpr (GT == 1) {
+            // one query: the packed form's operations one half at a time, in its order (v_sub_f32, v_fma_f32, v_mul_f32: the same
+            // roundings, the same q), u16 entries in 512-byte rows
+            const float inv = (float)s_inv[0];
 #pragma unroll
-        for (int h = 0; h < GA / 2; h++) inv2[h] = q_f2{(float)s_inv[2 * h], (float)s_inv[2 * h + 1]};
+            for (int j = 0; j < Q_TU; j++) {
+                const int s = s0 + j;
+                float acc = 0.0f;
 #pragma unroll
-        for (int j = 0; j < Q_TU; j++) {
-            const int s = s0 + j;
-            q_f2 acc[GA / 2];
+                for (int t = 0; t < DSUB; t++) {
+                    float rv;
+                    if constexpr (FROM_LDS) rv = r32[(size_t)(s * DSUB + t) * 4];
+                    else rv = (float)s_r[s * DSUB + t];
+                    const float df = rv - ((t & 1) ? p[j][t >> 1].y : p[j][t >> 1].x);
+                    acc = __builtin_fmaf(df, df, acc);
+                }
+                const float x = acc * inv;  // >= 0 (or +inf: saturated; NaN -- inf x 0, a flagged query -- gives 4095)
+                *(unsigned short *)(smem + (size_t)s * 512 + (size_t)tid * 2) = (unsigned short)(u32)__builtin_fminf(x, 4095.0f);
+            }
+        } else {
+            q_f2 inv2[GT / 2];
 #pragma unroll
-            for (int h = 0; h < GA / 2; h++) acc[h] = q_f2{0.0f, 0.0f};
+            for (int h = 0; h < GT / 2; h++) inv2[h] = q_f2{(float)s_inv[2 * h], (float)s_inv[2 * h + 1]};
 #pragma unroll
-            for (int t = 0; t < DSUB; t++) {
-                q_f2 rv[GA / 2];
-                if constexpr (FROM_LDS) {
-                    if constexpr (GA == 4) {
-                        const q_f4 r4 = *(const q_f4 *)(r32 + (size_t)(s * DSUB + t) * 4);
-                        rv[0] = q_f2{r4.x, r4.y};
-                        rv[1] = q_f2{r4.z, r4.w};
+            for (int j = 0; j < Q_TU; j++) {
+                const int s = s0 + j;
+                q_f2 acc[GT / 2];
+#pragma unroll
+                for (int h = 0; h < GT / 2; h++) acc[h] = q_f2{0.0f, 0.0f};
+#pragma unroll
+                for (int t = 0; t < DSUB; t++) {
+                    q_f2 rv[GT / 2];
+                    if constexpr (FROM_LDS) {
+                        if constexpr (GT == 4) {
+                            const q_f4 r4 = *(const q_f4 *)(r32 + (size_t)(s * DSUB + t) * 4);
+                            rv[0] = q_f2{r4.x, r4.y};
+                            rv[1] = q_f2{r4.z, r4.w};
+                        } else {
+                            rv[0] = *(const q_f2 *)(r32 + (size_t)(s * DSUB + t) * 4);
+                        }
                     } else {
-                        rv[0] = *(const q_f2 *)(r32 + (size_t)(s * DSUB + t) * 4);
+#pragma unroll
+                        for (int h = 0; h < GT / 2; h++) rv[h] = q_f2{(float)s_r[(size_t)(2 * h) * D + s * DSUB + t], (float)s_r[(size_t)(2 * h + 1) * D + s * DSUB + t]};
                     }
-                } else {
 #pragma unroll
-                    for (int h = 0; h < GA / 2; h++) rv[h] = q_f2{(float)s_r[(size_t)(2 * h) * D + s * DSUB + t], (float)s_r[(size_t)(2 * h + 1) * D + s * DSUB + t]};
+                    for (int h = 0; h < GT / 2; h++) {
+                        const q_f2 df = (t & 1) ? q_pk_sub_hi(rv[h], p[j][t >> 1]) : q_pk_sub_lo(rv[h], p[j][t >> 1]);
+                        acc[h] = q_pk_fma(df, df, acc[h]);
+                    }
                 }
+                u32 qv[GT];
 #pragma unroll
-                for (int h = 0; h < GA / 2; h++) {
-                    const q_f2 df = (t & 1) ? q_pk_sub_hi(rv[h], p[j][t >> 1]) : q_pk_sub_lo(rv[h], p[j][t >> 1]);
-                    acc[h] = q_pk_fma(df, df, acc[h]);
+                for (int h = 0; h < GT / 2; h++) {
+                    const q_f2 x = q_pk_mul(acc[h], inv2[h]);  // >= 0 (or +inf: saturated)
+                    qv[2 * h] = (u32)__builtin_fminf(x.x, 4095.0f);  // (a NaN -- inf x 0, a flagged query's column -- gives 4095)
+                    qv[2 * h + 1] = (u32)__builtin_fminf(x.y, 4095.0f);
                 }
+                if constexpr (GT == 4) *(uint2 *)(smem + (size_t)s * 2048 + (size_t)tid * 8) = make_uint2(qv[0] | (qv[1] << 16), qv[2] | (qv[3] << 16));
+                else *(u32 *)(smem + (size_t)s * 1024 + (size_t)tid * 4) = qv[0] | (qv[1] << 16);
             }
-            u32 qv[GA];
-#pragma unroll
-            for (int h = 0; h < GA / 2; h++) {
-                const q_f2 x = q_pk_mul(acc[h], inv2[h]);  // >= 0 (or +inf: saturated)
-                qv[2 * h] = (u32)__builtin_fminf(x.x, 4095.0f);  // (a NaN -- inf x 0, a flagged query's column -- gives 4095)
-                qv[2 * h + 1] = (u32)__builtin_fminf(x.y, 4095.0f);
-            }
-            if constexpr (GA == 4) *(uint2 *)(smem + (size_t)s * 2048 + (size_t)tid * 8) = make_uint2(qv[0] | (qv[1] << 16), qv[2] | (qv[3] << 16));
-            else *(u32 *)(smem + (size_t)s * 1024 + (size_t)tid * 4) = qv[0] | (qv[1] << 16);
         }
     };
     auto build_table = [&](auto from_lds) {
@@ -418,12 +478,14 @@ __device__ __forceinline__ void q_scan_group(const QParams &QP, const int4 gd, u
         hi = 0;
 #pragma unroll
         for (int s = 0; s < M; s++) {
-            if constexpr (GA == 4) {
+            if constexpr (GT == 4) {
                 const q_u32x2 e = *(lds_cuint2 *)(size_t)(q_byte_shl<3>(cv.wd[s >> 2], s & 3) + (u32)s * 2048u);
                 lo += e.x;
                 hi += e.y;
-            } else {
+            } else if constexpr (GT == 2) {
                 lo += *(lds_cu32 *)(size_t)(q_byte_shl<2>(cv.wd[s >> 2], s & 3) + (u32)s * 1024u);
+            } else {
+                lo += (u32) * (lds_cu16 *)(size_t)(q_byte_shl<1>(cv.wd[s >> 2], s & 3) + (u32)s * 512u);
             }
         }
     };
@@ -446,10 +508,16 @@ __device__ __forceinline__ void q_scan_group(const QParams &QP, const int4 gd, u
             asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(r) : "v"(mask), "v"(a), "s"(st));
             return r;
         };
-        const u32 k0 = inb ? ((lo << 16) | step) : 0xFFFFFFFFu, k1 = inb ? bfi(lo, step) : 0xFFFFFFFFu;
-        insert(slot[0], k0);
-        insert(slot[1], k1);
-        if constexpr (GA == 4) {
+        if constexpr (GA == 1) {
+            insert(slot[0], inb ? ((lo << 16) | step) : 0xFFFFFFFFu);
+        } else {
+            const u32 k0 = inb ? ((lo << 16) | step) : 0xFFFFFFFFu, k1 = inb ? bfi(lo, step) : 0xFFFFFFFFu;
+            insert(slot[0], k0);
+            insert(slot[1], k1);
+        }
+        if constexpr (GA == 3) {
+            insert(slot[2], inb ? ((hi << 16) | step) : 0xFFFFFFFFu);
+        } else if constexpr (GA == 4) {
             const u32 k2 = inb ? ((hi << 16) | step) : 0xFFFFFFFFu, k3 = inb ? bfi(hi, step) : 0xFFFFFFFFu;
             insert(slot[2], k2);
             insert(slot[3], k3);
@@ -524,6 +592,28 @@ __device__ __forceinline__ void q_scan_group(const QParams &QP, const int4 gd, u
         bool bad = false;
         if (nvalid >= (u32)P.K1) {
             u32 lo_a = 0, hi_a = 0xFFFEu;  // smallest A with at least K1 values <= A
+#ifndef Q_FULL_BISECT
+            // A narrower bracket from the lanes' minima.  A lane's first slot is the smallest of its values, and dwords 0 .. 127 of
+            // the query's values (kk[0], kk[1]) are the 256 first slots.  INVARIANT of the loop: at least K1 values are <= hi_a, and
+            // no A < lo_a has K1 values <= A.  With at least K1 valid lane minima both hold for [smallest, largest] of them: K1
+            // minima are <= the largest, and no value at all lies under the smallest.  (A real sum is <= 16 x 4095 < 0xFFFE.)
+            {
+                const u32 m0 = kk[0] & 0xFFFFu, m1 = kk[0] >> 16, m2 = kk[1] & 0xFFFFu, m3 = kk[1] >> 16;
+                const u32 nmin = (u32)__popcll(__builtin_amdgcn_ballot_w64(m0 != 0xFFFFu)) + (u32)__popcll(__builtin_amdgcn_ballot_w64(m1 != 0xFFFFu)) +
+                                 (u32)__popcll(__builtin_amdgcn_ballot_w64(m2 != 0xFFFFu)) + (u32)__popcll(__builtin_amdgcn_ballot_w64(m3 != 0xFFFFu));
+                if (nmin >= (u32)P.K1) {  // wave-uniform
+                    auto top = [](const u32 v) { return v == 0xFFFFu ? 0u : v; };  // (an empty lane: no part in the maximum)
+                    u32 mn = min(min(m0, m1), min(m2, m3)), mx = max(max(top(m0), top(m1)), max(top(m2), top(m3)));
+#pragma unroll
+                    for (int off = 32; off > 0; off >>= 1) {
+                        mn = min(mn, (u32)__shfl_xor((int)mn, off));
+                        mx = max(mx, (u32)__shfl_xor((int)mx, off));
+                    }
+                    lo_a = mn;
+                    hi_a = min(mx, 0xFFFEu);
+                }
+            }
+#endif
             while (lo_a < hi_a) {
                 const u32 mid = lo_a + ((hi_a - lo_a) >> 1);
                 u32 c = 0;
@@ -791,15 +881,24 @@ __device__ __forceinline__ void q_scan_group(const QParams &QP, const int4 gd, u
 template <int M, int DSUB>
 __global__ __launch_bounds__(256, Q_WPS) void k_scan_q(const QParams QP) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    // block -> group, in order.  (Dealing the groups to the XCDs in eight contiguous ranges -- so that the two to four blocks of one list
+    // block -> group, in the order of gdesc[]: k_q_scan_groups puts the groups of three and four pairs first, then those of two, then
+    // those of one, so that the blocks resident at one time run one body and the kernel's tail drains on its cheapest blocks.  (Dealing the groups to the XCDs in eight contiguous ranges -- so that the two to four blocks of one list
     // share an L2 -- was measured: 0.765 against 0.750 ms per 7525 groups, 3.52 against 3.47 ms per 35796; the kernel is not bound by
     // the code stream, and neighbouring blocks in one phase of the kernel on one XCD cost more than the L2 hits bring.)
     const int grp = (int)blockIdx.x;
     if (grp >= *QP.n_groups) return;
     const int4 gd = QP.gdesc[grp];
-#ifndef Q_NO_GA2
-    if (gd.z <= 2) q_scan_group<M, DSUB, 2>(QP, gd, smem);
+#ifndef Q_NO_GA1
+    if (gd.z == 1) q_scan_group<M, DSUB, 1, 1>(QP, gd, smem);
     else
 #endif
-        q_scan_group<M, DSUB, 4>(QP, gd, smem);
+#ifndef Q_NO_GA2
+    if (gd.z <= 2) q_scan_group<M, DSUB, 2, 2>(QP, gd, smem);
+    else
+#endif
+#ifndef Q_NO_GA3
+    if (gd.z == 3) q_scan_group<M, DSUB, 4, 3>(QP, gd, smem);
+    else
+#endif
+        q_scan_group<M, DSUB, 4, 4>(QP, gd, smem);
 }

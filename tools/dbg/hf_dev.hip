@@ -56,9 +56,11 @@ int main(int argc, char **argv) {
     std::vector<double> coarse((size_t)C * D), Q((size_t)nq * D), pqT((size_t)M * dsub * ks);
     for (auto &v : coarse) v = N01(rng);
     for (auto &v : pqT) v = 0.15 * N01(rng);
+    // argv[3] = g > 0: exactly g queries per list (nq <= g C), every group of one size -- one body of K3q alone
+    const int per_list = argc > 3 ? atoi(argv[3]) : 0;
     std::vector<int32_t> cells(nq);
     for (int q = 0; q < nq; q++) {
-        cells[q] = (int32_t)(rng() % C);
+        cells[q] = per_list > 0 ? (int32_t)((q / per_list) % C) : (int32_t)(rng() % C);
         for (int j = 0; j < D; j++) Q[(size_t)q * D + j] = coarse[(size_t)cells[q] * D + j] + HRES * N01(rng);
     }
     double *d_coarse, *d_Q, *d_pqT;
@@ -187,7 +189,16 @@ int main(int argc, char **argv) {
             for (int o = i; o < j; o += MMIDX_Q_G) gdesc.push_back(make_int4(cells[order[i]], o, std::min(MMIDX_Q_G, j - o), 0));
             i = j;
         }
+#ifndef Q_NO_SIZE_ORDER
+        // k_q_scan_groups' order: three and four pairs, then two, then one; cell order within a class
+        std::stable_sort(gdesc.begin(), gdesc.end(), [](const int4 &a, const int4 &b) { return std::min(a.z, 3) > std::min(b.z, 3); });
+#endif
         const int ngr = (int)gdesc.size();
+        {
+            int bysz[MMIDX_Q_G + 1] = {};
+            for (const int4 &g : gdesc) bysz[g.z]++;
+            printf("groups of 1 / 2 / 3 / 4 pairs: %d / %d / %d / %d\n", bysz[1], bysz[2], bysz[3], bysz[4]);
+        }
         std::vector<double> pq((size_t)M * ks * dsub), pqstat((size_t)M * dsub + M, 0.0);
         for (int s = 0; s < M; s++)
             for (int j = 0; j < ks; j++) {
