@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Randomised differential test: random small IVFPQ / PQ configurations through the HIP path and through the CPU oracle
 (checker), ids and distance bits compared, ties included (the oracle replays the bounded queue).  Flat PQ draws with byte codes
-also make one call by internal id (symmetric distances, mmidx_search_sdc) under the same options.
+also make one call by internal id (symmetric distances, mmidx_search_sdc) under the same options.  One draw in five multiplies the
+whole problem -- base, centroids, codebook, queries -- by `mag`, a scale at which some fp32 filter of the search path must hand over
+to an exact kernel (tests/test_passb_bound_cpu.py, tests/test_coarse_bound_cpu.py).
 
     python tests/fuzz_parity.py [cases] [seed]
 """
@@ -76,7 +78,10 @@ for case in range(cases):
         paq = 1
     # the oracle's encoder is one thread ((C + ks) x D fp64 triples per vector): keep a case near a second of it
     n = max(1, min(n, int(1.5e9 / ((C + ks) * D))))
-    desc = dict(kind=kind, D=D, m=m, ks=ks, n=n, k=k, C=C, w=w, tr=tr, dup=dup, hist=hist, v1=v1, wide=wide, nogrp=nogrp, fused=fused, union=union, spre=spre, nomf=nomf, nosplit=nosplit, mfsub=mfsub, mfq=mfq, kcv1=kcv1, wsel=wsel, pam=pam, pamw=pamw, paq=paq)
+    # the magnitude of the whole problem, from a generator of its own: the cases keep the shapes and options they had before it
+    mrng = np.random.default_rng([int(sys.argv[2]) if len(sys.argv) > 2 else 0, case])
+    mag = 1.0 if mrng.random() < 0.8 else float(mrng.choice([1e-12, 1e-16, 1e-22, 1e14, 1e19]))
+    desc = dict(kind=kind, D=D, m=m, ks=ks, n=n, k=k, C=C, w=w, tr=tr, dup=dup, hist=hist, v1=v1, wide=wide, nogrp=nogrp, fused=fused, union=union, spre=spre, nomf=nomf, nosplit=nosplit, mfsub=mfsub, mfq=mfq, kcv1=kcv1, wsel=wsel, pam=pam, pamw=pamw, paq=paq, mag=mag)
     try:
         nb = min(n, 3000)
         if kind == "ivfpq":
@@ -86,6 +91,11 @@ for case in range(cases):
         base = rng.standard_normal((n, D)) * 0.6 + (p["coarse"][rng.integers(0, C, n)] if kind == "ivfpq" else 0.0)
         if dup and n > 10:
             base[n // 2:] = base[:n - n // 2]
+        base1 = base  # (unit scale: the queries are drawn from it below, then scaled like everything else)
+        base = base1 * mag
+        p["pq"] = p["pq"] * mag
+        if kind == "ivfpq":
+            p["coarse"] = p["coarse"] * mag
         perm = o.random_permutation(1, D) if tr == 2 else None
         rot = np.linalg.qr(rng.standard_normal((D, D)))[0] if tr == 1 else None
         if kind == "ivfpq":
@@ -127,7 +137,7 @@ for case in range(cases):
         ix.indexVectors([str(i) for i in range(half, n)], base[half:])
         ref.add_vectors(base)
         nself = 24 if q_shape else 4  # (K3q: several queries per list -- groups of one to four pairs, several groups per list)
-        Q = np.concatenate([base[rng.integers(0, n, nself)] + 0.01 * rng.standard_normal((nself, D)), p["queries"][:3]])
+        Q = np.concatenate([base1[rng.integers(0, n, nself)] + 0.01 * rng.standard_normal((nself, D)), p["queries"][:3]]) * mag
         got = ix.search_batch(k, Q)
         want = ref.search_batch(Q, k)
         # ids, counts and distance BITS, rotation included: the kernels rotate in the oracle's order (sequential over the
