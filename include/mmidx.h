@@ -542,6 +542,7 @@ int mmidx_set_profiling(mmidx_index *h, int enabled);
  *   "mfma_kc_v1": K3mk without LDS-DMA (k_scan_mfma_kc) also where k_scan_mfma_kc2 applies
  *   "mfma_kc_tpw": code tiles per wave of K3mk: 8 (default) or 16
  *   "flat_chunk": codes per chunk of a flat PQ list, from 4096 (0 = sized from the batch)
+ *   "sub_batch": > 0: at most this many queries per sub-batch of a search call (0 = from the memory caps alone); tests split small calls
  * A sharded handle passes these on to every shard and has options of its own (csrc/mmidx_sharded.h):
  *   "shard_exchange": 0 = partial lists stored into the owners' buffers over xGMI, 1 = ncclSend / ncclRecv
  *   "tie_slots": flagged queries per owner and replay round (0 = no replay)

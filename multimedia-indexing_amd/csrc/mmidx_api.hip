@@ -87,7 +87,7 @@ struct Switches {
     int smin_pre = -1, smin_bf16 = 1, smin_valu = 0;
     int no_mfma = 0, no_grp = 0, no_union = 0, no_split_table = 0, passb_small = 1, passb_main_grid = 0;
     int mfma_sub = 0, mfma_qcap = 0, mfma_blocks = 0, mfma_kc_v1 = 0, mfma_kc_tpw = 8;
-    int flat_chunk = 0, host_slots = 1;
+    int flat_chunk = 0, host_slots = 1, sub_batch = 0;
 };
 
 enum OptNorm {
@@ -143,6 +143,7 @@ const OptionRow kOptions[] = {
     {"mfma_kc_v1", &Switches::mfma_kc_v1, OPT_BOOL, nullptr, "K3mk without LDS-DMA (k_scan_mfma_kc) also where k_scan_mfma_kc2 applies"},
     {"mfma_kc_tpw", &Switches::mfma_kc_tpw, OPT_8_OR_16, nullptr, "code tiles per wave of K3mk: 8 (default) or 16"},
     {"flat_chunk", &Switches::flat_chunk, OPT_RAW, nullptr, "codes per chunk of a flat PQ list, from 4096 (0 = sized from the batch)"},
+    {"sub_batch", &Switches::sub_batch, OPT_MIN0, nullptr, "> 0: at most this many queries per sub-batch of a search call (0 = from the memory caps alone); tests split small calls"},
 };
 
 struct ShardGroup;  // mmidx_sharded.h
@@ -867,6 +868,9 @@ int make_plan(mmidx_index *h, int k, int64_t nq, SearchPlan &pl, bool need_coars
         HIPCK(h->ws_glut.reserve(slots * (size_t)h->m * h->ks));
         h->glut_slots = slots;
     }
+    // (applied last, and to nothing but qb: the table slots above stay reserved for the memory caps' qb, more than a split forced by
+    //  the option needs -- slots sized for the sub-batch that runs are reached by the 2 GiB cap itself)
+    if (h->sw.sub_batch > 0) qb = std::min<int64_t>(qb, h->sw.sub_batch);  // option "sub_batch" (tests split small calls)
     pl.qb = qb;
     return MMIDX_OK;
 }

@@ -44,9 +44,10 @@ def scan_lds_bytes(D, m, ks, transform, cap):
     return m * ks * 8 + (2 if transform else 1) * D * 8 + cap * 12 + 16
 
 
-def plan(D, m, ks, transform, n, k, nq, flat_chunk=0):
+def plan(D, m, ks, transform, n, k, nq, flat_chunk=0, sub_batch=0):
     """make_plan for a flat PQ handle of byte codes: dict(cap, lds, glut, chunk, nchunks, qb).  Without the option the chunk is 32768
-    or 65536 codes (by batch size and the K3m tables): every case that leaves it alone has fewer codes than either."""
+    or 65536 codes (by batch size and the K3m tables): every case that leaves it alone has fewer codes than either.  sub_batch: the
+    option of that name (tests/plan_model.py has the IVFPQ side)."""
     cap = cap_rule(k)
     lds = scan_lds_bytes(D, m, ks, transform, cap)
     glut = lds > LDS_BYTES  # the pl.glut predicate
@@ -61,6 +62,8 @@ def plan(D, m, ks, transform, n, k, nq, flat_chunk=0):
     qb = min(nq, 1 << 30, max(1, (16 << 30) // (poolq * 16)))
     if glut:  # one table slot per block in global scratch: at most 2 GiB of it
         qb = min(qb, max(1, (2 << 30) // (m * ks * 8 * nchunks)))
+    if sub_batch > 0:
+        qb = min(qb, sub_batch)
     return dict(cap=cap, lds=lds, glut=glut, chunk=chunk, nchunks=nchunks, qb=qb)
 
 
