@@ -543,6 +543,7 @@ int mmidx_set_profiling(mmidx_index *h, int enabled);
  *   "mfma_kc_tpw": code tiles per wave of K3mk: 8 (default) or 16
  *   "flat_chunk": codes per chunk of a flat PQ list, from 4096 (0 = sized from the batch)
  *   "sub_batch": > 0: at most this many queries per sub-batch of a search call (0 = from the memory caps alone); tests split small calls
+ *   "coarse_near": the coarse stage's one-probe certificate: -1 = wherever its conditions hold (default), 0 = off (every query gets its exact far ranking)
  * A sharded handle passes these on to every shard and has options of its own (csrc/mmidx_sharded.h):
  *   "shard_exchange": 0 = partial lists stored into the owners' buffers over xGMI, 1 = ncclSend / ncclRecv
  *   "tie_slots": flagged queries per owner and replay round (0 = no replay)
@@ -565,6 +566,8 @@ int mmidx_get_stats(mmidx_index *h, mmidx_stats *out);
  *   ";encode=<K6b' | K6b | ->"   the product quantisation kernel of the most recent encode
  *   ";flagged=<count | ->"   vectors that the most recent mmidx_encode / _add_vectors / _assign_device / _encode_device /
  *        _add_vectors_device call sent to the exact redo, summed over its internal chunks; "-" where no certified kernel ran in it
+ *   ";near_only=<count>"   queries of that search sub-batch the coarse stage answered with the nearest cell alone (the one-probe
+ *        certificate; option "coarse_near"); read from the device by this call
  * A sharded handle reports its first shard.  Diagnostic: not a stable format. */
 int mmidx_get_dispatch(mmidx_index *h, char *out, int cap);
 

@@ -88,6 +88,7 @@ struct Switches {
     int no_mfma = 0, no_grp = 0, no_union = 0, no_split_table = 0, passb_small = 1, passb_main_grid = 0;
     int mfma_sub = 0, mfma_qcap = 0, mfma_blocks = 0, mfma_kc_v1 = 0, mfma_kc_tpw = 8;
     int flat_chunk = 0, host_slots = 1, sub_batch = 0;
+    int coarse_near = -1;
 };
 
 enum OptNorm {
@@ -144,6 +145,7 @@ const OptionRow kOptions[] = {
     {"mfma_kc_tpw", &Switches::mfma_kc_tpw, OPT_8_OR_16, nullptr, "code tiles per wave of K3mk: 8 (default) or 16"},
     {"flat_chunk", &Switches::flat_chunk, OPT_RAW, nullptr, "codes per chunk of a flat PQ list, from 4096 (0 = sized from the batch)"},
     {"sub_batch", &Switches::sub_batch, OPT_MIN0, nullptr, "> 0: at most this many queries per sub-batch of a search call (0 = from the memory caps alone); tests split small calls"},
+    {"coarse_near", &Switches::coarse_near, OPT_TRI, nullptr, "the coarse stage's one-probe certificate: -1 = wherever its conditions hold (default), 0 = off (every query gets its exact far ranking)"},
 };
 
 struct ShardGroup;  // mmidx_sharded.h
@@ -269,6 +271,7 @@ struct MMIDX_HIDDEN mmidx_index {
     DevBuf<double> ws_lutpre;
     DevBuf<uint4> ws_surv;
     DevBuf<double> ws_R;               // RandomRotation: the kept pairs' exact rotated residuals [pairs][D]
+    DevBuf<u32> ws_near;               // k_coarse_front_sel: [nq] 1 where its one-probe certificate served the query
     DevBuf<u32> ws_defer;              // k_coarse_front_sel: count + list of the queries left to k_coarse_select_defer
     int hint_calls = 0;                // IVF pass-B stages launched so far (pin_hint[0] describes the last one)
     int64_t hint_last_nq = -1, hint_prev_nq = -1;  // batch size and probes of the stage launched last / the one before it (whose count pin_hint[0] holds
@@ -291,6 +294,7 @@ struct MMIDX_HIDDEN mmidx_index {
     size_t mf_ev_used = 0;
     // which kernel family served each stage of the most recent search sub-batch (mmidx_get_dispatch; host-side words, a few stores per call)
     const char *disp_coarse = "-", *disp_passa = "-", *disp_passb = "-", *disp_pre = "-", *disp_coarse_mm = "-";
+    int64_t near_nq = 0;  // > 0: the most recent search sub-batch ran the coarse stage with the one-probe certificate, ws_near holds its flags
     // ... and the build path: the kernels of the most recent assignment / encode, and the vectors the most recent public build call
     // sent to the exact redo, summed over its chunks (-1: no certified kernel ran in it); see BuildReport
     const char *disp_assign = "-", *disp_encode = "-";
@@ -1935,7 +1939,9 @@ static ApproxSel approx_sel_common(const mmidx_index *h, int cch, const double *
     return A;
 }
 
-int run_coarse(mmidx_index *h, int64_t nq, const double *dQ, int32_t *d_cells, hipStream_t st) {
+// near_min > 0 (search_batch_device alone): k_coarse_front_sel may answer a query with its nearest cell and w - 1 fillers where the
+// coarse bound is certain to prune every far probe; a nearest list of fewer codes than near_min is not certified
+int run_coarse(mmidx_index *h, int64_t nq, const double *dQ, int32_t *d_cells, hipStream_t st, long long near_min = 0) {
     constexpr int QT = 8;
     HIPCK(h->ws_cdist.reserve((size_t)nq * h->C));
     h->cdsel_valid = false;
@@ -1956,6 +1962,7 @@ int run_coarse(mmidx_index *h, int64_t nq, const double *dQ, int32_t *d_cells, h
         HIPCK(h->ws_gmin.reserve((size_t)nq * G * 2));
         HIPCK(h->ws_cdsel.reserve((size_t)nq * h->w));
         HIPCK(h->ws_defer.reserve((size_t)nq + 1));
+        if (near_min > 0) HIPCK(h->ws_near.reserve((size_t)nq));
         hipLaunchKernelGGL(k_split_bf16, dim3((unsigned)((nq + 3) / 4)), dim3(MMIDX_BLOCK), 0, st, dQ, (__bf16 *)h->ws_Qh.p, (__bf16 *)h->ws_Ql.p,
                            (float *)nullptr, h->ws_qn.p, h->D, h->Dp, (long long)nq, h->ws_defer.p);
         const int ntiles = h->Cp / G16_BC;
@@ -2005,6 +2012,14 @@ int run_coarse(mmidx_index *h, int64_t nq, const double *dQ, int32_t *d_cells, h
             const bool wave_sel = h->sw.coarse_wave_sel && h->w < 64 && (h->D == 64 || h->D == 128 || h->D == 256);
             const unsigned fgrid = (unsigned)((nq + 3) / 4);
             h->disp_coarse = wave_sel ? "K1e'+K1f(front_sel)" : "K1e'+K1f(front+select_list)";
+            if (wave_sel && near_min > 0) {
+                A.near_only = 1;
+                A.near_min = near_min;
+                A.list_off = h->d_off;
+                A.rmax = h->rmax;
+                A.near_flag = h->ws_near.p;
+                h->near_nq = nq;
+            }
             if (wave_sel && h->D == 128) hipLaunchKernelGGL((k_coarse_front_sel<8>), dim3((unsigned)nq), dim3(64), 0, st, A);  // (a wave a block)
             else if (wave_sel && h->D == 64) hipLaunchKernelGGL((k_coarse_front_sel<4>), dim3((unsigned)nq), dim3(64), 0, st, A);
             else if (wave_sel) hipLaunchKernelGGL((k_coarse_front_sel<16>), dim3((unsigned)nq), dim3(64), 0, st, A);
@@ -2068,9 +2083,25 @@ int search_batch_device(mmidx_index *h, const SearchPlan &pl, int k, int64_t nq,
         if (!ev) prof = plight = false;  // event pool exhausted: call mmidx_get_stats to drain it
     }
     const int32_t *d_cells = d_cells_in;
+    h->near_nq = 0;
     if (ivf && !d_cells) {
         HIPCK(h->ws_cells.reserve((size_t)nq * h->w));
-        int rc = run_coarse(h, nq, dQ, h->ws_cells.p, st);
+        // The one-probe certificate stands on what follows in THIS step: the coarse bound applied as k_pair_hist applies
+        // it (enabled, no rotation: lengths are kept exactly), a threshold that is the ADC distance of a code of the nearest list -- what
+        // K3q, K3h and K3 publish, each once a chunk of the list holds more than K1 codes; K3ma is not covered, nor symmetric distances --
+        // and nothing that reports on the probed lists (profiling 1 counts their codes).  A shard's phases and caller-given cells never
+        // come here with it.
+        long long near_min = 0;
+        if (phase == 0 && mode == 0 && h->sw.coarse_near != 0 && h->profiling != 1 && !sdc_tt && h->n_csr > 0 && h->w > 1 &&
+            h->transform != MMIDX_TR_ROTATION && !h->sw.no_bound && std::isfinite(h->rmax)) {
+            ScanParams G{};  // (what the pass A gates read of the parameters)
+            G.ivf = 1;
+            G.Q = dQ;
+            G.w = h->w;
+            const bool q_runs = passa_q_applies(h, G, pl, (long long)nq), ma = passa_mfma_applies(h, G, pl, (long long)nq);
+            if (!ma || (q_runs && h->sw.passa_mfma <= 0)) near_min = (long long)pl.K1 * std::max(pl.nchunks, 1) + 1;
+        }
+        int rc = run_coarse(h, nq, dQ, h->ws_cells.p, st, near_min);
         if (rc) return rc;
         d_cells = h->ws_cells.p;
     }
@@ -3698,8 +3729,17 @@ int mmidx_get_dispatch(mmidx_index *h, char *out, int cap) {
     if (!k3f_ok && pb[0] == 'K' && pb[1] == '3' && pb[2] == 'f') pb = "K3(exact scan: no K3f instance for this shape)";
     char flagged[24] = "-";  // (the build path: assign_device / encode_device / BuildReport)
     if (s->disp_flagged >= 0) snprintf(flagged, sizeof flagged, "%lld", (long long)s->disp_flagged);
-    snprintf(out, (size_t)cap, "coarse=%s;pass_a=%s;pre=%s;pass_b=%s;coarse_mm=%s;assign=%s;encode=%s;flagged=%s", s->disp_coarse, s->disp_passa,
-             s->disp_pre, pb, s->disp_coarse_mm, s->disp_assign, s->disp_encode, flagged);
+    // near_only: the queries of that sub-batch the coarse stage's one-probe certificate served (read from the device here)
+    u32 near = 0;
+    if (s->near_nq > 0 && s->ws_near.p) {
+        std::vector<u32> fl((size_t)s->near_nq);
+        HIPCK(hipSetDevice(s->device));
+        HIPCK(hipDeviceSynchronize());  // (the sub-batch may have run on a stream of the caller's)
+        HIPCK(hipMemcpy(fl.data(), s->ws_near.p, fl.size() * sizeof(u32), hipMemcpyDeviceToHost));
+        for (const u32 f : fl) near += f;
+    }
+    snprintf(out, (size_t)cap, "coarse=%s;pass_a=%s;pre=%s;pass_b=%s;coarse_mm=%s;assign=%s;encode=%s;flagged=%s;near_only=%u", s->disp_coarse, s->disp_passa,
+             s->disp_pre, pb, s->disp_coarse_mm, s->disp_assign, s->disp_encode, flagged, near);
     return MMIDX_OK;
 }
 

@@ -548,6 +548,13 @@ struct ApproxSel {
     u32 *defer;              // k_coarse_front_sel: [0] number of queries it left to k_coarse_select_defer, [1 ..] those queries
     int nq;
     int cand_chunk;          // candidates per round of the exact stage (<= MMIDX_CAND_CHUNK; the launch's LDS holds that many rows of terms)
+    // k_coarse_front_sel's one-probe certificate; near_only = 0 everywhere but in a whole search step
+    int near_only;             // 1: a query whose far probes the coarse bound is certain to prune gets its nearest cell alone
+    long long near_min;        // fewest codes in the nearest list: pass A must publish a threshold from it (> K1 codes in one chunk)
+    const int64_t *list_off;   // [C + 1]
+    double rmax;               // PairBound's
+    u32 *near_flag;            // [nq] 1 where the certificate served the query, else 0 (a plain store per query: 16384 atomics on one
+                               // counter cost more than the kernel -- 0.72 -> 0.85 ms per headline step)
 };
 #define MMIDX_CLIST 256
 
@@ -1708,6 +1715,102 @@ __global__ __launch_bounds__(64, 4) void k_coarse_front_sel(const ApproxSel A) {
             ry[i] = v.y;                              // (read only for a group that qualifies)
             km[i & 3] = m1[i] < km[i & 3] ? m1[i] : km[i & 3];
         }
+        // ---- the one-probe certificate.  a = the smallest d~, at centroid c0; b = the smallest d~ of every OTHER
+        //      centroid (the other groups' minima and c0's own runner-up, which is rounded towards zero); every centroid but c0 is
+        //      then at L = b - eps16 or farther.  With d0 = |c0 - q|^2 exact: every code of list c0 has an ADC distance of at most
+        //      U = (sqrt(d0) + Rmax)^2, so pass A's threshold T -- the distance of one of them -- is at most U; and pair_keep()'s
+        //      lower bound of any other cell, which grows with the cell's distance, is at least its value at L.  Where that value
+        //      exceeds U, k_pair_hist prunes all w - 1 far probes whatever they are: the query gets c0 with its exact key, w - 1
+        //      distinct valid cells with L for a distance (pair_keep then computes the very value tested here), and leaves.
+        if (A.near_only) {
+            float la = inf, lb = inf, lr = 0.0f;
+            u32 lid = 0;
+#pragma unroll
+            for (int i = 0; i < GPL; i++) {
+                const bool lt = m1[i] < la;
+                lb = lt ? la : (m1[i] < lb ? m1[i] : lb);
+                lr = lt ? ry[i] : lr;
+                lid = lt ? (u32)i : lid;
+                la = lt ? m1[i] : la;
+            }
+            {
+                const u32 rb = (u32)__float_as_int(lr);
+                const float m2 = __int_as_float((int)(rb & ~7u));
+                // (a negative or NaN runner-up: b = 0, L < 0, nothing is certified; a lane of groups past the end has no runner-up)
+                const float m2c = la < inf ? (m2 > 0.0f ? m2 : 0.0f) : inf;
+                lb = m2c < lb ? m2c : lb;
+                lid = (u32)lane | (lid << 6) | ((rb & 7u) << 10);
+            }
+            // (min, where, min of the rest) over the wave: the DPP steps of wave_min_u32 -- they join DISJOINT sets of lanes, and a
+            //  lane without a source takes (inf, inf), the neutral element -- the result stands in lane 63
+#define MMIDX_DPP_AB(ctrl, rmask)                                                                                              \
+    {                                                                                                                          \
+        const float oa = __int_as_float(__builtin_amdgcn_update_dpp(0x7f800000, __float_as_int(la), ctrl, rmask, 0xf, false)); \
+        const float ob = __int_as_float(__builtin_amdgcn_update_dpp(0x7f800000, __float_as_int(lb), ctrl, rmask, 0xf, false)); \
+        const u32 oi = (u32)__builtin_amdgcn_update_dpp(0, (int)lid, ctrl, rmask, 0xf, false);                                 \
+        const bool lt = oa < la;                                                                                               \
+        const float hi = lt ? la : oa;                                                                                         \
+        const float bb = ob < lb ? ob : lb;                                                                                    \
+        lb = hi < bb ? hi : bb;                                                                                                \
+        lid = lt ? oi : lid;                                                                                                   \
+        la = lt ? oa : la;                                                                                                     \
+    }
+            MMIDX_DPP_AB(0x111, 0xf) MMIDX_DPP_AB(0x112, 0xf) MMIDX_DPP_AB(0x114, 0xf) MMIDX_DPP_AB(0x118, 0xf)
+            MMIDX_DPP_AB(0x142, 0xa) MMIDX_DPP_AB(0x143, 0xc)
+#undef MMIDX_DPP_AB
+            const float b = __int_as_float((int)wave_read_u32((u32)__float_as_int(lb), 63));
+            const u32 id = wave_read_u32(lid, 63);
+            const int g0 = (int)(id & 1023u);  // lane + 64 slot
+            const int c0 = (g0 >> 4) * G16_BC + (g0 & 15) + 16 * (int)((id >> 10) & 7u);
+            const double L = (double)b - eps16;
+            const double gap = sqrt(L) * (1.0 - 1e-12) - A.rmax;  // (pair_keep's operations on cdsel = L; shrink = 1: no rotation)
+            const double lbv = gap * gap * (1.0 - 1e-9);
+            bool ok = c0 < C && b < inf && filter_norms_usable(sumn) && gap > 0.0;  // (all wave-uniform; a NaN fails every test)
+            if (ok) ok = A.list_off[c0 + 1] - A.list_off[c0] >= A.near_min;
+            if (ok) {
+                // d0: the terms (c_j - q_j)^2 of the one row through the tile, added in dimension order by every lane alike
+                // (broadcast reads) -- the exact stage's operations on the same operands in the same order, so the same bits
+                double *t = &s_terms[0][0];
+                const double *row = A.coarse + (size_t)c0 * (u32)D, *qv = A.Q + (size_t)q * D;
+                for (int p = lane; p < (D >> 1); p += 64) {
+                    const double2 cv = *(const double2 *)(row + 2 * p), qq = *(const double2 *)(qv + 2 * p);
+                    const double e0 = cv.x - qq.x, e1 = cv.y - qq.y;
+                    t[2 * p] = e0 * e0;
+                    t[2 * p + 1] = e1 * e1;
+                }
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                double acc = 0.0;
+                for (int j = 0; j < D; j += 16) {
+                    double tv[16];
+#pragma unroll
+                    for (int u = 0; u < 16; u++) tv[u] = t[j + u];
+#pragma unroll
+                    for (int u = 0; u < 16; u++) acc += tv[u];
+                }
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();  // (the tile is the exact stage's again)
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                const double su = sqrt(acc) + A.rmax;
+                ok = lbv > su * su * (1.0 + 1e-9);
+                if (ok) {
+                    if (lane < w) {
+                        const int cf = c0 + lane < C ? c0 + lane : c0 + lane - C;  // (w <= G / 4 - 1 < C: distinct, valid cells)
+                        A.cells[(size_t)q * w + lane] = cf;
+                        A.cdsel[(size_t)q * w + lane] = lane == 0 ? keyd(dkey(acc)) : L;
+                    }
+                    if (lane == 0) A.near_flag[q] = 1u;
+                    CFS_TICK(5);
+#ifdef CFS_TIMING
+                    if (lane == 0 && (q & 4095) == 77) printf("[cfs] q %d near only: cycles load+min+certificate %llu\n", q, tacc[5]);
+#endif
+                    return;
+                }
+            }
+            if (lane == 0) A.near_flag[q] = 0u;
+            CFS_TICK(5);
+        }
         // ---- tau: the R-th smallest of the 256 partial minima, by bisection on the bit patterns (as k_coarse_front)
         float tau;
         {
@@ -1970,7 +2073,8 @@ __global__ __launch_bounds__(64, 4) void k_coarse_front_sel(const ApproxSel A) {
     CFS_TICK(4);
 #ifdef CFS_TIMING
     if (lane == 0 && (q & 4095) == 77)
-        printf("[cfs] q %d n %u: cycles load+min %llu bisect %llu push %llu exact %llu rank %llu\n", q, n, tacc[0], tacc[1], tacc[2], tacc[3], tacc[4]);
+        printf("[cfs] q %d n %u: cycles load+min %llu bisect %llu push %llu exact %llu rank %llu; failed certificate (with the loads) %llu\n", q, n, tacc[0],
+               tacc[1], tacc[2], tacc[3], tacc[4], tacc[5]);
 #endif
     bool plain;
     {
