@@ -544,6 +544,8 @@ int mmidx_set_profiling(mmidx_index *h, int enabled);
  *   "flat_chunk": codes per chunk of a flat PQ list, from 4096 (0 = sized from the batch)
  *   "sub_batch": > 0: at most this many queries per sub-batch of a search call (0 = from the memory caps alone); tests split small calls
  *   "coarse_near": the coarse stage's one-probe certificate: -1 = wherever its conditions hold (default), 0 = off (every query gets its exact far ranking)
+ *   "coarse_screen": the head-only bf16 screen in front of that certificate (K1s): -1 = where it applies, resting seven calls
+ *        after one that handed on more than a quarter of its queries (default), 0 = off, 1 = wherever it applies
  * A sharded handle passes these on to every shard and has options of its own (csrc/mmidx_sharded.h):
  *   "shard_exchange": 0 = partial lists stored into the owners' buffers over xGMI, 1 = ncclSend / ncclRecv
  *   "tie_slots": flagged queries per owner and replay round (0 = no replay)
@@ -566,6 +568,8 @@ int mmidx_get_stats(mmidx_index *h, mmidx_stats *out);
  *   ";encode=<K6b' | K6b | ->"   the product quantisation kernel of the most recent encode
  *   ";flagged=<count | ->"   vectors that the most recent mmidx_encode / _add_vectors / _assign_device / _encode_device /
  *        _add_vectors_device call sent to the exact redo, summed over its internal chunks; "-" where no certified kernel ran in it
+ *   ";screened=<count | ->"   queries of that search sub-batch the screen's certificate served (option "coarse_screen"; the others went on to
+ *        the split kernels); "-" where the screen did not run; read from the device by this call
  *   ";near_only=<count>"   queries of that search sub-batch the coarse stage answered with the nearest cell alone (the one-probe
  *        certificate; option "coarse_near"); read from the device by this call
  * A sharded handle reports its first shard.  Diagnostic: not a stable format. */

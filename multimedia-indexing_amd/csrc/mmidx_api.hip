@@ -88,7 +88,7 @@ struct Switches {
     int no_mfma = 0, no_grp = 0, no_union = 0, no_split_table = 0, passb_small = 1, passb_main_grid = 0;
     int mfma_sub = 0, mfma_qcap = 0, mfma_blocks = 0, mfma_kc_v1 = 0, mfma_kc_tpw = 8;
     int flat_chunk = 0, host_slots = 1, sub_batch = 0;
-    int coarse_near = -1;
+    int coarse_near = -1, coarse_screen = -1;
 };
 
 enum OptNorm {
@@ -146,6 +146,7 @@ const OptionRow kOptions[] = {
     {"flat_chunk", &Switches::flat_chunk, OPT_RAW, nullptr, "codes per chunk of a flat PQ list, from 4096 (0 = sized from the batch)"},
     {"sub_batch", &Switches::sub_batch, OPT_MIN0, nullptr, "> 0: at most this many queries per sub-batch of a search call (0 = from the memory caps alone); tests split small calls"},
     {"coarse_near", &Switches::coarse_near, OPT_TRI, nullptr, "the coarse stage's one-probe certificate: -1 = wherever its conditions hold (default), 0 = off (every query gets its exact far ranking)"},
+    {"coarse_screen", &Switches::coarse_screen, OPT_TRI, nullptr, "the head-only bf16 screen in front of that certificate (K1s): -1 = where it applies, resting seven calls after one that handed on more than a quarter of its queries (default), 0 = off, 1 = wherever it applies"},
 };
 
 struct ShardGroup;  // mmidx_sharded.h
@@ -295,6 +296,13 @@ struct MMIDX_HIDDEN mmidx_index {
     // which kernel family served each stage of the most recent search sub-batch (mmidx_get_dispatch; host-side words, a few stores per call)
     const char *disp_coarse = "-", *disp_passa = "-", *disp_passb = "-", *disp_pre = "-", *disp_coarse_mm = "-";
     int64_t near_nq = 0;  // > 0: the most recent search sub-batch ran the coarse stage with the one-probe certificate, ws_near holds its flags
+    // the screen in front of it (K1s + k_coarse_near_cert; option "coarse_screen")
+    int64_t screen_nq = 0;        // > 0: the most recent search sub-batch ran the screen; ws_unc[0] = the queries it handed on
+    ScreenAuto screen_auto;       // the auto rule's state
+    DevBuf<unsigned short> ws_Qh2, ws_Ql2;  // the handed-on queries' split rows, compact (K1e'' runs on them)
+    DevBuf<double> ws_qn2;
+    DevBuf<u32> ws_unc;           // [0] their number, [1 ..] the queries
+    DevBuf<float> ws_rec;         // K1s's records [nq][gsplit][4]
     // ... and the build path: the kernels of the most recent assignment / encode, and the vectors the most recent public build call
     // sent to the exact redo, summed over its chunks (-1: no certified kernel ran in it); see BuildReport
     const char *disp_assign = "-", *disp_encode = "-";
@@ -1978,10 +1986,74 @@ int run_coarse(mmidx_index *h, int64_t nq, const double *dQ, int32_t *d_cells, h
                                (const __bf16 *)h->d_Cl, h->d_cn_pad, h->ws_qn.p, (float2 *)h->ws_gmin.p, h->Cp, shape...);
         };
         const dim3 qgrid((unsigned)qblocks, (unsigned)csplit);
+        // front end and selection as two kernels where a query's candidates fit the list between them (about 1.3 (w + 1))
+        const bool split = !h->sw.coarse_fused && G <= 1024 && 2 * (h->w + 1) + 32 < MMIDX_CLIST;
+        // front end + exact stage by one wave per query where its LDS tile applies (option "coarse_wave_sel", default on); what it
+        // leaves (more than 64 candidates) goes through the block-per-query form
+        const bool wave_sel = split && h->sw.coarse_wave_sel && h->w < 64 && (h->D == 64 || h->D == 128 || h->D == 256);
+        ApproxSel A = approx_sel_common(h, cch, dQ, d_cells);
+        A.gpair = (const float2 *)h->ws_gmin.p;
+        A.G = G;
+        A.Dp = h->Dp;
+        A.nq = (int)nq;
+        if (wave_sel && near_min > 0) {
+            A.near_only = 1;
+            A.near_min = near_min;
+            A.list_off = h->d_off;
+            A.rmax = h->rmax;
+            A.near_flag = h->ws_near.p;
+            h->near_nq = nq;
+        }
+        // The screen (K1s + k_coarse_near_cert): where the one-probe certificate is on and K1e'' would run, a head-only
+        // product and one record per query decide the certificate first; K1e'', k_coarse_front_sel and k_coarse_select_defer then run
+        // on the compact list of the queries it handed on, with worst-case grids that leave on the device count.  Option
+        // "coarse_screen": 0 off, 1 always, -1 by ScreenAuto over the pinned word the fallback K1e'' writes.
+        const int32_t SCREEN_HINT = 8;  // (the free word of pin_hint this rule owns)
+        bool screen = A.near_only && h->Dp == G16_KC && h->D == G16_KC && h->sw.coarse_groups && gsplit <= 65535 && h->sw.coarse_screen != 0;
+        if (screen && h->sw.coarse_screen < 0 && h->pin_hint) screen = h->screen_auto.step(*((volatile int32_t *)h->pin_hint + SCREEN_HINT), (long long)nq);
+        if (screen) {
+            HIPCK(h->ws_Qh2.reserve((size_t)nq * h->Dp));
+            HIPCK(h->ws_Ql2.reserve((size_t)nq * h->Dp));
+            HIPCK(h->ws_qn2.reserve((size_t)nq));
+            HIPCK(h->ws_unc.reserve((size_t)nq + 1));
+            HIPCK(h->ws_rec.reserve((size_t)nq * gsplit * 4));
+            HIPCK(h->ws_clist.reserve((size_t)nq * MMIDX_CLIST));
+            const int t_per = (ntiles + gsplit - 1) / gsplit;
+            ScreenCert S{};
+            S.rec = (const float4 *)h->ws_rec.p;
+            S.ny = gsplit;
+            S.ny_used = (ntiles + t_per - 1) / t_per;  // (split16_tile_range: the splits past it have no tiles and write no record)
+            S.unc = h->ws_unc.p;
+            S.Qh = (const uint4 *)h->ws_Qh.p;
+            S.Ql = (const uint4 *)h->ws_Ql.p;
+            S.Qh2 = (uint4 *)h->ws_Qh2.p;
+            S.Ql2 = (uint4 *)h->ws_Ql2.p;
+            S.qn2 = h->ws_qn2.p;
+            A.clist = (u32 *)h->ws_clist.p;
+            A.defer = h->ws_defer.p;
+            const dim3 ggrid((unsigned)gqblocks, (unsigned)gsplit);
+            hipLaunchKernelGGL(k_coarse_screen16, ggrid, dim3(G16G_BLOCK), 0, st, (const __bf16 *)h->ws_Qh.p, (const __bf16 *)h->d_Ch, h->d_cn_pad, h->ws_qn.p,
+                               (float4 *)h->ws_rec.p, h->Cp, (int)nq, h->ws_unc.p);
+            hipLaunchKernelGGL(k_coarse_near_cert, dim3((unsigned)((nq + 63) / 64)), dim3(MMIDX_BLOCK), 0, st, A, S);
+            hipLaunchKernelGGL(k_coarse_gmin16_grp, ggrid, dim3(G16G_BLOCK), 0, st, (const __bf16 *)h->ws_Qh2.p, (const __bf16 *)h->ws_Ql2.p,
+                               (const __bf16 *)h->d_Ch, (const __bf16 *)h->d_Cl, h->d_cn_pad, h->ws_qn2.p, (float2 *)h->ws_gmin.p, h->Cp, (int)nq, G,
+                               (const u32 *)h->ws_unc.p, h->pin_hint ? h->pin_hint + SCREEN_HINT : (int32_t *)nullptr);
+            A.n_dev = h->ws_unc.p;
+            A.qlist = h->ws_unc.p + 1;
+            hipLaunchKernelGGL((k_coarse_front_sel<8>), dim3((unsigned)nq), dim3(64), 0, st, A);
+            const unsigned dgrid = (unsigned)std::min<long long>(nq, 2ll * std::max(h->num_cus, 8));
+            for_cwidth<32>(h->C, [&](auto per) { hipLaunchKernelGGL(k_coarse_select_defer<decltype(per)::value>, dim3(dgrid), dim3(MMIDX_BLOCK), glds, st, A); });
+            HIPCK(hipGetLastError());
+            h->disp_coarse_mm = "groups";
+            h->disp_coarse = "K1e'+K1f(front_sel)";
+            h->screen_nq = nq;
+            h->cdsel_valid = true;
+            return MMIDX_OK;
+        }
         h->disp_coarse_mm = "staged";
         if (h->Dp == G16_KC && h->sw.coarse_groups && gsplit <= 65535) {
             h->disp_coarse_mm = "groups";
-            k1e(k_coarse_gmin16_grp, dim3((unsigned)gqblocks, (unsigned)gsplit), G16G_BLOCK, 0, (int)nq, G);
+            k1e(k_coarse_gmin16_grp, dim3((unsigned)gqblocks, (unsigned)gsplit), G16G_BLOCK, 0, (int)nq, G, (const u32 *)nullptr, (int32_t *)nullptr);
         } else if (h->Dp == G16_KC) {
             // one k chunk: centroid tiles by LDS-DMA into two half-tile buffers (static LDS)
             h->disp_coarse_mm = "dma";
@@ -1996,30 +2068,12 @@ int run_coarse(mmidx_index *h, int64_t nq, const double *dQ, int32_t *d_cells, h
             k1e(k_coarse_gmin16, qgrid, MMIDX_BLOCK, l16, h->Dp, (int)nq, G);
         }
         HIPCK(hipGetLastError());
-        ApproxSel A = approx_sel_common(h, cch, dQ, d_cells);
-        A.gpair = (const float2 *)h->ws_gmin.p;
-        A.G = G;
-        A.Dp = h->Dp;
-        A.nq = (int)nq;
-        // front end and selection as two kernels where a query's candidates fit the list between them (about 1.3 (w + 1))
-        const bool split = !h->sw.coarse_fused && G <= 1024 && 2 * (h->w + 1) + 32 < MMIDX_CLIST;
         if (split) {
             HIPCK(h->ws_clist.reserve((size_t)nq * MMIDX_CLIST));
             A.clist = (u32 *)h->ws_clist.p;
-            // front end + exact stage by one wave per query where its LDS tile applies (option "coarse_wave_sel", default on); what it
-            // leaves (more than 64 candidates) goes through the block-per-query form
             A.defer = h->ws_defer.p;
-            const bool wave_sel = h->sw.coarse_wave_sel && h->w < 64 && (h->D == 64 || h->D == 128 || h->D == 256);
             const unsigned fgrid = (unsigned)((nq + 3) / 4);
             h->disp_coarse = wave_sel ? "K1e'+K1f(front_sel)" : "K1e'+K1f(front+select_list)";
-            if (wave_sel && near_min > 0) {
-                A.near_only = 1;
-                A.near_min = near_min;
-                A.list_off = h->d_off;
-                A.rmax = h->rmax;
-                A.near_flag = h->ws_near.p;
-                h->near_nq = nq;
-            }
             if (wave_sel && h->D == 128) hipLaunchKernelGGL((k_coarse_front_sel<8>), dim3((unsigned)nq), dim3(64), 0, st, A);  // (a wave a block)
             else if (wave_sel && h->D == 64) hipLaunchKernelGGL((k_coarse_front_sel<4>), dim3((unsigned)nq), dim3(64), 0, st, A);
             else if (wave_sel) hipLaunchKernelGGL((k_coarse_front_sel<16>), dim3((unsigned)nq), dim3(64), 0, st, A);
@@ -2084,6 +2138,7 @@ int search_batch_device(mmidx_index *h, const SearchPlan &pl, int k, int64_t nq,
     }
     const int32_t *d_cells = d_cells_in;
     h->near_nq = 0;
+    h->screen_nq = 0;
     if (ivf && !d_cells) {
         HIPCK(h->ws_cells.reserve((size_t)nq * h->w));
         // The one-probe certificate stands on what follows in THIS step: the coarse bound applied as k_pair_hist applies
@@ -2639,7 +2694,7 @@ int mmidx_create(int kind, int D, int m, int ks, int C, int transform, const int
         h->num_cus = ncu > 0 ? ncu : 256;
     }
     if (h->pin_hint.alloc(16) == hipSuccess) {
-        memset(h->pin_hint, 0, 64);  // [0] pass B's pair count of the previous call, [1] codes its K3g verified
+        memset(h->pin_hint, 0, 64);  // [0] pass B's pair count of the previous call, [1] codes its K3g verified, .., [8] queries the coarse screen handed on
     } else {
         h->pin_hint.p = nullptr;  // (launches are then sized for the worst case)
         (void)hipGetLastError();
@@ -3738,8 +3793,17 @@ int mmidx_get_dispatch(mmidx_index *h, char *out, int cap) {
         HIPCK(hipMemcpy(fl.data(), s->ws_near.p, fl.size() * sizeof(u32), hipMemcpyDeviceToHost));
         for (const u32 f : fl) near += f;
     }
-    snprintf(out, (size_t)cap, "coarse=%s;pass_a=%s;pre=%s;pass_b=%s;coarse_mm=%s;assign=%s;encode=%s;flagged=%s;near_only=%u", s->disp_coarse, s->disp_passa,
-             s->disp_pre, pb, s->disp_coarse_mm, s->disp_assign, s->disp_encode, flagged, near);
+    // screened: the queries of that sub-batch the screen's certificate served (the others were handed on to the split kernels)
+    char screened[24] = "-";
+    if (s->screen_nq > 0 && s->ws_unc.p) {
+        u32 unc = 0;
+        HIPCK(hipSetDevice(s->device));
+        HIPCK(hipDeviceSynchronize());
+        HIPCK(hipMemcpy(&unc, s->ws_unc.p, sizeof(u32), hipMemcpyDeviceToHost));
+        snprintf(screened, sizeof screened, "%lld", (long long)s->screen_nq - (long long)unc);
+    }
+    snprintf(out, (size_t)cap, "coarse=%s;pass_a=%s;pre=%s;pass_b=%s;coarse_mm=%s;assign=%s;encode=%s;flagged=%s;screened=%s;near_only=%u", s->disp_coarse,
+             s->disp_passa, s->disp_pre, pb, s->disp_coarse_mm, s->disp_assign, s->disp_encode, flagged, screened, near);
     return MMIDX_OK;
 }
 

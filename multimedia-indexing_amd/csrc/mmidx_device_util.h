@@ -50,6 +50,23 @@ __device__ __forceinline__ double filter_eps_split16(int Dp, double epi, double 
     return (2.0 * 3.1 * 0x1p-16 * xnorm * cnorm_max + 2.0 * (3.0 * (double)Dp + 16.0) * 0x1p-22 * xnorm * cnorm_max +
             1e-12 * (cn2_max + xn2) + epi * sumn * sumn + filter_underflow_eps(Dp, sumn)) * (1.0 + 1e-9);
 }
+// bf16 heads alone, ONE matrix-core product accumulated in fp32 over Dp padded dimensions (K1s, the screen of the one-probe
+// certificate: DESIGN.md 5.1, "The screen"); epi as above.  Term by term:
+//   dropped cross terms: q.c - qh.ch = (q - qh).c + qh.(c - ch), |x - xh| <= 2^-8 |x| elementwise (the fp32 copy's rounding and the
+//             head's), |qh| <= (1 + 2^-8) |q|:  <= 2.01 * 2^-8 |q||c|, doubled in d~;
+//   accumulation of Dp exact products, any order, 2^-22 relative per step: (Dp + 16) 2^-22 |qh||ch| <= 1.01 (Dp + 16) 2^-22 |q||c|, doubled;
+//   the norms' 1e-12 and the epilogue's epi (|c| + |q|)^2: as the split's;
+//   the absolute part, recounted from filter_underflow_eps: elements -- fl32(x_j) and its head, two roundings, the dot product moves
+//             by at most 2.01 U sqrt(Dk) (|c| + |x|), twice that in d~: 6 U sqrt(Dk) sumn; Dk products and Dk additions, doubled: 4 Dk U;
+//             the epilogue's 16 U unchanged.
+__device__ __forceinline__ double filter_underflow_eps_head(int Dk, double sumn) {
+    return (4.0 * (double)Dk + 16.0 + 6.0 * sqrt((double)Dk) * sumn) * 0x1p-126;
+}
+__device__ __forceinline__ double filter_eps_head16(int Dp, double epi, double xnorm, double xn2, double cnorm_max, double cn2_max) {
+    const double sumn = cnorm_max + xnorm;
+    return (2.0 * 2.01 * 0x1p-8 * xnorm * cnorm_max + 2.0 * 1.01 * ((double)Dp + 16.0) * 0x1p-22 * xnorm * cnorm_max +
+            1e-12 * (cn2_max + xn2) + epi * sumn * sumn + filter_underflow_eps_head(Dp, sumn)) * (1.0 + 1e-9);
+}
 // fp32 fused multiply-add chain over D dimensions, fp64 epilogue, d~ stored as fp32 (K1c / K1d, K6a)
 __device__ __forceinline__ double filter_eps_fp32(int D, double xnorm, double xn2, double cnorm_max, double cn2_max) {
     const double sumn = cnorm_max + xnorm;

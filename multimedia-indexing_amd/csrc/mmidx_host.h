@@ -221,6 +221,32 @@ int combiner_submit(Combiner &c, SearchReq &me, int64_t max_q, Serve serve) {
 #define G16G_RING 4          // half-tile buffers of 32 KiB
 #define G16G_NORM_TILES 64   // centroid tiles whose norms a block keeps in LDS beside the ring (4 x 32 KiB + 32 KiB = the CU's 160 KiB)
 
+// The auto rule of option "coarse_screen" (the idiom of K3s's pre_skip): the screen runs, unless the pinned word says that the last
+// screened call handed on more than a quarter of its queries -- then seven calls go without it and the next one probes again.  A
+// stale word costs speed, never results.  (tests/coarse_screen_model.py restates step().)
+struct ScreenAuto {
+    int skip = 0;        // calls the screen still sits out
+    bool fresh = false;  // the pinned word describes a screened call that has not been judged yet ...
+    long long nq = 0;    // ... of this many queries
+    // handed: the pinned word as it reads now; returns whether this call, of nq_now queries, runs the screen
+    bool step(const long long handed, const long long nq_now) {
+        if (skip > 0) {
+            skip--;
+            return false;
+        }
+        if (fresh) {
+            fresh = false;
+            if (handed * 4 > nq) {
+                skip = 6;  // (this call is the first of the seven)
+                return false;
+            }
+        }
+        fresh = true;
+        nq = nq_now;
+        return true;
+    }
+};
+
 // ---- calls across units (hidden: none of these is exported) ----------------------------------------------------------------
 extern "C" {
 // mmidx_api.hip: what K8'' reads of an index handle's coarse quantizer (bf16 head / tail copies padded to Cp x Dp, |c|^2, maxima)

@@ -555,6 +555,8 @@ struct ApproxSel {
     double rmax;               // PairBound's
     u32 *near_flag;            // [nq] 1 where the certificate served the query, else 0 (a plain store per query: 16384 atomics on one
                                // counter cost more than the kernel -- 0.72 -> 0.85 ms per headline step)
+    // k_coarse_front_sel behind the screen (K1s + k_coarse_near_cert): block i serves query qlist[i] with row i of gpair, i < *n_dev
+    const u32 *qlist, *n_dev;  // null: block i serves query i
 };
 #define MMIDX_CLIST 256
 
@@ -1162,10 +1164,19 @@ __device__ unsigned long long g16g_cycles[2][8];  // [group][products, barrier, 
 __global__ __launch_bounds__(G16G_BLOCK, 1) void k_coarse_gmin16_grp(const __bf16 *__restrict__ Qh, const __bf16 *__restrict__ Ql,
                                                                   const __bf16 *__restrict__ Ch, const __bf16 *__restrict__ Cl,
                                                                   const double *__restrict__ cn, const double *__restrict__ qn,
-                                                                  float2 *__restrict__ gpair, int Cp, int nq, int G) {
+                                                                  float2 *__restrict__ gpair, int Cp, int nq, int G,
+                                                                  const u32 *__restrict__ nq_dev = nullptr, int32_t *__restrict__ hint_out = nullptr) {
     constexpr int Dp = G16_KC;               // 128 bf16 = 256 B = 16 units per row
     constexpr int HROWS = SPLIT16_HROWS, HBYTES = SPLIT16_HBYTES;
     constexpr int BUFB = 2 * HBYTES;         // a ring buffer: head + tail of a half tile
+    if (nq_dev) {
+        // behind the screen (K1s): the rows are the compact list of the queries it handed on, their number stands on the device.
+        // Block-uniform, before the first barrier; one thread reports the number to the host's pinned word on the way
+        const int nd = (int)*nq_dev;
+        if (hint_out && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) *hint_out = nd;
+        nq = nd < nq ? nd : nq;
+        if ((int)blockIdx.x * G16G_BQ >= nq) return;
+    }
     constexpr int NORM0 = G16G_RING * BUFB;  // the norms follow the ring
     __shared__ __attribute__((aligned(1024))) unsigned char lds[NORM0 + G16G_NORM_TILES * G16_BC * 4];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -1333,6 +1344,189 @@ __global__ __launch_bounds__(G16G_BLOCK, 1) void k_coarse_gmin16_grp(const __bf1
         atomicAdd(&g16g_cycles[grp][7], (unsigned long long)T);
     }
 #endif
+}
+
+// K1s: the head-only screen in front of K1e'' ("The screen"), Dp == 128.  The one-probe certificate needs three numbers
+// of a query -- the smallest d~, the smallest d~ of every OTHER centroid and one exact distance -- and none of the split's precision:
+// d~ from the head product qh.ch alone is within filter_eps_head16() of d.  So: K1e'''s grid, block, ring and slot table with
+//   * the head halves alone DMA'd (4 instructions per wave and tile, ring buffers of 16 KiB) and 64 matrix instructions per tile;
+//   * no store in the tile loop: per row a running (best, rest, where) over the block's tiles, `where` = tile << 3 | column tile;
+//     one record per (query, blockIdx.y) at the end: rec[q][y] = (a, b, index of a, -);
+//   * every wait a vmcnt(0): with no stores, the only vector-memory operations of a wave inside the loop are the DMA of ONE tile
+//     (group 0 issues tile j+1 at the start of slot 2j+1 and waits at the end of slot 2j+2, in front of its next issue; group 1
+//     issues tile j+2 at the start of slot 2j+3 and waits at the end of slot 2j+4, likewise).  Read after retire and restage
+//     after read are K1e'''s, barrier for barrier: every wave executes 2T + 1.
+// A step of the products is one (half, k step): four column tiles x two row tiles, the next step's four B fragments read behind
+// its first four products.  zero_word: a counter of the next kernel of the stream (as k_split_bf16).
+__global__ __launch_bounds__(G16G_BLOCK, 1) void k_coarse_screen16(const __bf16 *__restrict__ Qh, const __bf16 *__restrict__ Ch,
+                                                                const double *__restrict__ cn, const double *__restrict__ qn,
+                                                                float4 *__restrict__ rec, int Cp, int nq, u32 *__restrict__ zero_word) {
+    constexpr int Dp = G16_KC;
+    constexpr int HROWS = SPLIT16_HROWS, HBYTES = SPLIT16_HBYTES;
+    constexpr int NORM0 = G16G_RING * HBYTES;  // the norms follow the ring
+    __shared__ __attribute__((aligned(1024))) unsigned char lds[NORM0 + G16G_NORM_TILES * G16_BC * 4];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int grp = wave >> 2;
+    const int fr = lane & 15, fg = lane >> 4;
+    const int q0 = blockIdx.x * G16G_BQ + wave * 32;
+    if (zero_word && blockIdx.x == 0 && blockIdx.y == 0 && tid == 0) *zero_word = 0;
+    int t_lo, t_hi;  // (the host keeps the tiles per block <= G16G_NORM_TILES)
+    split16_tile_range(Cp / G16_BC, gridDim.y, blockIdx.y, t_lo, t_hi);
+    if (t_lo >= t_hi) return;  // block-uniform, before the first barrier (the certificate reads no record of such a y: see the host)
+    const int T = t_hi - t_lo;
+    auto issue = [&](const int h) { split16_dma_half_head<8>(lds + (h & (G16G_RING - 1)) * HBYTES, Ch, t_lo * G16_BC + h * HROWS, Dp, 0, wave, lane); };
+    issue(0);
+    issue(1);
+    float qn_r[2][4];
+    split16_row_norms<true>(qn_r, qn, q0, nq, fg);
+    bf16x8 ah[2][4];  // A fragments (heads): [row tile][k step of 32], resident for the whole block
+#pragma unroll
+    for (int rt = 0; rt < 2; rt++) {
+        int q = q0 + rt * 16 + fr;
+        q = q < nq ? q : nq - 1;  // (rows past nq: clamped for the loads, never stored)
+#pragma unroll
+        for (int ks = 0; ks < 4; ks++) ah[rt][ks] = *(const bf16x8 *)(Qh + (size_t)q * Dp + ks * 32 + fg * 8);
+    }
+    for (int i0 = 0; i0 < T * G16_BC; i0 += 4 * G16G_BLOCK) {  // the block's centroid norms, as K1e''
+        float cf[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const int i = i0 + k * G16G_BLOCK + tid;
+            cf[k] = (float)cn[(size_t)t_lo * G16_BC + (i < T * G16_BC ? i : T * G16_BC - 1)];
+        }
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const int i = i0 + k * G16G_BLOCK + tid;
+            if (i < T * G16_BC) ((float *)(lds + NORM0))[i] = split16_clamp_norm(cf[k]);
+        }
+    }
+    f32x4 acc[2][8];
+    auto tile_mma = [&](const int j) {
+        const unsigned char *tb = lds + (j & 1) * (2 * HBYTES);  // halves 2j, 2j+1 = ring buffers 2 (j & 1), 2 (j & 1) + 1
+        bf16x8 bh[2][4];                                         // [register set][column tile of the half]
+        auto read_b = [&](const int step, const int set) {
+            const int h = step >> 2, ks = step & 3;
+#pragma unroll
+            for (int u = 0; u < 4; u++) bh[set][u] = *(const bf16x8 *)(tb + h * HBYTES + split16_dma_frag_offset(u * 16 + fr, ks, fg, fr));
+        };
+        read_b(0, 0);
+#pragma unroll
+        for (int step = 0; step < 8; step++) {
+            const int set = step & 1, ks = step & 3, c0 = (step >> 2) * 4;
+#pragma unroll
+            for (int u = 0; u < 2; u++)
+#pragma unroll
+                for (int rt = 0; rt < 2; rt++)
+                    acc[rt][c0 + u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[rt][ks], bh[set][u], acc[rt][c0 + u], 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+            if (step + 1 < 8) read_b(step + 1, set ^ 1);
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int u = 2; u < 4; u++)
+#pragma unroll
+                for (int rt = 0; rt < 2; rt++)
+                    acc[rt][c0 + u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[rt][ks], bh[set][u], acc[rt][c0 + u], 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    };
+    // running (best, smallest of the rest, where) of each of the eight rows a lane holds results for, over the columns it holds
+    float ra[2][4], rb[2][4];
+    int rw[2][4];
+#pragma unroll
+    for (int rt = 0; rt < 2; rt++)
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            ra[rt][r] = rb[rt][r] = __int_as_float(0x7f7ffff8);  // (largest finite value with the position bits clear)
+            rw[rt][r] = 0;
+        }
+    // minima of tile j: split16_gmin_store's four instructions per value, then the pair folded into the running triple; a tie
+    // keeps the earlier tile and makes rest = best
+    auto minima = [&](const int j) {
+        const float *nrm = (const float *)(lds + NORM0) + j * G16_BC;
+        float cn_c[8];
+#pragma unroll
+        for (int ct = 0; ct < 8; ct++) cn_c[ct] = nrm[ct * 16 + fr];
+#pragma unroll
+        for (int rt = 0; rt < 2; rt++)
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                float m1 = __int_as_float(0x7f7ffff8), m2 = m1;
+#pragma unroll
+                for (int ct = 0; ct < 8; ct++) {
+                    const float tv = __builtin_fmaf(-2.0f, acc[rt][ct][r], cn_c[ct]);
+                    const float tp = __int_as_float((__float_as_int(tv) & ~7) | ct);
+                    m2 = __builtin_amdgcn_fmed3f(m1, m2, tp);
+                    m1 = __builtin_amdgcn_fmed3f(m1, tp, -3.0e38f);
+                }
+                const bool lt = m1 < ra[rt][r];
+                const float hi = lt ? ra[rt][r] : m1;
+                const float lo2 = m2 < rb[rt][r] ? m2 : rb[rt][r];
+                rb[rt][r] = hi < lo2 ? hi : lo2;
+                rw[rt][r] = lt ? ((j << 3) | (__float_as_int(m1) & 7)) : rw[rt][r];
+                ra[rt][r] = lt ? m1 : ra[rt][r];
+            }
+    };
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");  // halves 0 and 1, the fragments, the norms' LDS writes
+#pragma unroll
+    for (int rt = 0; rt < 2; rt++)
+#pragma unroll
+        for (int r = 0; r < 4; r++) asm volatile("" : "+v"(qn_r[rt][r]));  // (converted here, as in K1e'')
+#pragma unroll
+    for (int rt = 0; rt < 2; rt++)
+#pragma unroll
+        for (int ks = 0; ks < 4; ks++) asm volatile("" : "+v"(ah[rt][ks]));
+    G16G_SYNC();  // barrier 0
+    if (T > 1) {  // slot 1: tile 1
+        issue(2);
+        issue(3);
+    }
+    if (grp == 1) G16G_SYNC();  // slot 1: group 1 has no phase yet
+#pragma unroll 1
+    for (int j = 0; j < T; j++) {
+        const bool more = j + 1 < T;  // block-uniform
+        if (grp == 0) {
+            // slot 2j+1
+            if (j >= 1 && more) {
+                issue(2 * j + 2);
+                issue(2 * j + 3);
+            }
+            split16_zero_acc(acc);
+            tile_mma(j);
+            G16G_SYNC();
+            // slot 2j+2
+            minima(j);
+            if (more) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // tile j+1: this wave's only outstanding vector-memory operations
+            G16G_SYNC();
+        } else {
+            // slot 2j+2
+            split16_zero_acc(acc);
+            tile_mma(j);
+            if (more) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // tile j+1, issued a slot ago
+            G16G_SYNC();
+            // slot 2j+3
+            if (j + 2 < T) {
+                issue(2 * j + 4);
+                issue(2 * j + 5);
+            }
+            minima(j);
+            if (more) G16G_SYNC();
+        }
+    }
+    // the 16 lanes of a row merged (the smaller centroid index wins a tie, and rest = best then); |q|^2 added to the two survivors
+#pragma unroll
+    for (int rt = 0; rt < 2; rt++)
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            float m1 = ra[rt][r], m2 = rb[rt][r];
+            int ix = (t_lo + (rw[rt][r] >> 3)) * G16_BC + (rw[rt][r] & 7) * 16 + fr;
+            row16_best2_merge(m1, ix, m2);
+            float a = m1 + qn_r[rt][r], b = m2 + qn_r[rt][r];
+            a = a < 0.0f ? 0.0f : a;
+            b = b < 0.0f ? 0.0f : b;
+            const int q = q0 + rt * 16 + 4 * fg + r;
+            if (fr == 0 && q < nq) rec[(size_t)q * gridDim.y + blockIdx.y] = make_float4(a, b, __int_as_float(ix), 0.0f);
+        }
 }
 
 // K1e' for long vectors (Dp a multiple of 128, e.g. the 1024 dimensions of YFCC100MExample.java:85): the same LDS-DMA double
@@ -1667,6 +1861,22 @@ __global__ __launch_bounds__(MMIDX_BLOCK) void k_coarse_front(const ApproxSel A)
     if (lane == 0) list[0] = n <= MMIDX_CLIST - 1 ? n : (u32)(MMIDX_CSEL_CAP + 1);
 }
 
+// d0 of the one-probe certificate, the parts k_coarse_front_sel and k_coarse_near_cert share so that cdsel[q][0] has the same bits from
+// either: the terms (c_j - q_j)^2 of two dimensions (stored, never contracted into the sum), and sixteen of them -- `stride` doubles
+// apart -- added to acc in dimension order
+__device__ __forceinline__ void coarse_d0_terms(const double2 cv, const double2 qq, double &t0, double &t1) {
+    const double e0 = cv.x - qq.x, e1 = cv.y - qq.y;
+    t0 = e0 * e0;
+    t1 = e1 * e1;
+}
+__device__ __forceinline__ void coarse_d0_add16(double &acc, const double *t, const int stride) {
+    double tv[16];
+#pragma unroll
+    for (int u = 0; u < 16; u++) tv[u] = t[u * stride];
+#pragma unroll
+    for (int u = 0; u < 16; u++) acc += tv[u];
+}
+
 // K1f in ONE kernel where the exact stage fits a wave: front end as k_coarse_front, then -- for a query with at most 64 candidates
 // (the usual 1.3 (w + 1)) -- the exact distances, the ranking and the bounded-queue rule by the same wave, no block barrier and no
 // block-wide staging (k_coarse_select_list spent 117 us per 16384 queries of the headline workload between barriers: one block per
@@ -1681,7 +1891,12 @@ __global__ __launch_bounds__(64, 4) void k_coarse_front_sel(const ApproxSel A) {
     __shared__ __attribute__((aligned(16))) double s_terms[16][65];  // the exact stage's tile; the keys and the selection live in it afterwards
     __shared__ u32 s_cidx[128];  // up to 128 candidates: the exact stage takes them 64 at a time
     const int lane = threadIdx.x;
-    const int q = (int)blockIdx.x;
+    int q = (int)blockIdx.x;
+    const size_t grow = (size_t)blockIdx.x * A.G;  // the query's row of gpair
+    if (A.qlist) {  // (block-uniform)
+        if (blockIdx.x >= *A.n_dev) return;
+        q = (int)A.qlist[blockIdx.x];
+    }
     u64 *ckey = (u64 *)&s_terms[0][0], *sel_k = ckey + 128;
     u32 *cidx = s_cidx;
     int *sel_i = (int *)(sel_k + 64);  // [128] (ranks of up to 128 candidates pass through it)
@@ -1707,7 +1922,7 @@ __global__ __launch_bounds__(64, 4) void k_coarse_front_sel(const ApproxSel A) {
         for (int i = 0; i < GPL; i++) {
             const int g = lane + 64 * i;
             const int gc = g < G ? g : G - 1;
-            const float2 v = A.gpair[(size_t)q * G + gc];
+            const float2 v = A.gpair[grow + gc];
             // (a load on a clamped index ...
             // ... whose value every lane USES: written as selects of v the compiler sank each load into its own `g < G` block with a
             //     full wait behind it -- sixteen memory round trips in a row, a quarter of this kernel's time)
@@ -1774,21 +1989,13 @@ __global__ __launch_bounds__(64, 4) void k_coarse_front_sel(const ApproxSel A) {
                 const double *row = A.coarse + (size_t)c0 * (u32)D, *qv = A.Q + (size_t)q * D;
                 for (int p = lane; p < (D >> 1); p += 64) {
                     const double2 cv = *(const double2 *)(row + 2 * p), qq = *(const double2 *)(qv + 2 * p);
-                    const double e0 = cv.x - qq.x, e1 = cv.y - qq.y;
-                    t[2 * p] = e0 * e0;
-                    t[2 * p + 1] = e1 * e1;
+                    coarse_d0_terms(cv, qq, t[2 * p], t[2 * p + 1]);
                 }
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                 __builtin_amdgcn_wave_barrier();
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
                 double acc = 0.0;
-                for (int j = 0; j < D; j += 16) {
-                    double tv[16];
-#pragma unroll
-                    for (int u = 0; u < 16; u++) tv[u] = t[j + u];
-#pragma unroll
-                    for (int u = 0; u < 16; u++) acc += tv[u];
-                }
+                for (int j = 0; j < D; j += 16) coarse_d0_add16(acc, t + j, 1);
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                 __builtin_amdgcn_wave_barrier();  // (the tile is the exact stage's again)
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -1883,7 +2090,7 @@ __global__ __launch_bounds__(64, 4) void k_coarse_front_sel(const ApproxSel A) {
             for (u32 mm = allm; mm; mm &= mm - 1) {
                 const int g = lane + 64 * (__ffs(mm) - 1);
                 const int cb = (g >> 4) * G16_BC + (g & 15);
-                const int a1 = __float_as_int(A.gpair[(size_t)q * G + g].y) & 7;
+                const int a1 = __float_as_int(A.gpair[grow + g].y) & 7;
                 for (int ct = 0; ct < 8; ct++)
                     if (ct != a1 && cb + 16 * ct < C) {
                         const u32 slot = atomicAdd(cnt, 1u);
@@ -1903,7 +2110,7 @@ __global__ __launch_bounds__(64, 4) void k_coarse_front_sel(const ApproxSel A) {
 #pragma unroll 1
             for (int i = 0; i < GPL; i++) {
                 const int g = lane + 64 * i;
-                const float2 v = A.gpair[(size_t)q * G + (g < G ? g : G - 1)];
+                const float2 v = A.gpair[grow + (g < G ? g : G - 1)];
                 const int cb = (g >> 4) * G16_BC + (g & 15);
                 const int a1 = __float_as_int(v.y) & 7;
                 const float m2 = __int_as_float(__float_as_int(v.y) & ~7);
@@ -2144,6 +2351,130 @@ __global__ __launch_bounds__(MMIDX_BLOCK) void k_coarse_select_list(const Approx
     __syncthreads();
     const int n = (int)s_pad[0];
     coarse_select_finish<PER>(A, q, n, ckey, cidx, sel_k, sel_i, s_k, s_i);
+}
+
+// The one-probe certificate over the screen's records ("The screen"): a block of four waves takes 64 queries, a
+// THREAD of wave 0 per query.  (a, c0, b) from the ny records of the query -- b = the smallest of every other split's a and of all
+// the b's, strict <, so two equal minima give b = a and nothing certifies -- L = b - eps1, then the tests of k_coarse_front_sel's
+// near_only branch word for word; d0 from coarse_d0_terms / coarse_d0_add16 (all four waves compute the terms of 64 dimensions at
+// a time into the tile, the query's thread adds them in dimension order).  A certified query gets cells, cdsel = (d0, L, .., L) and
+// near_flag = 1.  Every other query takes a slot of unc[] (unc[0] = their number, zeroed by K1s; ONE atomic per block, none where
+// the block hands nothing on) and has its split rows and norm copied to that slot of the compact buffers K1e'' then runs on.
+struct ScreenCert {
+    const float4 *rec;  // [nq][ny] K1s's records
+    int ny, ny_used;    // record stride, and the splits that had tiles (the others wrote nothing)
+    u32 *unc;           // [0] number of queries handed on, [1 ..] those queries
+    const uint4 *Qh, *Ql;  // [nq][16] k_split_bf16's rows (Dp == 128: 256 B)
+    uint4 *Qh2, *Ql2;      // the compact copies
+    double *qn2;
+};
+__global__ __launch_bounds__(MMIDX_BLOCK) void k_coarse_near_cert(const ApproxSel A, const ScreenCert S) {
+    constexpr int D = G16_KC;  // (the host runs the screen at D == Dp == 128 alone)
+    __shared__ double s_terms[64][65];  // [dimension of the pass][query]
+    __shared__ double s_L[64], s_d0[64];
+    __shared__ int s_c0[64], s_slot[64];
+    __shared__ u32 s_ok[64], s_nunc;
+    const int tid = threadIdx.x;
+    const int qb = (int)blockIdx.x * 64, nq = A.nq, C = A.C, w = A.w;
+    const float inf = __int_as_float(0x7f800000);
+    bool ok = false, valid = false;
+    double lbv = 0.0;
+    if (tid < 64) {
+        const int q = qb + tid;
+        valid = q < nq;
+        const int qc = valid ? q : nq - 1;
+        float a = inf, b = inf;
+        int c0 = 0;
+        for (int y = 0; y < S.ny_used; y++) {
+            const float4 r = S.rec[(size_t)qc * S.ny + y];
+            const bool lt = r.x < a;
+            const float hi = lt ? a : r.x;
+            const float bb = r.y < b ? r.y : b;
+            b = hi < bb ? hi : bb;
+            c0 = lt ? __float_as_int(r.z) : c0;
+            a = lt ? r.x : a;
+        }
+        const double qn = A.qn[qc];
+        const double qnorm = sqrt(qn);
+        const double sumn = A.cnorm_max + qnorm;
+        const double eps1 = filter_eps_head16(A.Dp, 0x1p-21 + 0x1p-20, qnorm, qn, A.cnorm_max, A.cn_max);
+        const double L = (double)b - eps1;
+        const double gap = sqrt(L) * (1.0 - 1e-12) - A.rmax;  // (pair_keep's operations on cdsel = L; shrink = 1: no rotation)
+        lbv = gap * gap * (1.0 - 1e-9);
+        const bool in_c = c0 >= 0 && c0 < C;
+        ok = valid && in_c && b < inf && filter_norms_usable(sumn) && gap > 0.0;  // (a NaN fails every test)
+        if (ok) ok = A.list_off[c0 + 1] - A.list_off[c0] >= A.near_min;
+        s_c0[tid] = in_c ? c0 : 0;  // (d0 is computed for every query of the block, from a valid row)
+        s_L[tid] = L;
+    }
+    __syncthreads();
+    // d0: two passes of 64 dimensions; thread (ql, jp) holds dimensions 2 jp, 2 jp + 1 of the pass for queries ql + 8 i
+    const int jp = tid & 31, ql = tid >> 5;
+    double2 cv[8], qv[8];
+    auto load = [&](const int pass) {
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+            const int l = ql + 8 * i;
+            const int q = qb + l < nq ? qb + l : nq - 1;
+            cv[i] = *(const double2 *)(A.coarse + (size_t)s_c0[l] * D + pass * 64 + 2 * jp);
+            qv[i] = *(const double2 *)(A.Q + (size_t)q * D + pass * 64 + 2 * jp);
+        }
+    };
+    double acc = 0.0;
+    load(0);
+#pragma unroll
+    for (int pass = 0; pass < 2; pass++) {
+#pragma unroll
+        for (int i = 0; i < 8; i++) coarse_d0_terms(cv[i], qv[i], s_terms[2 * jp][ql + 8 * i], s_terms[2 * jp + 1][ql + 8 * i]);
+        if (pass == 0) load(1);  // (in flight while the first half is added up)
+        __syncthreads();
+        if (tid < 64)
+            for (int j = 0; j < 64; j += 16) coarse_d0_add16(acc, &s_terms[j][tid], 65);
+        __syncthreads();
+    }
+    if (tid < 64) {
+        if (ok) {
+            const double su = sqrt(acc) + A.rmax;
+            ok = lbv > su * su * (1.0 + 1e-9);
+        }
+        s_ok[tid] = ok ? 1u : 0u;
+        s_d0[tid] = keyd(dkey(acc));
+        if (valid) A.near_flag[qb + tid] = ok ? 1u : 0u;
+        const bool hand = valid && !ok;
+        const u64 mask = __builtin_amdgcn_ballot_w64(hand);
+        const u32 cnt = (u32)__popcll(mask);
+        u32 base = 0;
+        if (cnt && tid == 0) base = atomicAdd(S.unc, cnt);
+        base = wave_read_u32(base, 0);
+        int slot = -1;
+        if (hand) {
+            slot = (int)(base + (u32)__popcll(mask & ((1ull << tid) - 1ull)));
+            S.unc[1 + slot] = (u32)(qb + tid);
+        }
+        s_slot[tid] = slot;
+        if (tid == 0) s_nunc = cnt;
+    }
+    __syncthreads();
+    for (int idx = tid; idx < 64 * w; idx += MMIDX_BLOCK) {
+        const int l = idx / w, i = idx - l * w;
+        if (s_ok[l]) {
+            const int q = qb + l, c0 = s_c0[l];
+            const int cf = c0 + i < C ? c0 + i : c0 + i - C;  // (w <= G / 4 - 1 < C: distinct, valid cells)
+            A.cells[(size_t)q * w + i] = cf;
+            A.cdsel[(size_t)q * w + i] = i == 0 ? s_d0[l] : s_L[l];
+        }
+    }
+    if (s_nunc) {  // (block-uniform)
+        for (int idx = tid; idx < 64 * 32; idx += MMIDX_BLOCK) {
+            const int l = idx >> 5, u = idx & 31, slot = s_slot[l];
+            if (slot >= 0) {
+                const size_t q = (size_t)(qb + l);
+                if (u < 16) S.Qh2[(size_t)slot * 16 + u] = S.Qh[q * 16 + u];
+                else S.Ql2[(size_t)slot * 16 + (u - 16)] = S.Ql[q * 16 + (u - 16)];
+                if (u == 0) S.qn2[slot] = A.qn[q];
+            }
+        }
+    }
 }
 
 // the queries k_coarse_front_sel left (more than 64 candidates, or nothing certifiable): k_coarse_select_list over its list of them

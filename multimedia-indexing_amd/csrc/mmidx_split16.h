@@ -270,6 +270,19 @@ __device__ __forceinline__ void split16_dma_half(unsigned char *buf, const __bf1
                                          (__attribute__((address_space(3))) void *)(buf + SPLIT16_HBYTES + (i * NWAVES + wave) * 1024), 16, 0, 0);
     }
 }
+// the head part alone (k_coarse_screen16): 16 / NWAVES wave-instructions per wave, the same swizzle, buf holds SPLIT16_HBYTES
+template <int NWAVES>
+__device__ __forceinline__ void split16_dma_half_head(unsigned char *buf, const __bf16 *__restrict__ Ch, const int row0, const int Dp, const int kbase,
+                                                      const int wave, const int lane) {
+#pragma unroll
+    for (int i = 0; i < 16 / NWAVES; i++) {
+        const int pu = (i * NWAVES + wave) * 64 + lane;
+        const int row = pu >> 4, slot = pu & 15;
+        const size_t src = ((size_t)(row0 + row) * Dp + (size_t)kbase + (size_t)((slot ^ (row & 15)) * 8)) * 2;  // bytes
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)((const unsigned char *)Ch + src),
+                                         (__attribute__((address_space(3))) void *)(buf + (i * NWAVES + wave) * 1024), 16, 0, 0);
+    }
+}
 // where the fragment of (row, k step ks) lies in such a half (fr == row & 15)
 __device__ __forceinline__ int split16_dma_frag_offset(const int row, const int ks, const int fg, const int fr) {
     return row * (G16_KC * 2) + (((ks * 4 + fg) ^ fr) * 16);

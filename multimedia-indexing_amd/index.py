@@ -463,6 +463,8 @@ class _PQBase(AbstractSearchStructure):
         """which kernel family served each stage of the most recent search sub-batch: {"coarse": .., "pass_a": .., "pre": .., "pass_b": ..,
         "coarse_mm": ..}, and of the most recent build call: "assign" (K6a'(rows) | K6a'(copies) | K6a | exact | -), "encode" (K6b' | K6b | -)
         and "flagged", the number of vectors that call sent to the exact redo as text ("-" where no certified kernel ran).
+        "screened": the queries of that sub-batch the head-only screen's certificate served ("-" where the screen did not run; option
+        "coarse_screen"), and last "near_only": the queries the coarse stage answered with the nearest cell alone.
         "pass_a" names the kernel that was launched: "K3(table in two halves)" only where k_scan_split ran (ADC, m = 128 byte codes, a
         chunk of at most 32768 codes), "K3(table in global scratch)" for every other table beyond the LDS, "K3" / "K3(single pass)"
         otherwise.  After search_sdc_batch "pass_a" is one of these three K3 forms, "pre" is "-" and "pass_b" is
