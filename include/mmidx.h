@@ -192,6 +192,31 @@ int mmidx_search_ids(mmidx_index *h, int k, int64_t nq, const int32_t *iids, int
 int mmidx_search_ids_device(mmidx_index *h, int k, int64_t nq, const int32_t *d_iids, int32_t *d_iid_out,
                             double *d_dist_out, int32_t *d_count_out, void *stream);
 
+/* ---- removing records ---------------------------------------------------------------------
+ * An extension of the reference, which can only index: a record leaves its collection there by a rebuilt BDB environment.
+ * mmidx_remove takes n internal ids (host array) and removes every stored record that carries one of them:
+ *   - pending records are folded into the lists first, so a record appended a moment ago can be removed;
+ *   - mmidx_add_codes does not forbid two records with one iid: all of them go; an iid given twice in the request is one removal;
+ *   - found_out[n] (may be NULL): 1 where iids[i] was stored before the call, else 0 -- every occurrence of a repeated iid gets
+ *     the same answer.  A negative id, one beyond the largest stored id or one that is simply absent is no error: found 0;
+ *   - removed_out (may be NULL) counts records, not request entries;
+ *   - n == 0 is MMIDX_OK and touches nothing; so does a request none of whose ids is stored (no array moves);
+ *   - the survivors keep their list and their arrival order inside it (the order equal distances are resolved in): afterwards
+ *     the index is, array for array as mmidx_export returns them (list_off, ids, codes), the index that would exist had the
+ *     removed records never been added;
+ *   - all or nothing: the new arrays are built beside the old ones and swapped in at the end, so a failure before the swap
+ *     leaves the index as it was.  Peak extra device memory: one copy of the survivors' codes and ids, plus one bit per id of the
+ *     id space, one bit per record and a counter per 2048 records;
+ *   - mmidx_size, mmidx_list_sizes, mmidx_export and mmidx_save report the smaller index; a later mmidx_add_* may use a removed
+ *     iid again.  The per-code norms of the matrix-core pass B and the iid -> position table are rebuilt on their next use.
+ * mmidx_remove_device: the ids (and d_found_out) are device pointers.  The call orders itself after `stream`, runs on the
+ *   handle's own stream and SYNCHRONISES before it returns (the host copy of the list offsets must be current): d_found_out is
+ *   complete on return, removed_out is a host pointer.
+ * Both take the handle as an add that rebuilds the lists does (one at a time, never under a search of another thread or stream);
+ * IVFPQ and PQ handles, byte and short codes.  A sharded handle answers MMIDX_ERR_UNSUPPORTED before anything is launched. */
+int mmidx_remove(mmidx_index *h, int64_t n, const int32_t *iids, int32_t *found_out, int64_t *removed_out);
+int mmidx_remove_device(mmidx_index *h, int64_t n, const int32_t *d_iids, int32_t *d_found_out, int64_t *removed_out, void *stream);
+
 /* computeNearestCoarseIndex (IVFPQ.java:547-564) for n device-resident vectors: d_cell_out[i] = the exact
  * fp64 argmin cell, first index wins ties.  Needs only the coarse quantizer (used by the codebook learner). */
 int mmidx_assign_device(mmidx_index *h, int64_t n, const double *dX, int32_t *d_cell_out, void *stream);

@@ -96,6 +96,8 @@ SIGNATURES = {
     "mmidx_search_refine": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int64, _dp, _i32p, _dp, _i32p, C.POINTER(C.c_int64)]),
     "mmidx_search_refine_device": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int64, _dp, _i32p, _dp, _i32p, _vp, _vp]),
     "mmidx_search_refine_ids": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int64, _i32p, _i32p, _dp, _i32p, C.POINTER(C.c_int64)]),
+    "mmidx_remove": (C.c_int, [_vp, C.c_int64, _i32p, _i32p, C.POINTER(C.c_int64)]),
+    "mmidx_remove_device": (C.c_int, [_vp, C.c_int64, _i32p, _i32p, C.POINTER(C.c_int64), _vp]),
     "mmidx_truncate_l2_device": (C.c_int, [C.c_int, C.c_int64, C.c_int, C.c_int64, _dp, C.c_int, _i32p, _i32p, _vp, _vp]),
     "mmidx_linear_reindex": (C.c_int, [_vp, C.c_int64, C.c_int64, _vp, C.c_int, _i32p, _vp, _i32p, C.c_int64]),
     "mmidx_coarse_device": (C.c_int, [_vp, C.c_int64, _dp, _i32p, _dp, _vp]),

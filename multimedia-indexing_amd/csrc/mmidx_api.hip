@@ -4244,6 +4244,117 @@ int mmidx_search_refine_ids(mmidx_index *h, mmidx_linear *l, int k, int R, int64
     return refine_host(h, lr.rows, k, R, nq, nullptr, iids, iid_out, dist_out, count_out, missing_out);
 }
 
+/* ---- records taken back out (K13, mmidx_remove.h) -----------------------------------------------------
+ * The reference has no removal: indexVector is its only way in and a rebuilt BDB environment its only way out.  The survivors keep
+ * their list and their order inside it (the offer order the tie rule replays), so the index afterwards is, array for array, the
+ * index the removed records were never added to.  New arrays are built beside the old ones and swapped in last, as build_csr does. */
+int mmidx_remove_device(mmidx_index *h, int64_t n, const int32_t *d_iids, int32_t *d_found_out, int64_t *removed_out, void *stream) {
+    if (!h) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null handle");
+    if (n < 0) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "n < 0");
+    if (n > 0 && !d_iids) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null argument");
+    NOT_ON_SHARDED(h, "mmidx_remove_device");
+    if (removed_out) *removed_out = 0;
+    if (n == 0) return MMIDX_OK;
+    int rc = set_device(h);
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    std::lock_guard<std::recursive_mutex> alk(h->add_mu);
+    DeviceCall call(h, h->stream);  // (the arrays must not move under a search another stream is still running)
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (st != h->stream) HIPCK(hipStreamSynchronize(st));  // the caller's ids are ready; the work runs on the handle's own stream
+    rc = build_csr(h);  // pending records first: one appended a moment ago can be removed
+    if (rc) return rc;
+    const int64_t nrec = h->n_csr;
+    if (nrec == 0) {
+        if (d_found_out) {
+            HIPCK(hipMemsetAsync(d_found_out, 0, (size_t)n * sizeof(int32_t), h->stream));
+            HIPCK(hipStreamSynchronize(h->stream));
+        }
+        return MMIDX_OK;
+    }
+    rc = ensure_inverse(h);
+    if (rc) return rc;
+    const int nl = h->nlists;
+    size_t bw, kw, nt;
+    mmidx_internal_remove_ws(nrec, h->inv_size, &bw, &kw, &nt);
+    DevPtr<unsigned> d_bits, d_tile_cnt;
+    DevPtr<u64> d_keep;
+    DevPtr<int64_t> d_pre, d_off_new;
+    HIPCK(d_bits.alloc(bw));
+    HIPCK(d_keep.alloc(kw));
+    HIPCK(d_tile_cnt.alloc(nt));
+    HIPCK(d_pre.alloc(nt + 1));
+    HIPCK(d_off_new.alloc((size_t)nl + 1));
+    MmidxRemoveArgs a{};
+    a.d_ids = h->d_ids;
+    a.d_codes = h->d_codes;
+    a.n = nrec;
+    a.rec_bytes = (int)(h->m * h->code_bytes);
+    a.d_off = h->d_off;
+    a.nlists = nl;
+    a.d_req = d_iids;
+    a.nreq = n;
+    a.d_inv = h->ws_inv.p;
+    a.inv_size = h->inv_size;
+    a.d_found = d_found_out;
+    a.d_bits = d_bits;
+    a.d_keep = d_keep;
+    a.d_tile_cnt = d_tile_cnt;
+    a.d_pre = d_pre;
+    a.d_off_new = d_off_new;
+    rc = mmidx_internal_remove_plan(&a, h->stream);
+    if (rc) return rc;
+    std::vector<int64_t> off_new((size_t)nl + 1);  // (the removed count comes with the offsets: records before - off_new[nlists])
+    HIPCK(hipMemcpyAsync(off_new.data(), d_off_new, ((size_t)nl + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+    HIPCK(hipStreamSynchronize(h->stream));
+    const int64_t kept = off_new[(size_t)nl];
+    if (kept < 0 || kept > nrec) return mmidx_fail(MMIDX_ERR_HIP, "remove: %lld survivors of %lld records", (long long)kept, (long long)nrec);
+    if (removed_out) *removed_out = nrec - kept;
+    if (kept == nrec) return MMIDX_OK;  // none of the ids is stored: nothing moves
+    DevPtr<void> d_codes_new;
+    DevPtr<int32_t> d_ids_new;
+    HIPCK(d_codes_new.alloc(std::max<size_t>((size_t)kept * h->m * h->code_bytes, 16)));
+    HIPCK(d_ids_new.alloc(std::max<size_t>((size_t)kept, 4)));
+    rc = mmidx_internal_remove_compact(&a, d_ids_new, d_codes_new, h->stream);
+    if (rc) return rc;
+    HIPCK(hipStreamSynchronize(h->stream));
+    // the swap: from here on nothing can fail
+    h->d_off = std::move(d_off_new);
+    h->d_codes = std::move(d_codes_new);
+    h->d_ids = std::move(d_ids_new);
+    h->h_off = off_new;
+    h->n_csr = kept;
+    h->inv_valid = false;
+    h->xn_valid = false;  // (K3m's per-code norms are rebuilt from the new codes by the next search, as after build_csr)
+    h->max_list_len = 0;
+    h->nonempty_lists = 0;
+    for (int c = 0; c < nl; c++) {
+        const int64_t len = off_new[(size_t)c + 1] - off_new[(size_t)c];
+        h->max_list_len = std::max(h->max_list_len, len);
+        h->nonempty_lists += len > 0;
+    }
+    return MMIDX_OK;
+}
+
+int mmidx_remove(mmidx_index *h, int64_t n, const int32_t *iids, int32_t *found_out, int64_t *removed_out) {
+    if (!h) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null handle");
+    if (n < 0) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "n < 0");
+    if (n > 0 && !iids) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null argument");
+    NOT_ON_SHARDED(h, "mmidx_remove");
+    if (removed_out) *removed_out = 0;
+    if (n == 0) return MMIDX_OK;
+    int rc = set_device(h);
+    if (rc) return rc;
+    DevPtr<int32_t> d_i, d_f;
+    HIPCK(d_i.alloc((size_t)n));
+    if (found_out) HIPCK(d_f.alloc((size_t)n));
+    HIPCK(hipMemcpy(d_i, iids, (size_t)n * 4, hipMemcpyHostToDevice));
+    rc = mmidx_remove_device(h, n, d_i, found_out ? d_f.p : nullptr, removed_out, nullptr);
+    if (rc) return rc;
+    if (found_out) HIPCK(hipMemcpy(found_out, d_f, (size_t)n * 4, hipMemcpyDeviceToHost));
+    return MMIDX_OK;
+}
+
 /* snapshot of the in-memory index, list-major (the layout loadIndexInMemory builds) */
 int mmidx_export(mmidx_index *h, int64_t *list_off_out, int32_t *iids_out, void *codes_out) {
     if (!h || !list_off_out) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null argument");

@@ -294,6 +294,31 @@ MMIDX_HIDDEN int mmidx_internal_ids_found(const int32_t *d_iids, int64_t n, cons
 MMIDX_HIDDEN int mmidx_internal_transpose_square(const double *d_src, double *d_dst, int D, hipStream_t st);
 MMIDX_HIDDEN int mmidx_internal_mark_unknown_rows(const int32_t *d_found, int64_t nq, int k, int32_t *d_iid, double *d_dist, int32_t *d_cnt,
                                                   hipStream_t st);
+// mmidx_remove.hip: K13 on plain device pointers (mmidx_remove.h) -- the stable compaction of the list-major arrays behind mmidx_remove.
+// _ws: the sizes of the three workspaces for n records and a position table of inv_size entries.  _plan: marks the requested ids,
+// writes the keep words, the tile prefixes and the nlists + 1 new list offsets (d_off_new[nlists] = the survivors), and d_found where
+// asked for; nothing of the index is written.  _compact: the survivors' ids and records into arrays the caller sized from d_off_new.
+struct MmidxRemoveArgs {
+    const int32_t *d_ids;   // [n] list-major
+    const void *d_codes;    // [n][rec_bytes]
+    int64_t n;
+    int rec_bytes;          // m * code_bytes
+    const int64_t *d_off;   // [nlists + 1]
+    int nlists;
+    const int32_t *d_req;   // [nreq] the ids to take out
+    int64_t nreq;
+    const int32_t *d_inv;   // iid -> position, -1 = absent
+    int64_t inv_size;
+    int32_t *d_found;       // [nreq] or null
+    unsigned *d_bits;       // [bits_words] one bit per iid
+    void *d_keep;           // [keep_words] 64-bit words, bit l of word w = record 64 w + l stays
+    unsigned *d_tile_cnt;   // [ntiles]
+    int64_t *d_pre;         // [ntiles + 1]
+    int64_t *d_off_new;     // [nlists + 1]
+};
+MMIDX_HIDDEN void mmidx_internal_remove_ws(int64_t n, int64_t inv_size, size_t *bits_words, size_t *keep_words, size_t *ntiles);
+MMIDX_HIDDEN int mmidx_internal_remove_plan(const MmidxRemoveArgs *a, hipStream_t st);
+MMIDX_HIDDEN int mmidx_internal_remove_compact(const MmidxRemoveArgs *a, int32_t *d_ids_new, void *d_codes_new, hipStream_t st);
 // mmidx_linear.hip: what the exact re-ranking (mmidx_search_refine*) reads of a Linear handle -- the fp64 rows in arrival order
 // (row iid = the vector of internal id iid, IndexTransformation.java:113-122), their number, the vector length and the device.
 // _acquire locks l->mu and, where it returns MMIDX_OK, leaves it locked until _release: an add cannot move the rows under a

@@ -148,6 +148,55 @@ class AbstractSearchStructure:
             self.loadCounter += 1
         return len(keep)
 
+    # -- removal (an extension of the reference, which can only index: DESIGN.md section 5.13) --
+    def removeVectors(self, ids):
+        """Take the vectors with these external ids out of the index: their records leave the GPU (remove_batch) and both id maps
+        lose their entries, so isIndexed is false and getInternalId answers -1 afterwards.  An id that is not indexed is reported
+        with a printed line, in the style of indexVector's duplicate check, and skipped.  Returns the number of ids removed.
+        loadCounter is NOT decremented: it hands out internal ids, which must stay unique, and it bounds maxNumVectors as the
+        reference's capacity check does -- a removed record does not give its capacity back."""
+        iids, seen = [], set()
+        for id_ in ids:
+            if not self.isIndexed(id_):
+                print(f"Vector '{id_}' is not indexed!")
+                continue
+            if id_ in seen:
+                continue
+            seen.add(id_)
+            iids.append(self._id_to_iid[id_])
+        if not iids:
+            return 0
+        self.remove_batch(np.array(iids, np.int32))
+        for id_ in seen:
+            self._iid_to_id.pop(self._id_to_iid.pop(id_), None)
+        return len(iids)
+
+    def removeVector(self, id_):
+        """removeVectors for one id: False (and a printed line) where it is not indexed"""
+        return self.removeVectors([id_]) == 1
+
+    def replaceVector(self, id_, vector):
+        """Update: remove, then indexVector.  The record gets a fresh internal id (and, like any add, needs capacity left).
+        What can be refused is refused before the removal -- a wrong length, an id that is not indexed, a full index -- but the two
+        steps are NOT one atomic step: if the native add fails after the removal (a device error, say), the old record is gone and
+        the id is not indexed; the exception of indexVector reaches the caller, who indexes the vector again."""
+        vector = np.asarray(vector, dtype=np.float64)
+        if vector.ndim != 1 or vector.shape[0] != self.vectorLength:
+            raise MmidxError(N.ERR_WRONG_DIM, "The dimensionality of the vector is wrong!")
+        if not self.isIndexed(id_):
+            print(f"Vector '{id_}' is not indexed!")
+            return False
+        if self.loadCounter >= self.maxNumVectors:
+            print("Maximum index capacity reached, no more vectors can be indexed!")
+            return False
+        if not self.removeVector(id_):
+            return False
+        return self.indexVector(id_, vector)
+
+    def remove_batch(self, iids):
+        # (Linear: its internal id is the row number, and the exact re-ranking rests on that -- only PQ and IVFPQ override this)
+        raise MmidxError(N.ERR_UNSUPPORTED, "this index cannot remove records: its internal ids are row numbers")
+
     # -- ASS:281-291, :320-328, :345-373 --
     def computeNearestNeighbors(self, k, query):
         if isinstance(query, str):
@@ -371,6 +420,16 @@ class _PQBase(AbstractSearchStructure):
             i, d, c, _ = self.search_refine_batch(k, R, _f64(query).reshape(1, -1), linear)
         n = int(c[0])
         return self._look_up((i[0, :n].copy(), d[0, :n].copy()), time.perf_counter_ns() - start)
+
+    def remove_batch(self, iids):
+        """mmidx_remove: every stored record whose internal id occurs in `iids` leaves the index; the survivors keep their list and
+        their order inside it.  (found [n] int32: 1 where the id was stored before the call; removed: records, not request entries).
+        Unknown, negative and repeated ids are no error.  The id maps are not touched: removeVectors does that."""
+        q = np.ascontiguousarray(np.asarray(iids).reshape(-1), np.int32)
+        found = np.zeros(q.shape[0], np.int32)
+        removed = C.c_int64(0)
+        N.check(N.lib().mmidx_remove(self._h, q.shape[0], q.ctypes.data, found.ctypes.data, C.byref(removed)))
+        return found, removed.value
 
     def export(self):
         """List-major snapshot (list_off [nlists+1], iids [n], codes [n][m] stored form)."""

@@ -295,6 +295,43 @@ public class GpuIVFPQ extends AbstractSearchStructure {
 		return out;
 	}
 
+	/**
+	 * Takes the vectors with these ids out of the index (no counterpart in the reference, which can only index): their records leave
+	 * the device index in one native call (the survivors keep their list and their order inside it), then the id-map entries and the
+	 * persistent record of each id are deleted. An id that is not indexed is reported and skipped. loadCounter is not decremented: it
+	 * hands out internal ids, which stay unique, and it still bounds maxNumVectors -- a removed vector does not give its capacity back.
+	 * Returns the number of ids removed.
+	 */
+	public synchronized int removeVectors(String[] ids) throws Exception {
+		java.util.LinkedHashMap<String, Integer> present = new java.util.LinkedHashMap<String, Integer>();
+		for (String id : ids) {
+			int iid = getInternalId(id);
+			if (iid == -1) {
+				System.out.println("Vector '" + id + "' is not indexed!");
+				continue;
+			}
+			present.put(id, iid);
+		}
+		if (present.isEmpty()) {
+			return 0;
+		}
+		int[] iids = new int[present.size()];
+		int n = 0;
+		for (int iid : present.values()) {
+			iids[n++] = iid;
+		}
+		MmidxNative.remove(handle, iids, null);
+		for (java.util.Map.Entry<String, Integer> e : present.entrySet()) {
+			DatabaseEntry idKey = new DatabaseEntry(), iidKey = new DatabaseEntry();
+			com.sleepycat.bind.tuple.StringBinding.stringToEntry(e.getKey(), idKey);
+			IntegerBinding.intToEntry(e.getValue(), iidKey);
+			idToIidDB.delete(null, idKey);
+			iidToIdDB.delete(null, iidKey);
+			iidToIvfpqDB.delete(null, iidKey);
+		}
+		return present.size();
+	}
+
 	/** loadIndexInMemory IVFPQ.java:680-728: stream the BDB records to the native bulk add */
 	private void loadIndexInMemory() throws Exception {
 		final int B = 1 << 16;

@@ -82,6 +82,12 @@ public final class MmidxNative {
 	/** mmidx_reconstruct: out[iids.length * vectorLength] = the vectors the index holds for the given internal ids */
 	public static native void reconstruct(long handle, int[] iids, double[] out) throws Exception;
 
+	/**
+	 * mmidx_remove: every stored record with one of these internal ids leaves the index (the survivors keep their list and their
+	 * order inside it); found[n] (may be null) = 1 where the id was stored; returns the number of records removed
+	 */
+	public static native long remove(long handle, int[] iids, int[] found) throws Exception;
+
 	public static native void listSizes(long handle, int[] out) throws Exception;
 
 	/** mmidx_save / mmidx_load (ABI 8): the native flat snapshot -- list offsets, iids and stored codes as loadIndexInMemory builds them */

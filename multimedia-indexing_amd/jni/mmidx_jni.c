@@ -391,6 +391,24 @@ done:
     (*env)->ReleaseDoubleArrayElements(env, out, o, 0);
 }
 
+/* mmidx_remove: every record with one of these internal ids leaves the index; found[n] (may be null) says which ids were stored;
+ * returns the number of records removed */
+JNIEXPORT jlong JNICALL JFN(remove)(JNIEnv *env, jclass c, jlong h, jintArray iids, jintArray found) {
+    jint n, *i, *f = NULL;
+    int64_t removed = 0;
+    (void)c;
+    if (bad_len(env, iids, 0, 0, "iids")) return 0;
+    n = (*env)->GetArrayLength(env, iids);
+    if (bad_len(env, found, n, 1, "found")) return 0;
+    i = (*env)->GetIntArrayElements(env, iids, NULL);
+    if (found) f = (*env)->GetIntArrayElements(env, found, NULL);
+    CHECK(mmidx_remove(H(h), n, (const int32_t *)i, (int32_t *)f, &removed));
+done:
+    (*env)->ReleaseIntArrayElements(env, iids, i, JNI_ABORT);
+    if (found) (*env)->ReleaseIntArrayElements(env, found, f, 0);
+    return (jlong)removed;
+}
+
 JNIEXPORT void JNICALL JFN(listSizes)(JNIEnv *env, jclass c, jlong h, jintArray out) {
     dims_t d;
     jint *o;
