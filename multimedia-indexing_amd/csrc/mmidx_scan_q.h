@@ -47,9 +47,8 @@
 #define MMIDX_Q_SLOTS 6    // keys a lane keeps per query
 #define MMIDX_Q_HKQ 192    // most candidates of one query the final phase takes (< 255: an emitted candidate's pool slot rides in a byte)
 #ifndef MMIDX_Q_U
-#define MMIDX_Q_U 8
+#define MMIDX_Q_U 4       // codes per lane per round of the scan loop; three buffers of a round each, fetched two rounds ahead
 #endif
-//        // codes per lane per round of the scan loop
 #define MMIDX_Q_SCALE 4000.0
 #ifndef Q_STAGSEL
 #define Q_STAGSEL (blockIdx.x >> 8)
@@ -59,9 +58,6 @@
 #endif
 #ifndef Q_TU
 #define Q_TU 4  // table rows in flight per thread (fp32 pairs: 4 registers a row at dsub = 8; 2, 4 and 8 measured the same)
-#endif
-#ifndef Q_CH
-#define Q_CH 4  // independent lookup chains of the scan (2 / 4 / 8: 0.558 / 0.565 / 0.564 ms per 7525 groups -- no difference)
 #endif
 #ifndef Q_FR
 #define Q_FR 2  // codebook rows in flight per candidate where a thread loads its own rows (DSUB = 16); measured at DSUB = 8 before the
@@ -319,10 +315,12 @@ __device__ __forceinline__ void q_scan_group(const QParams &QP, const int4 gd, u
         const u32 ic = min(i, n_seg - 1u);
         dst.load(codes0 + ic * (u32)M);  // (32-bit offset from a uniform base; past the end: the list's last code, never used)
     };
-    // the first round's codes leave now: they are back before the table is built
-    CodeVec<M, unsigned char> X0[U], X1[U];
+    // the first two rounds' codes leave now: they are back before the table is built
+    CodeVec<M, unsigned char> X0[U], X1[U], X2[U];
 #pragma unroll
     for (int u = 0; u < U; u++) fetch(X0[u], (u32)u * NT + (u32)tid);
+#pragma unroll
+    for (int u = 0; u < U; u++) fetch(X1[u], (u32)(U + u) * NT + (u32)tid);
 
     // the table's input: Q_TU rows of the transposed codebook at a time (thread j <-> entry j of every row)
     static_assert(M % Q_TU == 0, "the table is built Q_TU rows at a time");
@@ -473,21 +471,41 @@ __device__ __forceinline__ void q_scan_group(const QParams &QP, const int4 gd, u
     for (int i = 0; i < GA; i++)
 #pragma unroll
         for (int k = 0; k < NS; k++) slot[i][k] = 0xFFFFFFFFu;
-    auto lookup = [&](const CodeVec<M, unsigned char> &cv, u32 &lo, u32 &hi) {
+    // A code's M table entries are REQUESTED back to back (issue) and added up afterwards (sum), each add waiting only for the reads
+    // it consumes (LDS reads return in order: counted lgkmcnt waits).  Left to itself the compiler, at the register limit, sinks
+    // every read to its use -- two reads, a drain, two adds: eight dependent LDS round trips per code.  The scheduling barriers keep
+    // the reads above whatever the caller puts between issue and sum; the reads in flight hold M entries' registers.
+    // (2 / 4 / 8 "independent" lookup chains written in the source measured 0.558 / 0.565 / 0.564 ms per 7525 groups: they never
+    //  reached the ISA.  DESIGN_NOTEBOOK.md 5.19, profiles/r12_k3q_reads_in_flight_harness.txt: the wait pattern before and after.)
+    using QEnt = std::conditional_t<GT == 4, q_u32x2, u32>;
+    auto issue = [&](const CodeVec<M, unsigned char> &cv, QEnt (&e)[M]) {
+#pragma unroll
+        for (int s = 0; s < M; s++) {
+            if constexpr (GT == 4) e[s] = *(lds_cuint2 *)(size_t)(q_byte_shl<3>(cv.wd[s >> 2], s & 3) + (u32)s * 2048u);
+            else if constexpr (GT == 2) e[s] = *(lds_cu32 *)(size_t)(q_byte_shl<2>(cv.wd[s >> 2], s & 3) + (u32)s * 1024u);
+            else e[s] = (u32) * (lds_cu16 *)(size_t)(q_byte_shl<1>(cv.wd[s >> 2], s & 3) + (u32)s * 512u);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    auto sum = [&](const QEnt (&e)[M], u32 &lo, u32 &hi) {
+        __builtin_amdgcn_sched_barrier(0);
         lo = 0;
         hi = 0;
 #pragma unroll
         for (int s = 0; s < M; s++) {
             if constexpr (GT == 4) {
-                const q_u32x2 e = *(lds_cuint2 *)(size_t)(q_byte_shl<3>(cv.wd[s >> 2], s & 3) + (u32)s * 2048u);
-                lo += e.x;
-                hi += e.y;
-            } else if constexpr (GT == 2) {
-                lo += *(lds_cu32 *)(size_t)(q_byte_shl<2>(cv.wd[s >> 2], s & 3) + (u32)s * 1024u);
+                lo += e[s].x;
+                hi += e[s].y;
             } else {
-                lo += (u32) * (lds_cu16 *)(size_t)(q_byte_shl<1>(cv.wd[s >> 2], s & 3) + (u32)s * 512u);
+                lo += e[s];
             }
         }
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    auto lookup = [&](const CodeVec<M, unsigned char> &cv, u32 &lo, u32 &hi) {
+        QEnt e[M];
+        issue(cv, e);
+        sum(e, lo, hi);
     };
     auto insert = [&](u32 (&sl)[NS], const u32 k) {  // sl ascending; k in, the largest out
         u32 prev = sl[0];
@@ -523,30 +541,45 @@ __device__ __forceinline__ void q_scan_group(const QParams &QP, const int4 gd, u
             insert(slot[3], k3);
         }
     };
-    // full rounds: every position is inside the list.  Two rounds per trip, the two code buffers changing roles (no register copies)
+    // full rounds: every position is inside the list.  Three rounds per trip, the three code buffers changing roles (no register
+    // copies): a round scans one buffer while the next one's codes are on their way and the third's are requested
     u32 seg = 0;
     auto round = [&](CodeVec<M, unsigned char> (&cur)[U], CodeVec<M, unsigned char> (&nxt)[U]) {
+        // the first code's reads fly over the next round's fetches, every other code's over the insertions of the code before it
+        QEnt e[M];
+        u32 lo, hi;
+        issue(cur[0], e);
 #pragma unroll
-        for (int u = 0; u < U; u++) fetch(nxt[u], seg + (u32)(U + u) * NT + (u32)tid);
+        for (int u = 0; u < U; u++) fetch(nxt[u], seg + (u32)(2 * U + u) * NT + (u32)tid);
+        sum(e, lo, hi);
 #pragma unroll
-        for (int h4 = 0; h4 < U; h4 += Q_CH) {  // Q_CH independent lookup chains at a time
-            u32 lo[Q_CH], hi[Q_CH];
-#pragma unroll
-            for (int u = 0; u < Q_CH; u++) lookup(cur[h4 + u], lo[u], hi[u]);
-#pragma unroll
-            for (int u = 0; u < Q_CH; u++) keep(lo[u], hi[u], (seg >> 8) + (u32)(h4 + u), true);
+        for (int u = 1; u < U; u++) {
+            const u32 plo = lo, phi = hi;
+            issue(cur[u], e);
+            keep(plo, phi, (seg >> 8) + (u32)(u - 1), true);
+            sum(e, lo, hi);
         }
+        keep(lo, hi, (seg >> 8) + (u32)(U - 1), true);
         seg += (u32)U * NT;
     };
 #pragma unroll 1
-    while (seg + 2u * U * NT <= n_seg) {
-        round(X0, X1);
+    while (seg + 3u * U * NT <= n_seg) {
+        round(X0, X2);
         round(X1, X0);
+        round(X2, X1);
     }
+    // INVARIANT wherever no round is under way: X0 holds the round at seg, X1 the one behind it (a trip puts every buffer back in
+    // its role).  One or two full rounds more -- X0, then X1 --, after which the round at seg is in X1 or in X2: copied to X0 for the tail
     if (seg + (u32)U * NT <= n_seg) {
-        round(X0, X1);
+        round(X0, X2);
+        if (seg + (u32)U * NT <= n_seg) {
+            round(X1, X0);
 #pragma unroll
-        for (int u = 0; u < U; u++) X0[u] = X1[u];
+            for (int u = 0; u < U; u++) X0[u] = X2[u];
+        } else {
+#pragma unroll
+            for (int u = 0; u < U; u++) X0[u] = X1[u];
+        }
     }
     // the rest of the list (fewer than U codes per lane; X0 holds them, clamped past the end)
 #pragma unroll 1
