@@ -289,7 +289,7 @@ struct MMIDX_HIDDEN mmidx_index {
     // profiling: HIP events recorded on the launch stream, resolved lazily by mmidx_get_stats
     int profiling = 0;  // 0 off, 1 full (six events per call + code counters), 2 light (the pass-A pair only)
     mmidx_stats stats{};
-    std::vector<Event> evpool;  // groups of 6: start, coarse end, scan start, scan end, end, pass A end
+    std::vector<Event> evpool;  // groups of EV_SLOTS (EvSlot)
     size_t ev_used = 0;
     std::vector<Event> mf_ev;   // K3m, full profiling: groups of 3 (scan start, scan end, verification end)
     size_t mf_ev_used = 0;
@@ -692,6 +692,15 @@ int launch_grid(const Params &P, dim3 grid, int nt, size_t lds, hipStream_t st, 
     return MMIDX_OK;
 }
 
+// the same for a kernel that takes its arguments one by one
+template <auto K, class... Args>
+int launch_grid_args(dim3 grid, int nt, size_t lds, hipStream_t st, Args... args) {
+    if (const int rc = prepare_launch<K>(lds, StaticLds::unchecked, "")) return rc;
+    hipLaunchKernelGGL(K, grid, dim3((unsigned)nt), lds, st, args...);
+    HIPCK(hipGetLastError());
+    return MMIDX_OK;
+}
+
 // a persistent grid: `blocks` of them (option "mfma_blocks"), or with blocks <= 0 as many as the occupancy allows on every CU; a
 // multiple of eight either way (the kernels map blocks to XCDs)
 template <auto K, class Params>
@@ -1033,6 +1042,11 @@ int use_permuted_queries(mmidx_index *h, Params &S, bool ivf, long long nq, hipS
     return MMIDX_OK;
 }
 
+// The six slots of a search step's event group (mmidx_index::evpool).  Invariant: a step that takes a group records, in stream order,
+// every slot mmidx_get_stats reads for the profiling mode -- profiling 1 all six, profiling 2 EV_SCAN_START and EV_PASSA_END alone -- on
+// every path: phases 0, 1 and 2, with records or without (search_batch_device).
+enum EvSlot { EV_START, EV_COARSE_END, EV_SCAN_START, EV_SCAN_END, EV_END, EV_PASSA_END, EV_SLOTS };
+
 // A group of n profiling events from a pool that grows on demand and is handed back by mmidx_get_stats (`used` = 0); null once the
 // pool holds cap_groups groups (the statistics then miss the call).  The group's first event is recorded on st unless the caller
 // says otherwise.
@@ -1254,11 +1268,11 @@ int launch_a1_verify_t(mmidx_index *h, const MfmaParams &MP, hipStream_t st) {
 
 // ---- K3q (mmidx_scan_q.h): pass A on integers, up to four queries of a nearest list per block -----------------------------------
 // does pass A of this call go through K3q?
-bool passa_q_applies(const mmidx_index *h, const ScanParams &P, const SearchPlan &pl, long long nq) {
-    if (h->sw.passa_q == 0 || !P.ivf || P.sdc_tt || nq <= 0 || !h->d_pqstat || !h->d_pqT32) return false;
+bool passa_q_applies(const mmidx_index *h, const SearchPlan &pl, long long nq, int w, const double *sdc_tt) {
+    if (h->sw.passa_q == 0 || h->kind != MMIDX_KIND_IVFPQ || sdc_tt || nq <= 0 || !h->d_pqstat || !h->d_pqT32) return false;
     if (h->code_bytes != 1 || h->ks != 256 || h->m != 16 || (h->dsub != 4 && h->dsub != 8 && h->dsub != 16)) return false;
     if (pl.K1 + 40 > MMIDX_Q_HKQ) return false;  // (~K1 + 10 candidates per query, and room for ties)
-    if (h->max_list_len >= (1ll << 24) || nq * (long long)P.w >= 0x7fffff00ll) return false;
+    if (h->max_list_len >= (1ll << 24) || nq * (long long)w >= 0x7fffff00ll) return false;
     if (h->transform == MMIDX_TR_ROTATION && !h->d_rot) return false;
     if (h->transform == MMIDX_TR_PERMUTATION && !h->d_perm) return false;
     if (h->sw.passa_q > 0) return true;
@@ -1349,10 +1363,10 @@ PassaMfmaShape passa_mfma_shape(const mmidx_index *h, long long npairs) {
 }
 
 // does pass A of this call go through K3ma?  (all the applicability checks: launch_passa_mfma itself must not fall back after its first launch)
-bool passa_mfma_applies(const mmidx_index *h, const ScanParams &P, const SearchPlan &pl, long long nq) {
-    if (h->sw.passa_mfma == 0 || !P.ivf || h->sw.no_mfma || !h->mfma_ok || !h->xn_valid || h->sw.no_filter || P.sdc_tt || nq <= 0 || h->D > 128) return false;
+bool passa_mfma_applies(const mmidx_index *h, const SearchPlan &pl, long long nq, const double *dQ, int w, const double *sdc_tt) {
+    if (h->sw.passa_mfma == 0 || h->kind != MMIDX_KIND_IVFPQ || h->sw.no_mfma || !h->mfma_ok || !h->xn_valid || h->sw.no_filter || sdc_tt || nq <= 0 || h->D > 128) return false;
     if (pl.K1 > 128) return false;                                             // (a pair keeps 256 values per piece: K1 of them must be there)
-    if (h->max_list_len >= (1ll << 24) || nq * (long long)P.w >= 0x7fffff00ll || ((uintptr_t)P.Q & 15) != 0) return false;
+    if (h->max_list_len >= (1ll << 24) || nq * (long long)w >= 0x7fffff00ll || ((uintptr_t)dQ & 15) != 0) return false;
     if (h->d_perm && !h->d_coarseP) return false;
     if (h->transform == MMIDX_TR_ROTATION && (!h->d_rot || (size_t)nq * h->D * 8 > ((size_t)8 << 30))) return false;
     if (!passa_mfma_shape(h, nq).fits) return false;  // (the sweep-2 bitmap would exceed 32 GiB: one very long list)
@@ -1360,6 +1374,18 @@ bool passa_mfma_applies(const mmidx_index *h, const ScanParams &P, const SearchP
     // from ~8 queries per nearest list, on an index of long lists (where K3h would run): a shard holding a part of the
     // lists sees the same number of queries per LOCAL list
     return nq >= 8ll * h->C && h->n_csr / std::max<int64_t>(1, h->nonempty_lists) >= 4096;
+}
+
+// Pass A's rung for a step of nq queries at dQ with w probes (flat PQ: chunks): K3q, K3ma, or what stage_pass_a tries behind them (K3h,
+// else the exact scan K3).  Chosen once per step, for the ladder and for the one-probe gate of the coarse stage in front of it.  The two
+// read the same inputs: the gates read the handle's options, index shape, tables and list statistics (written by set-up calls, build_csr,
+// build_grp_tables and build_mfma_tables: before the step), the plan and the step's arguments; run_coarse writes cdsel_valid, near_nq,
+// screen_nq, the dispatch labels, screen_auto and workspaces, none of which a gate reads.  K3q and K3ma take two-pass IVFPQ steps only.
+enum class PassA { q, mfma, hist_or_exact };
+PassA pass_a_rung(const mmidx_index *h, const SearchPlan &pl, long long nq, const double *dQ, int w, const double *sdc_tt) {
+    if (w <= 1) return PassA::hist_or_exact;
+    if (passa_q_applies(h, pl, nq, w, sdc_tt) && !(h->sw.passa_mfma > 0 && passa_mfma_applies(h, pl, nq, dQ, w, sdc_tt))) return PassA::q;
+    return passa_mfma_applies(h, pl, nq, dQ, w, sdc_tt) ? PassA::mfma : PassA::hist_or_exact;
 }
 
 // Pass A of the whole sub-batch through K3ma; the thresholds land in P.T and the exact candidates in the pools as K3h leaves them.
@@ -2121,411 +2147,504 @@ int run_coarse(mmidx_index *h, int64_t nq, const double *dQ, int32_t *d_cells, h
 }
 
 
-// one sub-batch (nq <= plan.qb) entirely on device
-int search_batch_device(mmidx_index *h, const SearchPlan &pl, int k, int64_t nq, const double *dQ, const int32_t *d_cells_in,
-                        int mode, int32_t *d_iid, double *d_dist, int32_t *d_cnt, double *d_pdist, long long *d_pkey,
-                        int phase, double *d_T_io, hipStream_t st, const double *sdc_tt = nullptr, const double *d_cdsel_in = nullptr) {
-    // phase 0: whole search.  Sharded search splits it so that the thresholds can be MIN-reduced
-    // across ranks in between: phase 1 = setup + pass A + export T, phase 2 = import T + pass B + merge.
-    const int ivf = h->kind == MMIDX_KIND_IVFPQ;
-    // profiling 1: all six events + the code counters; 2 ("light"): only the two events around pass A -- every event
-    // record is a ~5 us bubble in the stream, and a throughput run should carry as few as the roofline figure needs
-    bool prof = h->profiling == 1, plight = h->profiling == 2;
-    hipEvent_t *ev = nullptr;
-    if (prof || plight) {
-        if (const int rc = take_events(h->evpool, h->ev_used, 6, 4096, st, ev, prof)) return rc;
-        if (!ev) prof = plight = false;  // event pool exhausted: call mmidx_get_stats to drain it
+// ---- the search step ------------------------------------------------------------------------------------------------------------
+// where a step's answers go: ids, distances and counts (mode 0), or a shard's partial lists (mode 1: cnt, pdist, pkey)
+struct SearchOut {
+    int32_t *iid = nullptr;
+    double *dist = nullptr;
+    int32_t *cnt = nullptr;
+    double *pdist = nullptr;
+    long long *pkey = nullptr;
+    SearchOut at(int64_t q0, int k, int K1) const {  // (the rows from query q0 on)
+        return {iid ? iid + q0 * k : nullptr, dist ? dist + q0 * k : nullptr, cnt + q0, pdist ? pdist + q0 * K1 : nullptr, pkey ? pkey + q0 * K1 : nullptr};
     }
-    const int32_t *d_cells = d_cells_in;
-    h->near_nq = 0;
-    h->screen_nq = 0;
-    if (ivf && !d_cells) {
-        HIPCK(h->ws_cells.reserve((size_t)nq * h->w));
-        // The one-probe certificate (DESIGN.md 5.1) stands on what follows in THIS step: the coarse bound applied as k_pair_hist applies
-        // it (enabled, no rotation: lengths are kept exactly), a threshold that is the ADC distance of a code of the nearest list -- what
-        // K3q, K3h and K3 publish, each once a chunk of the list holds more than K1 codes; K3ma is not covered, nor symmetric distances --
-        // and nothing that reports on the probed lists (profiling 1 counts their codes).  A shard's phases and caller-given cells never
-        // come here with it.
-        long long near_min = 0;
-        if (phase == 0 && mode == 0 && h->sw.coarse_near != 0 && h->profiling != 1 && !sdc_tt && h->n_csr > 0 && h->w > 1 &&
-            h->transform != MMIDX_TR_ROTATION && !h->sw.no_bound && std::isfinite(h->rmax)) {
-            ScanParams G{};  // (what the pass A gates read of the parameters)
-            G.ivf = 1;
-            G.Q = dQ;
-            G.w = h->w;
-            const bool q_runs = passa_q_applies(h, G, pl, (long long)nq), ma = passa_mfma_applies(h, G, pl, (long long)nq);
-            if (!ma || (q_runs && h->sw.passa_mfma <= 0)) near_min = (long long)pl.K1 * std::max(pl.nchunks, 1) + 1;
-        }
-        int rc = run_coarse(h, nq, dQ, h->ws_cells.p, st, near_min);
-        if (rc) return rc;
-        d_cells = h->ws_cells.p;
-    }
-    if (prof) HIPCK(hipEventRecord(ev[1], st));
-    HIPCK(h->ws_T.reserve((size_t)nq));
-    HIPCK(h->ws_pcnt.reserve((size_t)nq));
-    HIPCK(h->ws_pkey.reserve((size_t)nq * pl.poolq));
-    HIPCK(h->ws_pval.reserve((size_t)nq * pl.poolq));
-    HIPCK(h->ws_flag.reserve((size_t)nq));
-    bool pcount_zeroed = false;
-    if (phase != 2) {
-        // thresholds, pool counters, per-cell pair counters and the K3h fallback header in one launch
-        int32_t *pc = nullptr;
-        if (ivf) {
-            HIPCK(h->ws_pcount.reserve((size_t)h->C + 1));
-            pc = h->ws_pcount.p;
-            pcount_zeroed = phase == 0;  // (phase 1 ends before the pair sort; phase 2 zeroes them itself)
-        }
-        HIPCK(h->ws_fb.reserve(2 * (size_t)nq * (size_t)std::max(1, pl.nchunks) + 4));
-        const long long span = std::max<long long>((long long)nq, ivf ? (long long)h->C + 1 : 0);
-        hipLaunchKernelGGL(k_step_init, dim3((unsigned)((span + 255) / 256)), dim3(256), 0, st, h->ws_T.p, h->ws_pcnt.p, (long long)nq, pc,
-                           h->C, h->ws_fb.p);
-        HIPCK(hipGetLastError());
-    }
+};
 
+// One sub-batch (nq <= plan.qb) entirely on device: what the caller gives, then what step_begin derives from it.
+// phase 0: whole search.  Sharded search splits it so that the thresholds can be MIN-reduced
+// across ranks in between: phase 1 = setup + pass A + export T, phase 2 = import T + pass B + merge.
+struct SearchStep {
+    mmidx_index *h;
+    const SearchPlan &pl;
+    int k;
+    int64_t nq;
+    const double *dQ;
+    const int32_t *cells_in;  // the caller's probe cells, or null: the step's own coarse stage
+    SearchOut out;
+    hipStream_t st;
+    int mode, phase;
+    const double *sdc_tt, *d_cdsel_in;
+    double *d_T_io;
+    // derived (step_begin; the coarse stage sets the cells in use, the initialisation the pools)
+    const int32_t *cells;
+    bool ivf, empty, two_pass;
+    long long npairs;
+    int grid_chunks;
+    ScanParams P;
+    PassA rung;
+    bool pcount_zeroed;  // ws_pcount holds zeroes for the pair sort: set by the step initialisation, withdrawn by a pass A that counts in it
+    hipEvent_t *ev;      // the step's event group (EvSlot) under prof (profiling 1) or plight (profiling 2)
+    bool prof, plight;
+};
+
+// the fields of the scan parameters that come from the index
+ScanParams index_scan_params(const mmidx_index *h) {
     ScanParams P{};
-    P.Q = dQ;
     P.coarse = h->d_coarse;
     P.pqT = h->d_pqT;
-    P.sdc_tt = sdc_tt;
     P.perm = h->d_perm;
     P.rot = h->d_rot;
-    P.cells = ivf ? d_cells : nullptr;
     P.list_off = h->d_off;
     P.codes = h->d_codes;
-    P.T = h->ws_T.p;
-    P.pool_cnt = h->ws_pcnt.p;
-    P.pool_key = h->ws_pkey.p;
-    P.pool_val = h->ws_pval.p;
     P.D = h->D;
     P.m = h->m;
     P.ks = h->ks;
     P.dsub = h->dsub;
-    P.w = ivf ? h->w : 1;
+    P.ivf = h->kind == MMIDX_KIND_IVFPQ;
+    P.w = P.ivf ? h->w : 1;
     P.transform = h->transform;
-    P.ivf = ivf;
+    return P;
+}
+
+// the event group and everything the stages share
+int step_begin(SearchStep &S) {
+    mmidx_index *h = S.h;
+    const SearchPlan &pl = S.pl;
+    S.ivf = h->kind == MMIDX_KIND_IVFPQ;
+    S.empty = h->n_csr <= 0;
+    // profiling 1: all six events + the code counters; 2 ("light"): only the two events around pass A -- every event
+    // record is a ~5 us bubble in the stream, and a throughput run should carry as few as the roofline figure needs
+    S.prof = h->profiling == 1, S.plight = h->profiling == 2;
+    if (S.prof || S.plight) {
+        if (const int rc = take_events(h->evpool, h->ev_used, EV_SLOTS, 4096, S.st, S.ev, S.prof)) return rc;
+        if (!S.ev) S.prof = S.plight = false;  // event pool exhausted: call mmidx_get_stats to drain it
+    }
+    S.cells = S.cells_in;
+    h->near_nq = 0;
+    h->screen_nq = 0;
+    ScanParams &P = S.P;
+    P = index_scan_params(h);
+    P.Q = S.dQ;
+    P.sdc_tt = S.sdc_tt;
     P.glut = pl.glut ? h->ws_glut.p : nullptr;
     P.chunk = pl.chunk;
     P.K1 = pl.K1;
     P.cap = pl.cap;
     P.poolq = pl.poolq;
-    if (h->n_csr > 0) {
-        // flat PQ: the chunks of the single list play the role of probes (P.w = number of chunks,
-        // item rank = chunk index, cell = 0), so the same two passes apply: chunk 0 fixes the
-        // threshold, the other chunks run through the filtered scan
-        const int grid_chunks = ivf ? pl.nchunks : 1;
-        if (!ivf) P.w = pl.nchunks;
-        const long long npairs = (long long)nq * P.w;
-        const bool two_pass = P.w > 1;
-        if (prof || plight) {
-            HIPCK(hipEventRecord(ev[2], st));
-            if (prof || phase == 2) HIPCK(hipEventRecord(ev[5], st));  // (recorded again behind pass A when it runs)
-        }
-        // pass A: probe rank 0 of every query (all of them for PQ) -- fixes a tight threshold
-        P.order = nullptr;
-        P.rank_lo = 0;
-        P.nrank = two_pass ? 1 : P.w;
-        P.n_items = (int)(nq * P.nrank);
-        P.xcd_remap = 0;
-        // the ladder: K3q -> K3ma -> K3h -> K3, the first whose gate holds.  (The adaptive filter K3f also works from T = +inf, but
-        //  for one list per query the exact scan measured faster -- 1.23 vs ~1.4 ms per 8192 queries -- so pass A never takes it.)
-        int rc = MMIDX_OK;
-        if (phase != 2) {
-            h->disp_passb = "-";
-            h->disp_pre = "-";
-            if (!ivf) h->disp_coarse = h->disp_coarse_mm = "-";
-            if (two_pass && passa_q_applies(h, P, pl, (long long)nq) && !(h->sw.passa_mfma > 0 && passa_mfma_applies(h, P, pl, (long long)nq))) {
-                // K3q: the queries of a nearest list four to a block, decided on integers (mmidx_scan_q.h)
-                h->disp_passa = "K3q";
-                rc = launch_passa_q(h, P, pl, (long long)nq, st);
-                // (its pair sort counted in ws_pcount -- and k_q_scan_groups zeroed the counters again: pcount_zeroed stands)
-            } else if (two_pass && passa_mfma_applies(h, P, pl, (long long)nq)) {
-                // K3ma: >= 8 queries per nearest list -- the list-major matrix-core form (mmidx_scan_mfma_a.h)
-                h->disp_passa = "K3ma";
-                rc = launch_passa_mfma(h, P, pl, (long long)nq, st);
-                pcount_zeroed = false;  // (its pair sort counted in ws_pcount)
-            } else if (two_pass && !sdc_tt && h->sw.passa_hist != 0 &&
-                       (h->sw.passa_hist > 0 || h->n_csr / std::max<int64_t>(1, ivf ? h->nonempty_lists : 1) >= 4096) &&
-                       (rc = launch_scan_hist(h, P, pl, dim3((unsigned)P.n_items, (unsigned)grid_chunks), st)) != 1) {
-                // (K3h ran -- its empty fallback launch is not counted as a scan launch -- or failed with rc > 1)
-                h->disp_passa = "K3h";
-            } else {
-                rc = MMIDX_OK;
-                // one code per thread per segment: smaller candidate buffer -> a fourth block per CU
-                ScanParams PA = P;
-                int su = 2;
-                size_t lds_a = pl.lds;
-                if (two_pass && ivf && !pl.glut && h->code_bytes == 1 && (h->m == 8 || h->m == 16 || h->m == 32)) {  // (the GLUT kernels are SU = 2 only: their buffer keeps pl.cap)
-                    int cap1 = 1;
-                    while (cap1 < pl.K1 + MMIDX_BLOCK) cap1 <<= 1;
-                    PA.cap = cap1;
-                    lds_a = scan_lds_bytes(h, cap1);
-                    su = 1;
-                }
-                // (the kernel launch_scan takes for these parameters)
-                h->disp_passa = pl.glut ? (scan_split_applies(h, PA, lds_a) ? "K3(table in two halves)" : "K3(table in global scratch)")
-                                        : (two_pass ? "K3" : "K3(single pass)");
-                rc = launch_scan(h, PA, dim3((unsigned)P.n_items, (unsigned)grid_chunks), lds_a, st, su);
-            }
-            if (rc) return rc;
-            DBG_SYNC("pass A scan");
-            if (prof || plight) {
-                HIPCK(hipEventRecord(ev[5], st));
-                h->passa_launches += 1;
-                if (!ivf) h->host_passa_codes += nq * std::min<int64_t>(h->n_csr, two_pass ? (int64_t)pl.chunk : h->n_csr);
-            }
-        }
-        if (phase == 1) {
-            hipLaunchKernelGGL(k_T_export, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, st, h->ws_T.p, d_T_io, (long long)nq);
-            HIPCK(hipGetLastError());
-            if (prof) {
-                HIPCK(hipEventRecord(ev[3], st));
-                HIPCK(hipEventRecord(ev[4], st));
-                h->launches += 1;
-            }
-            return MMIDX_OK;
-        }
-        if (phase == 2) {
-            hipLaunchKernelGGL(k_T_import, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, st, d_T_io, h->ws_T.p, (long long)nq);
-            HIPCK(hipGetLastError());
-        }
-        if (two_pass && !ivf) {
-            // flat PQ pass B: chunks 1.. of every query in natural order
-            P.order = nullptr;
-            P.rank_lo = 1;
-            P.nrank = P.w - 1;
-            P.n_items = (int)(nq * P.nrank);
-            P.xcd_remap = 0;
-            h->disp_passb = "K3f";
-            rc = launch_scan_grouped_flat(h, P, pl, (long long)nq, st);
-            if (rc == 1) rc = launch_scan_filtered(h, P, pl, dim3((unsigned)P.n_items, 1), st, 0, &h->disp_passb);
-            if (rc) return rc;
-            DBG_SYNC("pass B scan (flat)");
-        }
-        if (two_pass && ivf) {
-            // pass B order: pairs with probe rank >= 1 that survive the coarse bound, sorted by cell
-            // (device counting sort; needs the thresholds pass A just produced)
-            HIPCK(h->ws_pcount.reserve((size_t)h->C + 1));
-            HIPCK(h->ws_pstart.reserve((size_t)h->C + 1));
-            HIPCK(h->ws_pcursor.reserve((size_t)h->C));
-            HIPCK(h->ws_order.reserve((size_t)npairs));
-            HIPCK(h->ws_keep.reserve((size_t)npairs));
-            if (!pcount_zeroed) HIPCK(hipMemsetAsync(h->ws_pcount.p, 0, ((size_t)h->C + 1) * sizeof(int32_t), st));
-            PairBound PB{};
-            PB.Q = dQ;
-            PB.coarse = h->d_coarse;
-            PB.T = h->ws_T.p;
-            PB.cdsel = (ivf && !d_cells_in && h->cdsel_valid) ? h->ws_cdsel.p : ((ivf && d_cells_in) ? d_cdsel_in : nullptr);
-            PB.cdist = (ivf && !d_cells_in && !h->cdsel_valid) ? h->ws_cdist.p : nullptr;
-            PB.list_off = h->d_off;
-            PB.rmax = h->rmax;
-            PB.D = h->D;
-            PB.C = h->C;
-            PB.enabled = ((h->transform != MMIDX_TR_ROTATION || h->rot_shrink > 0.0) && !h->sw.no_bound) ? 1 : 0;
-            PB.shrink = h->transform == MMIDX_TR_ROTATION ? h->rot_shrink : 1.0;
-            const unsigned g = (unsigned)((npairs + 255) / 256);
-            DBG_SYNC("pair memset");
-            if (h->sw.debug_sync) {
-                std::vector<u64> ht((size_t)nq);
-                std::vector<int32_t> hc((size_t)npairs);
-                (void)hipMemcpy(ht.data(), h->ws_T.p, (size_t)nq * 8, hipMemcpyDeviceToHost);
-                (void)hipMemcpy(hc.data(), d_cells, (size_t)npairs * 4, hipMemcpyDeviceToHost);
-                int ninf = 0, cmin = 1 << 30, cmax = -(1 << 30);
-                for (u64 t : ht) ninf += t >= 0x7FF0000000000000ull;
-                for (int32_t c : hc) { cmin = std::min(cmin, c); cmax = std::max(cmax, c); }
-                fprintf(stderr, "[mmidx] nq=%lld npairs=%lld T inf=%d cells min=%d max=%d rmax=%g D=%d w=%d keep=%p cnt=%p Q=%p coarse=%p T=%p\n", (long long)nq, npairs, ninf, cmin, cmax,
-                        h->rmax, h->D, P.w, (void*)h->ws_keep.p, (void*)h->ws_pcount.p, (void*)dQ, (void*)h->d_coarse, (void*)h->ws_T.p);
-            }
-            // K3s: pairs whose certified Smin reaches the threshold leave before the sort (only where K3g would run, and only when
-            // the figures the device reported for the call before say it pays; a stale figure costs speed, never results)
-            const bool pre_ok = !h->sw.no_grp && h->grp_valid && h->d_pq32T && !h->sw.no_filter && !P.sdc_tt && h->max_list_len < (1 << 24) &&
-                                (h->dsub == 4 || h->dsub == 8 || h->dsub == 16) && npairs < 0x7fffff00ll && ((uintptr_t)dQ & 15) == 0;  // (16-byte loads of the query rows)
-            bool use_pre = false;
-            if (pre_ok && h->sw.smin_pre > 0) use_pre = true;
-            else if (pre_ok && h->sw.smin_pre < 0 && h->D > 128 && h->mfma_ok && !h->sw.no_mfma && h->xn_valid) {
-                // in front of K3mk: the bound costs a tenth of the scan it can save, and there are no K3g figures to go by -- on, unless
-                // the last run removed less than an eighth of the pairs it looked at ([2] in, [0] left): then seven calls go without
-                use_pre = true;
-                if (h->pin_hint) {
-                    volatile int32_t *ph = (volatile int32_t *)h->pin_hint;
-                    if (h->pre_skip > 0) {
-                        h->pre_skip--;
-                        use_pre = false;
-                    } else if (h->pre_on) {
-                        const long long in = ph[2], left = ph[0];
-                        if (in > 0 && left * 8 > in * 7) {
-                            h->pre_skip = 7;
-                            use_pre = false;
-                        }
-                    }
-                }
-            } else if (pre_ok && h->sw.smin_pre < 0 && h->pin_hint) {
-                volatile int32_t *ph = (volatile int32_t *)h->pin_hint;
-                if (h->pre_on) {  // [2] pairs K3s looked at, [0] pairs it left: it stays while it removes a quarter
-                    const long long in = ph[2], left = ph[0];
-                    use_pre = !(in > 0 && left * 4 > in * 3);
-                } else {  // [4] pairs K3g grouped, [5] pairs alive after its table build
-                    const long long in = ph[4], left = ph[5];
-                    use_pre = in > 0 && left * 2 < in;
-                }
-            }
-            h->pre_on = use_pre;
-            h->disp_pre = use_pre ? "K3s" : "-";
-            if (use_pre) {
-                HIPCK(h->ws_cand.reserve((size_t)npairs + 4));
-                HIPCK(h->ws_smin.reserve((size_t)npairs));
-                int32_t *ncand = h->ws_cand.p + npairs;
-                const int32_t *cand_list = h->ws_cand.p;
-                HIPCK(hipMemsetAsync(ncand, 0, sizeof(int32_t), st));
-                const int sgroups = h->m / SMIN_NW;
-                if (sgroups > 1) HIPCK(hipMemsetAsync(h->ws_smin.p, 0, (size_t)npairs * sizeof(double), st));
-                hipLaunchKernelGGL(k_pair_hist, dim3(g), dim3(256), 0, st, d_cells, P.w, 1, npairs, h->ws_pcount.p, h->ws_keep.p, PB, h->ws_cand.p, ncand);
-                DBG_SYNC("pair hist (candidates)");
-                SminParams SP{};
-                SP.Q = dQ;
-                SP.coarse = h->d_coarse;
-                SP.perm = h->d_perm;
-                if (h->d_perm && h->d_coarseP && !h->sw.smin_valu) {  // transformed copies: contiguous loads instead of 8-byte gathers
-                    if (const int rc = use_permuted_queries(h, SP, true, nq, st)) return rc;
-                }
-                SP.cells = d_cells;
-                SP.cand = h->ws_cand.p;
-                SP.ncand = ncand;
-                SP.pq32T = h->d_pq32T;
-                SP.pn32 = h->d_pn32;
-                SP.pnmax = h->d_pnmax;
-                SP.smin = h->ws_smin.p;
-                SP.D = h->D;
-                SP.w = P.w;
-                SP.M = h->m;
-                // (two blocks per CU, but no more blocks than batches: a one-query call would otherwise have 500 blocks load their codebook slices for nothing)
-                const long long nbatch = (npairs + 31) / 32;
-                const dim3 sg((unsigned)sgroups, (unsigned)std::max<long long>(1, std::min<long long>(2 * std::max(h->num_cus, 8) / sgroups, nbatch)));
-                int32_t *hint_cand = h->pin_hint ? h->pin_hint + 2 : nullptr;
-                if (h->dsub == 16 && h->sw.smin_bf16 && !h->sw.smin_valu) {
-                    // first stage: the bf16 bound over every candidate; what it cannot drop becomes the fp32 stage's candidate list
-                    HIPCK(h->ws_cand2.reserve((size_t)npairs + 4));
-                    HIPCK(h->ws_smin1.reserve((size_t)npairs));
-                    int32_t *ncand2 = h->ws_cand2.p + npairs;
-                    HIPCK(hipMemsetAsync(ncand2, 0, sizeof(int32_t), st));
-                    if (sgroups > 1) HIPCK(hipMemsetAsync(h->ws_smin1.p, 0, (size_t)npairs * sizeof(double), st));
-                    SminParams S1 = SP;
-                    S1.smin = h->ws_smin1.p;
-                    hipLaunchKernelGGL(k_pair_smin_bf16, sg, dim3(SMIN_NW * 64), 0, st, S1);
-                    hipLaunchKernelGGL(k_pair_filter1, dim3(g), dim3(256), 0, st, h->ws_cand.p, ncand, P.w, h->ws_T.p, h->ws_smin1.p, h->ws_keep.p,
-                                       h->ws_cand2.p, ncand2, hint_cand);
-                    HIPCK(hipGetLastError());
-                    DBG_SYNC("K3s bf16 stage");
-                    SP.cand = h->ws_cand2.p;
-                    SP.ncand = ncand2;
-                    ncand = ncand2;
-                    cand_list = h->ws_cand2.p;
-                    hint_cand = nullptr;  // (the figure the host steers by is the first stage's input)
-                }
-                for_dsub(h->dsub, [&](auto ds) {
-                    if (h->sw.smin_valu) hipLaunchKernelGGL(k_pair_smin<decltype(ds)::value>, sg, dim3(SMIN_NW * 64), 0, st, SP);  // (A/B: the packed-FMA form)
-                    else hipLaunchKernelGGL(k_pair_smin_mfma<decltype(ds)::value>, sg, dim3(SMIN_NW * 64), 0, st, SP);
-                });
-                HIPCK(hipGetLastError());
-                DBG_SYNC("K3s pair smin");
-                if (getenv("MMIDX_SMIN_DUMP")) {  // (debugging aid: how far above the thresholds the bounds lie)
-                    (void)hipStreamSynchronize(st);
-                    int32_t nc = 0;
-                    (void)hipMemcpy(&nc, ncand, 4, hipMemcpyDeviceToHost);
-                    std::vector<double> sm((size_t)std::max(nc, 1));
-                    std::vector<int32_t> cd((size_t)std::max(nc, 1));
-                    std::vector<u64> tt((size_t)nq);
-                    (void)hipMemcpy(sm.data(), h->ws_smin.p, (size_t)nc * 8, hipMemcpyDeviceToHost);
-                    (void)hipMemcpy(cd.data(), cand_list, (size_t)nc * 4, hipMemcpyDeviceToHost);
-                    (void)hipMemcpy(tt.data(), h->ws_T.p, (size_t)nq * 8, hipMemcpyDeviceToHost);
-                    long long hist[12] = {0};
-                    for (int i = 0; i < nc; i++) {
-                        double td;
-                        memcpy(&td, &tt[(size_t)(cd[(size_t)i] / P.w)], 8);
-                        const double r = sm[(size_t)i] / td;
-                        int b = r < 1.0 ? 0 : (r < 1.25 ? 1 : (r < 1.5 ? 2 : (r < 2 ? 3 : (r < 3 ? 4 : (r < 4 ? 5 : (r < 6 ? 6 : (r < 8 ? 7 : 8)))))));
-                        hist[b]++;
-                    }
-                    fprintf(stderr, "[mmidx] K3s: %d candidates; Smin_lo / T: <1: %lld, <1.25: %lld, <1.5: %lld, <2: %lld, <3: %lld, <4: %lld, <6: %lld, <8: %lld, more: %lld\n", nc,
-                            hist[0], hist[1], hist[2], hist[3], hist[4], hist[5], hist[6], hist[7], hist[8]);
-                }
-                hipLaunchKernelGGL(k_pair_recount, dim3(g), dim3(256), 0, st, cand_list, ncand, d_cells, P.w, h->ws_T.p, h->ws_smin.p, h->ws_keep.p,
-                                   h->ws_pcount.p, h->C, hint_cand);
-                DBG_SYNC("pair recount");
-            } else {
-                hipLaunchKernelGGL(k_pair_hist, dim3(g), dim3(256), 0, st, d_cells, P.w, 1, npairs, h->ws_pcount.p, h->ws_keep.p, PB, (int32_t *)nullptr,
-                                   (int32_t *)nullptr);
-            }
-            DBG_SYNC("pair hist");
-            hipLaunchKernelGGL(k_pair_scan, dim3(1), dim3(1024), 0, st, h->ws_pcount.p, h->C, h->ws_pstart.p, h->ws_pcursor.p, h->pin_hint);
-            if (h->hint_calls < (1 << 30)) h->hint_calls++;  // (this call's count reaches pin_hint[0] when the kernel has run)
-            h->hint_prev_nq = h->hint_last_nq;  // (what the count the next stage reads was measured on: the call before this one)
-            h->hint_prev_w = h->hint_last_w;
-            h->hint_last_nq = nq;
-            h->hint_last_w = P.w;
-            DBG_SYNC("pair scan");
-            hipLaunchKernelGGL(k_pair_scatter, dim3(g), dim3(256), 0, st, d_cells, P.w, 1, npairs, h->ws_pstart.p, h->ws_pcursor.p,
-                               h->ws_order.p, h->ws_keep.p);
-            HIPCK(hipGetLastError());
-            DBG_SYNC("pair sort");
-            if (h->sw.debug_sync) {
-                int32_t nsurv = 0;
-                (void)hipMemcpy(&nsurv, h->ws_pstart.p + h->C, 4, hipMemcpyDeviceToHost);
-                fprintf(stderr, "[mmidx] pass B: %d of %lld (query, probe) pairs survive the coarse bound (rmax %.4f)\n", nsurv,
-                        (long long)nq * (P.w - 1), h->rmax);
-            }
-            // pass B: the surviving pairs, list-major; the grid covers the worst case, blocks past
-            // the device-side count exit at once
-            P.order = h->ws_order.p;
-            P.n_order = h->ws_pstart.p + h->C;
-            P.n_items = (int)(nq * (P.w - 1));
-            P.xcd_remap = 1;
-            h->disp_passb = "K3f";
-            rc = launch_scan_grouped(h, P, pl, (long long)nq, npairs, st);
-            if (rc == 1) {
-                const unsigned gx = (unsigned)(((P.n_items + 7) / 8) * 8);
-                rc = launch_scan_filtered(h, P, pl, dim3(gx, (unsigned)pl.nchunks), st, 0, &h->disp_passb);
-            }
-            if (rc) return rc;
-            DBG_SYNC("pass B scan");
-        }
-        if (prof) HIPCK(hipEventRecord(ev[3], st));
-        if (prof) h->launches += (two_pass ? 1 : 0) + (phase != 2 ? 1 : 0);
+    // flat PQ: the chunks of the single list play the role of probes (P.w = number of chunks,
+    // item rank = chunk index, cell = 0), so the same two passes apply: chunk 0 fixes the
+    // threshold, the other chunks run through the filtered scan
+    if (!S.ivf && !S.empty) P.w = pl.nchunks;
+    S.grid_chunks = S.ivf ? pl.nchunks : 1;
+    S.npairs = (long long)S.nq * P.w;
+    S.two_pass = P.w > 1;
+    S.rung = PassA::hist_or_exact;
+    if (S.empty) return MMIDX_OK;
+    // pass A: probe rank 0 of every query (all of them for PQ), in natural order -- fixes a tight threshold
+    P.nrank = S.two_pass ? 1 : P.w;
+    P.n_items = (int)(S.nq * P.nrank);
+    if (S.phase != 2) S.rung = pass_a_rung(h, pl, (long long)S.nq, S.dQ, P.w, S.sdc_tt);
+    return MMIDX_OK;
+}
+
+int stage_coarse(SearchStep &S) {
+    mmidx_index *h = S.h;
+    const SearchPlan &pl = S.pl;
+    if (S.ivf && !S.cells_in) {
+        HIPCK(h->ws_cells.reserve((size_t)S.nq * h->w));
+        // The one-probe certificate (DESIGN.md 5.1) stands on what follows in THIS step: the coarse bound applied as k_pair_hist applies
+        // it (enabled, no rotation: lengths are kept exactly), a threshold that is the ADC distance of a code of the nearest list -- what
+        // K3q, K3h and K3 publish, each once a chunk of the list holds more than K1 codes; K3ma is not covered (pass_a_rung, the choice
+        // stage_pass_a follows), nor symmetric distances -- and nothing that reports on the probed lists (profiling 1 counts their
+        // codes).  A shard's phases and caller-given cells never come here with it.
+        long long near_min = 0;
+        if (S.phase == 0 && S.mode == 0 && h->sw.coarse_near != 0 && h->profiling != 1 && !S.sdc_tt && !S.empty && h->w > 1 &&
+            h->transform != MMIDX_TR_ROTATION && !h->sw.no_bound && std::isfinite(h->rmax) && S.rung != PassA::mfma)
+            near_min = (long long)pl.K1 * std::max(pl.nchunks, 1) + 1;
+        if (const int rc = run_coarse(h, S.nq, S.dQ, h->ws_cells.p, S.st, near_min)) return rc;
+        S.cells = h->ws_cells.p;
+    }
+    S.P.cells = S.ivf ? S.cells : nullptr;
+    return MMIDX_OK;
+}
+
+// the per-query workspaces and k_step_init
+int stage_init(SearchStep &S) {
+    mmidx_index *h = S.h;
+    const SearchPlan &pl = S.pl;
+    const int64_t nq = S.nq;
+    HIPCK(h->ws_T.reserve((size_t)nq));
+    HIPCK(h->ws_pcnt.reserve((size_t)nq));
+    HIPCK(h->ws_pkey.reserve((size_t)nq * pl.poolq));
+    HIPCK(h->ws_pval.reserve((size_t)nq * pl.poolq));
+    HIPCK(h->ws_flag.reserve((size_t)nq));
+    S.P.T = h->ws_T.p;
+    S.P.pool_cnt = h->ws_pcnt.p;
+    S.P.pool_key = h->ws_pkey.p;
+    S.P.pool_val = h->ws_pval.p;
+    if (S.phase == 2) return MMIDX_OK;
+    // thresholds, pool counters, per-cell pair counters and the K3h fallback header in one launch
+    int32_t *pc = nullptr;
+    if (S.ivf) {
+        HIPCK(h->ws_pcount.reserve((size_t)h->C + 1));
+        pc = h->ws_pcount.p;
+        S.pcount_zeroed = S.phase == 0;  // (phase 1 ends before the pair sort; phase 2 zeroes them itself)
+    }
+    HIPCK(h->ws_fb.reserve(2 * (size_t)nq * (size_t)std::max(1, pl.nchunks) + 4));
+    const long long span = std::max<long long>((long long)nq, S.ivf ? (long long)h->C + 1 : 0);
+    hipLaunchKernelGGL(k_step_init, dim3((unsigned)((span + 255) / 256)), dim3(256), 0, S.st, h->ws_T.p, h->ws_pcnt.p, (long long)nq, pc,
+                       h->C, h->ws_fb.p);
+    HIPCK(hipGetLastError());
+    return MMIDX_OK;
+}
+
+// the ladder: K3q -> K3ma -> K3h -> K3, the first whose gate holds.  (The adaptive filter K3f also works from T = +inf, but
+//  for one list per query the exact scan measured faster -- 1.23 vs ~1.4 ms per 8192 queries -- so pass A never takes it.)
+int stage_pass_a(SearchStep &S) {
+    mmidx_index *h = S.h;
+    const SearchPlan &pl = S.pl;
+    const ScanParams &P = S.P;
+    hipStream_t st = S.st;
+    const long long nq = (long long)S.nq;
+    const bool ivf = S.ivf, two_pass = S.two_pass;
+    int rc = MMIDX_OK;
+    h->disp_passb = "-";
+    h->disp_pre = "-";
+    if (!ivf) h->disp_coarse = h->disp_coarse_mm = "-";
+    if (S.rung == PassA::q) {
+        // K3q: the queries of a nearest list four to a block, decided on integers (mmidx_scan_q.h)
+        h->disp_passa = "K3q";
+        rc = launch_passa_q(h, P, pl, nq, st);
+        // (its pair sort counted in ws_pcount -- and k_q_scan_groups zeroed the counters again: pcount_zeroed stands)
+    } else if (S.rung == PassA::mfma) {
+        // K3ma: >= 8 queries per nearest list -- the list-major matrix-core form (mmidx_scan_mfma_a.h)
+        h->disp_passa = "K3ma";
+        rc = launch_passa_mfma(h, P, pl, nq, st);
+        S.pcount_zeroed = false;  // (its pair sort counted in ws_pcount)
+    } else if (two_pass && !S.sdc_tt && h->sw.passa_hist != 0 &&
+               (h->sw.passa_hist > 0 || h->n_csr / std::max<int64_t>(1, ivf ? h->nonempty_lists : 1) >= 4096) &&
+               (rc = launch_scan_hist(h, P, pl, dim3((unsigned)P.n_items, (unsigned)S.grid_chunks), st)) != 1) {
+        // (K3h ran -- its empty fallback launch is not counted as a scan launch -- or failed with rc > 1)
+        h->disp_passa = "K3h";
     } else {
-        if (plight) {
-            HIPCK(hipEventRecord(ev[2], st));
-            HIPCK(hipEventRecord(ev[5], st));
+        rc = MMIDX_OK;
+        // one code per thread per segment: smaller candidate buffer -> a fourth block per CU
+        ScanParams PA = P;
+        int su = 2;
+        size_t lds_a = pl.lds;
+        if (two_pass && ivf && !pl.glut && h->code_bytes == 1 && (h->m == 8 || h->m == 16 || h->m == 32)) {  // (the GLUT kernels are SU = 2 only: their buffer keeps pl.cap)
+            int cap1 = 1;
+            while (cap1 < pl.K1 + MMIDX_BLOCK) cap1 <<= 1;
+            PA.cap = cap1;
+            lds_a = scan_lds_bytes(h, cap1);
+            su = 1;
         }
-        if (prof) {
-            HIPCK(hipEventRecord(ev[2], st));
-            HIPCK(hipEventRecord(ev[5], st));
-            HIPCK(hipEventRecord(ev[3], st));
+        // (the kernel launch_scan takes for these parameters)
+        h->disp_passa = pl.glut ? (scan_split_applies(h, PA, lds_a) ? "K3(table in two halves)" : "K3(table in global scratch)")
+                                : (two_pass ? "K3" : "K3(single pass)");
+        rc = launch_scan(h, PA, dim3((unsigned)P.n_items, (unsigned)S.grid_chunks), lds_a, st, su);
+    }
+    if (rc) return rc;
+    DBG_SYNC("pass A scan");
+    if (S.prof || S.plight) {
+        h->passa_launches += 1;
+        if (!ivf) h->host_passa_codes += nq * std::min<int64_t>(h->n_csr, two_pass ? (int64_t)pl.chunk : h->n_csr);
+    }
+    return MMIDX_OK;
+}
+
+// a shard's thresholds out (phase 1), the reduced ones back in (phase 2)
+int stage_thresholds(SearchStep &S) {
+    const dim3 g((unsigned)((S.nq + 255) / 256));
+    if (S.phase == 1) hipLaunchKernelGGL(k_T_export, g, dim3(256), 0, S.st, S.h->ws_T.p, S.d_T_io, (long long)S.nq);
+    else hipLaunchKernelGGL(k_T_import, g, dim3(256), 0, S.st, S.d_T_io, S.h->ws_T.p, (long long)S.nq);
+    HIPCK(hipGetLastError());
+    return MMIDX_OK;
+}
+
+// flat PQ pass B: chunks 1.. of every query in natural order
+int stage_pass_b_flat(SearchStep &S) {
+    mmidx_index *h = S.h;
+    ScanParams &P = S.P;
+    hipStream_t st = S.st;
+    P.order = nullptr;
+    P.rank_lo = 1;
+    P.nrank = P.w - 1;
+    P.n_items = (int)(S.nq * P.nrank);
+    P.xcd_remap = 0;
+    h->disp_passb = "K3f";
+    int rc = launch_scan_grouped_flat(h, P, S.pl, (long long)S.nq, st);
+    if (rc == 1) rc = launch_scan_filtered(h, P, S.pl, dim3((unsigned)P.n_items, 1), st, 0, &h->disp_passb);
+    if (rc) return rc;
+    DBG_SYNC("pass B scan (flat)");
+    return MMIDX_OK;
+}
+
+// (debug_sync) what the pair bound is about to read
+void dump_pair_inputs(const SearchStep &S) {
+    const mmidx_index *h = S.h;
+    std::vector<u64> ht((size_t)S.nq);
+    std::vector<int32_t> hc((size_t)S.npairs);
+    (void)hipMemcpy(ht.data(), h->ws_T.p, (size_t)S.nq * 8, hipMemcpyDeviceToHost);
+    (void)hipMemcpy(hc.data(), S.cells, (size_t)S.npairs * 4, hipMemcpyDeviceToHost);
+    int ninf = 0, cmin = 1 << 30, cmax = -(1 << 30);
+    for (u64 t : ht) ninf += t >= 0x7FF0000000000000ull;
+    for (int32_t c : hc) { cmin = std::min(cmin, c); cmax = std::max(cmax, c); }
+    fprintf(stderr, "[mmidx] nq=%lld npairs=%lld T inf=%d cells min=%d max=%d rmax=%g D=%d w=%d keep=%p cnt=%p Q=%p coarse=%p T=%p\n", (long long)S.nq, S.npairs, ninf, cmin, cmax,
+            h->rmax, h->D, S.P.w, (void*)h->ws_keep.p, (void*)h->ws_pcount.p, (void*)S.dQ, (void*)h->d_coarse, (void*)h->ws_T.p);
+}
+
+// (debug_sync) how many pairs the sort kept
+void dump_pair_survivors(const SearchStep &S) {
+    const mmidx_index *h = S.h;
+    int32_t nsurv = 0;
+    (void)hipMemcpy(&nsurv, h->ws_pstart.p + h->C, 4, hipMemcpyDeviceToHost);
+    fprintf(stderr, "[mmidx] pass B: %d of %lld (query, probe) pairs survive the coarse bound (rmax %.4f)\n", nsurv,
+            (long long)S.nq * (S.P.w - 1), h->rmax);
+}
+
+// (MMIDX_SMIN_DUMP, a debugging aid) how far above the thresholds K3s's bounds lie
+void dump_smin_hist(const SearchStep &S, const int32_t *ncand, const int32_t *cand_list) {
+    const mmidx_index *h = S.h;
+    (void)hipStreamSynchronize(S.st);
+    int32_t nc = 0;
+    (void)hipMemcpy(&nc, ncand, 4, hipMemcpyDeviceToHost);
+    std::vector<double> sm((size_t)std::max(nc, 1));
+    std::vector<int32_t> cd((size_t)std::max(nc, 1));
+    std::vector<u64> tt((size_t)S.nq);
+    (void)hipMemcpy(sm.data(), h->ws_smin.p, (size_t)nc * 8, hipMemcpyDeviceToHost);
+    (void)hipMemcpy(cd.data(), cand_list, (size_t)nc * 4, hipMemcpyDeviceToHost);
+    (void)hipMemcpy(tt.data(), h->ws_T.p, (size_t)S.nq * 8, hipMemcpyDeviceToHost);
+    long long hist[12] = {0};
+    for (int i = 0; i < nc; i++) {
+        double td;
+        memcpy(&td, &tt[(size_t)(cd[(size_t)i] / S.P.w)], 8);
+        const double r = sm[(size_t)i] / td;
+        int b = r < 1.0 ? 0 : (r < 1.25 ? 1 : (r < 1.5 ? 2 : (r < 2 ? 3 : (r < 3 ? 4 : (r < 4 ? 5 : (r < 6 ? 6 : (r < 8 ? 7 : 8)))))));
+        hist[b]++;
+    }
+    fprintf(stderr, "[mmidx] K3s: %d candidates; Smin_lo / T: <1: %lld, <1.25: %lld, <1.5: %lld, <2: %lld, <3: %lld, <4: %lld, <6: %lld, <8: %lld, more: %lld\n", nc,
+            hist[0], hist[1], hist[2], hist[3], hist[4], hist[5], hist[6], hist[7], hist[8]);
+}
+
+// K3s: pairs whose certified Smin reaches the threshold leave before the sort (only where K3g would run, and only when
+// the figures the device reported for the call before say it pays; a stale figure costs speed, never results).  The decision, which
+// keeps its state on the handle: pre_on (K3s ran in the call before) and pre_skip (calls still to go without it).
+bool k3s_decide(mmidx_index *h, const SearchStep &S) {
+    const bool pre_ok = !h->sw.no_grp && h->grp_valid && h->d_pq32T && !h->sw.no_filter && !S.sdc_tt && h->max_list_len < (1 << 24) &&
+                        (h->dsub == 4 || h->dsub == 8 || h->dsub == 16) && S.npairs < 0x7fffff00ll && ((uintptr_t)S.dQ & 15) == 0;  // (16-byte loads of the query rows)
+    bool use_pre = false;
+    if (pre_ok && h->sw.smin_pre > 0) use_pre = true;
+    else if (pre_ok && h->sw.smin_pre < 0 && h->D > 128 && h->mfma_ok && !h->sw.no_mfma && h->xn_valid) {
+        // in front of K3mk: the bound costs a tenth of the scan it can save, and there are no K3g figures to go by -- on, unless
+        // the last run removed less than an eighth of the pairs it looked at ([2] in, [0] left): then seven calls go without
+        use_pre = true;
+        if (h->pin_hint) {
+            volatile int32_t *ph = (volatile int32_t *)h->pin_hint;
+            if (h->pre_skip > 0) {
+                h->pre_skip--;
+                use_pre = false;
+            } else if (h->pre_on) {
+                const long long in = ph[2], left = ph[0];
+                if (in > 0 && left * 8 > in * 7) {
+                    h->pre_skip = 7;
+                    use_pre = false;
+                }
+            }
         }
-        if (phase == 1) {
-            hipLaunchKernelGGL(k_T_export, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, st, h->ws_T.p, d_T_io, (long long)nq);
-            HIPCK(hipGetLastError());
-            if (prof) HIPCK(hipEventRecord(ev[4], st));
-            return MMIDX_OK;
+    } else if (pre_ok && h->sw.smin_pre < 0 && h->pin_hint) {
+        volatile int32_t *ph = (volatile int32_t *)h->pin_hint;
+        if (h->pre_on) {  // [2] pairs K3s looked at, [0] pairs it left: it stays while it removes a quarter
+            const long long in = ph[2], left = ph[0];
+            use_pre = !(in > 0 && left * 4 > in * 3);
+        } else {  // [4] pairs K3g grouped, [5] pairs alive after its table build
+            const long long in = ph[4], left = ph[5];
+            use_pre = in > 0 && left * 2 < in;
         }
     }
+    h->pre_on = use_pre;
+    return use_pre;
+}
+
+// K3s's launches: the pair bound with a candidate list, the Smin bounds of the candidates, the recount of what they leave
+int launch_k3s(SearchStep &S, const PairBound &PB, unsigned g) {
+    mmidx_index *h = S.h;
+    const ScanParams &P = S.P;
+    hipStream_t st = S.st;
+    const long long npairs = S.npairs;
+    HIPCK(h->ws_cand.reserve((size_t)npairs + 4));
+    HIPCK(h->ws_smin.reserve((size_t)npairs));
+    int32_t *ncand = h->ws_cand.p + npairs;
+    const int32_t *cand_list = h->ws_cand.p;
+    HIPCK(hipMemsetAsync(ncand, 0, sizeof(int32_t), st));
+    const int sgroups = h->m / SMIN_NW;
+    if (sgroups > 1) HIPCK(hipMemsetAsync(h->ws_smin.p, 0, (size_t)npairs * sizeof(double), st));
+    hipLaunchKernelGGL(k_pair_hist, dim3(g), dim3(256), 0, st, S.cells, P.w, 1, npairs, h->ws_pcount.p, h->ws_keep.p, PB, h->ws_cand.p, ncand);
+    DBG_SYNC("pair hist (candidates)");
+    SminParams SP{};
+    SP.Q = S.dQ;
+    SP.coarse = h->d_coarse;
+    SP.perm = h->d_perm;
+    if (h->d_perm && h->d_coarseP && !h->sw.smin_valu) {  // transformed copies: contiguous loads instead of 8-byte gathers
+        if (const int rc = use_permuted_queries(h, SP, true, S.nq, st)) return rc;
+    }
+    SP.cells = S.cells;
+    SP.cand = h->ws_cand.p;
+    SP.ncand = ncand;
+    SP.pq32T = h->d_pq32T;
+    SP.pn32 = h->d_pn32;
+    SP.pnmax = h->d_pnmax;
+    SP.smin = h->ws_smin.p;
+    SP.D = h->D;
+    SP.w = P.w;
+    SP.M = h->m;
+    // (two blocks per CU, but no more blocks than batches: a one-query call would otherwise have 500 blocks load their codebook slices for nothing)
+    const long long nbatch = (npairs + 31) / 32;
+    const dim3 sg((unsigned)sgroups, (unsigned)std::max<long long>(1, std::min<long long>(2 * std::max(h->num_cus, 8) / sgroups, nbatch)));
+    int32_t *hint_cand = h->pin_hint ? h->pin_hint + 2 : nullptr;
+    if (h->dsub == 16 && h->sw.smin_bf16 && !h->sw.smin_valu) {
+        // first stage: the bf16 bound over every candidate; what it cannot drop becomes the fp32 stage's candidate list
+        HIPCK(h->ws_cand2.reserve((size_t)npairs + 4));
+        HIPCK(h->ws_smin1.reserve((size_t)npairs));
+        int32_t *ncand2 = h->ws_cand2.p + npairs;
+        HIPCK(hipMemsetAsync(ncand2, 0, sizeof(int32_t), st));
+        if (sgroups > 1) HIPCK(hipMemsetAsync(h->ws_smin1.p, 0, (size_t)npairs * sizeof(double), st));
+        SminParams S1 = SP;
+        S1.smin = h->ws_smin1.p;
+        hipLaunchKernelGGL(k_pair_smin_bf16, sg, dim3(SMIN_NW * 64), 0, st, S1);
+        hipLaunchKernelGGL(k_pair_filter1, dim3(g), dim3(256), 0, st, h->ws_cand.p, ncand, P.w, h->ws_T.p, h->ws_smin1.p, h->ws_keep.p,
+                           h->ws_cand2.p, ncand2, hint_cand);
+        HIPCK(hipGetLastError());
+        DBG_SYNC("K3s bf16 stage");
+        SP.cand = h->ws_cand2.p;
+        SP.ncand = ncand2;
+        ncand = ncand2;
+        cand_list = h->ws_cand2.p;
+        hint_cand = nullptr;  // (the figure the host steers by is the first stage's input)
+    }
+    for_dsub(h->dsub, [&](auto ds) {
+        if (h->sw.smin_valu) hipLaunchKernelGGL(k_pair_smin<decltype(ds)::value>, sg, dim3(SMIN_NW * 64), 0, st, SP);  // (A/B: the packed-FMA form)
+        else hipLaunchKernelGGL(k_pair_smin_mfma<decltype(ds)::value>, sg, dim3(SMIN_NW * 64), 0, st, SP);
+    });
+    HIPCK(hipGetLastError());
+    DBG_SYNC("K3s pair smin");
+    if (getenv("MMIDX_SMIN_DUMP")) dump_smin_hist(S, ncand, cand_list);
+    hipLaunchKernelGGL(k_pair_recount, dim3(g), dim3(256), 0, st, cand_list, ncand, S.cells, P.w, h->ws_T.p, h->ws_smin.p, h->ws_keep.p,
+                       h->ws_pcount.p, h->C, hint_cand);
+    DBG_SYNC("pair recount");
+    return MMIDX_OK;
+}
+
+// pass B order: pairs with probe rank >= 1 that survive the coarse bound, sorted by cell
+// (device counting sort; needs the thresholds pass A just produced)
+int stage_pair_sort(SearchStep &S) {
+    mmidx_index *h = S.h;
+    const ScanParams &P = S.P;
+    hipStream_t st = S.st;
+    const long long npairs = S.npairs;
+    HIPCK(h->ws_pcount.reserve((size_t)h->C + 1));
+    HIPCK(h->ws_pstart.reserve((size_t)h->C + 1));
+    HIPCK(h->ws_pcursor.reserve((size_t)h->C));
+    HIPCK(h->ws_order.reserve((size_t)npairs));
+    HIPCK(h->ws_keep.reserve((size_t)npairs));
+    if (!S.pcount_zeroed) HIPCK(hipMemsetAsync(h->ws_pcount.p, 0, ((size_t)h->C + 1) * sizeof(int32_t), st));
+    PairBound PB{};
+    PB.Q = S.dQ;
+    PB.coarse = h->d_coarse;
+    PB.T = h->ws_T.p;
+    PB.cdsel = (!S.cells_in && h->cdsel_valid) ? h->ws_cdsel.p : (S.cells_in ? S.d_cdsel_in : nullptr);
+    PB.cdist = (!S.cells_in && !h->cdsel_valid) ? h->ws_cdist.p : nullptr;
+    PB.list_off = h->d_off;
+    PB.rmax = h->rmax;
+    PB.D = h->D;
+    PB.C = h->C;
+    PB.enabled = ((h->transform != MMIDX_TR_ROTATION || h->rot_shrink > 0.0) && !h->sw.no_bound) ? 1 : 0;
+    PB.shrink = h->transform == MMIDX_TR_ROTATION ? h->rot_shrink : 1.0;
+    const unsigned g = (unsigned)((npairs + 255) / 256);
+    DBG_SYNC("pair memset");
+    if (h->sw.debug_sync) dump_pair_inputs(S);
+    const bool use_pre = k3s_decide(h, S);
+    h->disp_pre = use_pre ? "K3s" : "-";
+    if (use_pre) {
+        if (const int rc = launch_k3s(S, PB, g)) return rc;
+    } else {
+        hipLaunchKernelGGL(k_pair_hist, dim3(g), dim3(256), 0, st, S.cells, P.w, 1, npairs, h->ws_pcount.p, h->ws_keep.p, PB, (int32_t *)nullptr,
+                           (int32_t *)nullptr);
+    }
+    DBG_SYNC("pair hist");
+    hipLaunchKernelGGL(k_pair_scan, dim3(1), dim3(1024), 0, st, h->ws_pcount.p, h->C, h->ws_pstart.p, h->ws_pcursor.p, h->pin_hint);
+    if (h->hint_calls < (1 << 30)) h->hint_calls++;  // (this call's count reaches pin_hint[0] when the kernel has run)
+    h->hint_prev_nq = h->hint_last_nq;  // (what the count the next stage reads was measured on: the call before this one)
+    h->hint_prev_w = h->hint_last_w;
+    h->hint_last_nq = S.nq;
+    h->hint_last_w = P.w;
+    DBG_SYNC("pair scan");
+    hipLaunchKernelGGL(k_pair_scatter, dim3(g), dim3(256), 0, st, S.cells, P.w, 1, npairs, h->ws_pstart.p, h->ws_pcursor.p,
+                       h->ws_order.p, h->ws_keep.p);
+    HIPCK(hipGetLastError());
+    DBG_SYNC("pair sort");
+    if (h->sw.debug_sync) dump_pair_survivors(S);
+    return MMIDX_OK;
+}
+
+// pass B: the surviving pairs, list-major; the grid covers the worst case, blocks past
+// the device-side count exit at once
+int stage_pass_b_ivf(SearchStep &S) {
+    mmidx_index *h = S.h;
+    ScanParams &P = S.P;
+    hipStream_t st = S.st;
+    P.order = h->ws_order.p;
+    P.n_order = h->ws_pstart.p + h->C;
+    P.n_items = (int)(S.nq * (P.w - 1));
+    P.xcd_remap = 1;
+    h->disp_passb = "K3f";
+    int rc = launch_scan_grouped(h, P, S.pl, (long long)S.nq, S.npairs, st);
+    if (rc == 1) {
+        const unsigned gx = (unsigned)(((P.n_items + 7) / 8) * 8);
+        rc = launch_scan_filtered(h, P, S.pl, dim3(gx, (unsigned)S.pl.nchunks), st, 0, &h->disp_passb);
+    }
+    if (rc) return rc;
+    DBG_SYNC("pass B scan");
+    return MMIDX_OK;
+}
+
+// K4's two block sizes
+template <class F>
+auto for_merge_block(bool small, F &&f) {
+    if (small) return f(std::integral_constant<int, 128>{});
+    return f(std::integral_constant<int, MMIDX_BLOCK>{});
+}
+// a scan's code form: (CodeT, SDC) = symmetric distances on byte codes, byte codes, short codes
+template <class F>
+auto for_code_form(bool sdc, int code_bytes, F &&f) {
+    if (sdc) return f((unsigned char)0, std::true_type{});
+    if (code_bytes == 1) return f((unsigned char)0, std::false_type{});
+    return f((unsigned short)0, std::false_type{});
+}
+
+int stage_merge(SearchStep &S) {
+    mmidx_index *h = S.h;
+    const SearchPlan &pl = S.pl;
+    hipStream_t st = S.st;
     MergeParams M{};
     M.T = h->ws_T.p;
     M.pool_cnt = h->ws_pcnt.p;
     M.pool_key = h->ws_pkey.p;
     M.pool_val = h->ws_pval.p;
     M.poolq = pl.poolq;
-    M.cells = ivf ? d_cells : nullptr;
+    M.cells = S.ivf ? S.cells : nullptr;
     M.list_off = h->d_off;
     M.ids = h->d_ids;
-    M.w = P.w;
-    M.k = k;
-    M.mode = mode;
-    M.iid_out = d_iid;
-    M.dist_out = d_dist;
-    M.count_out = d_cnt;
+    M.w = S.P.w;
+    M.k = S.k;
+    M.mode = S.mode;
+    M.iid_out = S.out.iid;
+    M.dist_out = S.out.dist;
+    M.count_out = S.out.cnt;
     M.flag_out = h->ws_flag.p;
-    M.pdist = d_pdist;
-    M.pkey = d_pkey;
-    if (mode == 1 && phase == 2 && h->shard_dest) {  // a shard of a sharded handle: the lists go to the queries' owners
+    M.pdist = S.out.pdist;
+    M.pkey = S.out.pkey;
+    if (S.mode == 1 && S.phase == 2 && h->shard_dest) {  // a shard of a sharded handle: the lists go to the queries' owners
         M.dest = h->shard_dest;
         M.dest_per = h->shard_dest_per;
         M.dest_me = h->shard_dest_me;
@@ -2533,94 +2652,138 @@ int search_batch_device(mmidx_index *h, const SearchPlan &pl, int k, int64_t nq,
     int mcap = 512;
     while (mcap < 2 * pl.K1) mcap <<= 1;  // <= 8192 (k <= MMIDX_K_MAX)
     M.cap = mcap;
-    const size_t mlds = (size_t)mcap * 16 + ((ivf && P.w <= 1024) ? (size_t)P.w * 8 : 0);
-    if (pl.K1 <= 128) {
-        HIPCK(hipFuncSetAttribute((const void *)k_merge<128>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mlds));
-        hipLaunchKernelGGL(k_merge<128>, dim3((unsigned)nq), dim3(128), mlds, st, M);
-    } else {
-        HIPCK(hipFuncSetAttribute((const void *)k_merge<MMIDX_BLOCK>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mlds));
-        hipLaunchKernelGGL(k_merge<MMIDX_BLOCK>, dim3((unsigned)nq), dim3(MMIDX_BLOCK), mlds, st, M);
-    }
-    HIPCK(hipGetLastError());
+    const size_t mlds = (size_t)mcap * 16 + ((S.ivf && S.P.w <= 1024) ? (size_t)S.P.w * 8 : 0);
+    if (const int rc = for_merge_block(pl.K1 <= 128, [&](auto nt) { return launch_grid<k_merge<decltype(nt)::value>>(M, dim3((unsigned)S.nq), nt, mlds, st); }))
+        return rc;
     DBG_SYNC("merge");
-    if (mode == 0 && h->n_csr > 0) {
-        // exact replay for queries whose k-th / (k+1)-th distances tie (rare)
-        TieParams TP{};
-        TP.S = P;
-        TP.flag = h->ws_flag.p;
-        TP.ids = h->d_ids;
-        TP.iid_out = d_iid;
-        TP.dist_out = d_dist;
-        TP.k = k;
-        TP.nq = (int)nq;
-        const unsigned tgrid = (unsigned)std::min<int64_t>((nq + MMIDX_BLOCK - 1) / MMIDX_BLOCK, 4096);  // (a block reads MMIDX_BLOCK flags at once; flagged queries are rare)
-        const size_t tlds = (P.glut ? 0 : (size_t)h->m * h->ks * 8) + 2 * (size_t)h->D * 8;
-        if (P.glut) {  // (the table in global scratch: one slot per query of the sub-batch)
-            if ((size_t)nq > h->glut_slots) return mmidx_fail(MMIDX_ERR_UNSUPPORTED, "lookup-table scratch too small for the tie replay");
-            if (sdc_tt) {
-                hipLaunchKernelGGL((k_tie_resolve<unsigned char, true, true>), dim3(tgrid), dim3(MMIDX_BLOCK), tlds, st, TP);
-            } else if (h->code_bytes == 1) {
-                hipLaunchKernelGGL((k_tie_resolve<unsigned char, false, true>), dim3(tgrid), dim3(MMIDX_BLOCK), tlds, st, TP);
-            } else {
-                hipLaunchKernelGGL((k_tie_resolve<unsigned short, false, true>), dim3(tgrid), dim3(MMIDX_BLOCK), tlds, st, TP);
-            }
-        } else if (sdc_tt) {
-            HIPCK(hipFuncSetAttribute((const void *)k_tie_resolve<unsigned char, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tlds));
-            hipLaunchKernelGGL((k_tie_resolve<unsigned char, true>), dim3(tgrid), dim3(MMIDX_BLOCK), tlds, st, TP);
-        } else if (h->code_bytes == 1) {
-            HIPCK(hipFuncSetAttribute((const void *)k_tie_resolve<unsigned char, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tlds));
-            hipLaunchKernelGGL((k_tie_resolve<unsigned char, false>), dim3(tgrid), dim3(MMIDX_BLOCK), tlds, st, TP);
-        } else {
-            HIPCK(hipFuncSetAttribute((const void *)k_tie_resolve<unsigned short, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tlds));
-            hipLaunchKernelGGL((k_tie_resolve<unsigned short, false>), dim3(tgrid), dim3(MMIDX_BLOCK), tlds, st, TP);
-        }
-        HIPCK(hipGetLastError());
-    }
-    if (prof) {
-        HIPCK(hipEventRecord(ev[4], st));
-        if (!ivf) h->host_codes += nq * h->n_csr;
-        if (ivf || mode == 0) {
-            const long long tot = (long long)nq * h->w;
-            hipLaunchKernelGGL(k_count_stats, dim3(256), dim3(256), 0, st, ivf ? d_cells : nullptr, h->d_off, tot, h->w,
-                               mode == 0 ? h->ws_flag.p : nullptr, (long long)nq, h->d_counters);
-        }
-        HIPCK(hipGetLastError());
-    }
     return MMIDX_OK;
 }
 
-int search_common(mmidx_index *h, int k, int64_t nq, const double *dQ, const int32_t *d_cells, int mode, int32_t *d_iid,
-                  double *d_dist, int32_t *d_cnt, double *d_pdist, long long *d_pkey, hipStream_t st,
-                  const double *sdc_tt = nullptr) {
+// exact replay for queries whose k-th / (k+1)-th distances tie (rare)
+int stage_tie_replay(SearchStep &S) {
+    mmidx_index *h = S.h;
+    const ScanParams &P = S.P;
+    hipStream_t st = S.st;
+    TieParams TP{};
+    TP.S = P;
+    TP.flag = h->ws_flag.p;
+    TP.ids = h->d_ids;
+    TP.iid_out = S.out.iid;
+    TP.dist_out = S.out.dist;
+    TP.k = S.k;
+    TP.nq = (int)S.nq;
+    const unsigned tgrid = (unsigned)std::min<int64_t>((S.nq + MMIDX_BLOCK - 1) / MMIDX_BLOCK, 4096);  // (a block reads MMIDX_BLOCK flags at once; flagged queries are rare)
+    const size_t tlds = (P.glut ? 0 : (size_t)h->m * h->ks * 8) + 2 * (size_t)h->D * 8;
+    // (the table in global scratch: one slot per query of the sub-batch)
+    if (P.glut && (size_t)S.nq > h->glut_slots) return mmidx_fail(MMIDX_ERR_UNSUPPORTED, "lookup-table scratch too small for the tie replay");
+    return for_code_form(S.sdc_tt != nullptr, h->code_bytes, [&](auto code, auto sdc) -> int {
+        using CodeT = decltype(code);
+        constexpr bool SDC = decltype(sdc)::value;
+        if (!P.glut) return launch_grid<k_tie_resolve<CodeT, SDC>>(TP, dim3(tgrid), MMIDX_BLOCK, tlds, st);
+        // open-coded: the GLUT forms keep two vectors in LDS, below the default limit, and have never set the attribute -- launch_grid
+        // would add that driver call to every step of such an index
+        hipLaunchKernelGGL((k_tie_resolve<CodeT, SDC, true>), dim3(tgrid), dim3(MMIDX_BLOCK), tlds, st, TP);
+        HIPCK(hipGetLastError());
+        return MMIDX_OK;
+    });
+}
+
+// profiling 1: the codes the step looked at and its flagged queries
+int stage_stats(SearchStep &S) {
+    mmidx_index *h = S.h;
+    if (!S.ivf) h->host_codes += S.nq * h->n_csr;
+    if (S.ivf || S.mode == 0) {
+        const long long tot = (long long)S.nq * h->w;
+        hipLaunchKernelGGL(k_count_stats, dim3(256), dim3(256), 0, S.st, S.ivf ? S.cells : nullptr, h->d_off, tot, h->w,
+                           S.mode == 0 ? h->ws_flag.p : nullptr, (long long)S.nq, h->d_counters);
+    }
+    HIPCK(hipGetLastError());
+    return MMIDX_OK;
+}
+
+// The step: its stages in order, and between them every event record of the step's group (EvSlot): EV_START by step_begin, the
+// others here.  An empty index (no records yet) skips the scan stages and nothing else.  EV_PASSA_END follows EV_SCAN_START at once
+// where pass A will not run (phase 2, the empty index) and under profiling 1 (recorded again behind pass A when it runs).
+int search_batch_device(SearchStep &S) {
+    auto record = [&S](EvSlot slot) {
+        HIPCK(hipEventRecord(S.ev[slot], S.st));
+        return (int)MMIDX_OK;
+    };
+    int rc;
+    if ((rc = step_begin(S))) return rc;
+    const bool prof = S.prof, pany = S.prof || S.plight, pass_a = !S.empty && S.phase != 2;
+    if ((rc = stage_coarse(S))) return rc;
+    if (prof && (rc = record(EV_COARSE_END))) return rc;
+    if ((rc = stage_init(S))) return rc;
+    if (pany && (rc = record(EV_SCAN_START))) return rc;
+    if ((prof || (pany && !pass_a)) && (rc = record(EV_PASSA_END))) return rc;
+    if (pass_a && ((rc = stage_pass_a(S)) || (pany && (rc = record(EV_PASSA_END))))) return rc;
+    if (!S.empty && S.phase != 0 && (rc = stage_thresholds(S))) return rc;
+    if (!S.empty && S.phase != 1 && S.two_pass) {
+        if (!S.ivf && (rc = stage_pass_b_flat(S))) return rc;
+        if (S.ivf && ((rc = stage_pair_sort(S)) || (rc = stage_pass_b_ivf(S)))) return rc;  // (the K3s pre-filter: inside the sort)
+    }
+    if (prof && (rc = record(EV_SCAN_END))) return rc;
+    if (prof && !S.empty) S.h->launches += (pass_a ? 1 : 0) + (S.two_pass && S.phase != 1 ? 1 : 0);  // (scan launches: pass A, pass B)
+    if (S.phase == 1) {
+        if (S.empty && (rc = stage_thresholds(S))) return rc;  // (nothing was scanned: the export follows the closed interval)
+        return prof ? record(EV_END) : MMIDX_OK;
+    }
+    if ((rc = stage_merge(S))) return rc;
+    if (S.mode == 0 && !S.empty && (rc = stage_tie_replay(S))) return rc;
+    if (prof && ((rc = record(EV_END)) || (rc = stage_stats(S)))) return rc;
+    return MMIDX_OK;
+}
+
+// what every search does before its first step: the handle is ready, its device current, the pending records and the tables that
+// follow the records are built, and the plan is made
+int prepare_search(mmidx_index *h, int k, int64_t nq, bool need_coarse, SearchPlan &pl) {
     int rc = check_ready(h);
     if (rc) return rc;
     if (nq < 0) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "nq < 0");
-    const int ivf = h->kind == MMIDX_KIND_IVFPQ;
-    if (ivf && (h->w < 1 || h->w > h->C))
+    if (h->kind == MMIDX_KIND_IVFPQ && (h->w < 1 || h->w > h->C))
         return mmidx_fail(MMIDX_ERR_INVALID_ARG, "w = %d outside 1..%d (setW)", h->w, h->C);
     rc = set_device(h);
     if (rc) return rc;
     {
         std::lock_guard<std::mutex> lk(h->mu);
-        rc = build_csr(h);
-        if (rc) return rc;
-        rc = build_grp_tables(h);
-        if (rc) return rc;
-        rc = build_mfma_tables(h);
-        if (rc) return rc;
+        if ((rc = build_csr(h)) || (rc = build_grp_tables(h)) || (rc = build_mfma_tables(h))) return rc;
     }
+    return make_plan(h, k, nq, pl, need_coarse);
+}
+
+// a whole search in sub-batches of the plan's size; d_cells: the caller's probe cells (a partial search, mode 1)
+int search_common(mmidx_index *h, int k, int64_t nq, const double *dQ, const SearchOut &out, hipStream_t st, const double *sdc_tt = nullptr,
+                  const int32_t *d_cells = nullptr, int mode = 0) {
     SearchPlan pl;
-    rc = make_plan(h, k, nq, pl, d_cells == nullptr);
+    int rc = prepare_search(h, k, nq, d_cells == nullptr, pl);
     if (rc) return rc;
     for (int64_t q0 = 0; q0 < nq; q0 += pl.qb) {
         const int64_t nb = std::min<int64_t>(pl.qb, nq - q0);
-        rc = search_batch_device(h, pl, k, nb, dQ + (size_t)q0 * h->D, d_cells ? d_cells + (size_t)q0 * h->w : nullptr, mode,
-                                 d_iid ? d_iid + (size_t)q0 * k : nullptr, d_dist ? d_dist + (size_t)q0 * k : nullptr,
-                                 d_cnt + q0, d_pdist ? d_pdist + (size_t)q0 * pl.K1 : nullptr,
-                                 d_pkey ? d_pkey + (size_t)q0 * pl.K1 : nullptr, 0, nullptr, st,
-                                 sdc_tt ? sdc_tt + (size_t)q0 * h->m * h->ks * h->dsub : nullptr);
+        SearchStep S{h, pl, k, nb, dQ + (size_t)q0 * h->D, d_cells ? d_cells + (size_t)q0 * h->w : nullptr, out.at(q0, k, pl.K1), st, mode, 0,
+                     sdc_tt ? sdc_tt + (size_t)q0 * h->m * h->ks * h->dsub : nullptr};
+        rc = search_batch_device(S);
         if (rc) return rc;
     }
+    return MMIDX_OK;
+}
+
+// the answer workspaces of a host round of nb queries (with the query rows)
+int reserve_answers(mmidx_index *h, int64_t nb, int k) {
+    HIPCK(h->ws_Q.reserve((size_t)nb * h->D));
+    HIPCK(h->ws_oiid.reserve((size_t)nb * k));
+    HIPCK(h->ws_odist.reserve((size_t)nb * k));
+    HIPCK(h->ws_ocnt.reserve((size_t)nb));
+    return MMIDX_OK;
+}
+SearchOut answer_ws(const mmidx_index *h) { return {h->ws_oiid.p, h->ws_odist.p, h->ws_ocnt.p}; }
+
+// a round's nb answers from the workspaces to the host arrays at query q0; they have arrived on return
+int fetch_answers(mmidx_index *h, int64_t q0, int64_t nb, int k, int32_t *iid_out, double *dist_out, int32_t *count_out, hipStream_t st) {
+    HIPCK(hipMemcpyAsync(iid_out + (size_t)q0 * k, h->ws_oiid.p, (size_t)nb * k * 4, hipMemcpyDeviceToHost, st));
+    HIPCK(hipMemcpyAsync(dist_out + (size_t)q0 * k, h->ws_odist.p, (size_t)nb * k * 8, hipMemcpyDeviceToHost, st));
+    HIPCK(hipMemcpyAsync(count_out + q0, h->ws_ocnt.p, (size_t)nb * 4, hipMemcpyDeviceToHost, st));
+    HIPCK(hipStreamSynchronize(st));
     return MMIDX_OK;
 }
 
@@ -2634,17 +2797,10 @@ int launch_merge_partials(int k, int64_t nq, int nshards, const double *d_pdist,
     int mcap = small ? 512 : MMIDX_MCAP;
     while (mcap < 2 * (k + 1)) mcap <<= 1;
     const size_t mlds = (size_t)mcap * 16;
-    if (small) {
-        HIPCK(hipFuncSetAttribute((const void *)k_merge_partials<128>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mlds));
-        hipLaunchKernelGGL(k_merge_partials<128>, dim3((unsigned)nq), dim3(128), mlds, st, k, (int)nq, nshards, mcap, d_pdist,
-                           (const long long *)d_pkey, d_pcount, (const long long *)d_poff, d_iid_out, d_dist_out, d_count_out, d_flag_out, d_nflag_out);
-    } else {
-        HIPCK(hipFuncSetAttribute((const void *)k_merge_partials<MMIDX_BLOCK>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mlds));
-        hipLaunchKernelGGL(k_merge_partials<MMIDX_BLOCK>, dim3((unsigned)nq), dim3(MMIDX_BLOCK), mlds, st, k, (int)nq, nshards, mcap, d_pdist,
-                           (const long long *)d_pkey, d_pcount, (const long long *)d_poff, d_iid_out, d_dist_out, d_count_out, d_flag_out, d_nflag_out);
-    }
-    HIPCK(hipGetLastError());
-    return MMIDX_OK;
+    return for_merge_block(small, [&](auto nt) {
+        return launch_grid_args<k_merge_partials<decltype(nt)::value>>(dim3((unsigned)nq), nt, mlds, st, k, (int)nq, nshards, mcap, d_pdist, (const long long *)d_pkey,
+                                                                        d_pcount, (const long long *)d_poff, d_iid_out, d_dist_out, d_count_out, d_flag_out, d_nflag_out);
+    });
 }
 
 }  // namespace
@@ -3145,7 +3301,7 @@ int mmidx_search_device(mmidx_index *h, int k, int64_t nq, const double *dQ, int
     NOT_ON_SHARDED(h, "mmidx_search_device");
     hipStream_t st = (hipStream_t)stream;
     DeviceCall call(h, st);
-    return search_common(h, k, nq, dQ, nullptr, 0, d_iid_out, d_dist_out, d_count_out, nullptr, nullptr, st);
+    return search_common(h, k, nq, dQ, {d_iid_out, d_dist_out, d_count_out}, st);
 }
 
 // Queries of several concurrent callers in one device batch.  The reference's API is one query per call
@@ -3157,18 +3313,10 @@ int mmidx_search_device(mmidx_index *h, int k, int64_t nq, const double *dQ, int
 static int search_host_direct(mmidx_index *h, const SearchReq &r) {
     const int k = r.k;
     const int64_t nq = r.nq;
-    HIPCK(h->ws_Q.reserve((size_t)nq * h->D));
-    HIPCK(h->ws_oiid.reserve((size_t)nq * k));
-    HIPCK(h->ws_odist.reserve((size_t)nq * k));
-    HIPCK(h->ws_ocnt.reserve((size_t)nq));
+    if (const int rc = reserve_answers(h, nq, k)) return rc;
     HIPCK(hipMemcpyAsync(h->ws_Q.p, r.Q, (size_t)nq * h->D * 8, hipMemcpyHostToDevice, h->stream));
-    int rc = search_common(h, k, nq, h->ws_Q.p, nullptr, 0, h->ws_oiid.p, h->ws_odist.p, h->ws_ocnt.p, nullptr, nullptr, h->stream);
-    if (rc) return rc;
-    HIPCK(hipMemcpyAsync(r.iid, h->ws_oiid.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCK(hipMemcpyAsync(r.dist, h->ws_odist.p, (size_t)nq * k * 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCK(hipMemcpyAsync(r.cnt, h->ws_ocnt.p, (size_t)nq * 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCK(hipStreamSynchronize(h->stream));
-    return MMIDX_OK;
+    if (const int rc = search_common(h, k, nq, h->ws_Q.p, answer_ws(h), h->stream)) return rc;
+    return fetch_answers(h, 0, nq, k, r.iid, r.dist, r.cnt, h->stream);
 }
 
 // A request of more than MMIDX_COMB_MAX_Q queries, outside the combiner.  The caller takes one of the handle's slots (its own copy
@@ -3222,7 +3370,7 @@ static int search_host_big(mmidx_index *h, const SearchReq &r) {
     {
         DeviceCall call(h, h->stream);  // search_mu; a _device call on another stream is waited for
         HIPCK(hipStreamWaitEvent(h->stream, sl->e_in, 0));
-        rc = search_common(h, k, nq, sl->dQ.p, nullptr, 0, d_iid, d_dist, d_cnt, nullptr, nullptr, h->stream);
+        rc = search_common(h, k, nq, sl->dQ.p, {d_iid, d_dist, d_cnt}, h->stream);
         if (rc) {
             (void)hipStreamSynchronize(h->stream);
             return rc;
@@ -3289,7 +3437,7 @@ static int search_host_batch(mmidx_index *h, SearchReq *const *batch, size_t nb)
         }
         if (off > sent) HIPCK(hipMemcpyAsync((unsigned char *)h->ws_Q.p + sent, hin + sent, off - sent, hipMemcpyHostToDevice, h->stream));
     }
-    rc = search_common(h, k, tot, h->ws_Q.p, nullptr, 0, d_iid, d_dist, d_cnt, nullptr, nullptr, h->stream);
+    rc = search_common(h, k, tot, h->ws_Q.p, {d_iid, d_dist, d_cnt}, h->stream);
     if (rc) return rc;
     // stage out: the answers come back in up to four slices of whole requests; a slice is copied to the callers' arrays while the
     // next one is still on the bus (events between the slices; the handle keeps them)
@@ -3376,21 +3524,15 @@ int mmidx_search_sdc(mmidx_index *h, int k, int64_t nq, const int32_t *iids, int
         const int64_t nb = std::min(QB, nq - q0);
         HIPCK(h->ws_sdc.reserve((size_t)nb * per));
         HIPCK(h->ws_aidx.reserve((size_t)nb));
-        HIPCK(h->ws_Q.reserve((size_t)nb * h->D));  // unused by the SDC kernels, but the scan parameters want a valid pointer
-        HIPCK(h->ws_oiid.reserve((size_t)nb * k));
-        HIPCK(h->ws_odist.reserve((size_t)nb * k));
-        HIPCK(h->ws_ocnt.reserve((size_t)nb));
+        rc = reserve_answers(h, nb, k);  // (the query rows: unused by the SDC kernels, but the scan parameters want a valid pointer)
+        if (rc) return rc;
         HIPCK(hipMemcpyAsync(h->ws_aidx.p, iids + q0, (size_t)nb * 4, hipMemcpyHostToDevice, h->stream));
         const long long tot = (long long)nb * (long long)per;
         hipLaunchKernelGGL(k_sdc_terms<unsigned char>, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, h->stream, h->d_pq,
                            (const unsigned char *)h->d_codes, h->ws_aidx.p, h->ws_sdc.p, h->m, h->ks, h->dsub, tot);
         HIPCK(hipGetLastError());
-        rc = search_common(h, k, nb, h->ws_Q.p, nullptr, 0, h->ws_oiid.p, h->ws_odist.p, h->ws_ocnt.p, nullptr, nullptr, h->stream, h->ws_sdc.p);
-        if (rc) return rc;
-        HIPCK(hipMemcpyAsync(iid_out + (size_t)q0 * k, h->ws_oiid.p, (size_t)nb * k * 4, hipMemcpyDeviceToHost, h->stream));
-        HIPCK(hipMemcpyAsync(dist_out + (size_t)q0 * k, h->ws_odist.p, (size_t)nb * k * 8, hipMemcpyDeviceToHost, h->stream));
-        HIPCK(hipMemcpyAsync(count_out + q0, h->ws_ocnt.p, (size_t)nb * 4, hipMemcpyDeviceToHost, h->stream));
-        HIPCK(hipStreamSynchronize(h->stream));
+        if ((rc = search_common(h, k, nb, h->ws_Q.p, answer_ws(h), h->stream, h->ws_sdc.p))) return rc;
+        if ((rc = fetch_answers(h, q0, nb, k, iid_out, dist_out, count_out, h->stream))) return rc;
     }
     return MMIDX_OK;
 }
@@ -3415,50 +3557,40 @@ int mmidx_search_partial_device(mmidx_index *h, int k, int64_t nq, const double 
     if (h->kind == MMIDX_KIND_IVFPQ && nq > 0 && !d_cells) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "IVFPQ partial search needs the probe cells");
     hipStream_t st = (hipStream_t)stream;
     DeviceCall call(h, st);
-    return search_common(h, k, nq, dQ, h->kind == MMIDX_KIND_IVFPQ ? d_cells : nullptr, 1, nullptr, nullptr, d_pcount, d_pdist,
-                         (long long *)d_pkey, st);
+    return search_common(h, k, nq, dQ, {nullptr, nullptr, d_pcount, d_pdist, (long long *)d_pkey}, st, nullptr, h->kind == MMIDX_KIND_IVFPQ ? d_cells : nullptr, 1);
 }
 
 // two-phase sharded search: thresholds are exchanged between the phases (MIN all-reduce)
 static int shard_phase(mmidx_index *h, int k, int64_t nq, const double *dQ, const int32_t *d_cells, const double *d_cdist, int phase,
-                       double *d_T, double *d_pdist, int64_t *d_pkey, int32_t *d_pcount, void *stream) {
+                       double *d_T, const SearchOut &out, void *stream) {
     if (!h) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null handle");
     NOT_ON_SHARDED(h, "the shard phases");
     if (nq > 0 && (!dQ || !d_T)) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null argument");
-    if (phase == 2 && nq > 0 && (!d_pdist || !d_pkey || !d_pcount)) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null argument");
+    if (phase == 2 && nq > 0 && (!out.pdist || !out.pkey || !out.cnt)) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null argument");
     int rc = check_ready(h);
     if (rc) return rc;
     const int ivf = h->kind == MMIDX_KIND_IVFPQ;
     if (ivf && nq > 0 && !d_cells) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "IVFPQ shard search needs the probe cells");
     if (ivf && (h->w < 1 || h->w > h->C)) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "w = %d outside 1..%d (setW)", h->w, h->C);
     if (nq == 0) return MMIDX_OK;
-    rc = set_device(h);
+    rc = set_device(h);  // (current before DeviceCall may have to wait for it)
     if (rc) return rc;
     DeviceCall call(h, (hipStream_t)stream);
-    {
-        std::lock_guard<std::mutex> lk(h->mu);
-        rc = build_csr(h);
-        if (rc) return rc;
-        rc = build_grp_tables(h);
-        if (rc) return rc;
-        rc = build_mfma_tables(h);
-        if (rc) return rc;
-    }
     SearchPlan pl;
-    rc = make_plan(h, k, nq, pl, false);
+    rc = prepare_search(h, k, nq, false, pl);
     if (rc) return rc;
     if (nq > pl.qb) return mmidx_fail(MMIDX_ERR_UNSUPPORTED, "shard phases take at most %lld queries per call for this index", (long long)pl.qb);
-    return search_batch_device(h, pl, k, nq, dQ, ivf ? d_cells : nullptr, 1, nullptr, nullptr, d_pcount, d_pdist, (long long *)d_pkey, phase,
-                               d_T, (hipStream_t)stream, nullptr, ivf ? d_cdist : nullptr);
+    SearchStep S{h, pl, k, nq, dQ, ivf ? d_cells : nullptr, out, (hipStream_t)stream, 1, phase, nullptr, ivf ? d_cdist : nullptr, d_T};
+    return search_batch_device(S);
 }
 
 int mmidx_shard_pass_a_device(mmidx_index *h, int k, int64_t nq, const double *dQ, const int32_t *d_cells, double *d_T_out, void *stream) {
-    return shard_phase(h, k, nq, dQ, d_cells, nullptr, 1, d_T_out, nullptr, nullptr, nullptr, stream);
+    return shard_phase(h, k, nq, dQ, d_cells, nullptr, 1, d_T_out, {}, stream);
 }
 
 int mmidx_shard_pass_b_device(mmidx_index *h, int k, int64_t nq, const double *dQ, const int32_t *d_cells, const double *d_cdist,
                               const double *d_T_in, double *d_pdist, int64_t *d_pkey, int32_t *d_pcount, void *stream) {
-    return shard_phase(h, k, nq, dQ, d_cells, d_cdist, 2, (double *)d_T_in, d_pdist, d_pkey, d_pcount, stream);
+    return shard_phase(h, k, nq, dQ, d_cells, d_cdist, 2, (double *)d_T_in, {nullptr, nullptr, d_pcount, d_pdist, (long long *)d_pkey}, stream);
 }
 
 int mmidx_merge_partials_device(int device, int k, int64_t nq, int nshards, const double *d_pdist, const int64_t *d_pkey,
@@ -3497,21 +3629,9 @@ int mmidx_shard_tie_phase_device(mmidx_index *h, int phase, int k, int64_t nf, c
         if (rc) return rc;
     }
     TieShardParams TP{};
+    TP.S = index_scan_params(h);
     TP.S.Q = dQ;
-    TP.S.coarse = h->d_coarse;
-    TP.S.pqT = h->d_pqT;
-    TP.S.perm = h->d_perm;
-    TP.S.rot = h->d_rot;
     TP.S.cells = d_cells;
-    TP.S.list_off = h->d_off;
-    TP.S.codes = h->d_codes;
-    TP.S.D = h->D;
-    TP.S.m = h->m;
-    TP.S.ks = h->ks;
-    TP.S.dsub = h->dsub;
-    TP.S.w = h->w;
-    TP.S.transform = h->transform;
-    TP.S.ivf = 1;
     TP.ids = h->d_ids;
     TP.fq = d_fq;
     TP.tau = d_tau;
@@ -3526,17 +3646,15 @@ int mmidx_shard_tie_phase_device(mmidx_index *h, int phase, int k, int64_t nf, c
         h->glut_slots = std::max(h->glut_slots, (size_t)nf);
         TP.S.glut = h->ws_glut.p;
         lds = 2 * (size_t)h->D * 8;
-        if (h->code_bytes == 1) hipLaunchKernelGGL((k_shard_tie<unsigned char, true>), dim3((unsigned)nf), dim3(MMIDX_BLOCK), lds, st, TP);
-        else hipLaunchKernelGGL((k_shard_tie<unsigned short, true>), dim3((unsigned)nf), dim3(MMIDX_BLOCK), lds, st, TP);
-    } else if (h->code_bytes == 1) {
-        HIPCK(hipFuncSetAttribute((const void *)k_shard_tie<unsigned char>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(k_shard_tie<unsigned char>, dim3((unsigned)nf), dim3(MMIDX_BLOCK), lds, st, TP);
-    } else {
-        HIPCK(hipFuncSetAttribute((const void *)k_shard_tie<unsigned short>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(k_shard_tie<unsigned short>, dim3((unsigned)nf), dim3(MMIDX_BLOCK), lds, st, TP);
     }
-    HIPCK(hipGetLastError());
-    return MMIDX_OK;
+    return for_code_form(false, h->code_bytes, [&](auto code, auto) -> int {
+        using CodeT = decltype(code);
+        if (!TP.S.glut) return launch_grid<k_shard_tie<CodeT>>(TP, dim3((unsigned)nf), MMIDX_BLOCK, lds, st);
+        // open-coded: the GLUT forms have never set the attribute (two vectors in LDS), and launch_grid would add that driver call
+        hipLaunchKernelGGL((k_shard_tie<CodeT, true>), dim3((unsigned)nf), dim3(MMIDX_BLOCK), lds, st, TP);
+        HIPCK(hipGetLastError());
+        return MMIDX_OK;
+    });
 }
 
 int mmidx_assign_device(mmidx_index *h, int64_t n, const double *dX, int32_t *d_cell_out, void *stream) {
@@ -3628,19 +3746,19 @@ int mmidx_get_stats(mmidx_index *h, mmidx_stats *out) {
     mmidx_stats s{};
     if (h->ev_used) HIPCK(hipEventSynchronize(h->evpool[h->ev_used - 1]));
     HIPCK(hipDeviceSynchronize());
-    for (size_t g = 0; g + 6 <= h->ev_used; g += 6) {
+    for (size_t g = 0; g + EV_SLOTS <= h->ev_used; g += EV_SLOTS) {
         const Event *ev = h->evpool.data() + g;
         float a = 0, b = 0, c = 0, t = 0, pa = 0;
         if (h->profiling == 2) {  // light: only the pass-A pair was recorded
-            HIPCK(hipEventElapsedTime(&pa, ev[2], ev[5]));
+            HIPCK(hipEventElapsedTime(&pa, ev[EV_SCAN_START], ev[EV_PASSA_END]));
             s.passa_ms += pa;
             continue;
         }
-        HIPCK(hipEventElapsedTime(&a, ev[0], ev[1]));
-        HIPCK(hipEventElapsedTime(&b, ev[2], ev[3]));
-        HIPCK(hipEventElapsedTime(&c, ev[3], ev[4]));
-        HIPCK(hipEventElapsedTime(&t, ev[0], ev[4]));
-        HIPCK(hipEventElapsedTime(&pa, ev[2], ev[5]));
+        HIPCK(hipEventElapsedTime(&a, ev[EV_START], ev[EV_COARSE_END]));
+        HIPCK(hipEventElapsedTime(&b, ev[EV_SCAN_START], ev[EV_SCAN_END]));
+        HIPCK(hipEventElapsedTime(&c, ev[EV_SCAN_END], ev[EV_END]));
+        HIPCK(hipEventElapsedTime(&t, ev[EV_START], ev[EV_END]));
+        HIPCK(hipEventElapsedTime(&pa, ev[EV_SCAN_START], ev[EV_PASSA_END]));
         s.coarse_ms += a;
         s.scan_ms += b;
         s.merge_ms += c;
@@ -3864,18 +3982,8 @@ int mmidx_distance(mmidx_index *h, int64_t n, const double *Q, const int32_t *ii
     if (e == hipSuccess) e = hipMemcpyAsync(dQ, Q, (size_t)n * h->D * 8, hipMemcpyHostToDevice, h->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(d_cell, cells.data(), (size_t)n * 4, hipMemcpyHostToDevice, h->stream);
     if (e == hipSuccess) {
-        ScanParams P{};
+        ScanParams P = index_scan_params(h);
         P.Q = dQ;
-        P.coarse = h->d_coarse;
-        P.perm = h->d_perm;
-        P.rot = h->d_rot;
-        P.codes = h->d_codes;
-        P.D = h->D;
-        P.m = h->m;
-        P.ks = h->ks;
-        P.dsub = h->dsub;
-        P.transform = h->transform;
-        P.ivf = h->kind == MMIDX_KIND_IVFPQ;
         const size_t lds = 2 * (size_t)h->D * 8;
         if (h->code_bytes == 1)
             hipLaunchKernelGGL(k_pair_distance<unsigned char>, dim3((unsigned)n), dim3(MMIDX_BLOCK), lds, h->stream, P, h->d_pq, d_pos, d_cell, d_out);
@@ -4026,7 +4134,7 @@ int mmidx_search_ids_device(mmidx_index *h, int k, int64_t nq, const int32_t *d_
         // the decoded vectors never leave the device: K10 writes the query workspace, the search reads it on the same stream
         rc = idq_decode(h, nb, d_iids + q0, h->ws_Q.p, h->ws_found.p, st);
         if (rc) return rc;
-        rc = search_common(h, k, nb, h->ws_Q.p, nullptr, 0, d_iid_out + (size_t)q0 * k, d_dist_out + (size_t)q0 * k, d_count_out + q0, nullptr, nullptr, st);
+        rc = search_common(h, k, nb, h->ws_Q.p, {d_iid_out + (size_t)q0 * k, d_dist_out + (size_t)q0 * k, d_count_out + q0}, st);
         if (rc) return rc;
         rc = mmidx_internal_mark_unknown_rows(h->ws_found.p, nb, k, d_iid_out + (size_t)q0 * k, d_dist_out + (size_t)q0 * k, d_count_out + q0, st);
         if (rc) return rc;
@@ -4054,18 +4162,9 @@ int mmidx_search_ids(mmidx_index *h, int k, int64_t nq, const int32_t *iids, int
         const int64_t nb = std::min<int64_t>(MMIDX_COMB_MAX_Q, nq - q0);
         rc = idq_prepare(h);  // (records added since the round before move the positions)
         if (rc) return rc;
-        HIPCK(h->ws_Q.reserve((size_t)nb * h->D));
-        HIPCK(h->ws_oiid.reserve((size_t)nb * k));
-        HIPCK(h->ws_odist.reserve((size_t)nb * k));
-        HIPCK(h->ws_ocnt.reserve((size_t)nb));
-        rc = idq_decode(h, nb, h->ws_idq.p + q0, h->ws_Q.p, nullptr, h->stream);
-        if (rc) return rc;
-        rc = search_common(h, k, nb, h->ws_Q.p, nullptr, 0, h->ws_oiid.p, h->ws_odist.p, h->ws_ocnt.p, nullptr, nullptr, h->stream);
-        if (rc) return rc;
-        HIPCK(hipMemcpyAsync(iid_out + (size_t)q0 * k, h->ws_oiid.p, (size_t)nb * k * 4, hipMemcpyDeviceToHost, h->stream));
-        HIPCK(hipMemcpyAsync(dist_out + (size_t)q0 * k, h->ws_odist.p, (size_t)nb * k * 8, hipMemcpyDeviceToHost, h->stream));
-        HIPCK(hipMemcpyAsync(count_out + q0, h->ws_ocnt.p, (size_t)nb * 4, hipMemcpyDeviceToHost, h->stream));
-        HIPCK(hipStreamSynchronize(h->stream));
+        if ((rc = reserve_answers(h, nb, k)) || (rc = idq_decode(h, nb, h->ws_idq.p + q0, h->ws_Q.p, nullptr, h->stream))) return rc;
+        if ((rc = search_common(h, k, nb, h->ws_Q.p, answer_ws(h), h->stream))) return rc;
+        if ((rc = fetch_answers(h, q0, nb, k, iid_out, dist_out, count_out, h->stream))) return rc;
     }
     return MMIDX_OK;
 }
@@ -4126,7 +4225,7 @@ int refine_reserve(mmidx_index *h, int64_t nb, int R, hipStream_t st) {
 // one round of nb queries on the device: answers [nb][k], counts [nb]; d_missing (may be null) is added to
 int refine_round(mmidx_index *h, const MmidxLinearRows &rows, int k, int R, int64_t nb, const double *dQ, const int32_t *d_qvalid, int32_t *d_iid,
                  double *d_dist, int32_t *d_cnt, int64_t *d_missing, hipStream_t st) {
-    int rc = search_common(h, R, nb, dQ, nullptr, 0, h->ws_rfi.p, h->ws_rfd.p, h->ws_rfc.p, nullptr, nullptr, st);
+    int rc = search_common(h, R, nb, dQ, {h->ws_rfi.p, h->ws_rfd.p, h->ws_rfc.p}, st);
     if (rc) return rc;
     MmidxRefineArgs a{};
     a.dX = rows.dX;
@@ -4153,16 +4252,14 @@ int refine_host(mmidx_index *h, const MmidxLinearRows &rows, int k, int R, int64
                 double *dist_out, int32_t *count_out, int64_t *missing_out) {
     hipStream_t st = h->stream;
     const int64_t qb = std::min<int64_t>(nq, MMIDX_COMB_MAX_Q);
-    HIPCK(h->ws_Q.reserve((size_t)qb * h->D));
-    HIPCK(h->ws_oiid.reserve((size_t)qb * k));
-    HIPCK(h->ws_odist.reserve((size_t)qb * k));
-    HIPCK(h->ws_ocnt.reserve((size_t)qb));
+    int rc = reserve_answers(h, qb, k);
+    if (rc) return rc;
     HIPCK(h->ws_rfm.reserve(1));
     if (iids) {
         HIPCK(h->ws_idq.reserve((size_t)qb));
         HIPCK(h->ws_found.reserve((size_t)qb));
     }
-    int rc = refine_reserve(h, qb, R, st);
+    rc = refine_reserve(h, qb, R, st);
     if (rc) return rc;
     HIPCK(hipMemsetAsync(h->ws_rfm.p, 0, 8, st));
     for (int64_t q0 = 0; q0 < nq; q0 += qb) {
@@ -4175,10 +4272,7 @@ int refine_host(mmidx_index *h, const MmidxLinearRows &rows, int k, int R, int64
             HIPCK(hipMemcpyAsync(h->ws_Q.p, Q + (size_t)q0 * h->D, (size_t)nb * h->D * 8, hipMemcpyHostToDevice, st));
         rc = refine_round(h, rows, k, R, nb, h->ws_Q.p, iids ? h->ws_found.p : nullptr, h->ws_oiid.p, h->ws_odist.p, h->ws_ocnt.p, h->ws_rfm.p, st);
         if (rc) return rc;
-        HIPCK(hipMemcpyAsync(iid_out + (size_t)q0 * k, h->ws_oiid.p, (size_t)nb * k * 4, hipMemcpyDeviceToHost, st));
-        HIPCK(hipMemcpyAsync(dist_out + (size_t)q0 * k, h->ws_odist.p, (size_t)nb * k * 8, hipMemcpyDeviceToHost, st));
-        HIPCK(hipMemcpyAsync(count_out + q0, h->ws_ocnt.p, (size_t)nb * 4, hipMemcpyDeviceToHost, st));
-        HIPCK(hipStreamSynchronize(st));
+        if ((rc = fetch_answers(h, q0, nb, k, iid_out, dist_out, count_out, st))) return rc;
     }
     int64_t missing = 0;
     HIPCK(hipMemcpyAsync(&missing, h->ws_rfm.p, 8, hipMemcpyDeviceToHost, st));

@@ -4,7 +4,7 @@ tests/test_sdc_cases_cpu.py and tests/test_gpu_sdc.py.  Pure numpy plus the orac
 mmidx_search_sdc has no scan of its own: k_sdc_terms writes a [nq][m][ks][dsub] table of squared terms and search_common runs the
 SDC = true instances of the exact scan and of the tie replay over it.  Every case below names the form it is meant to reach
 (`reach`); the host mirrors (`plan`, `sdc_round`, `scan_instance`, `merge_instance`, `split_applies`, `labels`) restate the gates
-of csrc/mmidx_api.hip (make_plan, launch_scan, search_batch_device, mmidx_search_sdc) and the CPU test holds every case to them.
+of csrc/mmidx_api.hip (make_plan, launch_scan, the step's stage_pass_a / stage_pass_b_flat / stage_merge / stage_tie_replay, mmidx_search_sdc) and the CPU test holds every case to them.
 
 The TWIN (`sdc_dists`, `sdc_twin`) is the independent statement of the answer: the full distance of every record as ONE chain
 (s outer, t inner, one rounding per operation, no early abandon), then the bounded queue of np_twin.  The oracle

@@ -1,8 +1,8 @@
 """GPU parity of a handle driven through every kernel switch of pass A, in every order, across an add.
 
 The pass-A kernels share workspace with pass B (ws_pcount, ws_pstart, ws_gdesc, ws_gfb) and some of them rely on what the launch
-before left there: K3q's k_q_scan_groups leaves the per-cell counters zeroed so that pass B skips its memset (pcount_zeroed in
-search_batch_device), K3ma does not, k_pair_scan leaves at once on a zero total.  One handle of a long-list IVFPQ index (m = 16 x 256,
+before left there: K3q's k_q_scan_groups leaves the per-cell counters zeroed so that pass B skips its memset (SearchStep::pcount_zeroed:
+set by stage_init, read by stage_pair_sort), K3ma does not (stage_pass_a withdraws it), k_pair_scan leaves at once on a zero total.  One handle of a long-list IVFPQ index (m = 16 x 256,
 D = 128, six cells: five of >= 4096 codes and one that starts empty) serves a walk over eight dispatch states -- reached by options, k,
 setW and the batch size -- in which every ordered pair of states follows each other at least once (an Eulerian circuit of the complete
 directed graph with loops).  Which state a call was in is read back from mmidx_get_dispatch and the statistics, not assumed, and the

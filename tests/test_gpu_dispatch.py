@@ -2,8 +2,8 @@
 
 Every row builds a small index of the given shape, runs one batch search (parity with the oracle on a few queries: the kernel that
 ran must also be right) and compares the kernel families the library reports for the coarse stage, pass A, the pair pre-filter and
-pass B with the documented ones.  The gates live in csrc/mmidx_api.hip (run_coarse, search_batch_device, launch_scan_grouped,
-launch_mfma_common, launch_mfma_kc, passa_q_applies, passa_mfma_applies); a change there has to change this table and DESIGN.md with it."""
+pass B with the documented ones.  The gates live in csrc/mmidx_api.hip (run_coarse, the stages of search_batch_device -- stage_coarse,
+pass_a_rung and stage_pass_a, k3s_decide --, launch_scan_grouped, launch_mfma_common, launch_mfma_kc, passa_q_applies, passa_mfma_applies); a change there has to change this table and DESIGN.md with it."""
 import numpy as np
 import pytest
 

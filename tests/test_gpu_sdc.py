@@ -63,7 +63,7 @@ def test_sdc_case(mi, oracle, name):
         ix.close()
 
 
-# every one of these is gated off for symmetric distances (search_batch_device, launch_scan_grouped_flat, launch_scan_filtered):
+# every one of these is gated off for symmetric distances (pass_a_rung and k3s_decide of the search step, launch_scan_grouped_flat, launch_scan_filtered):
 # forced in turn, none may change an answer.  (name, forced value, default)
 SWEEP = [("passa_hist", 1, -1), ("no_filter", 1, 0), ("no_grp", 1, 0), ("no_mfma", 1, 0), ("smin_pre", 1, -1), ("passb_small", 1, 1),
          ("passb_small", 0, 1), ("debug_sync", 1, 0)]

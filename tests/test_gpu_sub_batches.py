@@ -2,7 +2,7 @@
 
 A call of more than `pl.qb` queries (make_plan, csrc/mmidx_api.hip; tests/plan_model.py restates it) runs as a loop of sub-batches.
 From the second one on every pointer of the caller carries an offset of its own -- queries, probe cells, ids, distances, counts, the
-partial lists at q0 (k + 1), the SDC term tables -- every gate inside search_batch_device sees the sub-batch's size, and no host
+partial lists at q0 (k + 1), the SDC term tables -- every gate of the step (search_batch_device: pass_a_rung, stage_coarse, k3s_decide) sees the sub-batch's size, and no host
 synchronisation separates two sub-batches, so the pinned hint words a stage steers by may describe the stage two back.  The caps that
 decide `qb` are memory caps (gibibytes): the option "sub_batch" lowers `qb` so that calls of a few dozen queries are split, and three
 cases at the end reach the caps themselves with the option at 0.
@@ -274,7 +274,7 @@ def test_pass_b_families_and_ties(mi, oracle, row):
     want = ref.search_batch(Q, k, nthreads=8)
     runs = [({}, family), ({"no_mfma": 1}, "K3g"), ({"no_mfma": 1, "no_grp": 1}, "K3f")]
     if row == "K3s":
-        # K3s stands in front of K3m and K3g only: search_batch_device asks for the grouped tables (`pre_ok` needs !no_grp), so there
+        # K3s stands in front of K3m and K3g only: k3s_decide asks for the grouped tables (`pre_ok` needs !no_grp), so there
         # is no K3s + K3f run to make -- checked below: under no_grp the forced option leaves the pre-filter off
         runs = [({"smin_pre": 1}, family), ({"smin_pre": -1}, family), ({"smin_pre": 1, "no_mfma": 1}, "K3g"), ({"smin_pre": -1, "no_mfma": 1}, "K3g"),
                 ({"smin_pre": 1, "no_mfma": 1, "no_grp": 1}, "K3f")]
