@@ -7,6 +7,7 @@ by its indexing examples), on one MI355X:
      -> a fresh PCA loads the file with whitening -> projection -> IVFPQ index / search
 
   python examples/learn_pca.py --images 4000 --centroids 32 --components 64
+  python examples/learn_pca.py --streaming     # PCA.streaming: the VLAD batches are folded in as they come and are not kept
 """
 import argparse
 import importlib
@@ -23,7 +24,7 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 
-def run(n_images=4000, ncent=32, nc_out=64, n_queries=64, k=10, seed=0, cells=64, w=8, pca_file=None, verbose=True):
+def run(n_images=4000, ncent=32, nc_out=64, n_queries=64, k=10, seed=0, cells=64, w=8, pca_file=None, verbose=True, streaming=False):
     mi = importlib.import_module("multimedia-indexing_amd")
     rng = np.random.default_rng(seed)
     dl = 64
@@ -41,8 +42,13 @@ def run(n_images=4000, ncent=32, nc_out=64, n_queries=64, k=10, seed=0, cells=64
     ss = V.shape[1]
     # ---- learn the basis: PCA(numComponents, numSamples, sampleSize), addSample x n, computeBasis, savePCAToFile ----
     t0 = time.time()
-    learner = mi.PCA(nc_out, n_images, ss, False)
-    learner.addSamples(V)
+    if streaming:  # no sample count up front; any split over the calls gives the same bytes
+        learner = mi.PCA.streaming(nc_out, ss, False)
+        for i in range(0, n_images, 1000):
+            learner.addSamples(V[i:i + 1000])
+    else:
+        learner = mi.PCA(nc_out, n_images, ss, False)
+        learner.addSamples(V)
     learner.computeBasis(tol=1e-10, max_iter=500)
     t_learn = time.time() - t0
     path = pca_file or os.path.join(tempfile.mkdtemp(), "pca.txt")
@@ -65,7 +71,7 @@ def run(n_images=4000, ncent=32, nc_out=64, n_queries=64, k=10, seed=0, cells=64
     qimgs = [images[i] + 0.02 * rng.standard_normal(images[i].shape) for i in qi]
     Q = mi.frontend.ImageVectorizer(vlad, pca).transform_batch(qimgs)
     iids, _, _ = ix.search_batch(k, Q)
-    out = {"images": n_images, "vlad_length": ss, "components": nc_out, "pca_learn_seconds": round(t_learn, 3),
+    out = {"images": n_images, "vlad_length": ss, "components": nc_out, "streaming": bool(streaming), "pca_learn_seconds": round(t_learn, 3),
            "pca_iterations": learner.iterations, "pca_residual": learner.residual,
            "singular_values_first_last": [float(learner.singularValues[0]), float(learner.singularValues[-1])],
            "self_hit_rate": float(np.mean(iids[:, 0] == qi)), "pca_file": path}
@@ -82,5 +88,6 @@ if __name__ == "__main__":
     ap.add_argument("--centroids", type=int, default=32)
     ap.add_argument("--components", type=int, default=64)
     ap.add_argument("--pca-file", default=None)
+    ap.add_argument("--streaming", action="store_true", help="learn with PCA.streaming (mmidx_pca_stream_*)")
     a = ap.parse_args()
-    run(a.images, a.centroids, a.components, pca_file=a.pca_file)
+    run(a.images, a.centroids, a.components, pca_file=a.pca_file, streaming=a.streaming)

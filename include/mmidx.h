@@ -608,10 +608,15 @@ int mmidx_get_dispatch(mmidx_index *h, char *out, int cap);
  * mmidx_probe_split_gather: the m = 16 loop with the last kg (1, 2 or 4) rows gathered through the vector-memory path (a
  *   per-block copy in global memory, L1-resident) and the others from the LDS -- the experiment behind DESIGN section 9's
  *   "share the gather between the two pipes"; out as mmidx_probe_lds_gather.
- * mmidx_probe_f64_mfma: back-to-back v_mfma_f64_16x16x4_f64 on every SIMD; out[0] = TFLOP/s, out[1] = seconds. */
+ * mmidx_probe_f64_mfma: back-to-back v_mfma_f64_16x16x4_f64 on every SIMD; out[0] = TFLOP/s, out[1] = seconds.
+ * mmidx_probe_sym_eig: the PCA learners' device eigen-solver alone (cyclic Jacobi, csrc/mmidx_dense_solve.h), 1 <= b <= 1056.  T is
+ *   a host matrix [b][b] (symmetrised as (T + T^T) / 2); lam_out[b] descending, Wt_out[b][b] with row i the unit eigenvector of
+ *   lam_out[i] (the layout of the host solver), *sweeps_out the Jacobi sweeps run.  A non-finite entry: MMIDX_ERR_INVALID_ARG,
+ *   nothing written. */
 int mmidx_probe_lds_gather(int device, int m, int chains, double *out);
 int mmidx_probe_split_gather(int device, int kg, double *out);
 int mmidx_probe_f64_mfma(int device, double *out);
+int mmidx_probe_sym_eig(int device, int b, const double *T, double *lam_out, double *Wt_out, int32_t *sweeps_out);
 
 /* ---- front end of BASELINE config 5 ----------------------------------------------------------
  * PCA projection: PCA.loadPCAFromFile (J/dimreduction/PCA.java:257-318) + sampleToEigenSpace
@@ -655,6 +660,43 @@ int mmidx_pca_learn_add_device(mmidx_pca_learner *l, int64_t n, const double *dX
 int mmidx_pca_learn_compute(mmidx_pca_learner *l, double tol, int max_iter, double *means_out, double *sv_out,
                             double *Vt_out, int32_t *iters_out, double *residual_out);
 int mmidx_pca_learn_destroy(mmidx_pca_learner *l);
+
+/* The same basis from a STREAM of samples: no num_samples, rows are folded into the Gram matrix as they arrive and are not kept.
+ * This is the learner for the flagship front end (4 x 128 SURF centroids, a 32768-long VLAD vector, 32768 -> 1024), whose samples
+ * do not fit a device.  add / add_device as above; count = rows so far; compute = computeBasis over the rows so far, with the
+ * outputs, sign rule, determinism and MMIDX_ERR_NOT_CONVERGED behaviour of mmidx_pca_learn_compute:
+ *   means_out   BIT-EXACT: the reference's sequential column sums (:142-153) kept running across add calls, one division by the count;
+ *   sv_out, Vt_out   as above, for the Gram matrix centred by the exact mean of the rows (it differs from the resident learner's,
+ *               centred by the rounded sequential mean, by n delta delta^T: second order in the rounding of the mean).  One step
+ *               more than the resident learner: every row of Vt_out is divided by its 2-norm, so |v| = 1 to an ulp where the
+ *               resident learner's rows are unit to the 10-20 eps that V = Q W leaves (its output bytes are kept as they were).
+ * THE RESULT BYTES DO NOT DEPEND ON HOW THE ROWS WERE SPLIT OVER add CALLS: rows wait in a staging block of R rows, R fixed by ss
+ * alone (2^25 / ss rounded down to a multiple of 64, within 64 .. 4096: at most 256 MiB), and a full block is folded in one launch:
+ * Gt += (X - m0)^T (X - m0) on the f64 matrix cores and st += sum (x - m0), where the shift m0 is the first row; compute folds the
+ * tail and finalises G = Gt - st st^T / n.  (Accumulating uncentred X^T X and subtracting n mu mu^T would cancel catastrophically
+ * for data with an offset.)  After compute the Gram matrix is final: add is MMIDX_ERR_INVALID_ARG; compute may be called again, for
+ * example with another tol or after MMIDX_ERR_NOT_CONVERGED.  MMIDX_PCA_STREAM_ROWS (read at create; a multiple of 8, at least 8)
+ * overrides R for tests.
+ * Device memory: ss^2 * 8 bytes for the Gram matrix (8 GiB at 32768) + R * ss * 8 for the staging block (256 MiB) + 4 * ss * 8
+ * (column sums, shift, shifted sums, a zero vector) from create to destroy; during compute 5 * ss * b * 8 + nc * ss * 8 for the
+ * iteration's blocks (b = min(ss, nc + 32): 1.6 GiB at 32768 -> 1024), 2 * b^2 * 8 for S and the factor, and with the device solves
+ * 6 * b^2 * 8 more (two copies each of T and Wt, the unpolished eigenvectors, the polish factor: 51 MiB at b = 1056).
+ * A device call that fails in the middle of an add or of the finalisation leaves the running sums unusable: every later add or
+ * compute on that handle returns MMIDX_ERR_HIP; destroy it.
+ * Envelope: 1 <= nc <= ss <= 32768, nc <= 1024, fewer than 2^31 rows in all (else MMIDX_ERR_UNSUPPORTED).  MMIDX_ERR_INVALID_ARG
+ * before any device call: nc > ss "More components requested than the data's length."; compute with fewer rows than nc "More data
+ * needed to compute the desired number of components"; add after compute.
+ * Both learners solve the b x b eigenproblems of an iteration on the device (cyclic Jacobi) for
+ * 256 < b <= 512 and on the host otherwise: below as always, above until the device form has been measured to win there;
+ * MMIDX_PCA_LEARN_SOLVE=host|device, read by compute, forces either at any b. */
+typedef struct mmidx_pca_stream mmidx_pca_stream;
+int mmidx_pca_stream_create(int nc, int ss, int device, mmidx_pca_stream **out);
+int mmidx_pca_stream_add(mmidx_pca_stream *s, int64_t n, const double *X);
+int mmidx_pca_stream_add_device(mmidx_pca_stream *s, int64_t n, const double *dX, void *stream);
+int mmidx_pca_stream_count(const mmidx_pca_stream *s, int64_t *n_out);
+int mmidx_pca_stream_compute(mmidx_pca_stream *s, double tol, int max_iter, double *means_out, double *sv_out,
+                             double *Vt_out, int32_t *iters_out, double *residual_out);
+int mmidx_pca_stream_destroy(mmidx_pca_stream *s);
 
 /* VLAD aggregation: VladAggregator.aggregateInternal (J/aggregation/VladAggregator.java:56-70) with
  * computeNearestCentroid (AbstractFeatureAggregator.java:136-155), and the multi-vocabulary wrapper

@@ -116,6 +116,12 @@ SIGNATURES = {
     "mmidx_pca_learn_add_device": (C.c_int, [_vp, C.c_int64, _dp, _vp]),
     "mmidx_pca_learn_compute": (C.c_int, [_vp, C.c_double, C.c_int, _dp, _dp, _dp, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
     "mmidx_pca_learn_destroy": (C.c_int, [_vp]),
+    "mmidx_pca_stream_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "mmidx_pca_stream_add": (C.c_int, [_vp, C.c_int64, _dp]),
+    "mmidx_pca_stream_add_device": (C.c_int, [_vp, C.c_int64, _dp, _vp]),
+    "mmidx_pca_stream_count": (C.c_int, [_vp, C.POINTER(C.c_int64)]),
+    "mmidx_pca_stream_compute": (C.c_int, [_vp, C.c_double, C.c_int, _dp, _dp, _dp, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
+    "mmidx_pca_stream_destroy": (C.c_int, [_vp]),
     "mmidx_vlad_create": (C.c_int, [C.c_int, _i32p, C.c_int, _dp, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "mmidx_vlad_destroy": (C.c_int, [_vp]),
     "mmidx_vlad_set_option": (C.c_int, [_vp, C.c_char_p, C.c_int]),
@@ -160,6 +166,7 @@ SIGNATURES = {
     "mmidx_linear_get_dim": (C.c_int, [_vp, C.POINTER(C.c_int)]),
     "mmidx_probe_lds_gather": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp]),
     "mmidx_probe_f64_mfma": (C.c_int, [C.c_int, _dp]),
+    "mmidx_probe_sym_eig": (C.c_int, [C.c_int, C.c_int, _dp, _dp, _dp, C.POINTER(C.c_int32)]),
     "mmidx_probe_split_gather": (C.c_int, [C.c_int, C.c_int, _dp]),
     "mmidx_set_profiling": (C.c_int, [_vp, C.c_int]),
     "mmidx_set_option": (C.c_int, [_vp, C.c_char_p, C.c_int]),

@@ -29,6 +29,7 @@
 
 #include "mmidx_host.h"
 #include "mmidx_small_solve.h"
+#include "mmidx_dense_solve.h"
 
 namespace {
 
@@ -78,7 +79,10 @@ __global__ __launch_bounds__(64) void k_pca_colsum(const double *__restrict__ X,
 #define GR_NA (GR_BK * GR_BM / 2 / GR_NT)  // pairs of doubles per thread: A tile
 #define GR_NB (GR_BK * GR_BN / 2 / GR_NT)  // ... B tile
 
-template <bool SYM>
+// ACC (the streaming learner's fold, SYM only): a tile starts from the stored values of the elements it owns instead of from zero,
+// C += (A - muA)^T (B - muB); the mirrored copy is rewritten with the same value.  Ownership is what it is without ACC, so no element
+// is read or written by two tiles and the sum of a fold does not depend on scheduling.
+template <bool SYM, bool ACC = false>
 __global__ __launch_bounds__(GR_NT, 4) void k_pca_gram(const double *__restrict__ A, const double *__restrict__ B, const double *__restrict__ muA,
                                                        const double *__restrict__ muB, double *__restrict__ Cm, long long n, int sa, int sb) {
     __shared__ __attribute__((aligned(16))) double As[GR_BK * GR_LDA];
@@ -89,6 +93,18 @@ __global__ __launch_bounds__(GR_NT, 4) void k_pca_gram(const double *__restrict_
     f64x4 acc[8];
 #pragma unroll
     for (int t = 0; t < 8; t++) acc[t] = f64x4{0.0, 0.0, 0.0, 0.0};
+    if constexpr (ACC) {
+        static_assert(SYM, "the accumulating form exists for the symmetric Gram matrix only");
+#pragma unroll
+        for (int t = 0; t < 8; t++) {
+            const int j = j0 + t * 16 + (lane & 15);
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                const int i = i0 + wave * 16 + (lane >> 4) + 4 * r;
+                if (i < sa && j < sb && i >= j) acc[t][r] = Cm[(size_t)i * sb + j];
+            }
+        }
+    }
     // staging: thread <-> (k, pair of columns); the means of its columns stay in registers
     double2 ra[GR_NA], rb[GR_NB], ma[GR_NA], mb[GR_NB];
 #pragma unroll
@@ -225,9 +241,10 @@ __global__ __launch_bounds__(256) void k_pca_resid(const double *__restrict__ ZW
     }
     if (threadIdx.x == 0) res[i] = sqrt(red[0]);
 }
-// component i: sign rule, transpose, singular value
+// component i: sign rule, transpose, singular value.  renorm (the streaming learner): the row is divided by its 2-norm (fixed tree), so
+// that |v| = 1 to an ulp instead of to the few eps the last orthonormalisation and V = Q W leave; 0 = the row as it is.
 __global__ __launch_bounds__(256) void k_pca_finish(const double *__restrict__ V, const double *__restrict__ lam, int ss, int b, double *__restrict__ Vt,
-                                                    double *__restrict__ sv) {
+                                                    double *__restrict__ sv, int renorm) {
     __shared__ double bv[256];
     __shared__ int bi[256];
     const int i = blockIdx.x;
@@ -255,6 +272,26 @@ __global__ __launch_bounds__(256) void k_pca_finish(const double *__restrict__ V
         __syncthreads();
     }
     const double sgn = V[(size_t)bi[0] * b + i] < 0.0 ? -1.0 : 1.0;
+    if (renorm) {
+        __syncthreads();  // (bi[0] has been read by every thread)
+        double s = 0.0;
+        for (int k = threadIdx.x; k < ss; k += 256) {
+            const double v = V[(size_t)k * b + i];
+            s += v * v;
+        }
+        bv[threadIdx.x] = s;
+        __syncthreads();
+        for (int off = 128; off > 0; off >>= 1) {
+            if ((int)threadIdx.x < off) bv[threadIdx.x] += bv[threadIdx.x + off];
+            __syncthreads();
+        }
+        const double nrm = sqrt(bv[0]);
+        if (nrm > 0.0 && nrm <= 1.79769313486231570815e308) {  // (a zero or non-finite column stays as it is)
+            for (int k = threadIdx.x; k < ss; k += 256) Vt[(size_t)i * ss + k] = sgn * V[(size_t)k * b + i] / nrm;
+            if (threadIdx.x == 0) sv[i] = sqrt(lam[i] > 0.0 ? lam[i] : 0.0);
+            return;
+        }
+    }
     for (int k = threadIdx.x; k < ss; k += 256) Vt[(size_t)i * ss + k] = sgn * V[(size_t)k * b + i];
     if (threadIdx.x == 0) sv[i] = sqrt(lam[i] > 0.0 ? lam[i] : 0.0);
 }
@@ -273,6 +310,78 @@ int launch_gram(bool sym, const double *A, const double *B, const double *muA, c
     HIPCK(hipGetLastError());
     return MMIDX_OK;
 }
+
+// ------------------------------------------------------------------------------------------------
+// the streaming learner's running quantities (mmidx_pca_stream_*): with the shift m0 = the first row,
+//   fold      Gt += (X - m0)^T (X - m0) over a staging block (k_pca_gram<true, true>), st[c] += sum_r (X[r][c] - m0[c]) in row order
+//   finalise  G = Gt - st st^T / n: the Gram matrix centred by the exact mean; s_i * s_j commutes, so G is exactly symmetric
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void k_pca_shiftsum(const double *__restrict__ X, long long n, int ss, const double *__restrict__ m0,
+                                                     double *__restrict__ sum) {
+    const int c = blockIdx.x * 64 + threadIdx.x;
+    if (c >= ss) return;
+    double s = sum[c];
+    const double m = m0[c];
+    const double *x = X + c;
+    for (long long r = 0; r < n; r++) s += x[(size_t)r * ss] - m;
+    sum[c] = s;
+}
+__global__ __launch_bounds__(256) void k_pca_finalise(double *__restrict__ G, const double *__restrict__ s, int ss, double n) {
+    const int i = blockIdx.y, j = blockIdx.x * 256 + threadIdx.x;
+    if (j < ss) G[(size_t)i * ss + j] -= s[i] * s[j] / n;
+}
+
+int launch_fold(const double *X, const double *m0, double *G, double *ssum, long long n, int ss, hipStream_t st) {
+    dim3 grid((unsigned)((ss + GR_BN - 1) / GR_BN), (unsigned)((ss + GR_BM - 1) / GR_BM));
+    hipLaunchKernelGGL((k_pca_gram<true, true>), grid, dim3(GR_NT), 0, st, X, X, m0, m0, G, n, ss, ss);
+    hipLaunchKernelGGL(k_pca_shiftsum, dim3((unsigned)((ss + 63) / 64)), dim3(64), 0, st, X, n, ss, m0, ssum);
+    HIPCK(hipGetLastError());
+    return MMIDX_OK;
+}
+
+// The device eigen-solver as the learners and the probe use it: cyclic Jacobi (mmidx_dense_solve.h), then one Newton-Schulz step
+// Wt <- Wt (3 I - Wt^T Wt) / 2 on the kernels of this file, which takes the orthonormality of the eigenvectors from the ~100 eps the
+// rotations' rounding leaves to the few eps of one b-long product (the components' own orthonormality is held to 16 x LAPACK's).
+struct DeviceEig {
+    dense_solve::DenseSolver solver;
+    DevPtr<double> M, Wraw, zero;
+    int cap = 0;
+    int sym_eig(const double *dS, int b, double *d_lam, double *d_Wt, hipStream_t st, int *sweeps_out, const char *what, const char *nonfinite) {
+        if (b > cap) {
+            HIPCK(M.alloc((size_t)b * b));
+            HIPCK(Wraw.alloc((size_t)b * b));
+            HIPCK(zero.alloc((size_t)b));
+            HIPCK(hipMemsetAsync(zero.p, 0, (size_t)b * 8, st));
+            cap = b;
+        }
+        int rc = solver.sym_eig(dS, b, d_lam, Wraw.p, st, sweeps_out, what, nonfinite);
+        if (rc) return rc;
+        rc = launch_gram(true, Wraw.p, Wraw.p, zero.p, zero.p, M.p, b, b, b, st);
+        if (rc) return rc;
+        hipLaunchKernelGGL(dense_solve::k_ds_newton, dim3((unsigned)((b + DS_NT - 1) / DS_NT), (unsigned)b), dim3(DS_NT), 0, st, M.p, b);
+        HIPCK(hipGetLastError());
+        return mmidx_internal_gemm_nt(Wraw.p, zero.p, M.p, d_Wt, b, b, b, st);  // (M is symmetric: Wraw M^T = Wraw M)
+    }
+};
+
+// what both learners hand to the eigenpair loop: the centred Gram matrix on the device and what the trace line reports of its making
+struct EigArgs {
+    const double *G;       // [ss][ss], exactly symmetric
+    const double *d_zero;  // [ss] zeros (the mean operand of K7 and k_pca_gram)
+    int ss, nc;
+    long long n;
+    double tol;
+    int max_iter;
+    hipStream_t st;
+    const char *who;  // "pca_learn" / "pca_stream"
+    bool renorm;      // k_pca_finish divides every component by its norm (the streaming learner)
+    float gram_ms;    // the resident learner's k_pca_gram; < 0: not measured here
+    double t_begin;
+    double *sv_out, *Vt_out;
+    int32_t *iters_out;
+    double *residual_out;
+};
+int pca_eigenpairs(const EigArgs &a);
 
 }  // namespace
 
@@ -375,9 +484,8 @@ int mmidx_pca_learn_compute(mmidx_pca_learner *l, double tol, int max_iter, doub
     if (!(tol >= 0.0) || max_iter < 1) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "tol must be >= 0 and max_iter >= 1");
     HIPCK(hipSetDevice(l->device));
     hipStream_t st = l->stream;
-    const int ss = l->ss, nc = l->nc, b = std::min(ss, nc + 32);
+    const int ss = l->ss, nc = l->nc;
     const long long n = (long long)l->num;
-    const bool trace = getenv("MMIDX_PCA_LEARN_TRACE") != nullptr;
     const double t_begin = now_s();
 
     // ---- means (PCA.java:150-153) ----
@@ -387,22 +495,10 @@ int mmidx_pca_learn_compute(mmidx_pca_learner *l, double tol, int max_iter, doub
     for (int j = 0; j < ss; j++) h_mu[(size_t)j] = h_mu[(size_t)j] / (double)n;
     if (means_out) memcpy(means_out, h_mu.data(), (size_t)ss * 8);
 
-    DevPtr<double> d_mu, d_zero, G, Q, Z, V, ZW, Qt, S, Wd, d_lam, d_res, d_Vt, d_sv;
-    const size_t sb = (size_t)ss * b, bb = (size_t)b * b;
+    DevPtr<double> d_mu, d_zero, G;
     HIPCK(d_mu.alloc((size_t)ss));
     HIPCK(d_zero.alloc((size_t)ss));
     HIPCK(G.alloc((size_t)ss * ss));
-    HIPCK(Q.alloc(sb));
-    HIPCK(Z.alloc(sb));
-    HIPCK(V.alloc(sb));
-    HIPCK(ZW.alloc(sb));
-    HIPCK(Qt.alloc(sb));
-    HIPCK(S.alloc(bb));
-    HIPCK(Wd.alloc(bb));
-    HIPCK(d_lam.alloc((size_t)b));
-    HIPCK(d_res.alloc((size_t)b));
-    HIPCK(d_Vt.alloc((size_t)nc * ss));
-    HIPCK(d_sv.alloc((size_t)nc));
     HIPCK(hipMemcpyAsync(d_mu.p, h_mu.data(), (size_t)ss * 8, hipMemcpyHostToDevice, st));
     HIPCK(hipMemsetAsync(d_zero.p, 0, (size_t)ss * 8, st));
 
@@ -417,24 +513,122 @@ int mmidx_pca_learn_compute(mmidx_pca_learner *l, double tol, int max_iter, doub
     HIPCK(hipStreamSynchronize(st));
     float gram_ms = 0.f;
     HIPCK(hipEventElapsedTime(&gram_ms, e0, e1));
+    const EigArgs ea = {G.p, d_zero.p, ss, nc, n, tol, max_iter, st, "pca_learn", false, gram_ms, t_begin, sv_out, Vt_out, iters_out, residual_out};
+    return pca_eigenpairs(ea);
+}
+
+}  // extern "C"
+
+namespace {
+
+// which of the two b x b solvers an iteration uses: mmidx_small_solve.h on the host, or mmidx_dense_solve.h on the device.  The
+// device serves PCA_DEVICE_SOLVE_ABOVE < b <= PCA_DEVICE_SOLVE_UPTO by default.  Below (never below 256) every shape runs the host
+// code it always ran.  The upper end is where the measurements end: the device won at b = 288, and no run of
+// the learner with device solves has been measured to converge and win at b = 544 or 1056, so there the default stays the parent's.
+// MMIDX_PCA_LEARN_SOLVE=host|device forces either at any b, for both learners.
+#ifndef PCA_DEVICE_SOLVE_ABOVE
+#define PCA_DEVICE_SOLVE_ABOVE 256
+#endif
+#ifndef PCA_DEVICE_SOLVE_UPTO
+#define PCA_DEVICE_SOLVE_UPTO DS_FUSED_MAX
+#endif
+static_assert(PCA_DEVICE_SOLVE_ABOVE >= 256, "the host solves stay for b <= 256");
+
+// The top-nc eigenpairs of G by blocked subspace iteration with Rayleigh-Ritz (the header of this file), sv and Vt from them.
+int pca_eigenpairs(const EigArgs &a) {
+    const int ss = a.ss, nc = a.nc, b = std::min(ss, nc + 32);
+    hipStream_t st = a.st;
+    const bool trace = getenv("MMIDX_PCA_LEARN_TRACE") != nullptr;
+    bool dev = b > PCA_DEVICE_SOLVE_ABOVE && b <= PCA_DEVICE_SOLVE_UPTO;
+    if (const char *e = getenv("MMIDX_PCA_LEARN_SOLVE")) {
+        if (!strcmp(e, "device")) dev = true;
+        else if (!strcmp(e, "host")) dev = false;
+        else return mmidx_fail(MMIDX_ERR_INVALID_ARG, "MMIDX_PCA_LEARN_SOLVE must be host or device");
+    }
+    DeviceEig deig;
+    dense_solve::DenseSolver &solver = deig.solver;
+    int rc = MMIDX_OK;
+
+    DevPtr<double> Q, Z, V, ZW, Qt, S, Wd, d_lam, d_res, d_Vt, d_sv, d_scale;
+    DevPtr<unsigned long long> d_defect;
+    const size_t sb = (size_t)ss * b, bb = (size_t)b * b;
+    if (dev) {  // (what the device solves alone use; DeviceEig allocates its own blocks at its first solve)
+        HIPCK(d_scale.alloc((size_t)b));
+        HIPCK(d_defect.alloc(1));
+    }
+    HIPCK(Q.alloc(sb));
+    HIPCK(Z.alloc(sb));
+    HIPCK(V.alloc(sb));
+    HIPCK(ZW.alloc(sb));
+    HIPCK(Qt.alloc(sb));
+    HIPCK(S.alloc(bb));
+    HIPCK(Wd.alloc(bb));
+    HIPCK(d_lam.alloc((size_t)b));
+    HIPCK(d_res.alloc((size_t)b));
+    HIPCK(d_Vt.alloc((size_t)nc * ss));
+    HIPCK(d_sv.alloc((size_t)nc));
 
     double t_small = 0.0;  // host time in the b x b solves
-    std::vector<double> hS(bb), Linv, lam, Wt;
+    std::vector<double> hS(bb), Linv, lam, Wt, h_scale((size_t)b);
     std::vector<int> deficient;
     unsigned long long salt = 1;
+    // the device form of one orthonormalisation pass: S = U L U^T, Wd <- rows u_j / sqrt(l_j) (tmp = src Wd^T = src U L^-1/2); a
+    // direction with l_j <= b 2^-52 l_max is deficient, as a pivot at that level is for the host's Cholesky factor
+    int near_identity = 0;  // passes served by the Newton-Schulz factor
+    auto orth_factor_device = [&]() -> int {
+        // S within 2^-26 of I (the repeat pass of a block that is orthonormal already): X (3 I - S) / 2 is orthonormal to 3/8 of the
+        // defect squared, below eps -- no eigen-solve, and no Jacobi on a spectrum that is one cluster at rounding level
+        unsigned long long bits = 0;
+        HIPCK(hipMemsetAsync(d_defect.p, 0, 8, st));
+        hipLaunchKernelGGL(dense_solve::k_ds_ident_defect, dim3((unsigned)b), dim3(DS_NT), 0, st, S.p, b, d_defect.p);
+        HIPCK(hipGetLastError());
+        HIPCK(hipMemcpyAsync(&bits, d_defect.p, 8, hipMemcpyDeviceToHost, st));
+        HIPCK(hipStreamSynchronize(st));
+        double defect;
+        memcpy(&defect, &bits, 8);
+        if (defect <= 0x1p-26) {
+            HIPCK(hipMemcpyAsync(Wd.p, S.p, bb * 8, hipMemcpyDeviceToDevice, st));
+            hipLaunchKernelGGL(dense_solve::k_ds_newton, dim3((unsigned)((b + DS_NT - 1) / DS_NT), (unsigned)b), dim3(DS_NT), 0, st, Wd.p, b);
+            HIPCK(hipGetLastError());
+            deficient.clear();
+            near_identity++;
+            return MMIDX_OK;
+        }
+        int r = deig.sym_eig(S.p, b, d_lam.p, Wd.p, st, nullptr, "PCA learning, orthonormalisation", NONFINITE);
+        if (r) return r;
+        lam.resize((size_t)b);
+        HIPCK(hipMemcpyAsync(lam.data(), d_lam.p, (size_t)b * 8, hipMemcpyDeviceToHost, st));
+        HIPCK(hipStreamSynchronize(st));
+        const double thr = (double)b * 0x1p-52 * lam[0];
+        deficient.clear();
+        for (int j = 0; j < b; j++) {
+            const bool ok = lam[(size_t)j] > thr;
+            if (!ok) deficient.push_back(j);
+            h_scale[(size_t)j] = ok ? 1.0 / std::sqrt(lam[(size_t)j]) : 0.0;
+        }
+        HIPCK(hipMemcpyAsync(d_scale.p, h_scale.data(), (size_t)b * 8, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(dense_solve::k_ds_scale_rows, dim3((unsigned)((b + DS_NT - 1) / DS_NT), (unsigned)b), dim3(DS_NT), 0, st, Wd.p, d_scale.p, b);
+        HIPCK(hipGetLastError());
+        return MMIDX_OK;
+    };
     // CholeskyQR until two passes in a row met no deficient direction (normally the first two): *src <- orthonormal basis of span(*src)
     auto orth = [&](double *&src, double *&tmp) -> int {
         for (int pass = 0, clean = 0; pass < 6; pass++) {
-            int r = launch_gram(true, src, src, d_zero.p, d_zero.p, S.p, ss, b, b, st);
+            int r = launch_gram(true, src, src, a.d_zero, a.d_zero, S.p, ss, b, b, st);
             if (r) return r;
-            HIPCK(hipMemcpyAsync(hS.data(), S.p, bb * 8, hipMemcpyDeviceToHost, st));
-            HIPCK(hipStreamSynchronize(st));
-            const double t0 = now_s();
-            if (!mmidx_small::chol_inverse(hS.data(), b, (double)b * 0x1p-52, Linv, deficient))
-                return mmidx_fail(MMIDX_ERR_INVALID_ARG, "%s", NONFINITE);
-            t_small += now_s() - t0;
-            HIPCK(hipMemcpyAsync(Wd.p, Linv.data(), bb * 8, hipMemcpyHostToDevice, st));
-            r = mmidx_internal_gemm_nt(src, d_zero.p, Wd.p, tmp, ss, b, b, st);  // tmp = src L^-T
+            if (dev) {
+                r = orth_factor_device();
+                if (r) return r;
+            } else {
+                HIPCK(hipMemcpyAsync(hS.data(), S.p, bb * 8, hipMemcpyDeviceToHost, st));
+                HIPCK(hipStreamSynchronize(st));
+                const double t0 = now_s();
+                if (!mmidx_small::chol_inverse(hS.data(), b, (double)b * 0x1p-52, Linv, deficient))
+                    return mmidx_fail(MMIDX_ERR_INVALID_ARG, "%s", NONFINITE);
+                t_small += now_s() - t0;
+                HIPCK(hipMemcpyAsync(Wd.p, Linv.data(), bb * 8, hipMemcpyHostToDevice, st));
+            }
+            r = mmidx_internal_gemm_nt(src, a.d_zero, Wd.p, tmp, ss, b, b, st);  // tmp = src L^-T (device solves: src U L^-1/2)
             if (r) return r;
             for (int j : deficient)
                 hipLaunchKernelGGL(k_pca_fill, dim3((unsigned)((ss + 255) / 256)), dim3(256), 0, st, tmp, ss, b, j, salt++);
@@ -462,13 +656,19 @@ int mmidx_pca_learn_compute(mmidx_pca_learner *l, double tol, int max_iter, doub
         iters++;
         hipLaunchKernelGGL(k_pca_transpose, dim3((unsigned)((b + 31) / 32), (unsigned)((ss + 31) / 32)), dim3(256), 0, st, q, Qt.p, ss, b);
         HIPCK(hipGetLastError());
-        rc = mmidx_internal_gemm_nt(G.p, d_zero.p, Qt.p, z, ss, b, ss, st);  // Z = G Q
+        rc = mmidx_internal_gemm_nt(a.G, a.d_zero, Qt.p, z, ss, b, ss, st);  // Z = G Q
         if (rc) return rc;
-        rc = launch_gram(false, q, z, d_zero.p, d_zero.p, S.p, ss, b, b, st);  // T = Q^T Z
+        rc = launch_gram(false, q, z, a.d_zero, a.d_zero, S.p, ss, b, b, st);  // T = Q^T Z
         if (rc) return rc;
-        HIPCK(hipMemcpyAsync(hS.data(), S.p, bb * 8, hipMemcpyDeviceToHost, st));
-        HIPCK(hipStreamSynchronize(st));
-        {
+        if (dev) {
+            rc = deig.sym_eig(S.p, b, d_lam.p, Wd.p, st, nullptr, "PCA learning, Rayleigh-Ritz", NONFINITE);
+            if (rc) return rc;
+            lam.resize((size_t)b);
+            HIPCK(hipMemcpyAsync(lam.data(), d_lam.p, (size_t)b * 8, hipMemcpyDeviceToHost, st));
+            HIPCK(hipStreamSynchronize(st));
+        } else {
+            HIPCK(hipMemcpyAsync(hS.data(), S.p, bb * 8, hipMemcpyDeviceToHost, st));
+            HIPCK(hipStreamSynchronize(st));
             const double t0 = now_s();
             for (int i = 0; i < b; i++)
                 for (int j = 0; j < i; j++) {
@@ -478,12 +678,12 @@ int mmidx_pca_learn_compute(mmidx_pca_learner *l, double tol, int max_iter, doub
                 }
             if (!mmidx_small::sym_eig(hS.data(), b, lam, Wt)) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "%s", NONFINITE);
             t_small += now_s() - t0;
+            HIPCK(hipMemcpyAsync(Wd.p, Wt.data(), bb * 8, hipMemcpyHostToDevice, st));
+            HIPCK(hipMemcpyAsync(d_lam.p, lam.data(), (size_t)b * 8, hipMemcpyHostToDevice, st));
         }
-        HIPCK(hipMemcpyAsync(Wd.p, Wt.data(), bb * 8, hipMemcpyHostToDevice, st));
-        HIPCK(hipMemcpyAsync(d_lam.p, lam.data(), (size_t)b * 8, hipMemcpyHostToDevice, st));
-        rc = mmidx_internal_gemm_nt(q, d_zero.p, Wd.p, V.p, ss, b, b, st);  // V = Q W (Ritz vectors)
+        rc = mmidx_internal_gemm_nt(q, a.d_zero, Wd.p, V.p, ss, b, b, st);  // V = Q W (Ritz vectors)
         if (rc) return rc;
-        rc = mmidx_internal_gemm_nt(z, d_zero.p, Wd.p, zw, ss, b, b, st);  // Z W = G V
+        rc = mmidx_internal_gemm_nt(z, a.d_zero, Wd.p, zw, ss, b, b, st);  // Z W = G V
         if (rc) return rc;
         hipLaunchKernelGGL(k_pca_resid, dim3((unsigned)nc), dim3(256), 0, st, zw, V.p, d_lam.p, ss, b, d_res.p);
         HIPCK(hipGetLastError());
@@ -493,12 +693,12 @@ int mmidx_pca_learn_compute(mmidx_pca_learner *l, double tol, int max_iter, doub
         for (int i = 0; i < nc; i++) mr = std::max(mr, h_res[(size_t)i]);
         residual = lam[0] > 0.0 ? mr / lam[0] : (mr == 0.0 ? 0.0 : HUGE_VAL);
         if (!(mr == mr)) residual = HUGE_VAL;  // NaN
-        if (trace) fprintf(stderr, "[mmidx] pca_learn: iteration %d residual %.3e\n", iters, residual);
-        if (residual <= tol) {
+        if (trace) fprintf(stderr, "[mmidx] %s: iteration %d residual %.3e\n", a.who, iters, residual);
+        if (residual <= a.tol) {
             converged = true;
             break;
         }
-        if (iters >= max_iter) break;
+        if (iters >= a.max_iter) break;
         std::swap(q, zw);  // next block: an orthonormal basis of span(Z W)
         rc = orth(q, z);
         if (rc) return rc;
@@ -506,22 +706,241 @@ int mmidx_pca_learn_compute(mmidx_pca_learner *l, double tol, int max_iter, doub
     const double t_iter1 = now_s();
 
     // ---- singular values, sign rule, transpose ----
-    hipLaunchKernelGGL(k_pca_finish, dim3((unsigned)nc), dim3(256), 0, st, V.p, d_lam.p, ss, b, d_Vt.p, d_sv.p);
+    hipLaunchKernelGGL(k_pca_finish, dim3((unsigned)nc), dim3(256), 0, st, V.p, d_lam.p, ss, b, d_Vt.p, d_sv.p, a.renorm ? 1 : 0);
     HIPCK(hipGetLastError());
-    if (Vt_out) HIPCK(hipMemcpyAsync(Vt_out, d_Vt.p, (size_t)nc * ss * 8, hipMemcpyDeviceToHost, st));
-    if (sv_out) HIPCK(hipMemcpyAsync(sv_out, d_sv.p, (size_t)nc * 8, hipMemcpyDeviceToHost, st));
+    if (a.Vt_out) HIPCK(hipMemcpyAsync(a.Vt_out, d_Vt.p, (size_t)nc * ss * 8, hipMemcpyDeviceToHost, st));
+    if (a.sv_out) HIPCK(hipMemcpyAsync(a.sv_out, d_sv.p, (size_t)nc * 8, hipMemcpyDeviceToHost, st));
     HIPCK(hipStreamSynchronize(st));
-    if (iters_out) *iters_out = iters;
-    if (residual_out) *residual_out = residual;
+    if (a.iters_out) *a.iters_out = iters;
+    if (a.residual_out) *a.residual_out = residual;
     if (trace) {
         long long tiles = 0;  // tiles k_pca_gram ran (lower triangle + the diagonal's): the TF/s figure counts what was executed
         for (int i0 = 0; i0 < ss; i0 += GR_BM)
             for (int j0 = 0; j0 < ss; j0 += GR_BN) tiles += i0 + GR_BM - 1 >= j0;
-        fprintf(stderr, "[mmidx] pca_learn: n %lld ss %d nc %d b %d: gram %.3f ms (%.2f TF/s executed), %d iterations %.3f s, host solves %.3f s (start block included), total %.3f s\n",
-                n, ss, nc, b, gram_ms, 2.0 * (double)n * (double)tiles * GR_BM * GR_BN / (gram_ms * 1e-3) * 1e-12, iters, t_iter1 - t_iter0, t_small, now_s() - t_begin);
+        char gram[96] = "";
+        if (a.gram_ms >= 0.f)
+            snprintf(gram, sizeof gram, " gram %.3f ms (%.2f TF/s executed),", a.gram_ms, 2.0 * (double)a.n * (double)tiles * GR_BM * GR_BN / (a.gram_ms * 1e-3) * 1e-12);
+        fprintf(stderr, "[mmidx] %s: n %lld ss %d nc %d b %d:%s %d iterations %.3f s, solver %s, host solves %.3f s (start block included), device solves %d in %.3f s, %.2f sweeps per solve, %d near-identity passes, total %.3f s\n",
+                a.who, a.n, ss, nc, b, gram, iters, t_iter1 - t_iter0, dev ? "device" : "host", t_small, solver.solves, solver.seconds,
+                solver.solves ? (double)solver.sweeps_total / solver.solves : 0.0, near_identity, now_s() - a.t_begin);
     }
     if (!converged)
-        return mmidx_fail(MMIDX_ERR_NOT_CONVERGED, "PCA basis not converged: residual %.3e > tol %.3e after %d iterations", residual, tol, iters);
+        return mmidx_fail(MMIDX_ERR_NOT_CONVERGED, "PCA basis not converged: residual %.3e > a.tol %.3e after %d iterations", residual, a.tol, iters);
+    return MMIDX_OK;
+}
+
+}  // namespace
+
+// ------------------------------------------------------------------------------------------------
+// the streaming learner: rows are folded into the Gram matrix as they arrive and are not kept
+// ------------------------------------------------------------------------------------------------
+struct MMIDX_HIDDEN mmidx_pca_stream {
+    std::mutex mu;
+    int nc = 0, ss = 0, device = 0;
+    int R = 0;             // rows of the staging block: a fold runs whenever it is full, whatever the add calls were
+    int fill = 0;          // rows waiting in it
+    int64_t count = 0;
+    bool finalised = false;  // compute has turned Gt into the centred G: no row can be folded any more
+    bool broken = false;     // a device call failed in the middle of an add or of the finalisation: the running sums are not to be trusted
+    Stream stream;
+    DevPtr<double> dG, dstage, dsum, dm0, dssum, dzero;
+    Event ev_own, ev_ext;
+};
+
+namespace {
+
+int stream_add_rows(mmidx_pca_stream *s, int64_t n, const double *src, hipMemcpyKind kind, hipStream_t st) {
+    if (n == 0) return MMIDX_OK;
+    HIPCK(hipSetDevice(s->device));
+    const int ss = s->ss;
+    if (st != s->stream) HIPCK(hipStreamWaitEvent(st, s->ev_own, 0));
+    while (n > 0) {
+        const int64_t chunk = std::min<int64_t>(n, (int64_t)(s->R - s->fill));
+        double *dst = s->dstage + (size_t)s->fill * ss;
+        HIPCK(hipMemcpyAsync(dst, src, (size_t)chunk * ss * 8, kind, st));
+        if (s->count == 0) HIPCK(hipMemcpyAsync(s->dm0.p, dst, (size_t)ss * 8, hipMemcpyDeviceToDevice, st));  // the shift: the first row
+        hipLaunchKernelGGL(k_pca_colsum, dim3((unsigned)((ss + 63) / 64)), dim3(64), 0, st, dst, (long long)chunk, ss, s->dsum);
+        HIPCK(hipGetLastError());
+        s->fill += (int)chunk;
+        s->count += chunk;
+        src += (size_t)chunk * ss;
+        n -= chunk;
+        if (s->fill == s->R) {
+            int rc = launch_fold(s->dstage, s->dm0, s->dG, s->dssum, s->R, ss, st);
+            if (rc) return rc;
+            s->fill = 0;
+        }
+    }
+    if (st != s->stream) {
+        HIPCK(hipEventRecord(s->ev_ext, st));
+        HIPCK(hipStreamWaitEvent(s->stream, s->ev_ext, 0));
+    } else {
+        HIPCK(hipStreamSynchronize(st));  // host rows: the caller may reuse its buffer
+    }
+    HIPCK(hipEventRecord(s->ev_own, s->stream));
+    return MMIDX_OK;
+}
+
+const char *const STREAM_BROKEN = "PCA stream: an earlier device call on this handle failed part-way; destroy it";
+
+// the state checks of both add forms, then the rows on `st` (already resolved: the handle's own stream for host rows)
+int stream_add_checked(mmidx_pca_stream *s, int64_t n, const double *X, hipMemcpyKind kind, hipStream_t st) {
+    if (s->broken) return mmidx_fail(MMIDX_ERR_HIP, "%s", STREAM_BROKEN);
+    if (s->finalised) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "PCA stream: the basis has been computed and the Gram matrix finalised: no more samples");
+    if (s->count + n > (int64_t)INT32_MAX) return mmidx_fail(MMIDX_ERR_UNSUPPORTED, "PCA stream: fewer than 2^31 samples in all");
+    const int rc = stream_add_rows(s, n, X, kind, st);
+    if (rc) s->broken = true;  // (fill and count may have advanced past rows that never arrived)
+    return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mmidx_pca_stream_create(int nc, int ss, int device, mmidx_pca_stream **out) {
+    if (!out) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null out pointer");
+    *out = nullptr;
+    if (nc < 1 || ss < 1) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "bad PCA shape");
+    if (nc > ss) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "More components requested than the data's length.");  // PCA.java:102-104
+    if (ss > 32768 || nc > 1024) return mmidx_fail(MMIDX_ERR_UNSUPPORTED, "PCA stream: sampleSize <= 32768, numComponents <= 1024");
+    int R = std::min(4096, std::max(64, ((1 << 25) / ss) & ~63));
+    if (const char *e = getenv("MMIDX_PCA_STREAM_ROWS")) {  // tests: a staging block of their choice
+        char *end = nullptr;
+        const long v = strtol(e, &end, 10);
+        if (end == e || *end || v < 8 || v % 8 || v > 65536)
+            return mmidx_fail(MMIDX_ERR_INVALID_ARG, "MMIDX_PCA_STREAM_ROWS must be a multiple of 8 in 8 .. 65536");
+        R = (int)v;
+    }
+    const int ndev = mmidx_device_count();
+    if (ndev < 1) return mmidx_fail(MMIDX_ERR_NO_DEVICE, "no HIP device: libmmidx_hip has no CPU fallback");
+    if (device < 0 || device >= ndev) return mmidx_fail(MMIDX_ERR_NO_DEVICE, "device outside the visible range");
+    HIPCK(hipSetDevice(device));
+    std::unique_ptr<mmidx_pca_stream, int (*)(mmidx_pca_stream *)> s(new mmidx_pca_stream(), mmidx_pca_stream_destroy);
+    s->nc = nc;
+    s->ss = ss;
+    s->R = R;
+    s->device = device;
+    hipError_t e = s->stream.create();
+    if (e == hipSuccess) e = s->ev_own.create(hipEventDisableTiming);
+    if (e == hipSuccess) e = s->ev_ext.create(hipEventDisableTiming);
+    if (e == hipSuccess) e = s->dG.alloc((size_t)ss * ss);
+    if (e == hipSuccess) e = s->dstage.alloc((size_t)R * ss);
+    if (e == hipSuccess) e = s->dsum.alloc((size_t)ss);
+    if (e == hipSuccess) e = s->dm0.alloc((size_t)ss);
+    if (e == hipSuccess) e = s->dssum.alloc((size_t)ss);
+    if (e == hipSuccess) e = s->dzero.alloc((size_t)ss);
+    if (e == hipSuccess) e = hipMemsetAsync(s->dG, 0, (size_t)ss * ss * 8, s->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(s->dsum, 0, (size_t)ss * 8, s->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(s->dm0, 0, (size_t)ss * 8, s->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(s->dssum, 0, (size_t)ss * 8, s->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(s->dzero, 0, (size_t)ss * 8, s->stream);
+    if (e == hipSuccess) e = hipEventRecord(s->ev_own, s->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
+    if (e != hipSuccess)
+        return mmidx_fail(MMIDX_ERR_HIP, "PCA stream: allocation of the %d x %d Gram matrix and %d staging rows failed: %s", ss, ss, R, hipGetErrorString(e));
+    *out = s.release();
+    return MMIDX_OK;
+}
+
+int mmidx_pca_stream_destroy(mmidx_pca_stream *s) {
+    if (!s) return MMIDX_OK;
+    (void)hipSetDevice(s->device);
+    if (s->stream) (void)hipStreamSynchronize(s->stream);  // (work of an add_device on another stream is ordered before it)
+    delete s;
+    return MMIDX_OK;
+}
+
+int mmidx_pca_stream_add(mmidx_pca_stream *s, int64_t n, const double *X) {
+    if (!s) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null handle");
+    if (n < 0 || (n > 0 && !X)) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null argument");
+    std::lock_guard<std::mutex> lk(s->mu);
+    return stream_add_checked(s, n, X, hipMemcpyHostToDevice, s->stream);
+}
+
+int mmidx_pca_stream_add_device(mmidx_pca_stream *s, int64_t n, const double *dX, void *stream) {
+    if (!s) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null handle");
+    if (n < 0 || (n > 0 && !dX)) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null argument");
+    std::lock_guard<std::mutex> lk(s->mu);
+    // (as mmidx_pca_learn_add_device: a null stream is the device's default stream, not the handle's)
+    return stream_add_checked(s, n, dX, hipMemcpyDeviceToDevice, (hipStream_t)stream);
+}
+
+int mmidx_pca_stream_count(const mmidx_pca_stream *s, int64_t *n_out) {
+    if (!s || !n_out) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null argument");
+    std::lock_guard<std::mutex> lk(const_cast<mmidx_pca_stream *>(s)->mu);
+    *n_out = s->count;
+    return MMIDX_OK;
+}
+
+int mmidx_pca_stream_compute(mmidx_pca_stream *s, double tol, int max_iter, double *means_out, double *sv_out, double *Vt_out,
+                             int32_t *iters_out, double *residual_out) {
+    if (!s) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null handle");
+    std::lock_guard<std::mutex> lk(s->mu);
+    if (s->broken) return mmidx_fail(MMIDX_ERR_HIP, "%s", STREAM_BROKEN);
+    if ((int64_t)s->nc > s->count)
+        return mmidx_fail(MMIDX_ERR_INVALID_ARG, "More data needed to compute the desired number of components");  // PCA.java:138-140
+    if (!(tol >= 0.0) || max_iter < 1) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "tol must be >= 0 and max_iter >= 1");
+    HIPCK(hipSetDevice(s->device));
+    hipStream_t st = s->stream;
+    const int ss = s->ss;
+    const double t_begin = now_s();
+    if (!s->finalised) {
+        // the tail's fold and the finalisation change Gt in place: the handle counts as finalised only once the stream has run them,
+        // and a device failure on the way leaves it unusable
+        auto finalise = [&]() -> int {
+            if (s->fill > 0) {
+                int rc = launch_fold(s->dstage, s->dm0, s->dG, s->dssum, s->fill, ss, st);
+                if (rc) return rc;
+            }
+            hipLaunchKernelGGL(k_pca_finalise, dim3((unsigned)((ss + 255) / 256), (unsigned)ss), dim3(256), 0, st, s->dG.p, s->dssum.p, ss, (double)s->count);
+            HIPCK(hipGetLastError());
+            HIPCK(hipStreamSynchronize(st));
+            return MMIDX_OK;
+        };
+        const int rc = finalise();
+        if (rc) {
+            s->broken = true;
+            return rc;
+        }
+        s->fill = 0;
+        s->finalised = true;
+    }
+    // ---- means (PCA.java:150-153) ----
+    std::vector<double> h_mu((size_t)ss);
+    HIPCK(hipMemcpyAsync(h_mu.data(), s->dsum, (size_t)ss * 8, hipMemcpyDeviceToHost, st));
+    HIPCK(hipStreamSynchronize(st));
+    for (int j = 0; j < ss; j++) h_mu[(size_t)j] = h_mu[(size_t)j] / (double)s->count;
+    if (means_out) memcpy(means_out, h_mu.data(), (size_t)ss * 8);
+    const EigArgs ea = {s->dG.p, s->dzero.p, ss, s->nc, (long long)s->count, tol, max_iter, st, "pca_stream", true, -1.f, t_begin, sv_out, Vt_out, iters_out, residual_out};
+    return pca_eigenpairs(ea);
+}
+
+int mmidx_probe_sym_eig(int device, int b, const double *T, double *lam_out, double *Wt_out, int32_t *sweeps_out) {
+    if (!T) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "null argument");
+    if (b < 1 || b > 1056) return mmidx_fail(MMIDX_ERR_INVALID_ARG, "mmidx_probe_sym_eig: 1 <= b <= 1056");
+    const int ndev = mmidx_device_count();
+    if (ndev < 1) return mmidx_fail(MMIDX_ERR_NO_DEVICE, "no HIP device: libmmidx_hip has no CPU fallback");
+    if (device < 0 || device >= ndev) return mmidx_fail(MMIDX_ERR_NO_DEVICE, "device outside the visible range");
+    HIPCK(hipSetDevice(device));
+    const size_t bb = (size_t)b * b;
+    Stream st;
+    DevPtr<double> dS, d_lam, d_Wt;
+    DeviceEig deig;
+    HIPCK(st.create());
+    HIPCK(dS.alloc(bb));
+    HIPCK(d_lam.alloc((size_t)b));
+    HIPCK(d_Wt.alloc(bb));
+    HIPCK(hipMemcpyAsync(dS.p, T, bb * 8, hipMemcpyHostToDevice, st));
+    int sweeps = 0;
+    int rc = deig.sym_eig(dS.p, b, d_lam.p, d_Wt.p, st, &sweeps, "mmidx_probe_sym_eig", "mmidx_probe_sym_eig: the matrix holds a non-finite entry");
+    if (rc) {
+        (void)hipStreamSynchronize(st);
+        return rc;
+    }
+    if (lam_out) HIPCK(hipMemcpyAsync(lam_out, d_lam.p, (size_t)b * 8, hipMemcpyDeviceToHost, st));
+    if (Wt_out) HIPCK(hipMemcpyAsync(Wt_out, d_Wt.p, bb * 8, hipMemcpyDeviceToHost, st));
+    HIPCK(hipStreamSynchronize(st));
+    if (sweeps_out) *sweeps_out = sweeps;
     return MMIDX_OK;
 }
 

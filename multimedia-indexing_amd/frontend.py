@@ -7,7 +7,8 @@
 
 Projection = one batched f64-MFMA GEMM, aggregation = one block per image.  The PCA basis is learned on the
 GPU as well (addSample / addSamples, computeBasis, savePCAToFile: `mmidx_pca_learn_*`, a Gram matrix on the f64
-matrix cores and a blocked subspace iteration in place of EJML's SVD); codebooks: quantization.py.
+matrix cores and a blocked subspace iteration in place of EJML's SVD; PCA.streaming: `mmidx_pca_stream_*`, the same from a
+stream of samples that are not kept, up to 32768 -> 1024); codebooks: quantization.py.
 """
 import ctypes as C
 
@@ -38,12 +39,33 @@ class PCA:
         self.means = self.singularValues = self.V_t = None
         self.iterations = self.residual = None
 
+    @classmethod
+    def streaming(cls, numComponents, sampleSize, doWhitening, device=0):
+        """A PCA that learns from a stream of samples (`mmidx_pca_stream_*`): no numTrainingSamples, the rows are folded into
+        the Gram matrix as they arrive and are not kept, sampleSize up to 32768 (the flagship 32768 -> 1024 basis).
+        addSample / addSamples / add_device feed it; computeBasis works on the rows so far and sets numTrainingSamples to their
+        count; after it no more samples are taken.  Everything else is as on PCA."""
+        p = cls(numComponents, 0, sampleSize, doWhitening, device)
+        p._streaming = True
+        return p
+
+    _streaming = False
+
     # ---- learning: addSample / computeBasis / savePCAToFile (PCA.java:120-177, :219-247) ----
     def addSamples(self, X):
         """Batch form of addSample: rows of X [n][sampleSize] in arrival order."""
         X = _f64(X)
         if X.ndim != 2:
             raise MmidxError(N.ERR_WRONG_DIM, "Unexpected sample size")
+        if self._streaming:
+            if X.shape[1] != self.sampleSize:
+                raise MmidxError(N.ERR_WRONG_DIM, "Unexpected sample size")  # PCA.java:123-124
+            if X.shape[0] == 0:
+                return
+            self._ensure_learner()
+            N.check(N.lib().mmidx_pca_stream_add(self._learner, X.shape[0], X.ctypes.data))
+            self.sampleIndex += X.shape[0]
+            return
         if self.sampleIndex + X.shape[0] > self.numTrainingSamples:
             raise MmidxError(N.ERR_INVALID_ARG, "Too many samples")  # PCA.java:121-122
         if X.shape[1] != self.sampleSize:
@@ -56,14 +78,32 @@ class PCA:
 
     def addSample(self, sampleData):
         """PCA.java:120-130"""
-        if self.sampleIndex >= self.numTrainingSamples:
+        if not self._streaming and self.sampleIndex >= self.numTrainingSamples:
             raise MmidxError(N.ERR_INVALID_ARG, "Too many samples")
         x = _f64(sampleData)
         if x.ndim != 1 or x.shape[0] != self.sampleSize:
             raise MmidxError(N.ERR_WRONG_DIM, "Unexpected sample size")
         self.addSamples(x.reshape(1, -1))
 
+    def add_device(self, dX, n, stream=None):
+        """n rows of sampleSize doubles that already lie in the HBM of this PCA's device (dX: a device address, or an object
+        with data_ptr()), in arrival order; asynchronous on `stream` (a stream address; None = the device's default stream)."""
+        ptr = dX.data_ptr() if hasattr(dX, "data_ptr") else int(dX)
+        n = int(n)
+        if not self._streaming and self.sampleIndex + n > self.numTrainingSamples:
+            raise MmidxError(N.ERR_INVALID_ARG, "Too many samples")
+        if n <= 0:
+            return
+        self._ensure_learner()
+        add = N.lib().mmidx_pca_stream_add_device if self._streaming else N.lib().mmidx_pca_learn_add_device
+        N.check(add(self._learner, n, ptr, stream))
+        self.sampleIndex += n
+
     def _ensure_learner(self):
+        if self._learner is None and self._streaming:
+            h = C.c_void_p()
+            N.check(N.lib().mmidx_pca_stream_create(self.numComponents, self.sampleSize, self.device, C.byref(h)))
+            self._learner = h
         if self._learner is None:
             h = C.c_void_p()
             N.check(N.lib().mmidx_pca_learn_create(self.numComponents, self.numTrainingSamples, self.sampleSize, self.device, C.byref(h)))
@@ -74,6 +114,8 @@ class PCA:
         sample matrix, descending -- NOT divided by n: the reference's line 2, W.get(i, i)) and .V_t [numComponents][sampleSize]
         (in every row the entry of largest magnitude is positive; EJML's row signs are arbitrary), .iterations, .residual.
         Raises MmidxError(status NOT_CONVERGED) when max_iter is reached above tol; the fields are filled all the same."""
+        if self._streaming:
+            self.numSamples = self.numTrainingSamples = self.sampleIndex  # the count at computeBasis
         if self.sampleIndex != self.numTrainingSamples:
             raise MmidxError(N.ERR_INVALID_ARG, "Not all the data has been added")  # PCA.java:136-137
         if self.numComponents > self.numTrainingSamples:
@@ -82,8 +124,8 @@ class PCA:
         means, sv = np.zeros(self.sampleSize), np.zeros(self.numComponents)
         Vt = np.zeros((self.numComponents, self.sampleSize))
         it, res = C.c_int32(0), C.c_double(0.0)
-        st = N.lib().mmidx_pca_learn_compute(self._learner, float(tol), int(max_iter), means.ctypes.data, sv.ctypes.data, Vt.ctypes.data,
-                                             C.byref(it), C.byref(res))
+        compute = N.lib().mmidx_pca_stream_compute if self._streaming else N.lib().mmidx_pca_learn_compute
+        st = compute(self._learner, float(tol), int(max_iter), means.ctypes.data, sv.ctypes.data, Vt.ctypes.data, C.byref(it), C.byref(res))
         if st in (N.OK, N.ERR_NOT_CONVERGED):
             self.means, self.singularValues, self.V_t = means, sv, Vt
             self.iterations, self.residual = int(it.value), float(res.value)
@@ -157,7 +199,7 @@ class PCA:
             N.lib().mmidx_pca_destroy(self._h)
             self._h = None
         if getattr(self, "_learner", None):
-            N.lib().mmidx_pca_learn_destroy(self._learner)
+            (N.lib().mmidx_pca_stream_destroy if self._streaming else N.lib().mmidx_pca_learn_destroy)(self._learner)
             self._learner = None
 
     def __del__(self):

@@ -147,6 +147,19 @@ public final class MmidxNative {
 	public static native int pcaLearnCompute(long learner, int numComponents, int sampleSize, double tol, int maxIter,
 			double[] means, double[] singularValues, double[] components, double[] residualOut) throws Exception;
 
+	/* ---- the same from a stream of samples that are not kept (mmidx_pca_stream_*): sampleSize up to 32768 ---- */
+	public static native long pcaStreamCreate(int numComponents, int sampleSize, int device) throws Exception;
+
+	public static native void pcaStreamDestroy(long stream);
+
+	public static native void pcaStreamAdd(long stream, int n, int sampleSize, double[] samples) throws Exception;
+
+	public static native long pcaStreamCount(long stream) throws Exception;
+
+	/** as pcaLearnCompute, over the rows added so far; afterwards the stream takes no more samples */
+	public static native int pcaStreamCompute(long stream, int numComponents, int sampleSize, double tol, int maxIter,
+			double[] means, double[] singularValues, double[] components, double[] residualOut) throws Exception;
+
 	/**
 	 * mmidx_pq_learn: the whole product quantizer in one call. vectors[n * D]; coarse[C * D] or null (flat PQ); perm[D] / rot[D * D]
 	 * or null as the transformation (0 none, 1 rotation, 2 permutation) wants; pq[m * ks * (D / m)]; sse / seed / k / iterations [m]

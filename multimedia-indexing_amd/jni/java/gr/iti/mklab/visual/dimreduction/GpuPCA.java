@@ -18,8 +18,9 @@ import java.io.FileWriter;
  */
 public class GpuPCA {
 
-	private final int numComponents, numSamples, sampleSize;
-	private final boolean doWhitening;
+	private final int numComponents, sampleSize;
+	private int numSamples; // streaming: the count at computeBasis
+	private final boolean doWhitening, streaming;
 	private long handle;
 	// learning side
 	private long learner;
@@ -36,10 +37,36 @@ public class GpuPCA {
 		this.numSamples = numTrainingSamples;
 		this.sampleSize = sampleSize;
 		this.doWhitening = doWhitening;
+		this.streaming = false;
+	}
+
+	/**
+	 * A PCA that learns from a stream of samples (mmidx_pca_stream_*): no numTrainingSamples, the samples are folded into the Gram
+	 * matrix as they arrive and are not kept, sampleSize up to 32768 (the 32768 to 1024 basis of the four-vocabulary SURF VLAD).
+	 * computeBasis works on the samples added so far; after it no more are taken. The result does not depend on how the samples
+	 * were split over addSample / addSamples calls.
+	 */
+	public GpuPCA(int numComponents, int sampleSize, boolean doWhitening) {
+		if (numComponents > sampleSize) {
+			throw new IllegalArgumentException("More components requested than the data's length.");
+		}
+		this.numComponents = numComponents;
+		this.numSamples = 0;
+		this.sampleSize = sampleSize;
+		this.doWhitening = doWhitening;
+		this.streaming = true;
+	}
+
+	private void ensureLearner() throws Exception {
+		if (learner != 0)
+			return;
+		int device = Integer.getInteger("mmidx.device", 0);
+		learner = streaming ? MmidxNative.pcaStreamCreate(numComponents, sampleSize, device)
+				: MmidxNative.pcaLearnCreate(numComponents, numSamples, sampleSize, device);
 	}
 
 	public void addSample(double[] sampleData) throws Exception { // PCA.java:120-130
-		if (sampleIndex >= numSamples)
+		if (!streaming && sampleIndex >= numSamples)
 			throw new IllegalArgumentException("Too many samples");
 		if (sampleData.length != sampleSize)
 			throw new IllegalArgumentException("Unexpected sample size");
@@ -48,14 +75,15 @@ public class GpuPCA {
 
 	/** n samples row-major, in arrival order */
 	public void addSamples(double[] samples, int n) throws Exception {
-		if (n < 0 || (long) sampleIndex + n > numSamples)
+		if (n < 0 || (!streaming && (long) sampleIndex + n > numSamples))
 			throw new IllegalArgumentException("Too many samples");
 		if (samples.length != (long) n * sampleSize)
 			throw new IllegalArgumentException("Unexpected sample size");
-		if (learner == 0)
-			learner = MmidxNative.pcaLearnCreate(numComponents, numSamples, sampleSize,
-					Integer.getInteger("mmidx.device", 0));
-		MmidxNative.pcaLearnAdd(learner, n, sampleSize, samples);
+		ensureLearner();
+		if (streaming)
+			MmidxNative.pcaStreamAdd(learner, n, sampleSize, samples);
+		else
+			MmidxNative.pcaLearnAdd(learner, n, sampleSize, samples);
 		sampleIndex += n;
 	}
 
@@ -65,21 +93,24 @@ public class GpuPCA {
 
 	/** stops when max_i ||G v_i - sv_i^2 v_i|| <= tol * sv_1^2; throws (results kept) when maxIter is reached first */
 	public void computeBasis(double tol, int maxIter) throws Exception {
+		if (streaming)
+			numSamples = sampleIndex;
 		if (sampleIndex != numSamples)
 			throw new IllegalArgumentException("Not all the data has been added");
 		if (numComponents > numSamples)
 			throw new IllegalArgumentException("More data needed to compute the desired number of components");
-		if (learner == 0)
-			learner = MmidxNative.pcaLearnCreate(numComponents, numSamples, sampleSize,
-					Integer.getInteger("mmidx.device", 0));
+		ensureLearner();
 		means = new double[sampleSize];
 		singularValues = new double[numComponents];
 		components = new double[numComponents * sampleSize];
 		double[] res = new double[1];
 		iterations = maxIter; // (what a not-converged call, which throws, has run)
 		try {
-			iterations = MmidxNative.pcaLearnCompute(learner, numComponents, sampleSize, tol, maxIter, means,
-					singularValues, components, res);
+			iterations = streaming
+					? MmidxNative.pcaStreamCompute(learner, numComponents, sampleSize, tol, maxIter, means, singularValues,
+							components, res)
+					: MmidxNative.pcaLearnCompute(learner, numComponents, sampleSize, tol, maxIter, means, singularValues,
+							components, res);
 		} finally {
 			residual = res[0]; // written back by the shim on both paths
 		}
@@ -109,6 +140,11 @@ public class GpuPCA {
 			out.write(components[i * sampleSize + sampleSize - 1] + "\n");
 		}
 		out.close();
+	}
+
+	/** samples the basis was computed from (streaming: the count at computeBasis) */
+	public int getNumSamples() {
+		return numSamples;
 	}
 
 	public int getIterations() {
@@ -176,8 +212,12 @@ public class GpuPCA {
 		if (handle != 0)
 			MmidxNative.pcaDestroy(handle);
 		handle = 0;
-		if (learner != 0)
-			MmidxNative.pcaLearnDestroy(learner);
+		if (learner != 0) {
+			if (streaming)
+				MmidxNative.pcaStreamDestroy(learner);
+			else
+				MmidxNative.pcaLearnDestroy(learner);
+		}
 		learner = 0;
 	}
 }

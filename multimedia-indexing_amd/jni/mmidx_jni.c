@@ -685,6 +685,56 @@ done:
     (*env)->ReleaseDoubleArrayElements(env, residualOut, r_, 0);
     return (jint)iters;
 }
+/* ---- the same from a stream of samples that are not kept (mmidx_pca_stream_*): no numSamples, sampleSize up to 32768 ---- */
+JNIEXPORT jlong JNICALL JFN(pcaStreamCreate)(JNIEnv *env, jclass c, jint nc, jint ss, jint device) {
+    mmidx_pca_stream *s = NULL;
+    (void)c;
+    CHECK(mmidx_pca_stream_create(nc, ss, device, &s));
+done:
+    return (jlong)(intptr_t)s;
+}
+JNIEXPORT void JNICALL JFN(pcaStreamDestroy)(JNIEnv *env, jclass c, jlong s) {
+    (void)env;
+    (void)c;
+    mmidx_pca_stream_destroy((mmidx_pca_stream *)(intptr_t)s);
+}
+JNIEXPORT void JNICALL JFN(pcaStreamAdd)(JNIEnv *env, jclass c, jlong s, jint n, jint ss, jdoubleArray x) {
+    jdouble *x_;
+    (void)c;
+    if (n < 0 || ss < 1 || bad_len(env, x, (int64_t)n * ss, 0, "samples")) return;
+    x_ = (*env)->GetDoubleArrayElements(env, x, NULL);
+    CHECK(mmidx_pca_stream_add((mmidx_pca_stream *)(intptr_t)s, n, x_));
+done:
+    (*env)->ReleaseDoubleArrayElements(env, x, x_, JNI_ABORT);
+}
+JNIEXPORT jlong JNICALL JFN(pcaStreamCount)(JNIEnv *env, jclass c, jlong s) {
+    int64_t n = 0;
+    (void)c;
+    CHECK(mmidx_pca_stream_count((const mmidx_pca_stream *)(intptr_t)s, &n));
+done:
+    return (jlong)n;
+}
+/* as pcaLearnCompute, over the rows added so far */
+JNIEXPORT jint JNICALL JFN(pcaStreamCompute)(JNIEnv *env, jclass c, jlong s, jint nc, jint ss, jdouble tol, jint maxIter, jdoubleArray means,
+                                             jdoubleArray sv, jdoubleArray vt, jdoubleArray residualOut) {
+    jdouble *m_, *s_, *v_, *r_;
+    int32_t iters = 0;
+    (void)c;
+    if (nc < 1 || ss < 1 || bad_len(env, means, ss, 0, "means") || bad_len(env, sv, nc, 0, "singular values") ||
+        bad_len(env, vt, (int64_t)nc * ss, 0, "components") || bad_len(env, residualOut, 1, 0, "residual"))
+        return 0;
+    m_ = (*env)->GetDoubleArrayElements(env, means, NULL);
+    s_ = (*env)->GetDoubleArrayElements(env, sv, NULL);
+    v_ = (*env)->GetDoubleArrayElements(env, vt, NULL);
+    r_ = (*env)->GetDoubleArrayElements(env, residualOut, NULL);
+    CHECK(mmidx_pca_stream_compute((mmidx_pca_stream *)(intptr_t)s, tol, maxIter, m_, s_, v_, &iters, r_));
+done:
+    (*env)->ReleaseDoubleArrayElements(env, means, m_, 0);
+    (*env)->ReleaseDoubleArrayElements(env, sv, s_, 0);
+    (*env)->ReleaseDoubleArrayElements(env, vt, v_, 0);
+    (*env)->ReleaseDoubleArrayElements(env, residualOut, r_, 0);
+    return (jint)iters;
+}
 /* ProductQuantizationLearning in one call (mmidx_pq_learn): x[n][D]; coarse[C][D] or null (flat PQ); perm[D] / rot[D][D] or null as the
  * transformation wants; pq[m][ks][dsub] and the kept repeat's sse / seed / k / iterations per sub-space ([m] each, any may be null) */
 JNIEXPORT void JNICALL JFN(pqLearn)(JNIEnv *env, jclass c, jint device, jint n, jint D, jint m, jint ks, jint maxIter, jint repeats,
